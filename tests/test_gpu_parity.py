@@ -832,7 +832,7 @@ def test_bench_plain_command_two_ranks():
     env.update(SOHIT_BENCH_BACKEND="gloo", SOHIT_BENCH_ONE_GPU="1")
     outs = {}
     for n in (1, 2):
-        p = _cli(["bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--workload", "c2", "--no-cpu-baseline"], env=env)
+        p = _cli(["bench.py", "--full", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--workload", "c2", "--no-cpu-baseline"], env=env)
         assert p.returncode == 0, p.stderr.decode()[-3000:]
         lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
         assert len(lines) == 1, p.stdout.decode()[-2000:]
@@ -841,6 +841,50 @@ def test_bench_plain_command_two_ranks():
     _check_per_rank(outs[2], 2)
     assert outs[1]["config"]["rows"] == outs[2]["config"]["rows"] > 10000
     assert outs[1]["config"]["workload"] == outs[2]["config"]["workload"]
+
+
+def test_bench_plain_run_dumps_the_last_steps_records(fs, tmp_path):
+    """`bench.py` without --full prints one lean line (the headline keys; profiled figures, sub-runs and baselines come with --full
+    only), and --dump-outputs writes what the timed path returned in its last step: float64 files, within 64 MB, identical in two
+    runs, and equal to the records of the same search run directly through the library."""
+    import bench
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        p = _cli(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c2", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout.decode()[-2000:]
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        for key in ("stage_ms_per_step", "roofline", "other_kernels", "cpu_baseline", "strong_scaling_aux", "ms_per_step_hit_cache_off"):
+            assert key not in line, key
+        names = sorted(os.listdir(d))
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in names) <= 64 << 20
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in names}
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+        assert int(got["hits_per_query"].sum()) == line["config"]["rows"] > 10000
+        dumps.append(got)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    from swiftortho_amd import synthprot
+    n, ssd = bench.WORKLOADS["c2"][:2]
+    fa = synthprot.synthprot(n, bench.L_PROT)
+    s = fs.Searcher(ssd=ssd, **bench.BASE)
+    s.load_ref_bytes(fa)
+    s.load_queries_bytes(fa)
+    h = s.search()
+    rec = h.array()
+    h.close()
+    s.close()
+    got = dumps[0]
+    assert len(rec) == line["config"]["rows"]
+    assert np.array_equal(got["hits_per_query"], np.bincount(rec["qidx"], minlength=n).astype(np.float64))
+    rows = got["sample_row"].astype(np.int64)
+    assert len(rows) == min(len(rec), bench.DUMP_SAMPLE)
+    for f in rec.dtype.names:
+        assert np.array_equal(got["sample_" + f], rec[f][rows].astype(np.float64)), f
 
 
 @pytest.mark.parametrize("poison", ["0xFF", "0x5A"])
@@ -963,7 +1007,7 @@ def test_two_rank_search_over_rccl_on_two_gpus(tmp_path):
         outs.append(out.read_bytes())
     assert outs[0].count(b"\n") > 5000 and outs[0] == outs[1]
     # ... and the bench's strong-scaling flow over RCCL: one JSON line that carries every rank's terms
-    p = _cli(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2", "--no-cpu-baseline"], env=env)
+    p = _cli(["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2", "--no-cpu-baseline"], env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout.decode()[-2000:]

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/ab_align; mkdir -p $OUT; cd $R
 for v in 1 0; do
   export SOHIT_ALIGN_LANE=$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v$v -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-aux > $OUT/v$v.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v$v -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-aux > $OUT/v$v.log 2>&1
   find $OUT/v$v -name "*kernel_trace.csv" -delete; find $OUT/v$v -name "*.db" -delete
   f=$(find $OUT/v$v -name "*kernel_stats.csv" | head -1)
   echo "== SOHIT_ALIGN_LANE=$v"; python3 -c "

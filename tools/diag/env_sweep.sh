@@ -5,7 +5,6 @@ mkdir -p gpurun_out
 wl=$1; shift
 for cfg in "$@"; do
   echo "== $wl $cfg"
-  env $cfg timeout 600 python bench.py --workload $wl --steps 3 --warmup 1 --no-aux --no-cpu-baseline > gpurun_out/sweep_b.json 2>gpurun_out/sweep_b.err
-  python tools/diag/bench_summary.py gpurun_out/sweep_b.json | head -2
+  env $cfg timeout 600 python bench.py --full --workload $wl --steps 3 --warmup 1 --no-aux --no-cpu-baseline | python tools/diag/bench_summary.py /dev/stdin | head -2
 done > gpurun_out/env_sweep.log 2>&1
 cat gpurun_out/env_sweep.log

@@ -3,7 +3,7 @@
 # rocprofv3 --kernel-trace run of bench.py, over the span of the timed steps.   bash tools/diag/gpu_idle.sh [bench args]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/gpu_idle; rm -rf $OUT; mkdir -p $OUT; cd $R
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/*/*kernel_trace.csv")[0]

@@ -3,7 +3,7 @@
 TAG=${1:-x}; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/kstats_$TAG; mkdir -p $OUT; cd $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*.db" -delete
 cp $(find $OUT -name "*kernel_stats.csv" | head -1) $R/gpurun_out/kstats_$TAG.csv
 python3 - <<PY

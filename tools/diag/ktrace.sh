@@ -3,7 +3,7 @@
 TAG=$1; RE=$2; shift; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/ktrace_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-aux "$@" > $OUT.log 2>&1
 python3 - <<PY
 import csv,glob,re
 f=glob.glob("$OUT/*/*kernel_trace.csv")[0]

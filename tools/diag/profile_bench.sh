@@ -9,12 +9,12 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/stats.log 2>&1
 find $OUT/stats -name "*kernel_trace.csv" -delete; find $OUT/stats -name "*.db" -delete
 if [ "$MODE" != "statsonly" ]; then
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > $OUT/fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline "$@" > $OUT/fetch.log 2>&1
 find $OUT/fetch -name "*kernel_trace.csv" -delete
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > $OUT/write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline "$@" > $OUT/write.log 2>&1
 find $OUT/write -name "*kernel_trace.csv" -delete
 fi
 du -sh $OUT; find $OUT -name "*.csv" | head -20
