@@ -189,6 +189,19 @@ int64_t so_masked_query(so_ctx *ctx, int64_t qidx, char *buf, int64_t cap);
 /* candidates [subject, ungapped score, qi, qj] x uint32 of query qidx from the last
  * so_search_loaded() call, in the order the reference's spill file holds them (chunk-major) */
 int64_t so_query_candidates(so_ctx *ctx, int64_t qidx, uint32_t *out4, int64_t cap);
+/* tests: align explicit windows with ONE phase-2 aligner (not used by the search).  Queries are the loaded query file (raw residues, no
+ * masking), subjects the loaded reference.
+ * task6: n x {qidx, sidx, qi, qj, qe, se}: windows [qi, qe) of the query and [qj, se) of the subject, aligned from (qi, qj) as kswat_st does;
+ *   qe / se = -1: the sequence's end (otherwise a kswat_st_long tile end; a window holds at most 4096 residues).
+ * kernel: 0 k_align<false>, 1 k_align_pk<false>, 2 k_align_lane, 3 k_align<true> + k_traceback, 4 k_align_pk<true> + k_traceback
+ *   (traced: variable trace offsets, as the final emission lays them out).
+ * order: the launch list (n positions, any permutation or repeats of 0 .. n-1; traced kernels: every task once) or NULL = 0 .. n-1.
+ * out: n x {maxscore, aln, matches, gap, qst, qed, sst, sed, cells, wide} per TASK (all -1 for a task the list does not hold): qst / sst
+ *   0-based exclusive starts as kswat_st returns them; aln ... sed only from the traced kernels; wide = 1 when k_task_rows would send the
+ *   task to the 32-bit kernel.
+ * Refused, with a message and nothing written: a packed kernel (1, 2, 4) on a wide task, k_align_lane on a tile or on a sequence of 4096
+ * residues or more, windows out of range. */
+int so_align_pairs(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, const uint32_t *order, int32_t *out);
 
 /* Markov clustering of one block of the orthology graph.  Replaces: the matrix loop of bin/find_cluster.py
  * `mcl` (652-689) with `normalize` (636-646) as `mcl_xyz` (1425-1467) calls it on a float32 scipy csr_matrix -- column

@@ -561,6 +561,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
 // host_phase2.hip: candidate order, banded alignments in rounds, row emission
 void emit_join(so_ctx* c, HitBuf& out);
 void phase2(so_ctx* c, Batch& b, HitBuf& out);
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out);   // so_align_pairs (tests)
 // host_search.hip: batches of a search, the work pre-pass
 void search_loaded(so_ctx* c, i64 q_lo, i64 q_hi, HitBuf& out);
 void query_work(so_ctx* c, i64 q_lo, i64 q_hi, u64* out);

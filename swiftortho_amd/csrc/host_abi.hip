@@ -530,5 +530,9 @@ int64_t so_query_candidates(so_ctx* c, int64_t q, uint32_t* out4, int64_t cap) {
     return n;
 }
 
+int so_align_pairs(so_ctx* c, int kernel, int64_t n, const int64_t* task6, const uint32_t* order, int32_t* out) {
+    return guarded(c, [&] { align_pairs(c, kernel, n, task6, order, out); });
+}
+
 }  // extern "C"
 

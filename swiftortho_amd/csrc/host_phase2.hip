@@ -262,8 +262,8 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
             if (wide_aside) HIP_CHECK(hipEventRecord(c->ev_ug_done, c->st_side));
             if (NR > n_wide) {
                 // (a lane walks a whole alignment alone: a launch lasts at least one alignment's ~0.4 ms however few tasks it holds -- the last
-                // rounds of config 3, 6.6 k and 64 tasks, took 0.63 and 0.40 ms; sixteen lanes per pair finish those in 0.1)
-                if (lane_on && NR - n_wide >= (1u << 18)) {
+                // rounds of config 3, 6.6 k and 64 tasks, took 0.63 and 0.40 ms; sixteen lanes per pair finish those in 0.1; SOHIT_ALIGN_LANE_MIN, default 2^18)
+                if (lane_on && (long long)(NR - n_wide) >= tune().align_lane_min) {
                     c->d_small.ensure(32);
                     launch_align_lane(b.tasks.p, rlist + n_wide, NR - n_wide, pkc, b.dev.d_off.p, c->ref.d_off.p, c->d_b62c.p, b.ares.p, c->d_small.p + 13, c->ncu, c->st);
                 } else {
@@ -612,4 +612,106 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
     }
     sc.lap("phase2.emit_host");
     c->cnt.phase2_ms += (wall() - t0) * 1e3;
+}
+
+// so_align_pairs (tests): explicit windows through ONE aligner of phase 2, by the product's own launch functions on the product's device arrays.
+// The raw loaded queries are the batch (upload_set, as for a batch masked on the host): a task's q is its query ordinal.  Every task the
+// search would never hand the chosen kernel is refused before anything runs, so a refused call writes nothing.
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out) {
+    if (!c->ref_loaded || !c->qry_loaded) throw SoError("so_align_pairs: load a reference and queries first");
+    if (kernel < 0 || kernel > 4) throw SoError("so_align_pairs: kernel must be 0 ... 4");
+    if (n < 0 || n > (1ll << 24)) throw SoError("so_align_pairs: n must be 0 ... 2^24");
+    if (n == 0) return;
+    if (!task6 || !out) throw SoError("so_align_pairs: task6 or out is NULL");
+    const SeqSet& Q = c->qry;
+    const SeqSet& R = c->ref;
+    const bool packed = kernel == 1 || kernel == 2 || kernel == 4, traced = kernel >= 3;
+    std::vector<AlnTask> tk((size_t)n);
+    for (i64 t = 0; t < n; ++t) {
+        const int64_t* v = task6 + 6 * t;
+        auto refuse = [&](const std::string& why) { throw SoError("so_align_pairs: task " + std::to_string(t) + ": " + why); };
+        if (v[0] < 0 || v[0] >= Q.N) refuse("query index out of range");
+        if (v[1] < 0 || v[1] >= R.N) refuse("subject index out of range");
+        const i64 lq = Q.len(v[0]), ls = R.len(v[1]);
+        const i64 qe = v[4] == -1 ? lq : v[4], se = v[5] == -1 ? ls : v[5];
+        if (v[2] < 0 || v[2] > qe || qe > lq) refuse("query window out of range");
+        if (v[3] < 0 || v[3] > se || se > ls) refuse("subject window out of range");
+        // (a pair with a sequence of 4096+ residues is aligned in kswat_st_long tiles of at most 4096 x 4096)
+        if (qe - v[2] > LONG_SEQ || se - v[3] > LONG_SEQ) refuse("window longer than 4096 residues");
+        if (kernel == 2 && (qe != lq || se != ls)) refuse("k_align_lane takes no tile: both windows must end where their sequences end");
+        if (kernel == 2 && (lq >= LONG_SEQ || ls >= LONG_SEQ)) refuse("k_align_lane takes no sequence of 4096 residues or more");
+        tk[(size_t)t] = AlnTask{(u32)v[0], (u32)v[1], (u32)v[2], (u32)v[3], 0u, 0u, (u32)qe, (u32)se};
+    }
+    std::vector<u32> list((size_t)n);
+    std::vector<char> listed((size_t)n, 0);
+    for (i64 p = 0; p < n; ++p) {
+        const u32 s = order ? order[p] : (u32)p;
+        if ((i64)s >= n) throw SoError("so_align_pairs: order[" + std::to_string(p) + "] out of range");
+        // (k_traceback reads the maximum's cell the aligner parked in the task's result: a task walked twice would read the other walk's result)
+        if (traced && listed[s]) throw SoError("so_align_pairs: a traced launch list holds every task once");
+        listed[s] = 1, list[(size_t)p] = s;
+    }
+    if (packed && !(tune().align_pk && align_pk_supported(c->st))) throw SoError("so_align_pairs: the packed aligners are switched off or not supported here");
+    SeqSet qs;
+    upload_set(c, qs, Q.res.data(), Q.off, (u32)Q.N);
+    DevBuf<AlnTask> d_tasks;
+    DevBuf<u32> d_list, d_cnt;
+    DevBuf<u64> d_keys;
+    DevBuf<AlnRes> d_res;
+    d_tasks.ensure((size_t)n + 4), d_list.ensure((size_t)n + 4), d_cnt.ensure(4), d_keys.ensure((size_t)n + 4), d_res.ensure((size_t)n + 4);
+    HIP_CHECK(hipMemcpyAsync(d_tasks.p, tk.data(), (size_t)n * sizeof(AlnTask), hipMemcpyHostToDevice, c->st));
+    HIP_CHECK(hipMemcpyAsync(d_list.p, list.data(), (size_t)n * sizeof(u32), hipMemcpyHostToDevice, c->st));
+    HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 4 * sizeof(u32), c->st));
+    // the split of a score-only round: bit 13 of the key clear = the task needs the 32-bit cells
+    launch_task_rows(d_tasks.p, d_list.p, (u32)n, qs.d_off.p, R.d_off.p, qs.d_bound.p, R.d_bound.p, align_pk_max_len(), align_pk_max_score(), d_cnt.p,
+                     nullptr, d_keys.p, c->st);
+    std::vector<u64> keys((size_t)n);
+    HIP_CHECK(hipMemcpyAsync(keys.data(), d_keys.p, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    std::vector<char> wide((size_t)n, 0);
+    for (i64 p = 0; p < n; ++p) wide[list[(size_t)p]] = (keys[(size_t)p] & 8192u) ? 0 : 1;
+    if (packed)
+        for (i64 t = 0; t < n; ++t)
+            if (listed[(size_t)t] && wide[(size_t)t])
+                throw SoError("so_align_pairs: task " + std::to_string(t) + ": its scores need 32-bit cells, the packed aligners do not take it");
+    const PkCls pkc{qs.d_pcls.p, qs.d_pcls4.p, R.d_pcls.p, R.d_pcls4.p};
+    DevBuf<u32> d_units, d_tofs, d_trace;
+    switch (kernel) {
+    case 0:
+        launch_align(d_tasks.p, d_list.p, (u32)n, qs.d_res.p, qs.d_scls.p, qs.d_scls4.p, qs.d_off.p, R.d_res.p, R.d_scls.p, R.d_scls4.p, R.d_off.p, c->d_b62c.p,
+                     nullptr, 0u, nullptr, d_res.p, false, c->st, 0u);
+        break;
+    case 1:
+        launch_align_pk(d_tasks.p, d_list.p, (u32)n, pkc, qs.d_off.p, R.d_off.p, c->d_b62c.p, d_res.p, c->st);
+        break;
+    case 2:
+        launch_align_lane(d_tasks.p, d_list.p, (u32)n, pkc, qs.d_off.p, R.d_off.p, c->d_b62c.p, d_res.p, d_cnt.p + 1, c->ncu, c->st);
+        break;
+    default: {
+        // variable trace offsets, as the final emission lays them out: trace room per task (k_trace_units), scanned
+        const u32 TU = align_trace_unit();
+        d_units.ensure((size_t)n + 4), d_tofs.ensure((size_t)n + 4);
+        c->d_scan_tmp.ensure(scan_u32_temp_elems((size_t)n + 1) + 8);
+        launch_trace_units(d_tasks.p, d_list.p, (u32)n, qs.d_off.p, R.d_off.p, d_units.p, c->st);
+        const size_t tw = (size_t)d2h_u32(c, scan_u32(d_units.p, d_tofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st)) * TU;
+        d_trace.ensure(tw + 64);
+        const bool wide32 = kernel == 3;
+        launch_align(d_tasks.p, d_list.p, (u32)n, qs.d_res.p, qs.d_scls.p, qs.d_scls4.p, qs.d_off.p, R.d_res.p, R.d_scls.p, R.d_scls4.p, R.d_off.p, c->d_b62c.p,
+                     d_trace.p, TU, d_tofs.p, d_res.p, true, c->st, wide32 ? (u32)n : 0u, wide32 ? PkCls{nullptr, nullptr, nullptr, nullptr} : pkc);
+        break;
+    }
+    }
+    std::vector<AlnRes> res((size_t)n);
+    HIP_CHECK(hipMemcpyAsync(res.data(), d_res.p, (size_t)n * sizeof(AlnRes), hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    for (i64 t = 0; t < n; ++t) {
+        int32_t* o = out + 10 * t;
+        const AlnRes& r = res[(size_t)t];
+        if (!listed[(size_t)t]) {   // (not in the launch list)
+            for (int k = 0; k < 10; ++k) o[k] = -1;
+            continue;
+        }
+        o[0] = r.maxscore, o[1] = r.aln, o[2] = r.matches, o[3] = r.gap, o[4] = r.qst, o[5] = r.qed, o[6] = r.sst, o[7] = r.sed, o[8] = r.cells;
+        o[9] = wide[(size_t)t];
+    }
 }

@@ -177,6 +177,22 @@ class Searcher:
         self.L.so_query_candidates(self.h, q, out.ctypes.data, n)
         return out[:n]
 
+    ALIGN_DTYPE = [(f, "<i4") for f in ("maxscore", "aln", "matches", "gap", "qst", "qed", "sst", "sed", "cells", "wide")]
+
+    def align_pairs(self, tasks, kernel, order=None):
+        """tests: the windows tasks[k] = (qidx, sidx, qi, qj, qe, se) aligned by ONE phase-2 aligner (so_align_pairs; qe / se = -1: the
+        sequence's end) -> one record per task, fields ALIGN_DTYPE.  order: the launch list (None: 0 .. n-1)."""
+        t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int64).reshape(-1, 6))
+        n = len(t)
+        out = np.zeros(max(n, 1), dtype=self.ALIGN_DTYPE)
+        o = None
+        if order is not None:
+            o = np.ascontiguousarray(np.asarray(order, dtype=np.uint32))
+            if len(o) != n:
+                raise ValueError("order must hold n positions")
+        self._chk(self.L.so_align_pairs(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data))
+        return out[:n]
+
 
 class DeviceHits:
     """so_hit records of one so_search_device() call, resident in the ctx's device memory until its next search."""

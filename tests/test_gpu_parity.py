@@ -7,6 +7,7 @@ Run on the GPU box:  python -m pytest tests -m gpu -x -q
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -1319,6 +1320,33 @@ def test_tile_boundary_lengths_vs_oracle(fs, oracle, tmp_path):
     oracle_vs_gpu(fs, oracle, fa, kw, tmp_path)
 
 
+# k_align_lane takes only score-only rounds of 2^18 packed tasks and more: the adversarial sets below run once more with it forced on every
+# round (SOHIT_ALIGN_LANE_MIN=0) and once with it off (SOHIT_ALIGN_LANE=0)
+LANE_VARIANTS = [{"SOHIT_ALIGN_LANE_MIN": "0"}, {"SOHIT_ALIGN_LANE": "0"}]
+LANE_IDS = ["lane_forced", "lane_off"]
+
+
+def run_lane_variant(monkeypatch, capfd, lane, body):
+    """body() under one k_align_lane variant; with SOHIT_DEBUG the kernel names its launches on stderr: forced, every search that aligned
+    anything ran it (the smallest micro references align nothing), off, none did"""
+    for k, v in lane.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("SOHIT_DEBUG", "1")
+    inner, runs = gpu_rows, []
+
+    def searched(*a, **kw):
+        capfd.readouterr()
+        s, hits, rows = inner(*a, **kw)
+        runs.append((s.counters()["alignments"], "k_align_lane:" in capfd.readouterr().err))
+        return s, hits, rows
+
+    monkeypatch.setattr(sys.modules[__name__], "gpu_rows", searched)
+    body()
+    assert runs
+    for n, ran in runs:
+        assert ran == (n > 0 and "SOHIT_ALIGN_LANE_MIN" in lane), (lane, n, ran)
+
+
 @pytest.mark.parametrize("flt", ["F", "T"])
 def test_tandem_repeats_and_homopolymers_vs_oracle(fs, oracle, tmp_path, flt):
     """Homopolymers and tandem repeats of period 2..11 (unmasked with -F F): hundreds of seed hits per diagonal, every
@@ -1374,3 +1402,50 @@ def test_micro_references_vs_oracle(fs, oracle, tmp_path, lens):
     for kw in (dict(ssd="111111", nr=oracle.AA9, ht=1000003, chk=50000, step=1, v=500, expect=10.0, flt="F"),
                dict(ssd="111111", nr=oracle.AA9, ht=13, chk=1, step=1, v=500, expect=1e300, flt="F", thr=1)):
         oracle_vs_gpu(fs, oracle, fa, kw, tmp_path)
+
+
+@pytest.mark.parametrize("lane", LANE_VARIANTS, ids=LANE_IDS)
+@pytest.mark.parametrize("flt", ["F", "T"])
+def test_tandem_repeats_and_homopolymers_lane_variants(fs, oracle, tmp_path, monkeypatch, capfd, flt, lane):
+    run_lane_variant(monkeypatch, capfd, lane, lambda: test_tandem_repeats_and_homopolymers_vs_oracle(fs, oracle, tmp_path, flt))
+
+
+@pytest.mark.parametrize("lane", LANE_VARIANTS, ids=LANE_IDS)
+@pytest.mark.parametrize("v", [500, 50])
+def test_massive_score_ties_lane_variants(fs, oracle, tmp_path, monkeypatch, capfd, v, lane):
+    run_lane_variant(monkeypatch, capfd, lane, lambda: test_massive_score_ties_vs_oracle(fs, oracle, tmp_path, v))
+
+
+@pytest.mark.parametrize("lane", LANE_VARIANTS, ids=LANE_IDS)
+@pytest.mark.parametrize("lens", [(6,), (7,), (6, 6), (30,), (12, 6, 40), (6, 7, 8, 9, 10, 11, 12)])
+def test_micro_references_lane_variants(fs, oracle, tmp_path, monkeypatch, capfd, lens, lane):
+    run_lane_variant(monkeypatch, capfd, lane, lambda: test_micro_references_vs_oracle(fs, oracle, tmp_path, lens))
+
+
+@pytest.mark.parametrize("lane", LANE_VARIANTS, ids=LANE_IDS)
+def test_fasta_quirks_lane_variants(fs, oracle, tmp_path, monkeypatch, capfd, lane):
+    run_lane_variant(monkeypatch, capfd, lane, lambda: test_fasta_quirks_vs_oracle(fs, oracle, tmp_path))
+
+
+@pytest.mark.parametrize("lane", LANE_VARIANTS, ids=LANE_IDS)
+def test_randomised_differential_lane_variants(fs, oracle, tmp_path, monkeypatch, capfd, lane):
+    run_lane_variant(monkeypatch, capfd, lane, lambda: test_randomised_differential(fs, oracle, tmp_path, monkeypatch, 11))
+
+
+def test_score_bound_edges_end_to_end(fs, oracle, tmp_path):
+    """A proteome at the edge of the packed aligners' 16-bit range: W x 742 + P (score bound 8169: packed, self score 8169) and
+    W x 742 + C (8171: the 32-bit kernel), W / C / H / Y / P-rich proteins of 739-1000 residues with mutated copies (bounds on both
+    sides of 8169) among ordinary ones: the oracle's rows, and the wide tasks really took the 32-bit kernel."""
+    from swiftortho_amd import synthprot
+    rng = np.random.default_rng(41)
+    recs = [("wp", "W" * 742 + "P"), ("wc", "W" * 742 + "C")]
+    for n in (739, 740, 741, 742, 800, 1000):
+        a = "".join(rng.choice(list("WCHYP"), n))
+        b = list(a)
+        for p in rng.integers(0, n, size=n // 40):
+            b[int(p)] = "ACDEFGHIKLMNPQRSTVWY"[int(rng.integers(0, 20))]
+        recs += [("h%d" % n, a), ("m%d" % n, "".join(b))]
+    fa = "".join(">%s\n%s\n" % r for r in recs).encode() + synthprot.synthprot(60, 150, 4)
+    kw = dict(ssd="111111", nr=oracle.AA9, ht=1000003, chk=50000, step=1, v=500, expect=1e-5, flt="F")
+    c, _ = oracle_vs_gpu(fs, oracle, fa, kw, tmp_path)
+    assert c["align_wide"] > 0

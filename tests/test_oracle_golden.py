@@ -59,6 +59,18 @@ def test_kswat_st(oracle, kat):
     for c in kat["kswat_st"]:
         got = oracle.kswat_st(c["q"], c["s"], c["qst"], c["sst"])
         assert got[0] == c["out"][0] and list(got[1:]) == c["out"][1:], (c, got)
+    # at the edges of the GPU aligners (band, 16-bit packed range, 4096-residue tiles, ties, raw FASTA bytes): the maximum itself and the
+    # band cells too -- the bit score alone maps ~2.6 consecutive maxima to one value.  Windows are prefixes of the file's sequences.
+    e = json.load(open(os.path.join(GOLD, "kswat_edges.json")))
+    seqs, pairs = e["seqs"], [dict(zip(e["fields"], p)) for p in e["pairs"]]
+    assert len(pairs) >= 150
+    for c in pairs:
+        q, s = seqs[c["q"]][:c["qlen"]], seqs[c["s"]][:c["slen"]]
+        got = oracle.kswat_st(q, s, c["qst"], c["sst"], full=True)
+        want = [c[f] for f in ("idy", "aln", "mis", "gap", "out_qst", "out_qed", "out_sst", "out_sed", "bit", "cells", "maxscore")]
+        assert list(got) == want, (q[:40], s[:40], c["qst"], c["sst"], got, want)
+    assert {8169, 8171} <= {c["maxscore"] for c in pairs}
+    assert {4095, 4096} <= {min(c["qlen"], c["slen"]) for c in pairs}
 
 
 def test_scalar_formulas(oracle, kat):

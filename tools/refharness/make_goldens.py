@@ -315,11 +315,124 @@ def kats(m):
     print("kat.json written")
 
 
+# every residue byte a FASTA line can carry besides the 20 amino acids: lower case, stop, gap, dot, digits, ambiguity and rare letters
+ODD_BYTES = "acdwy*-.0123456789BZJUOXx"
+
+
+def kswat_edges(m):
+    """kswat_st at the edges of the GPU aligners (band, tiles, 16-bit packed range): the reference's tuple, the maximum of the score
+    matrix over THIS call's band cells (the matrices are reused between calls) and the number of those cells."""
+    rng = np.random.default_rng(11)
+    aa = "ACDEFGHIKLMNPQRSTVWY"
+
+    def rnd(n, alpha=aa):
+        return "".join(alpha[i] for i in rng.integers(0, len(alpha), n))
+
+    def mut(a, rate=0.15, alpha=aa):
+        b = list(a)
+        for _ in range(int(rng.binomial(len(a), rate))):
+            p = int(rng.integers(0, len(b) + 1))
+            r = rng.random()
+            if r < 0.6 and p < len(b):
+                b[p] = alpha[int(rng.integers(0, len(alpha)))]
+            elif r < 0.8 and len(b) > 1:
+                del b[p:p + int(rng.integers(1, 4))]
+            else:
+                b[p:p] = list(rnd(int(rng.integers(1, 4)), alpha))
+        return "".join(b) or a[:1]
+
+    def sized(a, n):   # a related sequence of exactly n residues
+        b = mut(a)
+        return (b + rnd(n))[:n]
+
+    pairs = []
+    for la in (1, 2, 15, 16, 17, 31, 32, 33):
+        a = rnd(la)
+        for lb in (la, la + 1, la - 1, la + 16, la + 17, 3 * la + 40):
+            if lb < 1:
+                continue
+            pairs.append((a, sized(a, lb), 0, 0))
+            pairs.append((sized(a, lb), a, 0, 0))
+        pairs.append((a, rnd(la + 5), 0, 0))
+    # starts 0, len - 1, len (the reference is undefined on an empty alignment: such pairs are dropped below), equal windows, far longer
+    for la, lb in ((40, 40), (40, 35), (33, 50), (60, 200), (200, 60), (17, 17)):
+        a = rnd(la)
+        b = sized(a, lb)
+        for qst, sst in ((0, 0), (la - 1, 0), (0, lb - 1), (la - 1, lb - 1), (la, 0), (0, lb), (5, 0), (0, 5), (la - lb, 0) if la > lb else (0, lb - la)):
+            pairs.append((a, b, qst, sst))
+    # ties: homopolymers, period-2 and period-3 repeats (trace priority against the gap-extend cost)
+    for a, b in (("A" * 20, "A" * 20), ("A" * 20, "A" * 27), ("W" * 9, "W" * 40), ("AG" * 15, "GA" * 15), ("AG" * 15, "AG" * 12 + "A"),
+                 ("ACD" * 12, "CDA" * 12), ("ACD" * 12, "ACD" * 5 + "AC" + "ACD" * 6), ("AAAAGAAAA" * 3, "AAAAAAAA" * 3), ("KR" * 30, "KKRR" * 15),
+                 ("LLLLLLLLLLILLLLLLLLL", "LLLLLLLLLLLLLLLLLLLL"), ("P" * 5 + "A" * 30 + "P" * 5, "A" * 33), ("GGGGG", "G" * 60)):
+        pairs.append((a, b, 0, 0))
+        pairs.append((b, a, 0, 0))
+    # raw bytes of FASTA lines
+    for _ in range(6):
+        a = rnd(int(rng.integers(20, 80)), aa + ODD_BYTES)
+        pairs.append((a, mut(a, 0.2, aa + ODD_BYTES), 0, 0))
+    pairs.append((ODD_BYTES * 3, ODD_BYTES * 3, 0, 0))
+    pairs.append((aa + ODD_BYTES, ODD_BYTES + aa, 0, 0))
+    # W-rich pairs at the packed aligners' length limit (11 * min(rows, columns) <= 8179 <=> min <= 740): prefixes of one pair
+    w = "".join("W" if rng.random() < 0.8 else aa[int(rng.integers(0, 20))] for _ in range(742))
+    w2 = sized(w, 743)
+    for n in (739, 740, 741, 742):
+        pairs.append((w[:n], w[:n], 0, 0))
+        pairs.append((w[:n], w2[:n + 1], 0, 0))
+    pairs.append(("W" * 742 + "P", "W" * 742 + "P", 0, 0))
+    pairs.append(("W" * 742 + "C", "W" * 742 + "C", 0, 0))
+    # windows of 4095 and 4096 residues (a kswat_st_long tile)
+    a = rnd(4096)
+    b = sized(a, 4096)
+    pairs.append((a[:4095], b[:4095], 0, 0))
+    pairs.append((a, b, 0, 0))
+    pairs.append((a, a, 0, 0))
+
+    sm = [[0] * 4100 for _ in range(4100)]
+    tm = [["*"] * 4100 for _ in range(4100)]
+    out = []
+    for q, s, qst, sst in pairs:
+        try:
+            r = m.kswat_st(q, s, qst=qst, sst=sst, score=sm, trace=tm, al0=[], al1=[])
+        except ZeroDivisionError:   # empty alignment: idy *= 100. / 0 (no answer)
+            continue
+        # this call's band (kswat_st's swap and loops)
+        a0, b0 = min(max(qst, 0), len(q)), min(max(sst, 0), len(s))
+        la, lb = len(q) - a0, len(s) - b0
+        l0, l1 = (la + 1, lb + 1) if la < lb else (lb + 1, la + 1)
+        best, cells = 0, 0
+        for i in range(1, l1):
+            row = sm[i][max(1, i - 16):min(i + 16, l0)]
+            cells += len(row)
+            best = max([best] + row)
+        out.append((q, s, qst, sst, [r[0]] + [int(x) for x in r[1:]], best, cells))
+    # the sequences once (a window is a prefix of one of them): [sequence, length] per side
+    seqs = []
+    for x in sorted({x for p in out for x in p[:2]}, key=len, reverse=True):
+        if not any(y.startswith(x) for y in seqs):
+            seqs.append(x)
+
+    def ref(x):
+        return [next(i for i, y in enumerate(seqs) if y.startswith(x)), len(x)]
+
+    fields = ["q", "qlen", "s", "slen", "qst", "sst", "idy", "aln", "mis", "gap", "out_qst", "out_qed", "out_sst", "out_sed", "bit", "maxscore",
+              "cells"]
+    return {"fields": fields, "seqs": seqs, "pairs": [ref(q) + ref(s) + [qst, sst] + o + [best, cells] for q, s, qst, sst, o, best, cells in out]}
+
+
+def write_kswat_edges(m):
+    """kswat_edges.json: kswat_st at the aligners' edges (kept apart from kat.json, whose bytes stay as they are)"""
+    path = os.path.join(GOLD, "kswat_edges.json")
+    if FORCE or not os.path.isfile(path):
+        json.dump(kswat_edges(m), open(path, "w"), separators=(",", ":"))
+        print("kswat_edges.json written")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     m = refload.load()
     if FORCE or not os.path.isfile(os.path.join(GOLD, "kat.json")):
         kats(m)
+    write_kswat_edges(m)
     rng = np.random.default_rng(1)
     base = ["-e", "1e-5", "-v", "500", "-j", "1", "-F", "T"]
     run_e2e(m, "toy_default", synthprot.synthprot(99, 150, 21), base + ["-s", "111111", "-r", AA9, "-M", "1000003", "-c", "50000"])
