@@ -147,6 +147,16 @@ int so_search(so_ctx *ctx, const char *qry_fasta_path, int64_t q_lo, int64_t q_h
  * search; so_destroy() drops it, SOHIT_HIT_CACHE=0 disables it. */
 void so_free_hits(so_hit *hits);
 
+/* The search with the alignment behind every row.  Same rows as so_search_loaded() (same kernels and bytes); in addition
+ * *aln holds 2 * sum(hits[k].aln) bytes (*aln_bytes): row k's query string starts at byte 2 * sum_{m<k} hits[m].aln and
+ * is hits[k].aln bytes long, its subject string follows it.  The strings are kswat_st's al0 / al1 (fsearch.py:1417-1444,
+ * 3066-3070: al0 is the query side): the residues qst..qed of the query as the aligner saw it (SEG-masked when filtering is
+ * on, as fsearch.py:2963 hands it over) and sst..sed of the subject, in order, with '-' in every column where the other
+ * side advances alone.  A row of a 4096-wide tile (kswat_st_long, fsearch.py:1480-1498) carries its tile's strings.
+ * The row statistics follow from the strings as in fsearch.py:1454-1471.  Released with so_free_aln(). */
+int so_search_loaded_aln(so_ctx *ctx, int64_t q_lo, int64_t q_hi, so_hit **hits, int64_t *n_hits, char **aln, int64_t *aln_bytes);
+void so_free_aln(char *aln);
+
 /* Multi-GPU support.  The reference runs one fsearch-c process per query block and joins the part files with `cat`
  * (find_hit.py:107-146); here one process per GPU searches a query shard and the hit records are exchanged over RCCL, so
  * they must be able to stay in HBM until after the exchange:

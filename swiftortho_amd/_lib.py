@@ -39,7 +39,7 @@ class SoCounters(C.Structure):
 # every symbol include/sohit.h declares
 EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_last_error", "so_load_ref", "so_load_ref_mem", "so_build_index", "so_drop_index", "so_load_index",
            "so_load_queries", "so_load_queries_mem", "so_num_queries", "so_num_refs", "so_query_len", "so_search_loaded",
-           "so_search", "so_free_hits", "so_write_sc", "so_format_hit", "so_get_counters", "so_reset_counters", "so_timing_report",
+           "so_search", "so_free_hits", "so_search_loaded_aln", "so_free_aln", "so_write_sc", "so_format_hit", "so_get_counters", "so_reset_counters", "so_timing_report",
            "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_align_pairs", "so_set_profile",
            "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows"]
@@ -109,6 +109,8 @@ def load():
     L.so_search_loaded.argtypes = [vp, i64, i64, C.POINTER(C.POINTER(SoHit)), C.POINTER(i64)]
     L.so_search.argtypes = [vp, cp, i64, i64, C.POINTER(C.POINTER(SoHit)), C.POINTER(i64)]
     L.so_free_hits.argtypes = [C.POINTER(SoHit)]
+    L.so_search_loaded_aln.argtypes = [vp, i64, i64, C.POINTER(C.POINTER(SoHit)), C.POINTER(i64), C.POINTER(C.c_void_p), C.POINTER(i64)]
+    L.so_free_aln.argtypes = [vp]
     L.so_search_device.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.so_device_hits_copy.argtypes = [vp, vp, i64]
     L.so_query_work.argtypes = [vp, i64, i64, vp]

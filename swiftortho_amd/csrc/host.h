@@ -242,11 +242,17 @@ struct so_ctx {
     bool q_present[256];               // bytes that can occur in (masked) query residues
     void* pinned = nullptr;            // pinned host staging for result rows
     size_t pinned_cap = 0;
+    // alignments of the reported rows (so_search_loaded_aln): the walks' compacted columns + the batch's query residues, staged pinned
+    bool want_aln = false;
+    void* pinned_aln = nullptr;
+    size_t pinned_aln_cap = 0;
+    hipEvent_t ev_aln = nullptr;
     // host-side row emission of batch k runs on a worker thread while the GPU processes batch k + 1
     struct EmitJob {
         std::thread th;
         bool active = false;
         size_t base = 0, n = 0;
+        bool aln = false;   // the job appends the rows' strings to the result's AlnBytes
         std::atomic<i64> dropped{0};
         std::exception_ptr err;
     } emit;
@@ -391,6 +397,8 @@ struct Batch {
     DevBuf<u32> trace;
     DevBuf<u32> tr_units, tr_ofs;   // trace room per task of a launch list and its exclusive scan (k_trace_units)
     DevBuf<u32> tl_sorted, al_sorted;   // the trace pass's lists ordered by band rows (mixed-length batches)
+    // (alignments asked for) column slots per reported row and their offsets per task, the walks' columns, compacted in row order
+    DevBuf<u32> aunits, arofs, aofs, acode, awords, acofs, acomp;
 };
 
 // length classes of the queries: < 512 residues, < 1024, < 2048, < 4096, longer (the aligner's tiled path).  A pass's key widths and
@@ -492,9 +500,31 @@ extern HitCache g_hit_cache;
 
 
 // growable result array handed to the caller as-is: no zero-fill, no final copy
+// the rows' aligned strings (so_search_loaded_aln): row k's query string at 2 * sum_{m<k} aln_m, its subject string behind it
+struct AlnBytes {
+    char* p = nullptr;
+    size_t n = 0, cap = 0;
+    void grow(size_t extra) {
+        if (n + extra <= cap) return;
+        const size_t nc = std::max<size_t>(n + extra, cap + cap / 2 + 4096);
+        char* np_ = (char*)realloc(p, nc);
+        if (!np_) throw SoError("out of host memory for the alignment strings");
+        p = np_;
+        cap = nc;
+    }
+    char* release() {
+        char* r = p ? p : (char*)malloc(1);
+        p = nullptr;
+        n = cap = 0;
+        return r;
+    }
+    ~AlnBytes() { free(p); }
+};
+
 struct HitBuf {
     so_hit* p = nullptr;
     size_t n = 0, cap = 0;
+    AlnBytes aln;   // filled only when the search is asked for alignments
     void grow(size_t extra) {
         if (n + extra <= cap) return;
         if (!p) p = g_hit_cache.take(cap);  // the previous search's array, pages still mapped

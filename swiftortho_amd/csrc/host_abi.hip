@@ -160,6 +160,7 @@ so_ctx* so_create(int device, const so_params* params) {
         HIP_CHECK(hipStreamCreateWithFlags(&c->st_rows, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&c->ev_rows_done, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&c->ev_aln, hipEventDisableTiming));
         for (auto& e : c->ev_part) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_CHECK(hipStreamCreateWithFlags(&c->st_side, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreateWithFlags(&c->ev_side_go, hipEventDisableTiming));
@@ -186,12 +187,14 @@ void so_destroy(so_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     if (c->pinned) (void)hipHostFree(c->pinned);
+    if (c->pinned_aln) (void)hipHostFree(c->pinned_aln);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->h_qhits) (void)hipHostFree(c->h_qhits);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
     if (c->ev_rows_done) (void)hipEventDestroy(c->ev_rows_done);
+    if (c->ev_aln) (void)hipEventDestroy(c->ev_aln);
     for (auto& e : c->ev_part)
         if (e) (void)hipEventDestroy(e);
     if (c->st_rows) (void)hipStreamDestroy(c->st_rows);
@@ -285,6 +288,30 @@ int so_search_loaded(so_ctx* c, int64_t q_lo, int64_t q_hi, so_hit** hits, int64
         *hits = out.release();
     });
 }
+
+int so_search_loaded_aln(so_ctx* c, int64_t q_lo, int64_t q_hi, so_hit** hits, int64_t* n_hits, char** aln, int64_t* aln_bytes) {
+    return guarded(c, [&] {
+        if (!hits || !n_hits || !aln || !aln_bytes) throw SoError("so_search_loaded_aln: output pointers are NULL");
+        *hits = nullptr, *aln = nullptr;
+        *n_hits = 0, *aln_bytes = 0;
+        HitBuf out;
+        struct Off {   // the switch is per call
+            so_ctx* c;
+            ~Off() { c->want_aln = false; }
+        } off{c};
+        c->want_aln = true;
+        search_loaded(c, q_lo, q_hi, out);
+        i64 total = 0;
+        for (size_t k = 0; k < out.n; ++k) total += 2 * (i64)std::max(0, out.p[k].aln);
+        if ((size_t)total != out.aln.n) throw SoError("so_search_loaded_aln: the strings do not match the rows");
+        *aln_bytes = total;
+        *aln = out.aln.release();
+        *n_hits = (int64_t)out.n;
+        *hits = out.release();
+    });
+}
+
+void so_free_aln(char* aln) { free(aln); }
 
 int so_search(so_ctx* c, const char* qry_path, int64_t q_lo, int64_t q_hi, so_hit** hits, int64_t* n_hits) {
     int rc = so_load_queries(c, qry_path);

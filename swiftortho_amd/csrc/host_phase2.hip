@@ -17,9 +17,22 @@ void emit_join(so_ctx* c, HitBuf& out) {
         // doubles, so this never fires; kept as the reference has it.
         const double expect = c->expect;
         size_t wpos = c->emit.base;
-        for (size_t k = c->emit.base; k < c->emit.base + c->emit.n; ++k)
-            if (out.p[k].evalue <= expect) out.p[wpos++] = out.p[k];
+        // (alignments) the batch's strings are the last bytes of out.aln, row after row: they are moved along with their rows
+        size_t bytes = 0;
+        if (c->emit.aln)
+            for (size_t k = c->emit.base; k < c->emit.base + c->emit.n; ++k) bytes += 2 * (size_t)std::max(0, out.p[k].aln);
+        size_t rpos = out.aln.n - std::min(bytes, out.aln.n), apos = rpos;
+        for (size_t k = c->emit.base; k < c->emit.base + c->emit.n; ++k) {
+            const size_t nb = c->emit.aln ? 2 * (size_t)std::max(0, out.p[k].aln) : 0;
+            if (out.p[k].evalue <= expect) {
+                if (nb && apos != rpos) memmove(out.aln.p + apos, out.aln.p + rpos, nb);
+                apos += nb;
+                out.p[wpos++] = out.p[k];
+            }
+            rpos += nb;
+        }
         out.n = wpos;
+        if (c->emit.aln) out.aln.n = apos;
     }
 }
 
@@ -316,6 +329,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
         for (int p = 0; p <= EMIT_PARTS; ++p) part_row[p] = (u64)p * qstep < nq ? v[4 + p] : NO;
     }
     sc.lap("phase2.stop");
+    const bool aln_on = c->want_aln && !c->dev_out;
     if (NO) {
         // second aligner pass, with traces + traceback, over the rows that are reported (a few percent of the alignments)
         const int parts = (c->dev_out || NO < emit_min_rows) ? 1 : EMIT_PARTS;
@@ -342,6 +356,21 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
             }
         }
         const u32* slist = b.sel_idx.p;  // (ordering this pass by rows too costs more than it saves: 9.1 -> 9.9 ms on config 3)
+        // Alignments asked for (so_search_loaded_aln): every reported row gets a slot for the columns its walk can take, in row order, and
+        // the walks of this pass write them there (k_traceback<true>); the slots' offsets go to the walks per task, whatever list walks it.
+        u32* acode = nullptr;
+        const u32* aofs = nullptr;
+        if (aln_on) {
+            b.aunits.ensure((size_t)NO + 4), b.arofs.ensure((size_t)NO + 4), b.aofs.ensure((size_t)NT + 4);
+            c->d_scan_tmp.ensure(scan_u32_temp_elems((size_t)NO + 1) + 8);
+            // (a row takes at most 129 units: the 32-bit offsets -- and the word offsets of the compacted columns -- hold 8 M rows per batch)
+            if ((u64)NO * 129u >= (1ull << 30)) throw SoError("alignments: more than 8 M reported rows in one batch; search a smaller query range per call");
+            launch_aln_units(b.tasks.p, slist, NO, b.dev.d_off.p, c->ref.d_off.p, b.aunits.p, c->st);
+            const size_t units = d2h_u32(c, scan_u32(b.aunits.p, b.arofs.p, (size_t)NO + 1, false, c->d_scan_tmp.p, c->st));
+            b.acode.ensure(units * aln_unit_words() + 64);
+            launch_aln_scatter(slist, NO, b.arofs.p, b.aofs.p, c->st);
+            acode = b.acode.p, aofs = b.aofs.p;
+        }
         // Kept traces: rows that have one only need the walk, the others are aligned with traces now.  The row list is split stably
         // (flags, scan, scatter); range p's rows without a trace are list B's [pb[p], pb[p + 1]), the others list A's
         // [first row - pb[p], ...): the scan values at the ranges' first rows come back in one small copy.
@@ -425,7 +454,8 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                                 b.trace.p, TU, b.tr_ofs.p, b.ares.p, nullptr, 0u, c->st, 0u, pkc);
             // ... and walked at once, while their traces are in the L2 (walked range by range, the second range's came back from the Infinity
             // Cache behind the first range's 0.9 GB of kept traces: 0.94 instead of 0.27 ms)
-            launch_traceback_tofs(b.tasks.p, tlist, tn, b.dev.d_res.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_off.p, b.trace.p, TU, b.tr_ofs.p, b.ares.p, c->st);
+            launch_traceback_tofs(b.tasks.p, tlist, tn, b.dev.d_res.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_off.p, b.trace.p, TU, b.tr_ofs.p, b.ares.p, c->st,
+                                  acode, aofs);
             pt.stop();
         }
         auto align_traced = [&](u32 t0, u32 t1, int p) {   // tasks [t0, t1) of tlist = emission range p's
@@ -435,14 +465,14 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
             const u32 nw = !traced_pk ? t1 - t0 : (order_rows ? std::min(nwide_part[p], t1 - t0) : (pk_mixed ? t1 - t0 : 0u));
             if (tvar) {
                 launch_align(b.tasks.p, tlist + t0, t1 - t0, b.dev.d_res.p, b.dev.d_scls.p, b.dev.d_scls4.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_scls.p,
-                             c->ref.d_scls4.p, c->ref.d_off.p, c->d_b62c.p, b.trace.p, TU, b.tr_ofs.p + t0, b.ares.p, true, c->st, nw, pkc);
+                             c->ref.d_scls4.p, c->ref.d_off.p, c->d_b62c.p, b.trace.p, TU, b.tr_ofs.p + t0, b.ares.p, true, c->st, nw, pkc, acode, aofs);
                 return;
             }
             for (u32 t = t0; t < t1; t += slab) {
                 const u32 n = std::min(slab, t1 - t);
                 launch_align(b.tasks.p, tlist + t, n, b.dev.d_res.p, b.dev.d_scls.p, b.dev.d_scls4.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_scls.p,
                              c->ref.d_scls4.p, c->ref.d_off.p, c->d_b62c.p, b.trace.p, stride, nullptr, b.ares.p, true, c->st,
-                             std::min(n, nw > t - t0 ? nw - (t - t0) : 0u), pkc);
+                             std::min(n, nw > t - t0 ? nw - (t - t0) : 0u), pkc, acode, aofs);
             }
         };
         for (int p = 0; p < parts; ++p) {
@@ -453,7 +483,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                 ProfTimer pt(c, &c->cnt.align_ms, &c->cnt.align_launches);
                 align_traced(b0, b1, p);
                 launch_traceback(b.tasks.p, alist + a0, a1 - a0, b.dev.d_res.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_off.p, b.spec_trace.p, TU,
-                                 b.tpos.p, b.ares.p, c->st);
+                                 b.tpos.p, b.ares.p, c->st, acode, aofs);
                 pt.stop();
             } else if (r1 > r0) {
                 ProfTimer pt(c, &c->cnt.align_ms, &c->cnt.align_launches);
@@ -470,6 +500,25 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                 HIP_CHECK(hipEventRecord(c->ev_part[p], c->st_rows));
             }
             part_lo[p] = r0, part_hi[p] = r1;
+        }
+        // the rows' columns compacted in row order and sent to the host with the batch's query residues (as the walks read them: masked)
+        size_t aln_words = 0;
+        if (aln_on) {
+            b.awords.ensure((size_t)NO + 4), b.acofs.ensure((size_t)NO + 4);
+            launch_aln_words(slist, NO, b.ares.p, b.awords.p, c->st);
+            aln_words = d2h_u32(c, scan_u32(b.awords.p, b.acofs.p, (size_t)NO + 1, false, c->d_scan_tmp.p, c->st));
+            b.acomp.ensure(aln_words + 64);
+            launch_aln_compact(slist, NO, b.aofs.p, b.acode.p, b.acofs.p, b.acomp.p, c->st);
+            const size_t qbytes = b.h_off[nq], need = aln_words * 4 + qbytes + 64;
+            if (c->pinned_aln_cap < need) {   // (the previous batch's worker, which reads it, was joined above)
+                if (c->pinned_aln) (void)hipHostFree(c->pinned_aln);
+                c->pinned_aln = nullptr, c->pinned_aln_cap = 0;
+                HIP_CHECK(hipHostMalloc(&c->pinned_aln, need * 5 / 4 + 4096, hipHostMallocDefault));
+                c->pinned_aln_cap = need * 5 / 4 + 4096;
+            }
+            if (aln_words) HIP_CHECK(hipMemcpyAsync(c->pinned_aln, b.acomp.p, aln_words * 4, hipMemcpyDeviceToHost, c->st));
+            if (qbytes) HIP_CHECK(hipMemcpyAsync((char*)c->pinned_aln + aln_words * 4, b.dev.d_res.p, qbytes, hipMemcpyDeviceToHost, c->st));
+            HIP_CHECK(hipEventRecord(c->ev_aln, c->st));
         }
         sc.lap("phase2.trace_pass");
         {   // SOHIT_TEST_OOM_PHASE2=1 (tests): the first multi-query batch of the process fails here, as a device allocation of the
@@ -541,7 +590,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
             place = std::make_shared<std::vector<std::pair<u32, i64>>>(nq);
             for (u32 s = 0; s < nq; ++s) (*place)[s] = {b.qid[s], (i64)ocnt[b.qid[s]] - (i64)ooff[s]};
         }
-        c->emit.base = base, c->emit.n = NO;
+        c->emit.base = base, c->emit.n = NO, c->emit.aln = aln_on;
         c->emit.dropped.store(0);
         c->emit.active = true;
         // The worker converts range p's rows as soon as they have arrived, while the GPU traces range p + 1: behind the last copy only
@@ -550,7 +599,11 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
         struct PartSpan { u32 lo, hi; };
         std::array<PartSpan, EMIT_PARTS_MAX> spans{};
         for (int p = 0; p < parts; ++p) spans[(size_t)p] = {part_lo[p], part_hi[p]};
-        c->emit.th = std::thread([c, rows, dst, NO, D, expect, q_lo, p2p, place, spans, parts] {
+        // (alignments) the strings are rebuilt behind the rows: the batch's query offsets travel with the job (the next batch overwrites b.h_off)
+        std::shared_ptr<std::vector<u32>> aln_qoff;
+        if (aln_on) aln_qoff = std::make_shared<std::vector<u32>>(b.h_off.begin(), b.h_off.begin() + nq + 1);
+        AlnBytes* abuf = &out.aln;
+        c->emit.th = std::thread([c, rows, dst, NO, D, expect, q_lo, p2p, place, spans, parts, aln_qoff, abuf, aln_words] {
             try {
                 HIP_CHECK(hipSetDevice(c->device));
                 auto convert = [&](i64 i) {
@@ -605,6 +658,60 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                 worker();
                 for (auto& t : th) t.join();
                 if (werr) std::rethrow_exception(werr);
+                if (aln_qoff) {
+                    // row k of the result (file order) takes 2 aln_k bytes at the running sum; row i of the download has its columns at the
+                    // running sum of ceil(aln / 16) words in download order, in walk order (last column first)
+                    HIP_CHECK(hipEventSynchronize(c->ev_aln));
+                    const u32* codes = (const u32*)c->pinned_aln;
+                    const u8* qres = (const u8*)c->pinned_aln + aln_words * 4;
+                    std::vector<i64> boff((size_t)NO + 1), woff((size_t)NO + 1);
+                    boff[0] = 0, woff[0] = 0;
+                    for (i64 k = 0; k < (i64)NO; ++k) boff[k + 1] = boff[k] + 2 * (i64)std::max(0, dst[k].aln);
+                    for (i64 i = 0; i < (i64)NO; ++i) woff[i + 1] = woff[i] + (std::max(0, rows[i].v[2]) + 15) / 16;
+                    if ((size_t)woff[NO] != aln_words) throw SoError("alignments: column words do not add up");
+                    const size_t a0 = abuf->n;
+                    abuf->grow((size_t)boff[NO]);
+                    char* ab = abuf->p + a0;
+                    const u8* rres = c->ref.res.data();
+                    const std::vector<u32>& roff = c->ref.off;
+                    const std::vector<u32>& qoff = *aln_qoff;
+                    auto build = [&](i64 i) {
+                        const int* v = rows[i].v;
+                        const i64 di = place ? i + (*place)[(size_t)v[0]].second : i;
+                        const int AL = std::max(0, v[2]);
+                        if (!AL) return;
+                        char* sq = ab + boff[di];
+                        char* ss = sq + AL;
+                        const u8* qp = qres + qoff[(size_t)v[0]] + (v[5] - 1);
+                        const u8* sp = rres + roff[(size_t)v[1]] + (v[7] - 1);
+                        const u32* w = codes + woff[i];
+                        for (int f = 0; f < AL; ++f) {
+                            const int cc = AL - 1 - f;
+                            const u32 code = (w[cc >> 4] >> ((cc & 15) << 1)) & 3u;
+                            sq[f] = code != 2 ? (char)*qp++ : '-';
+                            ss[f] = code != 3 ? (char)*sp++ : '-';
+                        }
+                    };
+                    std::atomic<i64> nx{0};
+                    auto bworker = [&] {
+                        try {
+                            for (;;) {
+                                const i64 b0 = nx.fetch_add(4096);
+                                if (b0 >= (i64)NO) break;
+                                for (i64 i = b0; i < std::min<i64>(NO, b0 + 4096); ++i) build(i);
+                            }
+                        } catch (...) {
+                            std::lock_guard<std::mutex> g(wmu);
+                            werr = std::current_exception();
+                        }
+                    };
+                    th.clear();
+                    for (unsigned t = 1; t < nt; ++t) th.emplace_back(bworker);
+                    bworker();
+                    for (auto& t : th) t.join();
+                    if (werr) std::rethrow_exception(werr);
+                    abuf->n = a0 + (size_t)boff[NO];
+                }
             } catch (...) {
                 c->emit.err = std::current_exception();
             }

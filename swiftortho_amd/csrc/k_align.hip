@@ -254,6 +254,8 @@ __global__ __launch_bounds__(256) void k_align(const AlnTask* __restrict__ tasks
 // One thread per alignment; the 2-bit traces come from the slab k_align wrote in the same launch
 // sequence (kernel boundary = visibility), with the current trace word cached in a register.
 //
+#define ALN_UNIT 4   // words per unit of the walks' column slots (aofs): 32-bit offsets reach 64 GiB
+
 // LONG walks (wave mode, round 5).  A thread's walk is a chain of dependent steps -- ~0.4 us each once the wave is alone on its SIMD --
 // so a launch lasted as long as its longest walk: 1.6 ms for the 4096 columns of a giant's self-alignment, whatever else it held
 // (log-normal set: 4 launches, 7.2 ms per step).  The first `nw` blocks of the launch therefore take the first nw list positions
@@ -262,24 +264,34 @@ __global__ __launch_bounds__(256) void k_align(const AlnTask* __restrict__ tasks
 // diagonal columns -- code 1, no '-' residue -- is added in one go (columns, matches by popcount; behind a non-gap column the gap
 // machine's three counters are all f(-1)), and the column that ends the run takes the single step of the thread walk, served from the
 // lane that looked at it.  The other blocks walk 64 alignments each as before and skip what a wave took.
-template <bool WAVE>
+//
+// EMIT (alignments asked for): the walk also writes its columns, 2 bits each in walk order (from the maximum's cell back to the start):
+// 1 diagonal, 2 subject alone ('-' in the query string), 3 query alone -- the trace codes the walk follows, with '-' and '|' exchanged
+// when the query is on the columns (no swap).  Column c of the walk is
+// bits 2 (c % 16) of word c / 16 of the task's slot, which starts at word ALN_UNIT * aofs[slot] of `acode` (k_aln_units: room for the
+// la + lb columns a walk can take at most).  The thread walk gathers the columns of its rounds in a 64-bit register and stores one
+// 32-bit word per sixteen columns; the wave walk's columns are wave-uniform and lane 0 stores them.
+template <bool WAVE, bool EMIT>
 __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __restrict__ tasks, const u32* __restrict__ ridx,
                                               const u8* __restrict__ q_res, const u32* __restrict__ qoff, const u8* __restrict__ r_res,
                                               const u32* __restrict__ roff, const u32* __restrict__ trace, u32 trace_stride,
-                                              const u32* __restrict__ tpos, const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows);
+                                              const u32* __restrict__ tpos, const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows,
+                                              u32* __restrict__ acode, const u32* __restrict__ aofs);
 
+template <bool EMIT>
 __global__ __launch_bounds__(64) void k_traceback(const AlnTask* __restrict__ tasks, const u32* __restrict__ ridx, u32 ntasks,
                                                   const u8* __restrict__ q_res, const u32* __restrict__ qoff,
                                                   const u8* __restrict__ r_res, const u32* __restrict__ roff,
                                                   const u32* __restrict__ trace, u32 trace_stride, const u32* __restrict__ tpos,
-                                                  const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows) {
+                                                  const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows,
+                                                  u32* __restrict__ acode, const u32* __restrict__ aofs) {
     if (blockIdx.x < nw) {
-        traceback_one<true>(blockIdx.x, tasks, ridx, q_res, qoff, r_res, roff, trace, trace_stride, tpos, tofs, out, nw, wrows);
+        traceback_one<true, EMIT>(blockIdx.x, tasks, ridx, q_res, qoff, r_res, roff, trace, trace_stride, tpos, tofs, out, nw, wrows, acode, aofs);
         return;
     }
     const u32 tid = (blockIdx.x - nw) * 64u + threadIdx.x;
     if (tid >= ntasks) return;
-    traceback_one<false>(tid, tasks, ridx, q_res, qoff, r_res, roff, trace, trace_stride, tpos, tofs, out, nw, wrows);
+    traceback_one<false, EMIT>(tid, tasks, ridx, q_res, qoff, r_res, roff, trace, trace_stride, tpos, tofs, out, nw, wrows, acode, aofs);
 }
 
 __device__ __forceinline__ uint4 u1_load16g(const u8* p) {   // unaligned 16-byte global load
@@ -288,11 +300,12 @@ __device__ __forceinline__ uint4 u1_load16g(const u8* p) {   // unaligned 16-byt
     return v;
 }
 
-template <bool WAVE>
+template <bool WAVE, bool EMIT>
 __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __restrict__ tasks, const u32* __restrict__ ridx,
                                               const u8* __restrict__ q_res, const u32* __restrict__ qoff, const u8* __restrict__ r_res,
                                               const u32* __restrict__ roff, const u32* __restrict__ trace, u32 trace_stride,
-                                              const u32* __restrict__ tpos, const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows) {
+                                              const u32* __restrict__ tpos, const u32* __restrict__ tofs, AlnRes* __restrict__ out, u32 nw, int wrows,
+                                              u32* __restrict__ acode, const u32* __restrict__ aofs) {
     const u32 slot = ridx ? ridx[tid] : tid;
     const AlnTask tk = tasks[slot];
     const u32 qb = qoff[tk.q], sb = roff[tk.subj];
@@ -311,9 +324,23 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
     const u32* tr = trace + (size_t)(tpos ? tpos[slot] : tofs ? tofs[tid] : tid) * trace_stride;
     const int bi = r.qst, bj = r.qed;
     const int tagged = r.pad & 1;   // traces written by k_align_pk<true>: 3 diagonal, 1 up (here: 1 diagonal, 3 up) -- swapped on reading
+    u32* ap = EMIT ? acode + (size_t)aofs[slot] * ALN_UNIT : nullptr;   // the walk's columns (EMIT)
     if (WAVE) {
         const int t = threadIdx.x;
         int i = bi, j = bj, AL = 0, matches = 0, fm1 = 0, f0 = 0, f1 = 0;
+        u32 eb = 0;   // (EMIT) the columns not stored yet, en of them -- wave-uniform
+        int en = 0;
+        auto put = [&](u32 code, int n) {   // n columns of one code
+            while (n > 0) {
+                const int k = min(n, 16 - en);
+                eb |= ((code * 0x55555555u) & (k == 16 ? ~0u : (1u << (2 * k)) - 1u)) << (2 * en);
+                en += k, n -= k;
+                if (en == 16) {
+                    if (t == 0) *ap = eb;
+                    ++ap, eb = 0, en = 0;
+                }
+            }
+        };
         while (i > 0 || j > 0) {
             const int d = j - i + KB;
             const bool inband = i > 0 && j > 0 && d >= 0;   // (wave-uniform)
@@ -335,6 +362,7 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
                     AL += run, matches += __builtin_popcountll(run < 64 ? eqm & ((1ull << run) - 1ull) : eqm);
                     f0 = fm1, f1 = fm1;
                     i -= run, j -= run;
+                    if (EMIT) put(1u, run);
                 }
                 if (run == 64) continue;
                 if (!(i > 0 || j > 0)) break;
@@ -347,6 +375,7 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
             else tc = __builtin_amdgcn_readlane(tcl, run);
             if (tc == 0) break;
             ++AL;
+            if (EMIT) put((u32)(swp || tc == 1 ? tc : 5 - tc), 1);
             const int a0 = tc != 3 ? __builtin_amdgcn_readlane(a0l, run) : (int)'-', a1 = tc != 2 ? __builtin_amdgcn_readlane(a1l, run) : (int)'-';
             matches += (a0 == a1) ? 1 : 0;
             const bool g0 = a0 == '-', g1 = a1 == '-';
@@ -355,6 +384,7 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
             if (tc != 3) --j;
             if (tc != 2) --i;
         }
+        if (EMIT && en && t == 0) *ap = eb;
         if (t == 0) {
             r.aln = AL, r.matches = matches, r.gap = fm1;
             if (swp) r.qst = i + qi, r.qed = bi + qi, r.sst = j + qj, r.sed = bj + qj;
@@ -394,6 +424,8 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
     uint4 gv = make_uint4(0, 0, 0, 0), ngv = make_uint4(0, 0, 0, 0);
     int cb = 0x40000000, rb = 0x40000000;   // residue positions cb .. cb + 15 / rb .. rb + 15 are held (none yet)
     uint4 cw = make_uint4(0, 0, 0, 0), rw = make_uint4(0, 0, 0, 0);
+    u64 eb = 0;   // (EMIT) the columns not stored yet, en < 16 of them behind every round
+    int en = 0;
     while (__ballot(run && (i > 0 || j > 0)) != 0ull) {
         {   // ---- checkpoint ----
             const int d = j - i + KB;
@@ -435,8 +467,11 @@ __device__ __forceinline__ void traceback_one(const u32 tid, const AlnTask* __re
             fm1 = go ? nm1 : fm1, f0 = go ? n0 : f0, f1 = go ? n1 : f1;
             j -= (go && tc != 3) ? 1 : 0;
             i -= (go && tc != 2) ? 1 : 0;
+            if (EMIT) eb |= go ? (u64)(swp || tc == 1 ? tc : 5 - tc) << (2 * en) : 0ull, en += go ? 1 : 0;
         }
+        if (EMIT && en >= 16) *ap++ = (u32)eb, eb >>= 32, en -= 16;   // at most 15 + 8 columns held: one word per round at most
     }
+    if (EMIT && en) *ap = (u32)eb;
     r.aln = AL, r.matches = matches, r.gap = fm1;
     if (swp) {  // rows = query, columns = subject (1473-1474)
         r.qst = i + qi, r.qed = bi + qi, r.sst = j + qj, r.sed = bj + qj;
@@ -485,7 +520,7 @@ static inline u32 traceback_waves(u32 ntasks) {
 // list positions that need the 32-bit cells; the rest is aligned by the packed kernel (ntasks: all of them by the 32-bit one)
 void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u8* q_scls, const u8* q_scls4, const u32* qoff,
                   const u8* r_res, const u8* r_scls, const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride,
-                  const u32* tofs, AlnRes* out, bool with_traceback, hipStream_t st, u32 n_wide, PkCls pk) {
+                  const u32* tofs, AlnRes* out, bool with_traceback, hipStream_t st, u32 n_wide, PkCls pk, u32* acode, const u32* aofs) {
     if (!ntasks) return;
     if (!with_traceback) {
         hipLaunchKernelGGL((k_align<false>), dim3((ntasks + 15) / 16), dim3(256), 0, st, tasks, ridx, ntasks, q_scls, q_scls4, qoff, r_scls, r_scls4,
@@ -494,8 +529,8 @@ void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q
     }
     launch_align_traced(tasks, ridx, ntasks, q_scls, q_scls4, qoff, r_scls, r_scls4, roff, b62g, trace, trace_stride, tofs, out, nullptr, 0u, st, n_wide, pk);
     const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(k_traceback, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff, r_res, roff, trace,
-                       trace_stride, (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows);
+    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
+                       r_res, roff, trace, trace_stride, (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows, acode, aofs);
 }
 
 void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_scls, const u8* q_scls4, const u32* qoff, const u8* r_scls,
@@ -511,17 +546,66 @@ void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, cons
 
 // the walks alone over list positions whose traces sit at tofs[position] (the alignments were made by an earlier launch_align_traced)
 void launch_traceback_tofs(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st) {
+                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs) {
     if (!ntasks) return;
     const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(k_traceback, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff, r_res, roff, trace, trace_stride,
-                       (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows);
+    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
+                       r_res, roff, trace, trace_stride, (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows, acode, aofs);
 }
 
 void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st) {
+                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs) {
     if (!ntasks) return;
     const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(k_traceback, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff, r_res, roff, trace, trace_stride, tpos,
-                       (const u32*)nullptr, out, nw, (int)tune().trace_wave_rows);
+    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
+                       r_res, roff, trace, trace_stride, tpos, (const u32*)nullptr, out, nw, (int)tune().trace_wave_rows, acode, aofs);
+}
+
+// ---- the reported rows' alignments (so_search_loaded_aln) ------------------------------------------------------------------------
+// Room per reported row (row order: sel_idx[r] = its task) for the columns its walk can take -- at most la + lb, every column lowers i, j
+// or both -- in units of ALN_UNIT words (+ a 0 behind the last); scanned, they are the rows' slot offsets, handed to the walks per task.
+__global__ __launch_bounds__(256) void k_aln_units(const AlnTask* __restrict__ tasks, const u32* __restrict__ sel_idx, u32 n, const u32* __restrict__ qoff,
+                                                   const u32* __restrict__ roff, u32* __restrict__ units) {
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    if (t > n) return;
+    if (t == n) {
+        units[t] = 0;
+        return;
+    }
+    const AlnTask tk = tasks[sel_idx[t]];
+    const int lq = min((int)(qoff[tk.q + 1] - qoff[tk.q]), (int)tk.qe), ls = min((int)(roff[tk.subj + 1] - roff[tk.subj]), (int)tk.se);
+    const int la = lq - min((int)tk.qi, lq), lb = ls - min((int)tk.qj, ls);
+    units[t] = (u32)((la + lb) / 16 + 1 + ALN_UNIT - 1) / ALN_UNIT;
+}
+__global__ __launch_bounds__(256) void k_aln_scatter(const u32* __restrict__ sel_idx, u32 n, const u32* __restrict__ rofs, u32* __restrict__ aofs) {
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    if (t < n) aofs[sel_idx[t]] = rofs[t];
+}
+// words each row's columns take once the walks are done (+ a 0 behind the last): scanned, the rows' places in the compacted codes
+__global__ __launch_bounds__(256) void k_aln_words(const u32* __restrict__ sel_idx, u32 n, const AlnRes* __restrict__ res, u32* __restrict__ words) {
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    if (t > n) return;
+    words[t] = t == n ? 0u : (u32)(res[sel_idx[t]].aln + 15) / 16u;
+}
+// the rows' columns moved from their slots to one run in row order: sixteen lanes per row
+__global__ __launch_bounds__(256) void k_aln_compact(const u32* __restrict__ sel_idx, u32 n, const u32* __restrict__ aofs, const u32* __restrict__ acode,
+                                                     const u32* __restrict__ cofs, u32* __restrict__ dst) {
+    const u32 r = blockIdx.x * 16u + (threadIdx.x >> 4);
+    if (r >= n) return;
+    const u32* src = acode + (size_t)aofs[sel_idx[r]] * ALN_UNIT;
+    const u32 o = cofs[r], nwd = cofs[r + 1] - o;
+    for (u32 k = threadIdx.x & 15u; k < nwd; k += 16u) dst[(size_t)o + k] = src[k];
+}
+u32 aln_unit_words() { return ALN_UNIT; }
+void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const u32* qoff, const u32* roff, u32* units, hipStream_t st) {
+    hipLaunchKernelGGL(k_aln_units, dim3((n + 1 + 255) / 256), dim3(256), 0, st, tasks, sel_idx, n, qoff, roff, units);
+}
+void launch_aln_scatter(const u32* sel_idx, u32 n, const u32* rofs, u32* aofs, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_aln_scatter, dim3((n + 255) / 256), dim3(256), 0, st, sel_idx, n, rofs, aofs);
+}
+void launch_aln_words(const u32* sel_idx, u32 n, const AlnRes* res, u32* words, hipStream_t st) {
+    hipLaunchKernelGGL(k_aln_words, dim3((n + 1 + 255) / 256), dim3(256), 0, st, sel_idx, n, res, words);
+}
+void launch_aln_compact(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const u32* cofs, u32* dst, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_aln_compact, dim3((n + 15) / 16), dim3(256), 0, st, sel_idx, n, aofs, acode, cofs, dst);
 }

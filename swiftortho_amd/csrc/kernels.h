@@ -177,7 +177,9 @@ void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q
                   const u8* r_res, const u8* r_scls, const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride,
                   const u32* tofs /*traces: start of launch position t's trace in units of trace_stride words, or null = t*/, AlnRes* out,
                   bool with_traceback, hipStream_t st, u32 n_wide /*with_traceback: leading positions for the 32-bit kernel, the rest packed*/,
-                  PkCls pk = PkCls{nullptr, nullptr, nullptr, nullptr});
+                  PkCls pk = PkCls{nullptr, nullptr, nullptr, nullptr},
+                  u32* acode = nullptr /*non-null: the walks write their columns (k_traceback<true>) to the slots aofs[task] gives*/,
+                  const u32* aofs = nullptr);
 // trace room each task of a launch list needs, in units of align_trace_unit() words (+ a 0 behind the last): scanned, they are `tofs`
 u32 align_trace_unit();
 void launch_trace_units(const AlnTask* tasks, const u32* ridx, u32 n, const u32* qoff, const u32* roff, u32* units /*n + 1*/, hipStream_t st);
@@ -272,9 +274,17 @@ void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, cons
 void launch_align_pk_traced(const AlnTask* tasks, const u32* ridx, u32 t0, u32 t1, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g,
                             u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, u32* tpos_out, u32 tpos_base, hipStream_t st);
 void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st);
+                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st, u32* acode = nullptr, const u32* aofs = nullptr);
 void launch_traceback_tofs(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st);
+                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st, u32* acode = nullptr,
+                           const u32* aofs = nullptr);
+// the reported rows' alignments (k_align.hip): column slots per row (units of aln_unit_words() words, + a 0 behind the last), handed to the
+// walks per task; then the words each row's columns took (+ a 0), and the columns compacted in row order at the scan of those
+u32 aln_unit_words();
+void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const u32* qoff, const u32* roff, u32* units /*n + 1*/, hipStream_t st);
+void launch_aln_scatter(const u32* sel_idx, u32 n, const u32* rofs, u32* aofs /*per task*/, hipStream_t st);
+void launch_aln_words(const u32* sel_idx, u32 n, const AlnRes* res, u32* words /*n + 1*/, hipStream_t st);
+void launch_aln_compact(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const u32* cofs /*n + 1*/, u32* dst, hipStream_t st);
 void launch_stop_round_w(const AlnTask* tasks, const AlnRes* res, const u32* qcoff, const u32* ntask, const u32* ntile, const u32* roffc,
                          const u32* rk_slot, const u32* toff, const u32* rcnt, u32 nq, const u32* qoff, const u32* roff, const int* bittab,
                          int bittab_n, i64 D, double expect, double max_miss, i64 v, u32* sel, u32* st_state, int* bits,

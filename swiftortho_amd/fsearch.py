@@ -105,12 +105,18 @@ class Searcher:
         return np.array([self.L.so_ref_len(self.h, i) for i in range(n)], dtype=np.int64)
 
     # search -----------------------------------------------------------------------------------
-    def search(self, st=-1, ed=-1):
-        """Queries [st, ed) of the loaded query file -> Hits (owning wrapper)."""
+    def search(self, st=-1, ed=-1, alignments=False):
+        """Queries [st, ed) of the loaded query file -> Hits (owning wrapper).  alignments=True: every row also carries its
+        aligned query and subject strings (Hits.alignment / Hits.alignment_buffer)."""
         hits = C.POINTER(_lib.SoHit)()
         n = C.c_int64(0)
-        self._chk(self.L.so_search_loaded(self.h, st, ed, C.byref(hits), C.byref(n)))
-        return Hits(self, hits, n.value)
+        if not alignments:
+            self._chk(self.L.so_search_loaded(self.h, st, ed, C.byref(hits), C.byref(n)))
+            return Hits(self, hits, n.value)
+        aln = C.c_void_p()
+        nb = C.c_int64(0)
+        self._chk(self.L.so_search_loaded_aln(self.h, st, ed, C.byref(hits), C.byref(n), C.byref(aln), C.byref(nb)))
+        return Hits(self, hits, n.value, aln.value, nb.value)
 
     def search_device(self, st=-1, ed=-1):
         """Like search(), but the so_hit records stay in HBM (multi-GPU path: exchanged over RCCL before any host copy)."""
@@ -236,11 +242,40 @@ def hits_from_bytes(s, data):
 class Hits:
     """Result rows of one search; frees the library buffer on close."""
 
-    def __init__(self, s, ptr, n):
+    def __init__(self, s, ptr, n, aln_ptr=None, aln_bytes=0):
         self.s, self.ptr, self.n = s, ptr, n
+        self.aln_ptr, self.aln_bytes = aln_ptr, aln_bytes
+        self._aln_off = None
 
     def __len__(self):
         return self.n
+
+    def _aln_offsets(self):
+        if self.aln_ptr is None:
+            raise SohitError("this search was run without alignments: Searcher.search(..., alignments=True)")
+        if self._aln_off is None:
+            a = self.array()["aln"].astype(np.int64) if self.n else np.zeros(0, dtype=np.int64)
+            off = np.zeros(self.n + 1, dtype=np.int64)
+            np.cumsum(2 * a, out=off[1:])
+            self._aln_off = off
+        return self._aln_off
+
+    def alignment_buffer(self):
+        """(uint8 view of the strings -- no copy, valid until close() --, int64 offsets [n + 1]): row k's query string is
+        buf[off[k] : off[k] + aln_k], its subject string buf[off[k] + aln_k : off[k + 1]]."""
+        off = self._aln_offsets()
+        if not self.aln_bytes:
+            return np.zeros(0, dtype=np.uint8), off
+        return np.frombuffer((C.c_char * self.aln_bytes).from_address(self.aln_ptr), dtype=np.uint8), off
+
+    def alignment(self, k):
+        """(query string, subject string) of row k as bytes: kswat_st's al0 / al1 (fsearch.py:1417-1444)."""
+        off = self._aln_offsets()
+        if not 0 <= k < self.n:
+            raise IndexError(k)
+        a0, a1 = int(off[k]), int(off[k + 1])
+        mid = (a0 + a1) // 2
+        return C.string_at(self.aln_ptr + a0, mid - a0), C.string_at(self.aln_ptr + mid, a1 - mid)
 
     def array(self):
         """numpy structured view (copy) of the so_hit records."""
@@ -287,26 +322,66 @@ class Hits:
         if self.ptr:
             self.s.L.so_free_hits(self.ptr)
             self.ptr = None
+        if self.aln_ptr:
+            self.s.L.so_free_aln(self.aln_ptr)
+            self.aln_ptr = None
 
     __del__ = close
 
 
 def blastp(qry, ref, expect=1e-5, v=500, max_miss=1e-3, st=-1, ed=-1, rst=-1, red=-1, thr=-1, flt="T", ref_idx="", memory=True,
-           ssd="", nr="", step=4, ht=-1, chk=100000, tmpdir="./tmpdir", device=0):
+           ssd="", nr="", step=4, ht=-1, chk=100000, tmpdir="./tmpdir", device=0, alignments=False):
     """fsearch.py:2968 -- yields (i, j, li, lj, idy, aln, mis, gap, qst, qed, sst, sed, e, bit, seed) per reported row
-    (query ordinal, subject ordinal, lengths, identity, ..., 1-based starts as printed, e-value, bit, ungapped score)."""
+    (query ordinal, subject ordinal, lengths, identity, ..., 1-based starts as printed, e-value, bit, ungapped score);
+    alignments=True: + (query string, subject string) as bytes."""
     s = Searcher(ssd=ssd, nr=nr, ht=ht, chk=chk, step=step, v=v, thr=thr, expect=expect, max_miss=max_miss, flt=flt, device=device)
     try:
         s.load_ref(ref, rst, red)
         s.load_queries(qry)
-        hits = s.search(st, ed)
-        for r in hits.array():
-            yield (int(r["qidx"]), int(r["sidx"]), int(r["qlen"]), int(r["slen"]), float(r["identity"]), int(r["aln"]), int(r["mis"]),
+        hits = s.search(st, ed, alignments=alignments)
+        for k, r in enumerate(hits.array()):
+            row = (int(r["qidx"]), int(r["sidx"]), int(r["qlen"]), int(r["slen"]), float(r["identity"]), int(r["aln"]), int(r["mis"]),
                    int(r["gap"]), int(r["qst"]), int(r["qed"]), int(r["sst"]), int(r["sed"]), float(r["evalue"]), int(r["bit"]),
                    int(r["ungapped"]))
+            yield row + hits.alignment(k) if alignments else row
         hits.close()
     finally:
         s.close()
+
+
+def aln_stats(al0, al1):
+    """(matches, mis, gap, identity) of two aligned strings by the reference's rules (fsearch.py:1454-1471): a column counts
+    as a match when its two characters are equal, a mismatch otherwise; gap openings by the three-state machine over '-'
+    characters (a literal '-' residue counts like a gap); identity = matches * (100. / len).  The reference runs the machine over
+    its own order of the two strings, subject first when it put the subject on its columns; the orders can differ only where a
+    column holds '-' on both sides (a literal '-' residue opposite a gap), and aln_stats(al1, al0) gives the other one."""
+    if len(al0) != len(al1):
+        raise ValueError("aligned strings differ in length")
+    if isinstance(al0, str):
+        al0 = al0.encode("latin-1")
+    if isinstance(al1, str):
+        al1 = al1.encode("latin-1")
+    AL = len(al0)
+    idy = 0.
+    mis = gap = 0
+    op = -1
+    dash = 45   # '-'
+    for a, b in zip(al0, al1):
+        if a == b:
+            idy += 1.
+        else:
+            mis += 1
+        if a == dash and op != 0:
+            gap += 1
+            op = 0
+        elif b == dash and op != 1:
+            gap += 1
+            op = 1
+        else:
+            op = -1
+    matches = AL - mis
+    identity = idy * (100. / AL) if AL else float("nan")
+    return matches, mis, gap, identity
 
 
 def makedb(ref, space='11111111', nr=AA9, step=1, ht=-1, chk=500000, device=0):
