@@ -212,6 +212,12 @@ int64_t so_query_candidates(so_ctx *ctx, int64_t qidx, uint32_t *out4, int64_t c
  * Refused, with a message and nothing written: a packed kernel (1, 2, 4) on a wide task, k_align_lane on a tile or on a sequence of 4096
  * residues or more, windows out of range. */
 int so_align_pairs(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, const uint32_t *order, int32_t *out);
+/* tests: so_align_pairs for the traced kernels (3, 4) that also returns every task's alignment, built by the search's own emission chain
+ * (column slots, the emitting walk, compaction, the host decoder).  *aln holds 2 * sum(aln_t) bytes (*aln_bytes): task t's query string
+ * starts at byte 2 * sum_{m<t} aln_m and is aln_t bytes long, its subject string follows it (as so_search_loaded_aln lays out rows).
+ * Same tasks, order and refusals as so_align_pairs; released with so_free_aln(). */
+int so_align_pairs_aln(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, const uint32_t *order, int32_t *out, char **aln,
+                       int64_t *aln_bytes);
 
 /* Markov clustering of one block of the orthology graph.  Replaces: the matrix loop of bin/find_cluster.py
  * `mcl` (652-689) with `normalize` (636-646) as `mcl_xyz` (1425-1467) calls it on a float32 scipy csr_matrix -- column

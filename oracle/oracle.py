@@ -73,6 +73,13 @@ def lib():
         L.oc_result_nqueries.argtypes = [C.c_void_p]
         L.oc_result_cands.argtypes = [C.c_void_p, i64, C.c_void_p]
         L.oc_result_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oc_kswat_st_aln.restype = i64
+        L.oc_kswat_st_aln.argtypes = [C.c_char_p, i64, C.c_char_p, i64, i64, i64, C.POINTER(C.c_double), C.c_void_p, C.c_char_p, C.c_char_p, i64]
+        L.oc_blastp_aln.restype = C.c_void_p
+        L.oc_blastp_aln.argtypes = L.oc_blastp.argtypes
+        L.oc_result_aln_bytes.restype = i64
+        L.oc_result_aln_bytes.argtypes = [C.c_void_p]
+        L.oc_result_alns.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -134,13 +141,22 @@ def ungap_chain(q, s, locs):
     return tuple(int(x) for x in out)  # score, flag, x0, y0, x, y
 
 
-def kswat_st(q, s, qst=0, sst=0, full=False):
+def kswat_st(q, s, qst=0, sst=0, full=False, strings=False):
+    """-> the reference's tuple (+ cells, maximum when full); strings=True: (that tuple, (query string, subject string)), the
+    alignment's al0 / al1 with '-' in gap columns, query side first whichever sequence ran on the columns"""
     q, s = _b(q), _b(s)
     idy = C.c_double()
     out = np.zeros(10, dtype=np.int64)
-    lib().oc_kswat_st(q, len(q), s, len(s), qst, sst, C.byref(idy), out.ctypes.data)
+    if strings:
+        cap = len(q) + len(s) + 1
+        aq, as_ = C.create_string_buffer(cap), C.create_string_buffer(cap)
+        n = lib().oc_kswat_st_aln(q, len(q), s, len(s), qst, sst, C.byref(idy), out.ctypes.data, aq, as_, cap)
+        assert n >= 0
+    else:
+        lib().oc_kswat_st(q, len(q), s, len(s), qst, sst, C.byref(idy), out.ctypes.data)
     r = (idy.value,) + tuple(int(x) for x in out[:8])
-    return r + (int(out[8]), int(out[9])) if full else r
+    r = r + (int(out[8]), int(out[9])) if full else r
+    return (r, (aq.raw[:n], as_.raw[:n])) if strings else r
 
 
 def score2bit(s):
@@ -232,6 +248,20 @@ class Result:
         keys = ["n_queries", "query_aa", "rows", "seed_hits", "groups", "ungap_steps", "cands", "alignments", "cells"]
         self.stats = dict(zip(keys, (int(x) for x in s9)))
         self.stats.update(t_index=float(t3[0]), t_seed=float(t3[1]), t_align=float(t3[2]))
+        # (blastp(alignments=True)) every row's (query string, subject string), as Hits.alignment(k) gives them
+        self.alignments = None
+        nb = L.oc_result_aln_bytes(h)
+        if nb >= 0 and n:
+            buf = C.create_string_buffer(max(1, nb))
+            lens = np.zeros(2 * n, dtype=np.int64)
+            L.oc_result_alns(h, buf, lens.ctypes.data)
+            raw, pos, self.alignments = buf.raw, 0, []
+            for k in range(n):
+                a, b = int(lens[2 * k]), int(lens[2 * k + 1])
+                self.alignments.append((raw[pos:pos + a], raw[pos + a:pos + a + b]))
+                pos += a + b
+        elif nb >= 0:
+            self.alignments = []
 
     def cands(self, qrel):
         n = lib().oc_result_ncands(self.h, qrel)
@@ -262,6 +292,7 @@ class MergedResult:
             for k, v in p.stats.items():
                 self.stats[k] = self.stats.get(k, 0) + v
         self._first = np.cumsum([0] + [p.nqueries for p in parts])
+        self.alignments = None if any(p.alignments is None for p in parts) else [a for p in parts for a in p.alignments]
 
     def cands(self, qrel):
         k = int(np.searchsorted(self._first, qrel, side="right")) - 1
@@ -304,9 +335,10 @@ def blastp_parallel(qry, ref, out_path="", threads=0, st=-1, ed=-1, min_piece=64
 
 
 def blastp(qry, ref, out_path="", ssd="111111", nr=AA9, expect=1e-3, v=500, max_miss=1e-3, st=-1, ed=-1, rst=-1, red=-1,
-           thr=-1, step=1, flt="T", ht=120000000, chk=50000, mode="w"):
-    """End-to-end reference path for queries [st, ed) (fsearch.py blastp + entry_point)."""
-    h = lib().oc_blastp(_b(qry), _b(ref), _b(ssd), _b(nr), expect, v, max_miss, st, ed, rst, red, thr, step, _b(flt), ht, chk,
+           thr=-1, step=1, flt="T", ht=120000000, chk=50000, mode="w", alignments=False):
+    """End-to-end reference path for queries [st, ed) (fsearch.py blastp + entry_point).  alignments=True: Result.alignments holds
+    every row's (query string, subject string) in row order (a tile row: its own tile's)"""
+    h = (lib().oc_blastp_aln if alignments else lib().oc_blastp)(_b(qry), _b(ref), _b(ssd), _b(nr), expect, v, max_miss, st, ed, rst, red, thr, step, _b(flt), ht, chk,
                         _b(out_path), _b(mode))
     if not h:
         raise IOError("oracle blastp failed (cannot read %s / %s)" % (qry, ref))

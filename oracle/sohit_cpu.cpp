@@ -439,7 +439,9 @@ struct Aln {
     i64 maxscore;
 };
 
-Aln kswat_st(const std::string& S0, const std::string& S1, i64 qst, i64 sst, Mats& M) {
+// aq / as (optional): the alignment's query-side and subject-side strings ('-' in gap columns), al0 / al1 handed back in the
+// caller's order when the sequences were swapped, as the reference swaps its lists back
+Aln kswat_st(const std::string& S0, const std::string& S1, i64 qst, i64 sst, Mats& M, std::string* aq = nullptr, std::string* as = nullptr) {
     const int go = -11, ge = -1, kbound = 16;
     i64 qed = -1, sed = -1;
     qst = std::min<i64>(std::max<i64>(qst, 0), (i64)S0.size());
@@ -522,6 +524,11 @@ Aln kswat_st(const std::string& S0, const std::string& S1, i64 qst, i64 sst, Mat
         else op = -1;
     }
     idy *= (100. / (double)AL);  // AL == 0 -> nan (RPython C semantics; CPython would raise)
+    if (aq && as) {   // (the statistics above ran over the internal order: a literal '-' opposite a gap counts differently in the other)
+        std::string x(al0.begin(), al0.end()), y(al1.begin(), al1.end());
+        *aq = swap ? y : x;
+        *as = swap ? x : y;
+    }
     Aln r;
     r.idy = idy, r.aln = AL, r.mis = mis, r.gap = gap, r.cells = cells, r.maxscore = maxscore;
     r.bit = score2bit(maxscore);
@@ -534,19 +541,24 @@ Aln kswat_st(const std::string& S0, const std::string& S1, i64 qst, i64 sst, Mat
 }
 
 // kswat_st_long (fsearch.py:1480-1498): independent 4096x4096 tiles along the diagonal
-void kswat_st_long(const std::string& sqi, const std::string& sqj, i64 qi, i64 qj, Mats& M, std::vector<Aln>& out) {
+// strs (optional): every tile's (query string, subject string)
+void kswat_st_long(const std::string& sqi, const std::string& sqj, i64 qi, i64 qj, Mats& M, std::vector<Aln>& out,
+                   std::vector<std::pair<std::string, std::string>>* strs = nullptr) {
     const i64 chk = 4096, li = (i64)sqi.size();
     i64 j = qj;
     out.clear();
+    if (strs) strs->clear();
     for (i64 i0 = qi; i0 < li; i0 += chk) {
         i64 i = std::max<i64>(0, i0), ied = std::max<i64>(0, i0 + chk);
         j = std::max<i64>(0, j);
         i64 jed = std::max<i64>(0, j + chk);
         std::string a = i < (i64)sqi.size() ? sqi.substr((size_t)i, (size_t)(ied - i)) : std::string();
         std::string b = j < (i64)sqj.size() ? sqj.substr((size_t)j, (size_t)(jed - j)) : std::string();
-        Aln r = kswat_st(a, b, 0, 0, M);
+        std::pair<std::string, std::string> al;
+        Aln r = kswat_st(a, b, 0, 0, M, strs ? &al.first : nullptr, strs ? &al.second : nullptr);
         r.qst += i, r.qed += i, r.sst += j, r.sed += j;
         out.push_back(r);
+        if (strs) strs->push_back(std::move(al));
         j += chk;
     }
 }
@@ -909,8 +921,9 @@ struct HitRec {  // one reported alignment (fixed-width; mirrors include/sohit.h
     i64 aln, mis, gap, qst, qed, sst, sed, bit, qlen, slen, ungapped;
 };
 
+// alns (optional, with recs): every reported row's (query string, subject string), in row order
 int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats& stt, std::vector<HitRec>* recs = nullptr,
-           std::vector<std::vector<Cand>>* cand_dump = nullptr) {
+           std::vector<std::vector<Cand>>* cand_dump = nullptr, std::vector<std::pair<std::string, std::string>>* alns = nullptr) {
     init_b62();
     Params p = p0;
     p.max_miss = std::max(p.max_miss, 1e-3);
@@ -958,6 +971,7 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
     // PHASE 2 (3028-3110)
     double t2 = now();
     std::vector<Aln> longres;
+    std::vector<std::pair<std::string, std::string>> longstr;
     for (i64 i = st; i < ed; ++i) {
         auto& H = KDB[i - st];
         stt.cands += (i64)H.size();
@@ -976,6 +990,7 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
         struct M8 {
             HitRec r;
             std::string hj, desc;
+            std::pair<std::string, std::string> al;
         };
         std::vector<M8> m8s;
         std::string hi = hd.substr(0, hd.find(' '));
@@ -985,19 +1000,21 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
             i64 j = c.subj;
             DB.get(j, hdj, sqj);
             const i64 lj = (i64)sqj.size();
-            auto emit = [&](const Aln& a, double e) {
+            auto emit = [&](const Aln& a, double e, std::pair<std::string, std::string>* al) {
                 M8 m;
                 m.r = {i, j, a.idy, e, a.aln, a.mis, a.gap, a.qst + 1, a.qed, a.sst + 1, a.sed, a.bit, li, lj, (i64)c.score};
                 m.hj = hdj.substr(0, hdj.find(' '));
                 m.desc = hdj;
-                m8s.push_back(m);
+                if (al) m.al = std::move(*al);
+                m8s.push_back(std::move(m));
             };
             if (li < 4096 && lj < 4096) {
-                Aln a = kswat_st(sqi, sqj, c.qi, c.qj, *mats);
+                std::pair<std::string, std::string> al;
+                Aln a = kswat_st(sqi, sqj, c.qi, c.qj, *mats, alns ? &al.first : nullptr, alns ? &al.second : nullptr);
                 stt.alignments += 1, stt.cells += a.cells;
                 double e = bit2e(D, li, lj, a.bit);
                 if (e <= p.expect) {
-                    emit(a, e);
+                    emit(a, e, alns ? &al : nullptr);
                     unmch = 0;
                     bv += 1;
                 } else {
@@ -1005,12 +1022,13 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
                 }
             } else {
                 int flag = 1;
-                kswat_st_long(sqi, sqj, c.qi, c.qj, *mats, longres);
-                for (auto& a : longres) {
+                kswat_st_long(sqi, sqj, c.qi, c.qj, *mats, longres, alns ? &longstr : nullptr);
+                for (size_t t = 0; t < longres.size(); ++t) {
+                    const Aln& a = longres[t];
                     stt.alignments += 1, stt.cells += a.cells;
                     double e = bit2e(D, li, lj, a.bit);
                     if (e <= p.expect) {
-                        emit(a, e);
+                        emit(a, e, alns ? &longstr[t] : nullptr);
                         flag = 0;
                         bv += 1;
                     }
@@ -1029,6 +1047,7 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
             if (!(m.r.e <= p.expect)) continue;
             stt.rows += 1;
             if (recs) recs->push_back(m.r);
+            if (alns) alns->push_back(m.al);
             if (out) {
                 fprintf(out, "%s\t%s\t%s\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%s\t%lld\t%lld\t%lld\t%lld\t%s\n", hi.c_str(),
                         m.hj.c_str(), fmt_idy(m.r.idy).c_str(), (long long)m.r.aln, (long long)m.r.mis, (long long)m.r.gap,
@@ -1107,6 +1126,21 @@ void oc_kswat_st(const char* q, i64 ql, const char* s, i64 sl, i64 qst, i64 sst,
     out[7] = a.bit, out[8] = a.cells, out[9] = a.maxscore;
 }
 
+// oc_kswat_st and the alignment's strings: query side into aq, subject side into as (cap bytes each, ql + sl always suffice) -> aln
+i64 oc_kswat_st_aln(const char* q, i64 ql, const char* s, i64 sl, i64 qst, i64 sst, double* idy, i64* out, char* aq, char* as, i64 cap) {
+    init_b62();
+    if (!g_mats) g_mats = new Mats();
+    std::string x, y;
+    Aln a = kswat_st(std::string(q, (size_t)ql), std::string(s, (size_t)sl), qst, sst, *g_mats, &x, &y);
+    *idy = a.idy;
+    out[0] = a.aln, out[1] = a.mis, out[2] = a.gap, out[3] = a.qst, out[4] = a.qed, out[5] = a.sst, out[6] = a.sed,
+    out[7] = a.bit, out[8] = a.cells, out[9] = a.maxscore;
+    if ((i64)x.size() > cap || (i64)y.size() > cap) return -1;
+    memcpy(aq, x.data(), x.size());
+    memcpy(as, y.data(), y.size());
+    return (i64)x.size();
+}
+
 i64 oc_score2bit(i64 s) { return score2bit(s); }
 double oc_bit2e(i64 D, i64 li, i64 lj, i64 bit) { return bit2e(D, li, lj, bit); }
 void oc_f2s(double e, char* out, int cap) { snprintf(out, (size_t)cap, "%s", f2s(e).c_str()); }
@@ -1163,25 +1197,60 @@ struct OcResult {
     std::vector<HitRec> recs;
     std::vector<std::vector<Cand>> cands;
     Stats st;
+    std::vector<std::pair<std::string, std::string>> alns;   // (oc_blastp_aln) per record: query string, subject string
 };
 
-// params: expect, v, max_miss, st, ed, rst, red, thr, step, flt('T'/..), ht(NC), chk
-void* oc_blastp(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
-                i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
-                const char* mode) {
+static void* blastp_result(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
+                           i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
+                           const char* mode, bool with_alns) {
     Params p;
     p.ssd = ssd, p.nr = nr, p.expect = expect, p.v = v, p.max_miss = max_miss, p.st = st, p.ed = ed, p.rst = rst, p.red = red,
     p.thr = thr, p.step = step, p.flt = flt, p.ht = ht, p.chk = chk;
     OcResult* r = new OcResult();
     FILE* f = nullptr;
     if (out_path && out_path[0]) f = fopen(out_path, (mode && mode[0] == 'a') ? "ab" : "wb");
-    int rc = blastp(qry, ref, p, f, r->st, &r->recs, &r->cands);
+    int rc = blastp(qry, ref, p, f, r->st, &r->recs, &r->cands, with_alns ? &r->alns : nullptr);
     if (f) fclose(f);
     if (rc) {
         delete r;
         return nullptr;
     }
     return r;
+}
+
+// params: expect, v, max_miss, st, ed, rst, red, thr, step, flt('T'/..), ht(NC), chk
+void* oc_blastp(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
+                i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
+                const char* mode) {
+    return blastp_result(qry, ref, ssd, nr, expect, v, max_miss, st, ed, rst, red, thr, step, flt, ht, chk, out_path, mode, false);
+}
+
+// oc_blastp that also keeps every reported row's strings (oc_result_alns)
+void* oc_blastp_aln(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
+                    i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
+                    const char* mode) {
+    return blastp_result(qry, ref, ssd, nr, expect, v, max_miss, st, ed, rst, red, thr, step, flt, ht, chk, out_path, mode, true);
+}
+
+// bytes of all rows' strings (both sides), or -1 without them
+i64 oc_result_aln_bytes(void* h) {
+    OcResult* r = (OcResult*)h;
+    if (r->alns.size() != r->recs.size()) return -1;
+    i64 n = 0;
+    for (auto& a : r->alns) n += (i64)(a.first.size() + a.second.size());
+    return n;
+}
+// row k's query string then its subject string, row after row; lens2[2k], lens2[2k + 1] = their lengths
+void oc_result_alns(void* h, char* buf, i64* lens2) {
+    OcResult* r = (OcResult*)h;
+    for (size_t k = 0; k < r->alns.size(); ++k) {
+        const auto& a = r->alns[k];
+        memcpy(buf, a.first.data(), a.first.size());
+        buf += a.first.size();
+        memcpy(buf, a.second.data(), a.second.size());
+        buf += a.second.size();
+        lens2[2 * k] = (i64)a.first.size(), lens2[2 * k + 1] = (i64)a.second.size();
+    }
 }
 void oc_result_free(void* h) { delete (OcResult*)h; }
 i64 oc_result_nrecs(void* h) { return (i64)((OcResult*)h)->recs.size(); }

@@ -591,7 +591,11 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
 // host_phase2.hip: candidate order, banded alignments in rounds, row emission
 void emit_join(so_ctx* c, HitBuf& out);
 void phase2(so_ctx* c, Batch& b, HitBuf& out);
-void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out);   // so_align_pairs (tests)
+// so_align_pairs / so_align_pairs_aln (tests); aln (traced kernels only): the tasks' strings through the search's emission chain
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln = nullptr);
+// one alignment's strings from its compacted columns (k_aln_compact: 2 bits per column, walk order = last column first): AL bytes each into sq
+// (query side) and ss (subject side), reading the query from qp and the subject from sp (their first aligned residues) as the columns advance
+void aln_decode(const u32* w, int AL, const u8* qp, const u8* sp, char* sq, char* ss);
 // host_search.hip: batches of a search, the work pre-pass
 void search_loaded(so_ctx* c, i64 q_lo, i64 q_hi, HitBuf& out);
 void query_work(so_ctx* c, i64 q_lo, i64 q_hi, u64* out);

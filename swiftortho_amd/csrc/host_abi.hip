@@ -561,5 +561,17 @@ int so_align_pairs(so_ctx* c, int kernel, int64_t n, const int64_t* task6, const
     return guarded(c, [&] { align_pairs(c, kernel, n, task6, order, out); });
 }
 
+int so_align_pairs_aln(so_ctx* c, int kernel, int64_t n, const int64_t* task6, const uint32_t* order, int32_t* out, char** aln, int64_t* aln_bytes) {
+    return guarded(c, [&] {
+        if (!aln || !aln_bytes) throw SoError("so_align_pairs_aln: output pointers are NULL");
+        *aln = nullptr, *aln_bytes = 0;
+        if (kernel != 3 && kernel != 4) throw SoError("so_align_pairs_aln: only the traced kernels (3, 4) give alignments");
+        AlnBytes a;
+        align_pairs(c, kernel, n, task6, order, out, &a);
+        *aln_bytes = (int64_t)a.n;
+        *aln = a.release();
+    });
+}
+
 }  // extern "C"
 

@@ -2,6 +2,15 @@
 #include "host.h"
 
 
+void aln_decode(const u32* w, int AL, const u8* qp, const u8* sp, char* sq, char* ss) {
+    for (int f = 0; f < AL; ++f) {
+        const int cc = AL - 1 - f;
+        const u32 code = (w[cc >> 4] >> ((cc & 15) << 1)) & 3u;
+        sq[f] = code != 2 ? (char)*qp++ : '-';
+        ss[f] = code != 3 ? (char)*sp++ : '-';
+    }
+}
+
 // wait for the row-emission job of the previous batch (if any) and apply its rare post-filter
 void emit_join(so_ctx* c, HitBuf& out) {
     if (!c->emit.active) return;
@@ -160,12 +169,14 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
     // banded alignments in rounds (see k_round_counts / k_stop_round_w)
     const int maxrows = (int)std::min<u32>(std::max(maxwin_q, maxwin_s), std::min(maxwin_q, maxwin_s) + 16);
     const u32 stride = align_trace_stride(maxrows + 1);
-    const size_t budget_words = (size_t)1 << 30;  // 4 GiB of trace scratch for the fixed-stride slabs
+    // (SOHIT_TRACE_VAR_MAX, tests: both budgets lowered to its value, so that small sets take the slab route and the kept traces' fallback)
+    const long long trace_var_max = tune().trace_var_max;
+    const size_t budget_words = trace_var_max >= 0 ? (size_t)trace_var_max : (size_t)1 << 30;  // 4 GiB of trace scratch for the fixed-stride slabs
     const u32 slab = (u32)std::max<size_t>(16, std::min<size_t>(std::max<u32>(NT, 1), budget_words / std::max<u32>(stride, 1)));
     // Traces take what each task's own band needs: room per task (k_trace_units), scanned into b.tr_ofs; up to 8 GiB per launch list,
     // beyond that the list falls back to slabs of the batch-wide stride.  (`stride` follows the longest window of the batch: one
     // 4096-residue pair and every 300-row alignment owned 33 KB of trace, which its traceback then strode over.)
-    const size_t var_budget_words = (size_t)1 << 31;
+    const size_t var_budget_words = trace_var_max >= 0 ? (size_t)trace_var_max : (size_t)1 << 31;
     const u32 TU = align_trace_unit();
     auto trace_offsets = [&](const u32* list, u32 n) -> size_t {   // -> words the list's traces need
         // the offsets are a 32-bit scan of units: a list whose total could wrap (no task needs more units than the batch-wide stride holds)
@@ -245,6 +256,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                                         c->ref.d_off.p, c->d_b62c.p, b.spec_trace.p, TU, b.tr_ofs.p, b.ares.p, b.tpos.p, 0u, c->st, nw_s, pkc);
                     nspec = NS;
                 } else {   // the traces would not fit after all: these tasks score-only, like the rest of the round
+                    if (tune().debug) fprintf(stderr, "[sohit] kept traces do not fit: %u tasks scored only\n", NS);
                     launch_align(b.tasks.p, slist, NS, b.dev.d_res.p, b.dev.d_scls.p, b.dev.d_scls4.p, b.dev.d_off.p, c->ref.d_res.p, c->ref.d_scls.p,
                                  c->ref.d_scls4.p, c->ref.d_off.p, c->d_b62c.p, nullptr, stride, nullptr, b.ares.p, false, c->st, 0u);
                 }
@@ -441,6 +453,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
         }
         const size_t tw = tn ? trace_offsets(tlist, tn) : 0;
         const bool tvar = tw <= var_budget_words;
+        if (!tvar && tune().debug) fprintf(stderr, "[sohit] trace slabs: %u rows of %u per range at most, %u tasks per slab\n", tn, maxpart, slab);
         b.trace.ensure(tvar ? tw + 64 : (size_t)std::min(slab, std::max<u32>(maxpart, 1)) * stride + 64);
         // The rows without a kept trace are aligned in ONE launch in front of the ranges when none of them needs the 32-bit kernel (uniform
         // sets): a range's share (config 3: 87 k tasks = 1.3 fillings of the chip) left half a filling idle -- 0.35 + 1.0 ms in two launches,
@@ -681,16 +694,7 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
                         const int AL = std::max(0, v[2]);
                         if (!AL) return;
                         char* sq = ab + boff[di];
-                        char* ss = sq + AL;
-                        const u8* qp = qres + qoff[(size_t)v[0]] + (v[5] - 1);
-                        const u8* sp = rres + roff[(size_t)v[1]] + (v[7] - 1);
-                        const u32* w = codes + woff[i];
-                        for (int f = 0; f < AL; ++f) {
-                            const int cc = AL - 1 - f;
-                            const u32 code = (w[cc >> 4] >> ((cc & 15) << 1)) & 3u;
-                            sq[f] = code != 2 ? (char)*qp++ : '-';
-                            ss[f] = code != 3 ? (char)*sp++ : '-';
-                        }
+                        aln_decode(codes + woff[i], AL, qres + qoff[(size_t)v[0]] + (v[5] - 1), rres + roff[(size_t)v[1]] + (v[7] - 1), sq, sq + AL);
                     };
                     std::atomic<i64> nx{0};
                     auto bworker = [&] {
@@ -724,9 +728,13 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
 // so_align_pairs (tests): explicit windows through ONE aligner of phase 2, by the product's own launch functions on the product's device arrays.
 // The raw loaded queries are the batch (upload_set, as for a batch masked on the host): a task's q is its query ordinal.  Every task the
 // search would never hand the chosen kernel is refused before anything runs, so a refused call writes nothing.
-void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out) {
+// aln (so_align_pairs_aln): kernels 3 and 4 only; the walks write their columns through the search's own emission chain -- slots per task
+// (k_aln_units, scan, k_aln_scatter), the emitting walk, the words each task's columns took (k_aln_words, scan), k_aln_compact -- and the
+// compacted columns are decoded by aln_decode, as the emission worker does; task t's strings land at 2 * sum_{m<t} aln_m of *aln.
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln) {
     if (!c->ref_loaded || !c->qry_loaded) throw SoError("so_align_pairs: load a reference and queries first");
     if (kernel < 0 || kernel > 4) throw SoError("so_align_pairs: kernel must be 0 ... 4");
+    if (aln && kernel < 3) throw SoError("so_align_pairs_aln: only the traced kernels (3, 4) give alignments");
     if (n < 0 || n > (1ll << 24)) throw SoError("so_align_pairs: n must be 0 ... 2^24");
     if (n == 0) return;
     if (!task6 || !out) throw SoError("so_align_pairs: task6 or out is NULL");
@@ -783,6 +791,9 @@ void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint3
                 throw SoError("so_align_pairs: task " + std::to_string(t) + ": its scores need 32-bit cells, the packed aligners do not take it");
     const PkCls pkc{qs.d_pcls.p, qs.d_pcls4.p, R.d_pcls.p, R.d_pcls4.p};
     DevBuf<u32> d_units, d_tofs, d_trace;
+    DevBuf<u32> d_aunits, d_arofs, d_aofs, d_acode, d_awords, d_acofs, d_acomp;   // (aln) the emission chain's buffers
+    std::vector<u32> h_acomp;
+    size_t aln_words = 0;
     switch (kernel) {
     case 0:
         launch_align(d_tasks.p, d_list.p, (u32)n, qs.d_res.p, qs.d_scls.p, qs.d_scls4.p, qs.d_off.p, R.d_res.p, R.d_scls.p, R.d_scls4.p, R.d_off.p, c->d_b62c.p,
@@ -802,15 +813,59 @@ void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint3
         launch_trace_units(d_tasks.p, d_list.p, (u32)n, qs.d_off.p, R.d_off.p, d_units.p, c->st);
         const size_t tw = (size_t)d2h_u32(c, scan_u32(d_units.p, d_tofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st)) * TU;
         d_trace.ensure(tw + 64);
+        u32* acode = nullptr;
+        if (aln) {   // column slots per task, as the emission hands them out to the reported rows
+            d_aunits.ensure((size_t)n + 4), d_arofs.ensure((size_t)n + 4), d_aofs.ensure((size_t)n + 4);
+            launch_aln_units(d_tasks.p, d_list.p, (u32)n, qs.d_off.p, R.d_off.p, d_aunits.p, c->st);
+            const size_t units = d2h_u32(c, scan_u32(d_aunits.p, d_arofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st));
+            d_acode.ensure(units * aln_unit_words() + 64);
+            launch_aln_scatter(d_list.p, (u32)n, d_arofs.p, d_aofs.p, c->st);
+            acode = d_acode.p;
+        }
         const bool wide32 = kernel == 3;
         launch_align(d_tasks.p, d_list.p, (u32)n, qs.d_res.p, qs.d_scls.p, qs.d_scls4.p, qs.d_off.p, R.d_res.p, R.d_scls.p, R.d_scls4.p, R.d_off.p, c->d_b62c.p,
-                     d_trace.p, TU, d_tofs.p, d_res.p, true, c->st, wide32 ? (u32)n : 0u, wide32 ? PkCls{nullptr, nullptr, nullptr, nullptr} : pkc);
+                     d_trace.p, TU, d_tofs.p, d_res.p, true, c->st, wide32 ? (u32)n : 0u, wide32 ? PkCls{nullptr, nullptr, nullptr, nullptr} : pkc,
+                     acode, aln ? d_aofs.p : nullptr);
+        if (aln) {   // the columns compacted in list order and downloaded
+            d_awords.ensure((size_t)n + 4), d_acofs.ensure((size_t)n + 4);
+            launch_aln_words(d_list.p, (u32)n, d_res.p, d_awords.p, c->st);
+            aln_words = d2h_u32(c, scan_u32(d_awords.p, d_acofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st));
+            d_acomp.ensure(aln_words + 64);
+            launch_aln_compact(d_list.p, (u32)n, d_aofs.p, d_acode.p, d_acofs.p, d_acomp.p, c->st);
+            h_acomp.resize(aln_words + 1);
+            if (aln_words) HIP_CHECK(hipMemcpyAsync(h_acomp.data(), d_acomp.p, aln_words * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        }
         break;
     }
     }
     std::vector<AlnRes> res((size_t)n);
     HIP_CHECK(hipMemcpyAsync(res.data(), d_res.p, (size_t)n * sizeof(AlnRes), hipMemcpyDeviceToHost, c->st));
     HIP_CHECK(hipStreamSynchronize(c->st));
+    if (aln) {
+        // list position p's columns at the running sum of ceil(aln / 16) words in list order; task t's strings at the running sum of 2 aln in task order
+        std::vector<size_t> woff((size_t)n + 1, 0), boff((size_t)n + 1, 0);
+        for (i64 p = 0; p < n; ++p) woff[(size_t)p + 1] = woff[(size_t)p] + (size_t)(std::max(0, res[list[(size_t)p]].aln) + 15) / 16;
+        if (woff[(size_t)n] != aln_words) throw SoError("so_align_pairs_aln: column words do not add up");
+        for (i64 t = 0; t < n; ++t) boff[(size_t)t + 1] = boff[(size_t)t] + 2 * (size_t)std::max(0, res[(size_t)t].aln);
+        const size_t a0 = aln->n;
+        aln->grow(boff[(size_t)n]);
+        for (i64 p = 0; p < n; ++p) {
+            const u32 t = list[(size_t)p];
+            const AlnRes& r = res[t];
+            if (r.aln <= 0) continue;
+            const u32* w = h_acomp.data() + woff[(size_t)p];
+            int nq_adv = 0, ns_adv = 0;   // (the columns must cover the coordinates before anything is read through them)
+            for (int cc = 0; cc < r.aln; ++cc) {
+                const u32 code = (w[cc >> 4] >> ((cc & 15) << 1)) & 3u;
+                nq_adv += code != 2, ns_adv += code != 3;
+            }
+            if (r.qst < 0 || r.sst < 0 || nq_adv != r.qed - r.qst || ns_adv != r.sed - r.sst || r.qed > (int)Q.len(tk[t].q) || r.sed > (int)R.len(tk[t].subj))
+                throw SoError("so_align_pairs_aln: task " + std::to_string(t) + ": the columns do not cover its coordinates");
+            char* sq = aln->p + a0 + boff[t];
+            aln_decode(w, r.aln, Q.res.data() + Q.off[tk[t].q] + r.qst, R.res.data() + R.off[tk[t].subj] + r.sst, sq, sq + r.aln);
+        }
+        aln->n = a0 + boff[(size_t)n];
+    }
     for (i64 t = 0; t < n; ++t) {
         int32_t* o = out + 10 * t;
         const AlnRes& r = res[(size_t)t];

@@ -39,6 +39,7 @@
     X(I, spec, "SOHIT_SPEC", -1, "speculative traces in the first round: 0 off, 1 on, -1 from 2^21 tasks on")                                                  \
     X(D, spec_slack, "SOHIT_SPEC_SLACK", 1e6, "... the guess tests the ungapped score against expect x this (tests: 1e30 = every first-round task traced, 1e-30 = none)")          \
     X(I, spec_cap, "SOHIT_SPEC_CAP", -1, "tests: most speculative traces kept (-1: all)")                                                                      \
+    X(I, trace_var_max, "SOHIT_TRACE_VAR_MAX", -1, "tests: trace words a launch list's own-size traces may take, and the fixed-stride slabs' budget (-1: 2^31 / 2^30)") \
     X(I, emit_parts, "SOHIT_EMIT_PARTS", 4, "... and otherwise")                                                                                               \
     X(I, emit_min_rows, "SOHIT_EMIT_MIN_ROWS", 1 << 18, "rows below which the emission is one part")                                                           \
     X(P, test_oom_phase2, "SOHIT_TEST_OOM_PHASE2", 0, "tests: phase 2 of the first batch fails once with an out-of-memory error")                              \

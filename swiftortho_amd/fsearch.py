@@ -185,9 +185,10 @@ class Searcher:
 
     ALIGN_DTYPE = [(f, "<i4") for f in ("maxscore", "aln", "matches", "gap", "qst", "qed", "sst", "sed", "cells", "wide")]
 
-    def align_pairs(self, tasks, kernel, order=None):
+    def align_pairs(self, tasks, kernel, order=None, alignments=False):
         """tests: the windows tasks[k] = (qidx, sidx, qi, qj, qe, se) aligned by ONE phase-2 aligner (so_align_pairs; qe / se = -1: the
-        sequence's end) -> one record per task, fields ALIGN_DTYPE.  order: the launch list (None: 0 .. n-1)."""
+        sequence's end) -> one record per task, fields ALIGN_DTYPE.  order: the launch list (None: 0 .. n-1).  alignments=True (traced
+        kernels 3 and 4, so_align_pairs_aln): (records, [(query string, subject string) per task]), built by the search's emission chain."""
         t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int64).reshape(-1, 6))
         n = len(t)
         out = np.zeros(max(n, 1), dtype=self.ALIGN_DTYPE)
@@ -196,8 +197,24 @@ class Searcher:
             o = np.ascontiguousarray(np.asarray(order, dtype=np.uint32))
             if len(o) != n:
                 raise ValueError("order must hold n positions")
-        self._chk(self.L.so_align_pairs(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data))
-        return out[:n]
+        if not alignments:
+            self._chk(self.L.so_align_pairs(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data))
+            return out[:n]
+        ptr, nb = C.c_void_p(), C.c_int64()
+        self._chk(self.L.so_align_pairs_aln(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data,
+                                            C.byref(ptr), C.byref(nb)))
+        try:
+            raw = C.string_at(ptr.value, nb.value) if nb.value else b""
+        finally:
+            self.L.so_free_aln(ptr)
+        alns, pos = [], 0
+        for a in out[:n]["aln"].tolist():
+            a = max(0, a)
+            alns.append((raw[pos:pos + a], raw[pos + a:pos + 2 * a]))
+            pos += 2 * a
+        if pos != len(raw):
+            raise SohitError("so_align_pairs_aln: the strings do not match the records")
+        return out[:n], alns
 
 
 class DeviceHits:

@@ -101,8 +101,37 @@ def check(oracle, st, tasks, got, mode, what=""):
                        w[k].tolist()))
 
 
+_strings_cache = {}
+
+
+def expect_strings(oracle, st, tasks):
+    """oracle.kswat_st's (query string, subject string) of each task's windows"""
+    out = []
+    for t in tasks:
+        key = st.windows(t)
+        w = _strings_cache.get(key)
+        if w is None:
+            w = _strings_cache[key] = oracle.kswat_st(*key, strings=True)[1]
+        out.append(w)
+    return out
+
+
+def check_strings(oracle, st, tasks, got, alns, mode, what=""):
+    """every task's strings byte for byte: the oracle's kswat_st al0 / al1 (none where the reference has no answer)"""
+    tasks = [tuple(int(x) for x in t) for t in tasks]
+    want = expect_strings(oracle, st, tasks)
+    assert len(alns) == len(tasks)
+    bad = [k for k in range(len(tasks)) if alns[k] != want[k]]
+    if bad:
+        k = bad[0]
+        pytest.fail("%s mode %d: strings of %d of %d tasks differ; first: task %d = %s\n gpu    %r\n        %r\n oracle %r\n        %r"
+                    % (what, mode, len(bad), len(tasks), k, tasks[k], alns[k][0][:200], alns[k][1][:200], want[k][0][:200], want[k][1][:200]))
+    assert [len(a[0]) for a in alns] == got["aln"].tolist()
+
+
 def run_modes(oracle, st, tasks, rowmax, modes=(0, 1, 2, 3, 4), what=""):
-    """every mode on the tasks it can take; the wide flag against the predicate; packed modes refuse the others"""
+    """every mode on the tasks it can take; the wide flag against the predicate; packed modes refuse the others; the traced modes'
+    strings (so_align_pairs_aln) against the oracle's, with the same records as without them"""
     tasks = [tuple(int(x) for x in t) for t in tasks]
     wide = np.array([st.wide(t, rowmax) for t in tasks], dtype=bool)
     res = {}
@@ -113,6 +142,10 @@ def run_modes(oracle, st, tasks, rowmax, modes=(0, 1, 2, 3, 4), what=""):
         got = st.s.align_pairs(sub, mode)
         assert np.array_equal(got["wide"].astype(bool), wide[take]), "%s mode %d: wide flags differ from the predicate" % (what, mode)
         check(oracle, st, sub, got, mode, what)
+        if mode in TRACED:
+            got2, alns = st.s.align_pairs(sub, mode, alignments=True)
+            assert np.array_equal(got2, got), "%s mode %d: asking for the strings changed the records" % (what, mode)
+            check_strings(oracle, st, sub, got2, alns, mode, what)
         res[mode] = (take, got)
         if mode in PACKED and wide.any():
             k = int(np.flatnonzero(wide)[0])
@@ -317,6 +350,49 @@ def test_launch_list_shapes(oracle, pool, mode):
     keep = [k for k in range(33) if k not in (5, 20)]
     check(oracle, st, [sub[k] for k in keep], got[keep], mode, "a task listed three times")
     assert (got[[5, 20]]["maxscore"] == -1).all()
+
+
+@pytest.mark.parametrize("mode", TRACED)
+def test_traced_launch_list_orders_with_strings(oracle, pool, rowmax, mode):
+    """the traced modes on permuted launch lists (by rows, reversed, random; 1-row and 700-row tasks interleaved): the column slots,
+    walks and compaction follow the list, the strings land per task -- the oracle's whatever the order"""
+    st, tasks = pool
+    rng = np.random.default_rng(120 + mode)
+    tasks = [t for t in tasks if not (mode == 4 and st.wide(t, rowmax))]
+    rows = np.array([min(max(len(st.qs[t[0]]), len(st.ss[t[1]])), min(len(st.qs[t[0]]), len(st.ss[t[1]])) + 16) for t in tasks])
+    for n in (1, 17, 65, 513):
+        pick = rng.choice(len(tasks), n, replace=False)
+        sub = [tasks[int(k)] for k in pick]
+        r = rows[pick]
+        for name, order in (("by rows", np.argsort(-r, kind="stable")), ("reversed", np.arange(n)[::-1].copy()), ("random", rng.permutation(n))):
+            got, alns = st.s.align_pairs(sub, mode, order=order, alignments=True)
+            check(oracle, st, sub, got, mode, "n=%d %s" % (n, name))
+            check_strings(oracle, st, sub, got, alns, mode, "n=%d %s" % (n, name))
+    short, long_ = [t for t in tasks if len(st.qs[t[0]]) == 1][:30], tasks[40:70]
+    mixed = [x for pair in zip(short, long_) for x in pair]
+    got, alns = st.s.align_pairs(mixed, mode, alignments=True)
+    check_strings(oracle, st, mixed, got, alns, mode, "interleaved 1-row / 700-row")
+
+
+def test_edge_fixture_strings(fs, oracle, rowmax):
+    """every case of tests/golden/kswat_aln_edges.json (the REAL reference's strings at the edges: indels in homopolymers and tandem
+    repeats, literal '-' '*' lower-case and digit bytes, either side longer and equal lengths, the band edge, one-residue and empty
+    windows, 4096-residue tiles) through both traced modes: the fixture's strings byte for byte"""
+    from test_aln_fixtures import aln_edge_cases
+    cases = aln_edge_cases()
+    seqs = [x.decode("latin-1") for x in cases[0]["seqs"]]
+    st = Set(fs, seqs, seqs)
+    tasks = [(c["q"], c["s"], c["qlo"] + min(c["qst"], c["qhi"] - c["qlo"]), c["slo"] + min(c["sst"], c["shi"] - c["slo"]), c["qhi"], c["shi"])
+             for c in cases]
+    for mode in TRACED:
+        take = [k for k, t in enumerate(tasks) if not (mode == 4 and st.wide(t, rowmax))]
+        got, alns = st.s.align_pairs([tasks[k] for k in take], mode, alignments=True)
+        check(oracle, st, [tasks[k] for k in take], got, mode, "edge fixture")
+        for j, k in enumerate(take):
+            c = cases[k]
+            assert alns[j] == c["strings"], ("mode %d case %d" % (mode, k), c["cigar"], alns[j][0][:80], alns[j][1][:80])
+        assert len(take) > 0.9 * len(tasks)
+    st.close()
 
 
 def test_lane_kernel_persistent_waves(fs, oracle, rowmax):

@@ -427,12 +427,140 @@ def write_kswat_edges(m):
         print("kswat_edges.json written")
 
 
+def kswat_aln_edges(m):
+    """kswat_st's strings (al0 / al1, query side first) where a co-optimal path or the byte under a column could go wrong: indels in
+    homopolymer runs and tandem repeats, literal '-' '*' lower-case and digit bytes (opposite gaps too), either side the longer one and
+    equal lengths (the swap), maxima on the band edge, one-residue and empty windows, 4096-residue kswat_st_long tiles.  Every case is
+    windows [lo, hi) of two stored sequences aligned from (qst, sst); its strings are kept as a CIGAR over those windows from the
+    reported starts (aln_strings in make_aln_goldens.py), verified to rebuild them; an empty alignment (the reference has no answer:
+    idy *= 100. / 0) is kept with out = null."""
+    from make_aln_goldens import aln_strings, to_cigar
+    rng = np.random.default_rng(12)
+    aa = "ACDEFGHIKLMNPQRSTVWY"
+
+    def rnd(n, alpha=aa):
+        return "".join(alpha[i] for i in rng.integers(0, len(alpha), n))
+
+    def mut(a, rate, alpha=aa):
+        b = list(a)
+        for _ in range(int(rng.binomial(len(a), rate))):
+            p = int(rng.integers(0, len(b) + 1))
+            r = rng.random()
+            if r < 0.6 and p < len(b):
+                b[p] = alpha[int(rng.integers(0, len(alpha)))]
+            elif r < 0.8 and len(b) > 1:
+                del b[p:p + int(rng.integers(1, 4))]
+            else:
+                b[p:p] = list(rnd(int(rng.integers(1, 4)), alpha))
+        return "".join(b) or a[:1]
+
+    pairs = []   # (q, s, qst, sst) on whole strings, or (q, qlo, qhi, s, slo, shi, qst, sst) for tiles
+
+    def both(a, b):
+        pairs.append((a, b, 0, 0))
+        pairs.append((b, a, 0, 0))
+
+    L, R = "MKWHDECY", "PRTNYCWF"
+    # homopolymer runs with an indel (and a mismatch) inside
+    for c in "AGWLK":
+        for run in (3, 6, 11):
+            for d in (-2, -1, 1, 3):
+                both(L + c * run + R, L + c * (run + d) + R)
+            x = c * run
+            both(L + x + R, L + x[:run // 2] + "P" + x[run // 2 + 1:] + c + R)
+    core = rnd(30)
+    both(core + "A" * 20 + core[::-1], core + "A" * 17 + core[::-1])
+    # tandem repeats with one unit deleted or inserted
+    for unit in ("AG", "ACD", "KRWE", "PLNYT", "WC"):
+        for k in (3, 6):
+            both(L + unit * k + R, L + unit * (k - 1) + R)
+            both(L + unit * k + R, L + unit * (k + 1) + R)
+            f1, f2 = rnd(25), rnd(25)
+            both(f1 + unit * (k + 2) + f2, f1 + unit * (k + 1) + f2)
+    # literal '-', '*', lower case and digits, opposite gaps too
+    for a, b in (("WCH-DE-FGWC", "WCH-DEFGWC"), ("WCHAB*C*DWCH", "WCHAB*DWCH"), ("WCmkvLLwWC", "WCmkvLwWC"), ("WC0123456789WC", "WC012356789WC"),
+                 ("WC---WC", "WC-WC"), ("WCH--**--HCW", "WCH-*-HCW"), ("WWacdwyWW", "WWacdyWW"), ("CW-W-C", "CWWC"), ("W*W*W*W", "W*W*W"),
+                 ("HW.x.xWH", "HW.xWH"), ("WCWC" + "-" * 6 + "WCWC", "WCWC--WCWC")):
+        both(a, b)
+    for _ in range(6):
+        a = rnd(int(rng.integers(20, 70)), aa + ODD_BYTES)
+        both(a, mut(a, 0.2, aa + ODD_BYTES))
+    # query longer, shorter, equal (equal lengths take the swap branch)
+    for la, lb in ((50, 60), (60, 50), (55, 55), (120, 121), (121, 120), (200, 200), (1, 1), (2, 2)):
+        a = rnd(la)
+        b = (mut(a, 0.1) + rnd(lb))[:lb]
+        pairs.append((a, b, 0, 0))
+    # maxima on the band edge |i - j| = 16 (and one in, one out)
+    for off in (15, 16, 17):
+        cpart = rnd(40, "WCHYM")
+        both(cpart, rnd(off) + cpart)
+        both(cpart + rnd(5), rnd(off) + cpart)
+    # one-residue windows; starts at len - 1 and len (empty: no answer)
+    a, b = rnd(30), rnd(30)
+    b = a[:10] + b[10:]
+    for qst, sst in ((29, 0), (0, 29), (29, 29), (30, 0), (0, 30), (30, 30), (29, 5)):
+        pairs.append((a, b, qst, sst))
+    for a, b in (("W", "W"), ("W", "MKWV"), ("MKWV", "W"), ("A", "C")):
+        pairs.append((a, b, 0, 0))
+    # 4096-residue tiles as kswat_st_long frames them: [i, i + 4096) of the query against [j, j + 4096) of the subject, j = i
+    A = rnd(6000)
+    B = mut(A[:3000], 0.03) + "L" * 20 + mut(A[3000:], 0.05)
+    for i in (0, 4096):
+        pairs.append((A, i, min(len(A), i + 4096), B, i, min(len(B), i + 4096), 0, 0))
+    C_ = "AG" * 2048
+    pairs.append((C_, 0, 4096, C_[:2000] + C_[2002:] + "AG", 0, 4096, 0, 0))
+
+    sm = [[0] * 4100 for _ in range(4100)]
+    tm = [["*"] * 4100 for _ in range(4100)]
+    out = []
+    for p in pairs:
+        q, qlo, qhi, s, slo, shi, qst, sst = p if len(p) == 8 else (p[0], 0, len(p[0]), p[1], 0, len(p[1]), p[2], p[3])
+        qw, sw = q[qlo:qhi], s[slo:shi]
+        al0, al1 = [], []
+        try:
+            r = m.kswat_st(qw, sw, qst=qst, sst=sst, score=sm, trace=tm, al0=al0, al1=al1)
+        except ZeroDivisionError:   # empty alignment: no answer
+            out.append((q, qlo, qhi, s, slo, shi, qst, sst, None, None))
+            continue
+        a0, a1 = _b(al0), _b(al1)
+        qb, sb = qw.encode("latin-1"), sw.encode("latin-1")
+        cig = to_cigar(a0, a1, qb, sb, r[4] + 1, r[5], r[6] + 1, r[7])
+        assert cig is not None and aln_strings(cig, qb, sb, r[4] + 1, r[6] + 1) == (a0, a1), (qw[:40], sw[:40])
+        out.append((q, qlo, qhi, s, slo, shi, qst, sst, [r[0]] + [int(x) for x in r[1:]], cig))
+    seqs = []
+    for x in sorted({x for c in out for x in (c[0], c[3])}, key=lambda x: (-len(x), x)):   # (not set order: string hashes vary per process)
+        if not any(y.startswith(x) for y in seqs):
+            seqs.append(x)
+
+    def ref(x):
+        return next(i for i, y in enumerate(seqs) if y.startswith(x))
+
+    fields = ["q", "qlo", "qhi", "s", "slo", "shi", "qst", "sst", "out", "cigar"]
+    return {"fields": fields, "out_fields": ["idy", "aln", "mis", "gap", "qst", "qed", "sst", "sed", "bit"], "seqs": seqs,
+            "cases": [[ref(c[0]), c[1], c[2], ref(c[3])] + list(c[4:]) for c in out]}
+
+
+def _b(x):
+    return "".join(x).encode("latin-1") if not isinstance(x, (bytes, bytearray)) else bytes(x)
+
+
+def write_kswat_aln_edges(m):
+    """kswat_aln_edges.json: kswat_st's strings at the edges (kept apart from kswat_edges.json, whose bytes stay as they are)"""
+    path = os.path.join(GOLD, "kswat_aln_edges.json")
+    if FORCE or not os.path.isfile(path):
+        with open(path, "w") as f:
+            json.dump(kswat_aln_edges(m), f, separators=(",", ":"))
+            f.write("\n")
+        print("kswat_aln_edges.json written")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     m = refload.load()
     if FORCE or not os.path.isfile(os.path.join(GOLD, "kat.json")):
         kats(m)
     write_kswat_edges(m)
+    write_kswat_aln_edges(m)
     rng = np.random.default_rng(1)
     base = ["-e", "1e-5", "-v", "500", "-j", "1", "-F", "T"]
     run_e2e(m, "toy_default", synthprot.synthprot(99, 150, 21), base + ["-s", "111111", "-r", AA9, "-M", "1000003", "-c", "50000"])
