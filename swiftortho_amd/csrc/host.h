@@ -172,6 +172,23 @@ struct ChunkIndex {
 };
 
 
+// The reported rows leave in up to EMIT_PARTS_MAX query ranges (phase2)
+#define EMIT_PARTS_MAX 8
+// c->d_small: 32 device words of scratch.  Every use owns its slot or range here.
+enum SmallSlot : int {
+    SM_STASH0 = 0, SM_STASH1 = 1,   // stash_u32 / d2h_pair
+    SM_SEED_TOTAL = 2,              // seed stage: hits kept by the bucketed binning (k_bkt_extents reads it after later scans)
+    SM_ANY_RANK = 3,                // ranks left in the speculative round
+    SM_PART_ROW = 4,                // + p: first row of emission range p
+    SM_WIDE_ROUND = 12,             // tasks of a round's launch list that need the 32-bit cells
+    SM_LANE_CTR = 13,               // k_align_lane's work counter
+    SM_FLAG = 14,                   // range-table build / counting-pass differ flag
+    SM_WIDE_PART = 16,              // + p: tasks of emission range p's traced list that need the 32-bit cells
+    SM_WORDS = 32
+};
+static_assert(SM_PART_ROW > SM_ANY_RANK && SM_PART_ROW + EMIT_PARTS_MAX <= SM_WIDE_ROUND, "d_small: emission rows");
+static_assert(SM_WIDE_PART > SM_FLAG && SM_WIDE_PART + EMIT_PARTS_MAX <= SM_WORDS, "d_small: wide counts per range");
+
 struct so_ctx {
     int device = 0;
     u32 ncu = 256;          // compute units of the device
@@ -214,7 +231,7 @@ struct so_ctx {
     // scratch
     DevBuf<u32> d_scan_tmp, d_tmp32a, d_tmp32b;
     DevBuf<u64> d_stats;
-    DevBuf<u32> d_small;  // parked scan totals (stash_u32)
+    DevBuf<u32> d_small;  // SM_WORDS words, slots SmallSlot
     DevBuf<u32> ix_bkt, ix_bkt2, ix_flags, ix_ridx, ix_plan, ix_tk;  // index build scratch
     DevBuf<u64> ix_ent, ix_tv;
     DevBuf<u8> d_pcls;
@@ -222,7 +239,7 @@ struct so_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t st_rows = nullptr;  // result rows leave on their own stream: the download of one batch overlaps the next batch's kernels
     hipEvent_t ev_rows = nullptr, ev_rows_done = nullptr;
-    hipEvent_t ev_part[8] = {nullptr};   // emission range p's rows have arrived (the worker converts a range while the next is traced)
+    hipEvent_t ev_part[EMIT_PARTS_MAX] = {nullptr};   // emission range p's rows have arrived (the worker converts a range while the next is traced)
     // the k-mer order of queries too long for the LDS sort (one wave each, milliseconds for a 30 000-residue protein) runs beside the
     // batch's other preparation and the seed passes of the shorter length classes
     hipStream_t st_side = nullptr;
@@ -318,6 +335,10 @@ void parallel_for(i64 n, F f) {
 // ---------------------------------------------------------------------------------------------
 // Search
 // ---------------------------------------------------------------------------------------------
+inline AlnSide aln_side(const SeqSet& s) { return AlnSide{s.d_res.p, s.d_scls.p, s.d_scls4.p, s.d_pcls.p, s.d_pcls4.p, s.d_off.p, s.d_bound.p}; }
+// (alignments asked for) column slots per reported row and their offsets per task, the walks' columns, compacted in row order
+struct AlnChain { DevBuf<u32> units, rofs, aofs, code, words, cofs, comp; };
+
 #define QCLASSES_MAX 5
 struct Batch {
     i64 q_lo = 0, q_hi = 0;  // absolute query ordinals
@@ -397,8 +418,7 @@ struct Batch {
     DevBuf<u32> trace;
     DevBuf<u32> tr_units, tr_ofs;   // trace room per task of a launch list and its exclusive scan (k_trace_units)
     DevBuf<u32> tl_sorted, al_sorted;   // the trace pass's lists ordered by band rows (mixed-length batches)
-    // (alignments asked for) column slots per reported row and their offsets per task, the walks' columns, compacted in row order
-    DevBuf<u32> aunits, arofs, aofs, acode, awords, acofs, acomp;
+    AlnChain aln;
 };
 
 // length classes of the queries: < 512 residues, < 1024, < 2048, < 4096, longer (the aligner's tiled path).  A pass's key widths and

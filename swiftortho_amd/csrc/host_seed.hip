@@ -188,13 +188,13 @@ u32 d2h_u32(so_ctx* c, const u32* p) {
 // Totals of two scans that share d_scan_tmp, fetched with ONE synchronisation: the first total is parked in a
 // device word while the second scan runs.
 void stash_u32(so_ctx* c, const u32* p, int slot) {
-    c->d_small.ensure(32);
+    c->d_small.ensure(SM_WORDS);
     HIP_CHECK(hipMemcpyAsync(c->d_small.p + slot, p, sizeof(u32), hipMemcpyDeviceToDevice, c->st));
 }
 void d2h_pair(so_ctx* c, const u32* second, u32& a, u32& b) {
-    stash_u32(c, second, 1);
+    stash_u32(c, second, SM_STASH1);
     u32* v = (u32*)small_host(c);
-    HIP_CHECK(hipMemcpyAsync(v, c->d_small.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipMemcpyAsync(v, c->d_small.p + SM_STASH0, 2 * sizeof(u32), hipMemcpyDeviceToHost, c->st));
     HIP_CHECK(hipStreamSynchronize(c->st));
     a = v[0], b = v[1];
 }
@@ -408,7 +408,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         b.eff.ensure((size_t)AS * b.dev.Ppad + 4), b.nz.ensure((size_t)AS * b.dev.Ppad + 4);
         launch_effcnt(b.mark.p, b.scnt.p, AS, p_lo, p_hi, b.eff.p, b.nz.p, c->st);
         const u32* dH = scan_u32(b.eff.p + t_lo, b.hoff.p + t_lo, Tp, false, c->d_scan_tmp.p, c->st);
-        stash_u32(c, dH, 0);  // the scan's total lives in d_scan_tmp: park it before the next scan
+        stash_u32(c, dH, SM_STASH0);  // the scan's total lives in d_scan_tmp: park it before the next scan
         const u32* dK = scan_u32(b.nz.p + t_lo, b.cidx.p + t_lo, Tp, false, c->d_scan_tmp.p, c->st);
         d2h_pair(c, dK, H, K);
     }
@@ -546,10 +546,10 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
             if (tab && tune().count_tab == 2) {   // tests: the counting pass must give the same matrix
                 b.bpart.ensure(nm + 4);
                 launch_bkt_pass(false, b.btd.p, qseg, NT, b.cs_hoff.p, b.cs_beg.p, b.cs_kbase.p, dk32, c->ref.d_off.p + ch.seq_lo, L, b.bpart.p, nullptr, c->st);
-                c->d_small.ensure(32);
-                HIP_CHECK(hipMemsetAsync(c->d_small.p + 14, 0, sizeof(u32), c->st));
-                launch_u32_differ(b.bmat.p, b.bpart.p, nm, c->d_small.p + 14, c->st);
-                const u32 nd = d2h_u32(c, c->d_small.p + 14);
+                c->d_small.ensure(SM_WORDS);
+                HIP_CHECK(hipMemsetAsync(c->d_small.p + SM_FLAG, 0, sizeof(u32), c->st));
+                launch_u32_differ(b.bmat.p, b.bpart.p, nm, c->d_small.p + SM_FLAG, c->st);
+                const u32 nd = d2h_u32(c, c->d_small.p + SM_FLAG);
                 if (nd) throw SoError("range-table counts differ from the counting pass in " + std::to_string(nd) + " cells");
             }
         }
@@ -558,9 +558,9 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         c->d_scan_tmp.ensure(scan_u32_temp_elems(npart + 1) + 8);
         launch_bkt_colsum(b.bmat.p, NT, L.R, b.bpart.p, c->st);
         const u32* dHv = scan_u32(b.bpart.p, b.bpart.p, npart, false, c->d_scan_tmp.p, c->st);
-        stash_u32(c, dHv, 2);   // the total lives in d_scan_tmp: park it (k_bkt_extents reads it after later scans)
+        stash_u32(c, dHv, SM_SEED_TOTAL);   // the total lives in d_scan_tmp: park it (k_bkt_extents reads it after later scans)
         launch_bkt_colscan(b.bmat.p, NT, L.R, b.bpart.p, c->st);
-        const u32 Hv = d2h_u32(c, c->d_small.p + 2);  // hits kept (all but the dropped offset-0 ones)
+        const u32 Hv = d2h_u32(c, c->d_small.p + SM_SEED_TOTAL);  // hits kept (all but the dropped offset-0 ones)
         sc.lap("seed.bucket_count");
         b.hits32.ensure((size_t)H + 2);
         {
@@ -577,7 +577,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         if (w32) b.hits32s.ensure((size_t)H + 8);   // (k_ungap1's chains read four words ahead)
         else b.keys2.ensure((size_t)H + 2);
         b.bext.ensure((size_t)nb + 4);
-        launch_bkt_extents(b.bmat.p, b.bt0.p, NT, L.R, nqp, nb, c->d_small.p + 2, b.bext.p, c->st);
+        launch_bkt_extents(b.bmat.p, b.bt0.p, NT, L.R, nqp, nb, c->d_small.p + SM_SEED_TOTAL, b.bext.p, c->st);
         {
             ProfTimer pt(c, &c->cnt.bgroup_ms, &c->cnt.bgroup_launches);
             launch_bkt_group(b.hits32.p, b.bext.p, nb, L, kl, w32 ? nullptr : b.keys2.p, w32 ? b.hits32s.p : nullptr, b.bflag.p, c->st);
@@ -780,7 +780,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
             HIP_CHECK(hipMemcpyAsync(b.bccnt.p, qcnt + qa, (size_t)nqp * sizeof(u32), hipMemcpyDeviceToDevice, c->st));
             HIP_CHECK(hipMemsetAsync(b.bccnt.p + nqp, 0, 2 * sizeof(u32), c->st));
             const u32* dT = scan_u32(b.bccnt.p, b.bccnt.p, (size_t)nqp + 1, false, c->d_scan_tmp.p, c->st);
-            stash_u32(c, dT, 0);
+            stash_u32(c, dT, SM_STASH0);
             u32 flag = 0;
             d2h_pair(c, b.bflag.p, NS, flag);
             if (!flag) {
@@ -808,12 +808,12 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         ensure_sort_tmp(c, sort_pairs_u64_u32_temp_bytes(NP, 64));
         sort_pairs_u64_u32(c->d_sort_tmp.p, c->d_sort_tmp.cap, q_qs, b.p_qs2.p, b.pidx.p, b.pidx2.p, NP, klr.bs + kl.bq, c->st);
         b.flags.ensure((size_t)NP + 4), b.gidx.ensure((size_t)NP + 4);
-        c->d_small.ensure(32);
-        launch_seg_flags(b.p_qs2.p, NP, b.flags.p, c->d_small.p, c->st);
+        c->d_small.ensure(SM_WORDS);
+        launch_seg_flags(b.p_qs2.p, NP, b.flags.p, c->d_small.p + SM_STASH0, c->st);
         const u32* dS = scan_u32(b.flags.p, b.gidx.p, NP, false, c->d_scan_tmp.p, c->st);
-        // per-query candidate segments and the longest one (d_small[0]), fetched with the candidate total
+        // per-query candidate segments and the longest one (SM_STASH0), fetched with the candidate total
         b.qseg.ensure((size_t)b.nq + 4);
-        launch_qseg(b.p_qs2.p, NP, b.gidx.p, dS, klr.bs, qa, qb, b.qseg.p, c->d_small.p, c->st);
+        launch_qseg(b.p_qs2.p, NP, b.gidx.p, dS, klr.bs, qa, qb, b.qseg.p, c->d_small.p + SM_STASH0, c->st);
         d2h_pair(c, dS, maxseg, NS);
         b.shead.ensure((size_t)NS + 2);
         if (tune().debug) fprintf(stderr, "[sohit] seed pass: queries %u..%u hits %u seeds %u pass records %u candidates %u\n", qa, qb, H, K, NP, NS);

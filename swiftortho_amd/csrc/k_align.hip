@@ -507,58 +507,39 @@ __global__ __launch_bounds__(256) void k_trace_units(const AlnTask* __restrict__
     units[t] = ((w + 63u) & ~63u) / TRACE_UNIT;
 }
 u32 align_trace_unit() { return TRACE_UNIT; }
-void launch_trace_units(const AlnTask* tasks, const u32* ridx, u32 n, const u32* qoff, const u32* roff, u32* units /*n + 1*/, hipStream_t st) {
-    hipLaunchKernelGGL(k_trace_units, dim3((n + 1 + 255) / 256), dim3(256), 0, st, tasks, ridx, n, qoff, roff, units);
+void launch_trace_units(const AlnTask* tasks, const u32* ridx, u32 n, const AlnSeqs& s, u32* units /*n + 1*/, hipStream_t st) {
+    hipLaunchKernelGGL(k_trace_units, dim3((n + 1 + 255) / 256), dim3(256), 0, st, tasks, ridx, n, s.q.off, s.r.off, units);
 }
 
-// list positions offered to the wave walks (SOHIT_TRACE_WAVE_ROWS = 0: none)
-static inline u32 traceback_waves(u32 ntasks) {
-    return tune().trace_wave_rows > 0 ? (u32)std::min<long long>(ntasks, std::max<long long>(0, tune().trace_wave_max)) : 0u;
-}
-
-// with_traceback = false: scores only (trace may be null); true: traces + traceback statistics.  n_wide (with_traceback): the leading
-// list positions that need the 32-bit cells; the rest is aligned by the packed kernel (ntasks: all of them by the 32-bit one)
-void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u8* q_scls, const u8* q_scls4, const u32* qoff,
-                  const u8* r_res, const u8* r_scls, const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride,
-                  const u32* tofs, AlnRes* out, bool with_traceback, hipStream_t st, u32 n_wide, PkCls pk, u32* acode, const u32* aofs) {
+void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, hipStream_t st) {
     if (!ntasks) return;
-    if (!with_traceback) {
-        hipLaunchKernelGGL((k_align<false>), dim3((ntasks + 15) / 16), dim3(256), 0, st, tasks, ridx, ntasks, q_scls, q_scls4, qoff, r_scls, r_scls4,
-                           roff, b62g, trace, trace_stride, (const u32*)nullptr, out, (u32*)nullptr, 0u);
-        return;
-    }
-    launch_align_traced(tasks, ridx, ntasks, q_scls, q_scls4, qoff, r_scls, r_scls4, roff, b62g, trace, trace_stride, tofs, out, nullptr, 0u, st, n_wide, pk);
-    const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
-                       r_res, roff, trace, trace_stride, (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows, acode, aofs);
+    hipLaunchKernelGGL((k_align<false>), dim3((ntasks + 15) / 16), dim3(256), 0, st, tasks, ridx, ntasks, s.q.scls, s.q.scls4, s.q.off, s.r.scls, s.r.scls4,
+                       s.r.off, s.b62, (u32*)nullptr, 0u, (const u32*)nullptr, out, (u32*)nullptr, 0u);
 }
 
-void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_scls, const u8* q_scls4, const u32* qoff, const u8* r_scls,
-                         const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
-                         u32* tpos_out, u32 tpos_base, hipStream_t st, u32 n_wide, PkCls pk) {
+void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, const u32* trace, u32 trace_stride, const u32* tpos,
+                      const u32* tofs, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs) {
     if (!ntasks) return;
-    n_wide = pk.q ? std::min(n_wide, ntasks) : ntasks;   // (no padded arrays given: everything by the 32-bit kernel)
+    // list positions offered to the wave walks (SOHIT_TRACE_WAVE_ROWS = 0: none)
+    const u32 nw = tune().trace_wave_rows > 0 ? (u32)std::min<long long>(ntasks, std::max<long long>(0, tune().trace_wave_max)) : 0u;
+    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, s.q.res, s.q.off,
+                       s.r.res, s.r.off, trace, trace_stride, tpos, tofs, out, nw, (int)tune().trace_wave_rows, acode, aofs);
+}
+
+void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
+                         u32* tpos_out, u32 tpos_base, hipStream_t st, u32 n_wide) {
+    if (!ntasks) return;
+    n_wide = std::min(n_wide, ntasks);
     if (n_wide)
-        hipLaunchKernelGGL((k_align<true>), dim3((n_wide + 15) / 16), dim3(256), 0, st, tasks, ridx, n_wide, q_scls, q_scls4, qoff, r_scls, r_scls4, roff,
-                           b62g, trace, trace_stride, tofs, out, tpos_out, tpos_base);
-    launch_align_pk_traced(tasks, ridx, n_wide, ntasks, pk, qoff, roff, b62g, trace, trace_stride, tofs, out, tpos_out, tpos_base, st);
+        hipLaunchKernelGGL((k_align<true>), dim3((n_wide + 15) / 16), dim3(256), 0, st, tasks, ridx, n_wide, s.q.scls, s.q.scls4, s.q.off, s.r.scls, s.r.scls4,
+                           s.r.off, s.b62, trace, trace_stride, tofs, out, tpos_out, tpos_base);
+    launch_align_pk_traced(tasks, ridx, n_wide, ntasks, s, trace, trace_stride, tofs, out, tpos_out, tpos_base, st);
 }
 
-// the walks alone over list positions whose traces sit at tofs[position] (the alignments were made by an earlier launch_align_traced)
-void launch_traceback_tofs(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs) {
-    if (!ntasks) return;
-    const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
-                       r_res, roff, trace, trace_stride, (const u32*)nullptr, tofs, out, nw, (int)tune().trace_wave_rows, acode, aofs);
-}
-
-void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs) {
-    if (!ntasks) return;
-    const u32 nw = traceback_waves(ntasks);
-    hipLaunchKernelGGL(acode ? k_traceback<true> : k_traceback<false>, dim3(nw + (ntasks + 63) / 64), dim3(64), 0, st, tasks, ridx, ntasks, q_res, qoff,
-                       r_res, roff, trace, trace_stride, tpos, (const u32*)nullptr, out, nw, (int)tune().trace_wave_rows, acode, aofs);
+void launch_align_walk(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
+                       hipStream_t st, u32 n_wide, u32* acode, const u32* aofs) {
+    launch_align_traced(tasks, ridx, ntasks, s, trace, trace_stride, tofs, out, nullptr, 0u, st, n_wide);
+    launch_traceback(tasks, ridx, ntasks, s, trace, trace_stride, nullptr, tofs, out, st, acode, aofs);
 }
 
 // ---- the reported rows' alignments (so_search_loaded_aln) ------------------------------------------------------------------------
@@ -597,8 +578,8 @@ __global__ __launch_bounds__(256) void k_aln_compact(const u32* __restrict__ sel
     for (u32 k = threadIdx.x & 15u; k < nwd; k += 16u) dst[(size_t)o + k] = src[k];
 }
 u32 aln_unit_words() { return ALN_UNIT; }
-void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const u32* qoff, const u32* roff, u32* units, hipStream_t st) {
-    hipLaunchKernelGGL(k_aln_units, dim3((n + 1 + 255) / 256), dim3(256), 0, st, tasks, sel_idx, n, qoff, roff, units);
+void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const AlnSeqs& s, u32* units, hipStream_t st) {
+    hipLaunchKernelGGL(k_aln_units, dim3((n + 1 + 255) / 256), dim3(256), 0, st, tasks, sel_idx, n, s.q.off, s.r.off, units);
 }
 void launch_aln_scatter(const u32* sel_idx, u32 n, const u32* rofs, u32* aofs, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_aln_scatter, dim3((n + 255) / 256), dim3(256), 0, st, sel_idx, n, rofs, aofs);

@@ -352,20 +352,19 @@ int align_pk_max_len() { return 740; }
 // ... or whose score bound does: (score << 2) + 47 + 44 <= 32767
 u32 align_pk_max_score() { return 8169; }
 
-void launch_align_pk(const AlnTask* tasks, const u32* ridx, u32 ntasks, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g, AlnRes* out,
-                     hipStream_t st) {
+void launch_align_pk(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, hipStream_t st) {
     if (!ntasks) return;
     const u32 pairs = (ntasks + 1) / 2;
-    hipLaunchKernelGGL((k_align_pk<false>), dim3((pairs + PK_THREADS / 16 - 1) / (PK_THREADS / 16)), dim3(PK_THREADS), 0, st, tasks, ridx, ntasks, pk.q, pk.q4, qoff,
-                       pk.r, pk.r4, roff, b62g, out, (u32*)nullptr, 0u, (const u32*)nullptr, (u32*)nullptr, 0u, 0u);
+    hipLaunchKernelGGL((k_align_pk<false>), dim3((pairs + PK_THREADS / 16 - 1) / (PK_THREADS / 16)), dim3(PK_THREADS), 0, st, tasks, ridx, ntasks, s.q.pcls,
+                       s.q.pcls4, s.q.off, s.r.pcls, s.r.pcls4, s.r.off, s.b62, out, (u32*)nullptr, 0u, (const u32*)nullptr, (u32*)nullptr, 0u, 0u);
 }
 
 // with traces (the walk is k_traceback's), list positions [t0, t1) of a launch list: ridx, tofs (or the position itself) and the trace room
 // are the whole list's, as k_align<true> and k_traceback see them; tofs / tpos_out / tpos_base as for k_align<true>
-void launch_align_pk_traced(const AlnTask* tasks, const u32* ridx, u32 t0, u32 t1, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g,
-                            u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, u32* tpos_out, u32 tpos_base, hipStream_t st) {
+void launch_align_pk_traced(const AlnTask* tasks, const u32* ridx, u32 t0, u32 t1, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs,
+                            AlnRes* out, u32* tpos_out, u32 tpos_base, hipStream_t st) {
     if (t1 <= t0) return;
     const u32 pairs = (t1 - t0 + 1) / 2;
-    hipLaunchKernelGGL((k_align_pk<true>), dim3((pairs + PK_THREADS / 16 - 1) / (PK_THREADS / 16)), dim3(PK_THREADS), 0, st, tasks, ridx, t1, pk.q, pk.q4, qoff,
-                       pk.r, pk.r4, roff, b62g, out, trace, trace_stride, tofs, tpos_out, tpos_base, t0);
+    hipLaunchKernelGGL((k_align_pk<true>), dim3((pairs + PK_THREADS / 16 - 1) / (PK_THREADS / 16)), dim3(PK_THREADS), 0, st, tasks, ridx, t1, s.q.pcls,
+                       s.q.pcls4, s.q.off, s.r.pcls, s.r.pcls4, s.r.off, s.b62, out, trace, trace_stride, tofs, tpos_out, tpos_base, t0);
 }

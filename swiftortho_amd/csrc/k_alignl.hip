@@ -223,8 +223,8 @@ __global__ __launch_bounds__(AL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[0] = __builtin_readcyclecounter() - t_core, dbg[1] = __builtin_amdgcn_s_memrealtime() - t_real;
 }
 
-void launch_align_lane(const AlnTask* tasks, const u32* ridx, u32 ntasks, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g, AlnRes* out,
-                       u32* work_ctr /*one word, zeroed here*/, u32 ncu, hipStream_t st) {
+void launch_align_lane(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, u32* work_ctr /*one word, zeroed here*/, u32 ncu,
+                       hipStream_t st) {
     if (!ntasks) return;
     const u32 pairs = (ntasks + 1) / 2;
     HIP_CHECK(hipMemsetAsync(work_ctr, 0, sizeof(u32), st));
@@ -232,8 +232,8 @@ void launch_align_lane(const AlnTask* tasks, const u32* ridx, u32 ntasks, PkCls 
     static unsigned long long* d_dbg = nullptr;
     const bool dbg = tune().debug;
     if (dbg && !d_dbg) HIP_CHECK(hipMalloc((void**)&d_dbg, 16));
-    hipLaunchKernelGGL(k_align_lane, dim3(grid), dim3(AL_THREADS), 0, st, tasks, ridx, ntasks, pk.q, pk.q4, qoff, pk.r, pk.r4, roff, b62g, out, work_ctr,
-                       dbg ? d_dbg : nullptr);
+    hipLaunchKernelGGL(k_align_lane, dim3(grid), dim3(AL_THREADS), 0, st, tasks, ridx, ntasks, s.q.pcls, s.q.pcls4, s.q.off, s.r.pcls, s.r.pcls4, s.r.off, s.b62,
+                       out, work_ctr, dbg ? d_dbg : nullptr);
     if (dbg) {   // SOHIT_DEBUG: the shader clock the launch ran at (core-clock counter over the constant 100 MHz one, first workgroup)
         unsigned long long h[2];
         HIP_CHECK(hipMemcpyAsync(h, d_dbg, 16, hipMemcpyDeviceToHost, st));

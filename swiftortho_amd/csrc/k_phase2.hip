@@ -674,9 +674,8 @@ __global__ __launch_bounds__(256) void k_task_rows(const AlnTask* __restrict__ t
     }
 }
 
-void launch_task_rows(const AlnTask* tasks, const u32* ridx, u32 n, const u32* qoff, const u32* roff, const u32* qbound, const u32* rbound, int pk_len,
-                      u32 pk_score, u32* n_wide, unsigned long long* cells_wide, u64* keys, hipStream_t st) {
+void launch_task_rows(const AlnTask* tasks, const u32* ridx, u32 n, const AlnSeqs& s, u32* n_wide, unsigned long long* cells_wide, u64* keys, hipStream_t st) {
     if (!n) return;
-    hipLaunchKernelGGL(k_task_rows, dim3((n + 255) / 256), dim3(256), 0, st, tasks, ridx, n, qoff, roff, qbound, rbound, pk_len, pk_score, n_wide, cells_wide,
-                       keys);
+    hipLaunchKernelGGL(k_task_rows, dim3((n + 255) / 256), dim3(256), 0, st, tasks, ridx, n, s.q.off, s.r.off, s.q.bound, s.r.bound, align_pk_max_len(),
+                       align_pk_max_score(), n_wide, cells_wide, keys);
 }

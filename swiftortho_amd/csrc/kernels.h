@@ -43,9 +43,10 @@ void launch_layout(const u8* res, const u32* off, u32 nseq, u32 P, u32 Ppad, con
 // score classes of n residues; scls / scls4 point SCLS_PAD_FRONT bytes into allocations of n + SCLS_PAD_FRONT + SCLS_PAD_BACK
 // bytes, and the pads are zeroed here
 #define PCLS_PAD 48   // sentinel bytes behind every sequence of the packed aligner's class arrays (k_pad_cls)
-struct PkCls {   // the four padded class arrays of a (query batch, reference) pair
-    const u8 *q, *q4, *r, *r4;
-};
+// what the phase-2 aligners, the walk and the sizing kernels read of one side of a (query batch, reference) pair: residues, score classes
+// and class * 4 (launch_scls), the same with PCLS_PAD sentinels behind every sequence (launch_pad_cls), offsets, score bounds (launch_seq_bound)
+struct AlnSide { const u8 *res, *scls, *scls4, *pcls, *pcls4; const u32 *off, *bound; };
+struct AlnSeqs { AlnSide q, r; const signed char* b62 /*substitution scores by score class*/; };
 void launch_pad_cls(const u8* scls, const u32* off, u32 nseq, u8* out /*PCLS_PAD bytes into an allocation of nres + PCLS_PAD * (nseq + 2) + 64*/, u8* out4,
                     hipStream_t st);
 #define SCLS_PAD_FRONT 16
@@ -173,26 +174,33 @@ void launch_emit_cands(const u32* order, u32 n, const u64* sorted_key /*the fina
 // complete after four blocks.
 #define TRACE_WORD(b, l) ((((u32)(b) >> 2) << 6) | ((u32)(l) << 2) | ((u32)(b) & 3u))
 u32 align_trace_stride(int max_rows);
-void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u8* q_scls, const u8* q_scls4, const u32* qoff,
-                  const u8* r_res, const u8* r_scls, const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride,
-                  const u32* tofs /*traces: start of launch position t's trace in units of trace_stride words, or null = t*/, AlnRes* out,
-                  bool with_traceback, hipStream_t st, u32 n_wide /*with_traceback: leading positions for the 32-bit kernel, the rest packed*/,
-                  PkCls pk = PkCls{nullptr, nullptr, nullptr, nullptr},
-                  u32* acode = nullptr /*non-null: the walks write their columns (k_traceback<true>) to the slots aofs[task] gives*/,
-                  const u32* aofs = nullptr);
+// scores only (k_align<false>)
+void launch_align(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, hipStream_t st);
+// alignments with traces.  n_wide: the leading list positions that need the 32-bit cells (k_align<true>), the rest by the packed
+// kernel (n_wide = ntasks: all of them by the 32-bit one); tofs: start of position t's trace in units of trace_stride words, or null = t
+void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
+                         u32* tpos_out /*tofs: receives tpos_base + tofs[t]*/, u32 tpos_base, hipStream_t st, u32 n_wide);
+// the walks over the traces of an earlier launch_align_traced; exactly one of tpos (per task: the speculative round's kept traces) and
+// tofs (per list position) says where they sit.  acode (non-null): the walks write their columns (k_traceback<true>) to the slots aofs[task] gives
+void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, const u32* trace, u32 trace_stride, const u32* tpos,
+                      const u32* tofs, AlnRes* out, hipStream_t st, u32* acode, const u32* aofs);
+// launch_align_traced, then the walks at once
+void launch_align_walk(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
+                       hipStream_t st, u32 n_wide, u32* acode, const u32* aofs);
 // trace room each task of a launch list needs, in units of align_trace_unit() words (+ a 0 behind the last): scanned, they are `tofs`
 u32 align_trace_unit();
-void launch_trace_units(const AlnTask* tasks, const u32* ridx, u32 n, const u32* qoff, const u32* roff, u32* units /*n + 1*/, hipStream_t st);
+void launch_trace_units(const AlnTask* tasks, const u32* ridx, u32 n, const AlnSeqs& s, u32* units /*n + 1*/, hipStream_t st);
 
 // k_align16.hip: score-only aligner in packed 16-bit arithmetic, two alignments per register
 bool align_pk_supported(hipStream_t st);   // the d16 load behaviour k_align_pk relies on (probed once per process)
 int align_pk_max_len();   // largest min(rows, columns) it can score whatever the residues
 u32 align_pk_max_score(); // largest alignment score its cells hold
 // one lane per alignment pair, score-only, persistent waves (k_alignl.hip): tasks whose windows end where their sequences end
-void launch_align_lane(const AlnTask* tasks, const u32* ridx, u32 ntasks, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g, AlnRes* out,
-                       u32* work_ctr, u32 ncu, hipStream_t st);
-void launch_align_pk(const AlnTask* tasks, const u32* ridx, u32 ntasks, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g, AlnRes* out,
-                     hipStream_t st);
+void launch_align_lane(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, u32* work_ctr, u32 ncu, hipStream_t st);
+void launch_align_pk(const AlnTask* tasks, const u32* ridx, u32 ntasks, const AlnSeqs& s, AlnRes* out, hipStream_t st);
+// list positions [t0, t1) by the packed kernel, traces in the same layout (codes = tags: AlnRes.pad = 1)
+void launch_align_pk_traced(const AlnTask* tasks, const u32* ridx, u32 t0, u32 t1, const AlnSeqs& s, u32* trace, u32 trace_stride, const u32* tofs,
+                            AlnRes* out, u32* tpos_out, u32 tpos_base, hipStream_t st);
 
 // k_phase2.hip
 void launch_gather_cands(const u32* src_q, const u32* src_rec, u32 n, const u32* cqoff, const u32* prior, const u32* qcoff,
@@ -266,22 +274,10 @@ void launch_round_idx_spec(const u32* tcnt_pk, const u32* scnt, const u32* poff,
                            const u32* roffc, const u32* rk_slot, const u32* st_state, u32 nq, u32* ridx, u32* sidx, hipStream_t st);
 void launch_trace_flags(const u32* sel_idx, u32 n, const u32* tpos, u32* flags, hipStream_t st);
 void launch_trace_split(const u32* sel_idx, u32 n, const u32* flags, const u32* fscan, u32* list_b, u32* list_a, hipStream_t st);
-// k_align.hip: the two halves of launch_align(..., true) on their own (speculative traces: the walk runs long after the alignment)
-void launch_align_traced(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_scls, const u8* q_scls4, const u32* qoff, const u8* r_scls,
-                         const u8* r_scls4, const u32* roff, const signed char* b62g, u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out,
-                         u32* tpos_out /*tofs: receives tpos_base + tofs[t]*/, u32 tpos_base, hipStream_t st, u32 n_wide, PkCls pk);
-// k_align16.hip: list positions [t0, t1) by the packed kernel, traces in the same layout (codes = tags: AlnRes.pad = 1)
-void launch_align_pk_traced(const AlnTask* tasks, const u32* ridx, u32 t0, u32 t1, PkCls pk, const u32* qoff, const u32* roff, const signed char* b62g,
-                            u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, u32* tpos_out, u32 tpos_base, hipStream_t st);
-void launch_traceback(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                      const u32* trace, u32 trace_stride, const u32* tpos, AlnRes* out, hipStream_t st, u32* acode = nullptr, const u32* aofs = nullptr);
-void launch_traceback_tofs(const AlnTask* tasks, const u32* ridx, u32 ntasks, const u8* q_res, const u32* qoff, const u8* r_res, const u32* roff,
-                           const u32* trace, u32 trace_stride, const u32* tofs, AlnRes* out, hipStream_t st, u32* acode = nullptr,
-                           const u32* aofs = nullptr);
 // the reported rows' alignments (k_align.hip): column slots per row (units of aln_unit_words() words, + a 0 behind the last), handed to the
 // walks per task; then the words each row's columns took (+ a 0), and the columns compacted in row order at the scan of those
 u32 aln_unit_words();
-void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const u32* qoff, const u32* roff, u32* units /*n + 1*/, hipStream_t st);
+void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const AlnSeqs& s, u32* units /*n + 1*/, hipStream_t st);
 void launch_aln_scatter(const u32* sel_idx, u32 n, const u32* rofs, u32* aofs /*per task*/, hipStream_t st);
 void launch_aln_words(const u32* sel_idx, u32 n, const AlnRes* res, u32* words /*n + 1*/, hipStream_t st);
 void launch_aln_compact(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const u32* cofs /*n + 1*/, u32* dst, hipStream_t st);
@@ -291,5 +287,5 @@ void launch_stop_round_w(const AlnTask* tasks, const AlnRes* res, const u32* qco
                          unsigned long long* qcells /*[nq], += cells of the round*/, hipStream_t st);
 void launch_sum_u64(const unsigned long long* x, u32 n, unsigned long long* total, hipStream_t st);
 // keys[t] = 8191 - band rows of task t, | 8192 when the packed aligner can take it (n_wide != null: the others are counted there; null: all can)
-void launch_task_rows(const AlnTask* tasks, const u32* ridx, u32 n, const u32* qoff, const u32* roff, const u32* qbound, const u32* rbound, int pk_len,
-                      u32 pk_score, u32* n_wide, unsigned long long* cells_wide /*+= their band cells*/, u64* keys, hipStream_t st);
+void launch_task_rows(const AlnTask* tasks, const u32* ridx, u32 n, const AlnSeqs& s, u32* n_wide, unsigned long long* cells_wide /*+= their band cells*/,
+                      u64* keys, hipStream_t st);
