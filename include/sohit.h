@@ -157,6 +157,21 @@ void so_free_hits(so_hit *hits);
 int so_search_loaded_aln(so_ctx *ctx, int64_t q_lo, int64_t q_hi, so_hit **hits, int64_t *n_hits, char **aln, int64_t *aln_bytes);
 void so_free_aln(char *aln);
 
+/* The search with a CIGAR behind every row.  Same rows as so_search_loaded() (same kernels and bytes); in addition row k's
+ * alignment path is ops[op_off[k] .. op_off[k + 1]) (op_off holds *n_hits + 1 offsets, op_off[0] = 0): one uint32 per run,
+ * length << 4 | op with op 0 = M (both sides advance; match or mismatch), 1 = I (the query advances alone), 2 = D (the subject
+ * advances alone) -- the BAM packing --, first column first.  Canonical: no run of length 0, neighbouring runs differ in op.
+ * Per row: the lengths add up to hits[k].aln, the M + I lengths to qed - qst + 1, the M + D lengths to sed - sst + 1.  The runs
+ * are coded on the GPU from the columns the traceback walks write; they describe the same path as so_search_loaded_aln()'s
+ * strings (a row of a 4096-wide tile carries its tile's path) and, unlike the strings, stay unambiguous where a sequence holds a
+ * literal '-' residue.  One call gives strings or CIGARs, not both.  Released with so_free_cigar().
+ * so_format_cigar() renders runs as text, "<length><op>" per run with nothing between (35M2D10M): returns the length of the
+ * text and writes at most cap - 1 characters and a NUL into buf (buf may be NULL); -1 for a run of length 0 or an unknown op.
+ * Host-only: needs no ctx and no device. */
+int so_search_loaded_cigar(so_ctx *ctx, int64_t q_lo, int64_t q_hi, so_hit **hits, int64_t *n_hits, uint32_t **ops, int64_t **op_off);
+void so_free_cigar(uint32_t *ops, int64_t *op_off);
+int64_t so_format_cigar(const uint32_t *ops, int64_t n_ops, char *buf, int64_t cap);
+
 /* Multi-GPU support.  The reference runs one fsearch-c process per query block and joins the part files with `cat`
  * (find_hit.py:107-146); here one process per GPU searches a query shard and the hit records are exchanged over RCCL, so
  * they must be able to stay in HBM until after the exchange:
@@ -175,6 +190,10 @@ int so_query_work(so_ctx *ctx, int64_t q_lo, int64_t q_hi, uint64_t *work);
  * reference files.  mode "w" or "a" (-O).  so_format_hit() renders one row into buf. */
 int so_write_sc(so_ctx *ctx, const so_hit *hits, int64_t n_hits, const char *path, const char *mode);
 int64_t so_format_hit(so_ctx *ctx, const so_hit *hit, char *buf, int64_t cap);
+/* so_write_sc() with a 17th column: every row's first 16 columns are so_write_sc()'s bytes, followed by a tab and the row's CIGAR
+ * as so_format_cigar() renders it (ops / op_off as so_search_loaded_cigar() returns them). */
+int so_write_sc_cigar(so_ctx *ctx, const so_hit *hits, int64_t n_hits, const uint32_t *ops, const int64_t *op_off, const char *path,
+                      const char *mode);
 
 /* Introspection (tests, bench). */
 /* switch params.profile (HIP-event kernel timers + stage laps, which synchronise the stream) on or off */
@@ -218,6 +237,13 @@ int so_align_pairs(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, con
  * Same tasks, order and refusals as so_align_pairs; released with so_free_aln(). */
 int so_align_pairs_aln(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, const uint32_t *order, int32_t *out, char **aln,
                        int64_t *aln_bytes);
+
+/* tests: so_align_pairs for the traced kernels (3, 4) that also returns every task's CIGAR, built by the search's own chain (column
+ * slots, the emitting walk, the run counting, scan and run emitting kernels): task t's runs are ops[op_off[t] .. op_off[t + 1])
+ * (op_off: n + 1), packed as so_search_loaded_cigar() packs them; a task without an alignment has no runs.  Same tasks, order and
+ * refusals as so_align_pairs; released with so_free_cigar(). */
+int so_align_pairs_cigar(so_ctx *ctx, int kernel, int64_t n, const int64_t *task6, const uint32_t *order, int32_t *out, uint32_t **ops,
+                         int64_t **op_off);
 
 /* Markov clustering of one block of the orthology graph.  Replaces: the matrix loop of bin/find_cluster.py
  * `mcl` (652-689) with `normalize` (636-646) as `mcl_xyz` (1425-1467) calls it on a float32 scipy csr_matrix -- column

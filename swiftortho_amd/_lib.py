@@ -42,7 +42,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_search", "so_free_hits", "so_search_loaded_aln", "so_free_aln", "so_write_sc", "so_format_hit", "so_get_counters", "so_reset_counters", "so_timing_report",
            "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_align_pairs", "so_align_pairs_aln", "so_set_profile",
            "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
-           "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows"]
+           "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
+           "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar"]
 
 
 class SoMclResult(C.Structure):
@@ -111,6 +112,13 @@ def load():
     L.so_free_hits.argtypes = [C.POINTER(SoHit)]
     L.so_search_loaded_aln.argtypes = [vp, i64, i64, C.POINTER(C.POINTER(SoHit)), C.POINTER(i64), C.POINTER(C.c_void_p), C.POINTER(i64)]
     L.so_free_aln.argtypes = [vp]
+    L.so_search_loaded_cigar.argtypes = [vp, i64, i64, C.POINTER(C.POINTER(SoHit)), C.POINTER(i64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.so_free_cigar.argtypes = [vp, vp]
+    L.so_free_cigar.restype = None
+    L.so_format_cigar.restype = i64
+    L.so_format_cigar.argtypes = [vp, i64, vp, i64]
+    L.so_write_sc_cigar.argtypes = [vp, C.POINTER(SoHit), i64, vp, vp, cp, cp]
+    L.so_align_pairs_cigar.argtypes = [vp, C.c_int, i64, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.so_search_device.argtypes = [vp, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.so_device_hits_copy.argtypes = [vp, vp, i64]
     L.so_query_work.argtypes = [vp, i64, i64, vp]

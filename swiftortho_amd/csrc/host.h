@@ -261,6 +261,7 @@ struct so_ctx {
     size_t pinned_cap = 0;
     // alignments of the reported rows (so_search_loaded_aln): the walks' compacted columns + the batch's query residues, staged pinned
     bool want_aln = false;
+    bool want_cigar = false;   // (so_search_loaded_cigar) the rows' CIGARs instead: run offsets + runs, staged in the same buffer
     void* pinned_aln = nullptr;
     size_t pinned_aln_cap = 0;
     hipEvent_t ev_aln = nullptr;
@@ -270,6 +271,7 @@ struct so_ctx {
         bool active = false;
         size_t base = 0, n = 0;
         bool aln = false;   // the job appends the rows' strings to the result's AlnBytes
+        bool cig = false;   // the job appends the rows' runs to the result's CigarBuf
         std::atomic<i64> dropped{0};
         std::exception_ptr err;
     } emit;
@@ -337,7 +339,11 @@ void parallel_for(i64 n, F f) {
 // ---------------------------------------------------------------------------------------------
 inline AlnSide aln_side(const SeqSet& s) { return AlnSide{s.d_res.p, s.d_scls.p, s.d_scls4.p, s.d_pcls.p, s.d_pcls4.p, s.d_off.p, s.d_bound.p}; }
 // (alignments asked for) column slots per reported row and their offsets per task, the walks' columns, compacted in row order
-struct AlnChain { DevBuf<u32> units, rofs, aofs, code, words, cofs, comp; };
+// (CIGARs asked for) the same slots; runs per row, their offsets (op_off) and the runs, in row order
+struct AlnChain {
+    DevBuf<u32> units, rofs, aofs, code, words, cofs, comp, runs, oofs, ops;
+    size_t slot_words = 0;   // words of the slots aln_slots laid out last
+};
 
 #define QCLASSES_MAX 5
 struct Batch {
@@ -517,6 +523,50 @@ struct HitCache {
     }
 };
 extern HitCache g_hit_cache;
+// the same for a released CIGAR result (so_free_cigar): its runs (config 3: 118 MB) and its offsets, under the same switch and bounds
+struct BufCache {
+    std::mutex mu;
+    void* p = nullptr;
+    size_t bytes = 0;
+    void* take(size_t& cap_bytes) {
+        std::lock_guard<std::mutex> g(mu);
+        void* r = p;
+        cap_bytes = bytes;
+        p = nullptr, bytes = 0;
+        return r;
+    }
+    static void release(void* q) {
+        if (!q) return;
+        if (malloc_usable_size(q) < ((size_t)8 << 20)) {
+            free(q);
+            return;
+        }
+        try {
+            std::thread([q] { free(q); }).detach();
+        } catch (...) {
+            free(q);
+        }
+    }
+    void give(void* q) {
+        if (!q) return;
+        const size_t b = malloc_usable_size(q);
+        if (!HitCache::enabled() || b < ((size_t)1 << 20) || b > ((size_t)2 << 30)) {
+            release(q);
+            return;
+        }
+        void* drop = q;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (b > bytes) drop = p, p = q, bytes = b;
+        }
+        release(drop);
+    }
+    void clear() {
+        size_t n;
+        free(take(n));
+    }
+};
+extern BufCache g_cig_ops_cache, g_cig_off_cache;
 
 
 // growable result array handed to the caller as-is: no zero-fill, no final copy
@@ -541,10 +591,49 @@ struct AlnBytes {
     ~AlnBytes() { free(p); }
 };
 
+// the rows' CIGARs (so_search_loaded_cigar): row k's runs are ops[off[k] .. off[k + 1]), length << 4 | op in alignment order; off[0] = 0
+struct CigarBuf {
+    uint32_t* ops = nullptr;
+    int64_t* off = nullptr;
+    size_t n = 0, cap = 0, off_cap = 0;   // runs held, room for runs, room for offsets
+    void grow(size_t extra) {
+        if (n + extra <= cap) return;
+        if (!ops) ops = (uint32_t*)g_cig_ops_cache.take(cap), cap /= sizeof(uint32_t);   // the previous search's array, pages still mapped
+        if (n + extra <= cap) return;
+        const size_t nc = std::max<size_t>(n + extra, cap + cap / 2 + 1024);
+        uint32_t* np_ = (uint32_t*)realloc(ops, nc * sizeof(uint32_t));
+        if (!np_) throw SoError("out of host memory for the CIGARs");
+        ops = np_;
+        cap = nc;
+    }
+    void rows(size_t nrows) {   // room for the offsets of nrows rows
+        if (off && nrows + 1 <= off_cap) return;
+        const bool fresh = !off;
+        if (fresh) off = (int64_t*)g_cig_off_cache.take(off_cap), off_cap /= sizeof(int64_t);
+        if (!off || nrows + 1 > off_cap) {
+            const size_t nc = std::max<size_t>(nrows + 1, off_cap + off_cap / 2 + 1024);
+            int64_t* np_ = (int64_t*)realloc(off, nc * sizeof(int64_t));
+            if (!np_) throw SoError("out of host memory for the CIGARs");
+            off = np_;
+            off_cap = nc;
+        }
+        if (fresh) off[0] = 0;
+    }
+    void release(uint32_t** ops_out, int64_t** off_out) {
+        rows(0);
+        *ops_out = ops ? ops : (uint32_t*)malloc(sizeof(uint32_t));
+        *off_out = off;
+        ops = nullptr, off = nullptr;
+        n = cap = off_cap = 0;
+    }
+    ~CigarBuf() { free(ops), free(off); }
+};
+
 struct HitBuf {
     so_hit* p = nullptr;
     size_t n = 0, cap = 0;
     AlnBytes aln;   // filled only when the search is asked for alignments
+    CigarBuf cig;   // filled only when the search is asked for CIGARs
     void grow(size_t extra) {
         if (n + extra <= cap) return;
         if (!p) p = g_hit_cache.take(cap);  // the previous search's array, pages still mapped
@@ -612,7 +701,8 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
 void emit_join(so_ctx* c, HitBuf& out);
 void phase2(so_ctx* c, Batch& b, HitBuf& out);
 // so_align_pairs / so_align_pairs_aln (tests); aln (traced kernels only): the tasks' strings through the search's emission chain
-void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln = nullptr);
+// cig (so_align_pairs_cigar): the tasks' CIGARs instead, through the search's count, scan and emit -- task t's runs at cig->off[t] (no runs for a task the list does not hold)
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln = nullptr, CigarBuf* cig = nullptr);
 // one alignment's strings from its compacted columns (k_aln_compact: 2 bits per column, walk order = last column first): AL bytes each into sq
 // (query side) and ss (subject side), reading the query from qp and the subject from sp (their first aligned residues) as the columns advance
 void aln_decode(const u32* w, int AL, const u8* qp, const u8* sp, char* sq, char* ss);

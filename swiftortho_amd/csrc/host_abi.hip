@@ -210,6 +210,7 @@ void so_destroy(so_ctx* c) {
     if (&c->tune == &tune()) set_tune(nullptr);
     delete c;
     g_hit_cache.clear();
+    g_cig_ops_cache.clear(), g_cig_off_cache.clear();
 }
 
 const char* so_last_error(const so_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -313,6 +314,59 @@ int so_search_loaded_aln(so_ctx* c, int64_t q_lo, int64_t q_hi, so_hit** hits, i
 
 void so_free_aln(char* aln) { free(aln); }
 
+int so_search_loaded_cigar(so_ctx* c, int64_t q_lo, int64_t q_hi, so_hit** hits, int64_t* n_hits, uint32_t** ops, int64_t** op_off) {
+    return guarded(c, [&] {
+        if (!hits || !n_hits || !ops || !op_off) throw SoError("so_search_loaded_cigar: output pointers are NULL");
+        *hits = nullptr, *ops = nullptr, *op_off = nullptr;
+        *n_hits = 0;
+        HitBuf out;
+        struct Off {   // the switch is per call
+            so_ctx* c;
+            ~Off() { c->want_cigar = false; }
+        } off{c};
+        c->want_cigar = true;
+        search_loaded(c, q_lo, q_hi, out);
+        out.cig.rows(out.n);
+        if (out.n == 0) out.cig.off[0] = 0;
+        if ((size_t)out.cig.off[out.n] != out.cig.n) throw SoError("so_search_loaded_cigar: the runs do not match the rows");
+        out.cig.release(ops, op_off);
+        *n_hits = (int64_t)out.n;
+        *hits = out.release();
+    });
+}
+
+void so_free_cigar(uint32_t* ops, int64_t* op_off) { g_cig_ops_cache.give(ops), g_cig_off_cache.give(op_off); }
+
+// "<length><op>" per run; -1: a run of length 0 or an unknown op
+static int64_t cigar_text(const uint32_t* ops, int64_t n_ops, std::vector<char>& out) {
+    for (int64_t k = 0; k < n_ops; ++k) {
+        const uint32_t len = ops[k] >> 4, op = ops[k] & 15u;
+        if (!len || op > 2u) return -1;
+        char tmp[12];
+        int m = 0;
+        for (uint32_t v = len; v; v /= 10) tmp[m++] = (char)('0' + v % 10);
+        while (m) out.push_back(tmp[--m]);
+        out.push_back("MID"[op]);
+    }
+    return 0;
+}
+
+int64_t so_format_cigar(const uint32_t* ops, int64_t n_ops, char* buf, int64_t cap) {
+    if (n_ops < 0 || (n_ops && !ops)) return -1;
+    std::vector<char> t;
+    try {
+        if (cigar_text(ops, n_ops, t) != 0) return -1;
+    } catch (const std::exception&) {
+        return -1;
+    }
+    if (buf && cap > 0) {
+        const size_t k = std::min<size_t>(t.size(), (size_t)cap - 1);
+        memcpy(buf, t.data(), k);
+        buf[k] = 0;
+    }
+    return (int64_t)t.size();
+}
+
 int so_search(so_ctx* c, const char* qry_path, int64_t q_lo, int64_t q_hi, so_hit** hits, int64_t* n_hits) {
     int rc = so_load_queries(c, qry_path);
     if (rc) return rc;
@@ -372,8 +426,10 @@ int64_t so_format_hit(so_ctx* c, const so_hit* hit, char* buf, int64_t cap) {
     return need;
 }
 
-int so_write_sc(so_ctx* c, const so_hit* hits, int64_t n, const char* path, const char* mode) {
+// so_write_sc / so_write_sc_cigar: the rows' text (ops non-null: + a tab and the row's CIGAR in front of the line's end)
+static int write_rows(so_ctx* c, const so_hit* hits, int64_t n, const uint32_t* ops, const int64_t* op_off, const char* path, const char* mode) {
     return guarded(c, [&] {
+        if (n > 0 && ops == nullptr && op_off != nullptr) throw SoError("so_write_sc_cigar: ops is NULL");
         FILE* f = fopen(path, (mode && mode[0] == 'a') ? "ab" : "wb");
         if (!f) throw SoError(std::string("cannot open output ") + path);
         // Rows are formatted in slabs of 16384 by a few threads that take slabs in order from a counter; the calling thread writes
@@ -403,7 +459,15 @@ int so_write_sc(so_ctx* c, const so_hit* hits, int64_t n, const char* path, cons
                         std::vector<char>& b = bufs[(size_t)k];
                         const int64_t lo = k * SLAB, hi = std::min<int64_t>(n, lo + SLAB);
                         b.reserve((size_t)(hi - lo) * 128);
-                        for (int64_t i = lo; i < hi; ++i) format_hit_into(c, hits[i], b);
+                        for (int64_t i = lo; i < hi; ++i) {
+                            format_hit_into(c, hits[i], b);
+                            if (op_off) {   // the 17th column
+                                b.back() = '\t';
+                                if (op_off[i + 1] < op_off[i] || cigar_text(ops + op_off[i], op_off[i + 1] - op_off[i], b) != 0)
+                                    throw SoError("so_write_sc_cigar: row " + std::to_string(i) + ": not a CIGAR");
+                                b.push_back('\n');
+                            }
+                        }
                     } catch (...) {
                         std::lock_guard<std::mutex> g(mu);
                         if (!err) err = std::current_exception();
@@ -427,6 +491,14 @@ int so_write_sc(so_ctx* c, const so_hit* hits, int64_t n, const char* path, cons
         if (err) std::rethrow_exception(err);
         if (!ok) throw SoError(std::string("short write to ") + path + " (disk full or I/O error)");
     });
+}
+
+int so_write_sc(so_ctx* c, const so_hit* hits, int64_t n, const char* path, const char* mode) { return write_rows(c, hits, n, nullptr, nullptr, path, mode); }
+
+int so_write_sc_cigar(so_ctx* c, const so_hit* hits, int64_t n, const uint32_t* ops, const int64_t* op_off, const char* path, const char* mode) {
+    if (c && n > 0 && !op_off) return guarded(c, [&] { throw SoError("so_write_sc_cigar: op_off is NULL"); });
+    static const int64_t none[1] = {0};
+    return write_rows(c, hits, n, ops, n > 0 ? op_off : none, path, mode);
 }
 
 // "%f" of v[0..n) (the library's own exact formatter) and f2s (fsearch.py:43-61) of the same values, one per line: "<%f>\t<f2s>\n".
@@ -570,6 +642,17 @@ int so_align_pairs_aln(so_ctx* c, int kernel, int64_t n, const int64_t* task6, c
         align_pairs(c, kernel, n, task6, order, out, &a);
         *aln_bytes = (int64_t)a.n;
         *aln = a.release();
+    });
+}
+
+int so_align_pairs_cigar(so_ctx* c, int kernel, int64_t n, const int64_t* task6, const uint32_t* order, int32_t* out, uint32_t** ops, int64_t** op_off) {
+    return guarded(c, [&] {
+        if (!ops || !op_off) throw SoError("so_align_pairs_cigar: output pointers are NULL");
+        *ops = nullptr, *op_off = nullptr;
+        if (kernel != 3 && kernel != 4) throw SoError("so_align_pairs_cigar: only the traced kernels (3, 4) give alignments");
+        CigarBuf g;
+        align_pairs(c, kernel, n, task6, order, out, nullptr, &g);
+        g.release(ops, op_off);
     });
 }
 

@@ -25,6 +25,21 @@ void emit_join(so_ctx* c, HitBuf& out) {
         // entry_point re-checks e <= expect (3234).  k_stop_round_w applied the same test to the same
         // doubles, so this never fires; kept as the reference has it.
         const double expect = c->expect;
+        if (c->emit.cig) {   // (CIGARs) the batch's runs are the last of out.cig, found through the rows' offsets: compacted first, while the rows still lie where their offsets say
+            CigarBuf& g = out.cig;
+            size_t w = c->emit.base;
+            int64_t rp = g.off[c->emit.base], ap = rp;
+            for (size_t k = c->emit.base; k < c->emit.base + c->emit.n; ++k) {
+                const int64_t re = g.off[k + 1], nr = re - rp;
+                if (out.p[k].evalue <= expect) {
+                    if (nr && ap != rp) memmove(g.ops + ap, g.ops + rp, (size_t)nr * sizeof(uint32_t));
+                    ap += nr;
+                    g.off[++w] = ap;
+                }
+                rp = re;
+            }
+            g.n = (size_t)ap;
+        }
         size_t wpos = c->emit.base;
         // (alignments) the batch's strings are the last bytes of out.aln, row after row: they are moved along with their rows
         size_t bytes = 0;
@@ -65,7 +80,8 @@ static void aln_slots(so_ctx* c, AlnChain& a, const AlnTask* tasks, const u32* l
     if ((u64)n * 129u >= (1ull << 30)) throw SoError("alignments: more than 8 M reported rows in one batch; search a smaller query range per call");
     launch_aln_units(tasks, list, n, s, a.units.p, c->st);
     const size_t units = d2h_u32(c, scan_u32(a.units.p, a.rofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st));
-    a.code.ensure(units * aln_unit_words() + 64);
+    a.slot_words = units * aln_unit_words();
+    a.code.ensure(a.slot_words + 64);
     launch_aln_scatter(list, n, a.rofs.p, a.aofs.p, c->st);
 }
 // the walks' columns compacted in list order into a.comp (k_aln_words, scan, k_aln_compact) -> their words
@@ -76,6 +92,17 @@ static size_t aln_compact(so_ctx* c, AlnChain& a, const u32* list, u32 n, const 
     a.comp.ensure(words + 64);
     launch_aln_compact(list, n, a.aofs.p, a.code.p, a.cofs.p, a.comp.p, c->st);
     return words;
+}
+// the walks' columns run-length coded in list order (k_cigar_count, scan, k_cigar_emit): a.oofs (n + 1 offsets) and a.ops -> the runs
+static size_t cigar_code(so_ctx* c, AlnChain& a, const u32* list, u32 n, const AlnRes* res) {
+    // (a run is at least one column and a slot word holds sixteen: the 32-bit scan of the runs holds as long as the slots' words stay below 2^28)
+    if (a.slot_words * 16ull >= (1ull << 32)) throw SoError("CIGARs: the reported rows of one batch hold 2^32 columns or more; search a smaller query range per call");
+    a.runs.ensure((size_t)n + 4), a.oofs.ensure((size_t)n + 4);
+    launch_cigar_count(list, n, a.aofs.p, a.code.p, res, a.runs.p, c->st);
+    const size_t n_ops = d2h_u32(c, scan_u32(a.runs.p, a.oofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st));
+    a.ops.ensure(n_ops + 64);
+    launch_cigar_emit(list, n, a.aofs.p, a.code.p, res, a.oofs.p, a.ops.p, c->st);
+    return n_ops;
 }
 // where list position i's compacted columns start: the running sum of ceil(aln_at(i) / 16) words, which must come to the compacted total
 template <class F>
@@ -93,9 +120,9 @@ struct P2 {
     StageClock sc;
     u32 nq, Ntot = 0, NT = 0, nspec = 0, NO = 0;
     AlnSeqs seqs{};
-    bool align_sort = false, pk_on = false, pk_mixed = false, lane_on = false, traced_pk = false, aln_on = false;
+    bool align_sort = false, pk_on = false, pk_mixed = false, lane_on = false, traced_pk = false, aln_on = false, cig_on = false;
     u32 stride = 0, slab = 0, TU = 0;   // batch-wide trace stride, tasks per trace slab, trace unit
-    size_t var_budget_words = 0, aln_words = 0;
+    size_t var_budget_words = 0, aln_words = 0, cig_ops = 0;
     int parts = 1; u32 qstep = 0;       // emission ranges, queries per range
     std::array<u32, EMIT_PARTS_MAX + 1> part_row{};   // first row of emission range q, NO behind the last
     std::vector<u32> h_ooff;   // (permuted batch, host rows: the slots' first rows, for the file-order placement -- fetched with the totals)
@@ -409,6 +436,7 @@ static void select_rows(so_ctx* c, Batch& b, P2& p) {
     p.parts = (c->dev_out || NO < emit_min_rows) ? 1 : emit_parts;
     if (p.parts == 1) p.part_row[1] = NO;
     p.aln_on = c->want_aln && !c->dev_out;
+    p.cig_on = c->want_cigar && !c->dev_out;
     p.sc.lap("phase2.stop");
 }
 
@@ -482,9 +510,11 @@ static void trace_pass(so_ctx* c, Batch& b, P2& p, HitBuf& out) {
     const u32* slist = b.sel_idx.p;  // (ordering this pass by rows too costs more than it saves: 9.1 -> 9.9 ms on config 3)
     // Alignments asked for (so_search_loaded_aln): every reported row gets a slot for the columns its walk can take, in row order, and
     // the walks of this pass write them there (k_traceback<true>); the slots' offsets go to the walks per task, whatever list walks it.
-    if (p.aln_on) aln_slots(c, b.aln, b.tasks.p, slist, NO, p.NT, p.seqs);
-    u32* acode = p.aln_on ? b.aln.code.p : nullptr;
-    const u32* aofs = p.aln_on ? b.aln.aofs.p : nullptr;
+    // CIGARs asked for (so_search_loaded_cigar): the same slots and walks; the runs are coded from the slots behind the last range.
+    const bool emit_cols = p.aln_on || p.cig_on;
+    if (emit_cols) aln_slots(c, b.aln, b.tasks.p, slist, NO, p.NT, p.seqs);
+    u32* acode = emit_cols ? b.aln.code.p : nullptr;
+    const u32* aofs = emit_cols ? b.aln.aofs.p : nullptr;
     // the list aligned with traces now: the rows without a kept trace (nspec), or all rows -- range q's are its [pb[q], pb[q + 1]); its
     // traces take their own sizes (b.tr_ofs) when the whole list fits the budget, else slabs of the batch-wide stride
     std::array<u32, EMIT_PARTS_MAX + 1> pb = p.part_row;
@@ -565,6 +595,20 @@ static void trace_pass(so_ctx* c, Batch& b, P2& p, HitBuf& out) {
         if (qbytes) HIP_CHECK(hipMemcpyAsync((char*)c->pinned_aln + aln_words * 4, b.dev.d_res.p, qbytes, hipMemcpyDeviceToHost, c->st));
         HIP_CHECK(hipEventRecord(c->ev_aln, c->st));
     }
+    // (CIGARs) runs per row from the slots, scanned, every run written once in row order: the offsets and the runs leave in one piece each
+    if (p.cig_on) {
+        const size_t n_ops = p.cig_ops = cigar_code(c, b.aln, slist, NO, b.ares.p);
+        const size_t need = ((size_t)NO + 1 + n_ops) * sizeof(u32) + 64;
+        if (c->pinned_aln_cap < need) {   // (the previous batch's worker, which reads it, was joined above)
+            if (c->pinned_aln) (void)hipHostFree(c->pinned_aln);
+            c->pinned_aln = nullptr, c->pinned_aln_cap = 0;
+            HIP_CHECK(hipHostMalloc(&c->pinned_aln, need * 5 / 4 + 4096, hipHostMallocDefault));
+            c->pinned_aln_cap = need * 5 / 4 + 4096;
+        }
+        HIP_CHECK(hipMemcpyAsync(c->pinned_aln, b.aln.oofs.p, ((size_t)NO + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        if (n_ops) HIP_CHECK(hipMemcpyAsync((u32*)c->pinned_aln + NO + 1, b.aln.ops.p, n_ops * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipEventRecord(c->ev_aln, c->st));
+    }
     p.sc.lap("phase2.trace_pass");
     {   // SOHIT_TEST_OOM_PHASE2=1 (tests): the first multi-query batch of the process fails here, as a device allocation of the
         // emission stage would -- search_loaded() reruns it as two halves
@@ -628,7 +672,8 @@ static void emit_host(so_ctx* c, Batch& b, P2& p, HitBuf& out) {
         place = std::make_shared<std::vector<std::pair<u32, i64>>>(nq);
         for (u32 s = 0; s < nq; ++s) (*place)[s] = {b.qid[s], (i64)ocnt[b.qid[s]] - (i64)ooff[s]};
     }
-    c->emit.base = base, c->emit.n = NO, c->emit.aln = p.aln_on;
+    c->emit.base = base, c->emit.n = NO, c->emit.aln = p.aln_on, c->emit.cig = p.cig_on;
+    if (p.cig_on) out.cig.rows(base + NO);   // (the worker fills the batch's offsets and appends its runs)
     c->emit.dropped.store(0);
     c->emit.active = true;
     // The worker converts range q's rows as soon as they have arrived, while the GPU traces range q + 1: behind the last copy only
@@ -638,7 +683,7 @@ static void emit_host(so_ctx* c, Batch& b, P2& p, HitBuf& out) {
     std::shared_ptr<std::vector<u32>> aln_qoff;
     if (p.aln_on) aln_qoff = std::make_shared<std::vector<u32>>(b.h_off.begin(), b.h_off.begin() + nq + 1);
     c->emit.th = std::thread([c, rows, dst, NO, D = c->ref.N, expect = c->expect, q_lo = b.q_lo, p2p = pow2_table(), place, part_row = p.part_row, parts = p.parts, aln_qoff,
-                              abuf = &out.aln, aln_words = p.aln_words] {
+                              abuf = &out.aln, aln_words = p.aln_words, cbuf = p.cig_on ? &out.cig : nullptr, cig_ops = p.cig_ops, base] {
         try {
             HIP_CHECK(hipSetDevice(c->device));
             auto convert = [&](i64 i) {
@@ -718,6 +763,30 @@ static void emit_host(so_ctx* c, Batch& b, P2& p, HitBuf& out) {
                 });
                 abuf->n = a0 + (size_t)boff[NO];
             }
+            if (cbuf) {
+                // row i of the download has its runs at [roff[i], roff[i + 1]) of the downloaded runs; row k of the result (file order) takes
+                // them at the running sum of the rows' run counts
+                HIP_CHECK(hipEventSynchronize(c->ev_aln));
+                const u32* roff = (const u32*)c->pinned_aln;
+                const u32* rops = roff + NO + 1;
+                if (roff[NO] != cig_ops) throw SoError("CIGARs: the runs do not add up");
+                const size_t g0 = cbuf->n;
+                cbuf->grow(cig_ops);
+                int64_t* goff = cbuf->off + base;
+                goff[0] = (int64_t)g0;
+                if (!place) {
+                    parallel_for((i64)NO, [&](i64 i) { goff[i + 1] = (int64_t)g0 + roff[i + 1]; });
+                } else {
+                    for (i64 i = 0; i < (i64)NO; ++i) goff[i + (*place)[(size_t)rows[i].v[0]].second + 1] = roff[i + 1] - roff[i];
+                    for (i64 k = 0; k < (i64)NO; ++k) goff[k + 1] += goff[k];
+                }
+                // (row by row on all threads: a config-3 result is 118 MB of runs)
+                parallel_for((i64)NO, [&](i64 i) {
+                    const i64 di = place ? i + (*place)[(size_t)rows[i].v[0]].second : i;
+                    if (roff[i + 1] > roff[i]) memcpy(cbuf->ops + goff[di], rops + roff[i], (size_t)(roff[i + 1] - roff[i]) * sizeof(u32));
+                });
+                cbuf->n = g0 + cig_ops;
+            }
         } catch (...) {
             c->emit.err = std::current_exception();
         }
@@ -748,10 +817,13 @@ void phase2(so_ctx* c, Batch& b, HitBuf& out) {
 // aln (so_align_pairs_aln): kernels 3 and 4 only; the walks write their columns through the search's own chain -- aln_slots, the emitting
 // walk, aln_compact -- and the compacted columns are found by aln_word_offsets and decoded by aln_decode, as the emission worker does;
 // task t's strings land at 2 * sum_{m<t} aln_m of *aln.
-void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln) {
+// cig (so_align_pairs_cigar): the same slots and walks, then the search's cigar_code; task t's runs land at cig->off[t] .. cig->off[t + 1].
+void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint32_t* order, int32_t* out, AlnBytes* aln, CigarBuf* cig) {
     if (!c->ref_loaded || !c->qry_loaded) throw SoError("so_align_pairs: load a reference and queries first");
     if (kernel < 0 || kernel > 4) throw SoError("so_align_pairs: kernel must be 0 ... 4");
     if (aln && kernel < 3) throw SoError("so_align_pairs_aln: only the traced kernels (3, 4) give alignments");
+    if (cig && kernel < 3) throw SoError("so_align_pairs_cigar: only the traced kernels (3, 4) give alignments");
+    if (cig) cig->rows((size_t)std::max<i64>(n, 0)), std::fill(cig->off, cig->off + std::max<i64>(n, 0) + 1, (int64_t)0);
     if (n < 0 || n > (1ll << 24)) throw SoError("so_align_pairs: n must be 0 ... 2^24");
     if (n == 0) return;
     if (!task6 || !out) throw SoError("so_align_pairs: task6 or out is NULL");
@@ -808,7 +880,7 @@ void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint3
                 throw SoError("so_align_pairs: task " + std::to_string(t) + ": its scores need 32-bit cells, the packed aligners do not take it");
     DevBuf<u32> d_units, d_tofs, d_trace;
     AlnChain chain;   // (aln)
-    std::vector<u32> h_acomp;
+    std::vector<u32> h_acomp, h_oofs, h_ops;
     size_t aln_words = 0;
     switch (kernel) {
     case 0:
@@ -828,10 +900,16 @@ void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint3
         launch_trace_units(d_tasks.p, d_list.p, (u32)n, seqs, d_units.p, c->st);
         const size_t tw = (size_t)d2h_u32(c, scan_u32(d_units.p, d_tofs.p, (size_t)n + 1, false, c->d_scan_tmp.p, c->st)) * TU;
         d_trace.ensure(tw + 64);
-        if (aln) aln_slots(c, chain, d_tasks.p, d_list.p, (u32)n, (u32)n, seqs);
+        if (aln || cig) aln_slots(c, chain, d_tasks.p, d_list.p, (u32)n, (u32)n, seqs);
         // kernel 3: every task by the 32-bit kernel; 4: every task by the packed one
-        launch_align_walk(d_tasks.p, d_list.p, (u32)n, seqs, d_trace.p, TU, d_tofs.p, d_res.p, c->st, kernel == 3 ? (u32)n : 0u, aln ? chain.code.p : nullptr,
-                          aln ? chain.aofs.p : nullptr);
+        launch_align_walk(d_tasks.p, d_list.p, (u32)n, seqs, d_trace.p, TU, d_tofs.p, d_res.p, c->st, kernel == 3 ? (u32)n : 0u, aln || cig ? chain.code.p : nullptr,
+                          aln || cig ? chain.aofs.p : nullptr);
+        if (cig) {   // the runs coded in list order and downloaded with their offsets
+            const size_t n_ops = cigar_code(c, chain, d_list.p, (u32)n, d_res.p);
+            h_oofs.resize((size_t)n + 1), h_ops.resize(n_ops + 1);
+            HIP_CHECK(hipMemcpyAsync(h_oofs.data(), chain.oofs.p, ((size_t)n + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+            if (n_ops) HIP_CHECK(hipMemcpyAsync(h_ops.data(), chain.ops.p, n_ops * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        }
         if (aln) {   // the columns compacted in list order and downloaded
             aln_words = aln_compact(c, chain, d_list.p, (u32)n, d_res.p);
             h_acomp.resize(aln_words + 1);
@@ -866,6 +944,24 @@ void align_pairs(so_ctx* c, int kernel, i64 n, const int64_t* task6, const uint3
             aln_decode(w, r.aln, Q.res.data() + Q.off[tk[t].q] + r.qst, R.res.data() + R.off[tk[t].subj] + r.sst, sq, sq + r.aln);
         }
         aln->n = a0 + boff[(size_t)n];
+    }
+    if (cig) {
+        // list position p's runs at h_oofs[p]; task t's at the running sum of the tasks' run counts
+        for (i64 p = 0; p < n; ++p) cig->off[list[(size_t)p] + 1] = (int64_t)h_oofs[(size_t)p + 1] - (int64_t)h_oofs[(size_t)p];
+        for (i64 t = 0; t < n; ++t) cig->off[t + 1] += cig->off[t];
+        cig->grow((size_t)cig->off[n]);
+        for (i64 p = 0; p < n; ++p) {
+            const u32 t = list[(size_t)p];
+            const AlnRes& r = res[t];
+            const u32* w = h_ops.data() + h_oofs[(size_t)p];
+            const i64 nr = cig->off[t + 1] - cig->off[t];
+            i64 cols = 0, nq_adv = 0, ns_adv = 0;   // (the runs must cover the coordinates)
+            for (i64 k = 0; k < nr; ++k) cols += w[k] >> 4, nq_adv += (w[k] & 15u) != 2u ? w[k] >> 4 : 0u, ns_adv += (w[k] & 15u) != 1u ? w[k] >> 4 : 0u;
+            if (cols != std::max(0, r.aln) || (nr && (nq_adv != r.qed - r.qst || ns_adv != r.sed - r.sst)))
+                throw SoError("so_align_pairs_cigar: task " + std::to_string(t) + ": the runs do not cover its coordinates");
+            if (nr) memcpy(cig->ops + cig->off[t], w, (size_t)nr * sizeof(u32));
+        }
+        cig->n = (size_t)cig->off[n];
     }
     for (i64 t = 0; t < n; ++t) {
         int32_t* o = out + 10 * t;

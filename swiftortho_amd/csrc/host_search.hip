@@ -2,6 +2,7 @@
 #include "host.h"
 
 HitCache g_hit_cache;
+BufCache g_cig_ops_cache, g_cig_off_cache;
 
 
 void search_loaded(so_ctx* c, i64 q_lo, i64 q_hi, HitBuf& out) {

@@ -590,3 +590,88 @@ void launch_aln_words(const u32* sel_idx, u32 n, const AlnRes* res, u32* words, 
 void launch_aln_compact(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const u32* cofs, u32* dst, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_aln_compact, dim3((n + 15) / 16), dim3(256), 0, st, sel_idx, n, aofs, acode, cofs, dst);
 }
+
+// ---- the reported rows' CIGARs (so_search_loaded_cigar) --------------------------------------------------------------------------
+// The walk's columns run-length coded on the device, straight from the walks' slots: one u32 per run, length << 4 | op with op 0 = M
+// (code 1, both sides advance), 1 = I (code 3, the query alone), 2 = D (code 2, the subject alone), in ALIGNMENT order -- the reverse of
+// the walk's.  A run starts at every column whose code differs from its predecessor's: per word of sixteen codes a shift (with the
+// previous word's last code carried in), an xor, a fold of the two bits and a popcount.  Sixteen lanes per row, a word each per round.
+__device__ __forceinline__ u32 cigar_bounds(u32 w, u32 prev, int nvalid, bool first) {   // bit 2p: column p of the word starts a run
+    const u32 x = w ^ ((w << 2) | prev);
+    u32 d = (x | (x >> 1)) & 0x55555555u;
+    if (first) d &= ~1u;                                  // (column 0 starts the first run: counted apart)
+    if (nvalid < 16) d &= (1u << (2 * nvalid)) - 1u;      // the row's last word: the columns behind the alignment are not its own
+    return d;
+}
+// runs per reported row (+ a 0 behind the last): scanned, the rows' places in the runs
+__global__ __launch_bounds__(256) void k_cigar_count(const u32* __restrict__ sel_idx, u32 n, const u32* __restrict__ aofs, const u32* __restrict__ acode,
+                                                     const AlnRes* __restrict__ res, u32* __restrict__ runs) {
+    const u32 r = blockIdx.x * 16u + (threadIdx.x >> 4), l = threadIdx.x & 15u;
+    if (r > n) return;
+    if (r == n) {
+        if (l == 0) runs[n] = 0;
+        return;
+    }
+    const u32 task = sel_idx[r];
+    const int AL = max(res[task].aln, 0);
+    const u32* src = acode + (size_t)aofs[task] * ALN_UNIT;
+    const u32 nwd = (u32)(AL + 15) / 16u;
+    u32 c = 0;
+    for (u32 k = l; k < nwd; k += 16u) c += (u32)__builtin_popcount(cigar_bounds(src[k], k ? src[k - 1] >> 30 : 0u, AL - 16 * (int)k, k == 0));
+    for (int d = 8; d; d >>= 1) c += (u32)__shfl_xor((int)c, d, 16);
+    if (l == 0) runs[r] = AL ? c + 1u : 0u;
+}
+// every run written once: the run that ends in front of a boundary is written by the lane that holds the boundary -- its start is the
+// boundary before (a running maximum over the lanes and rounds), its place the number of boundaries before (a running sum), counted
+// from the row's end.  The row's first column closes the last run written (lane 0).
+__global__ __launch_bounds__(256) void k_cigar_emit(const u32* __restrict__ sel_idx, u32 n, const u32* __restrict__ aofs, const u32* __restrict__ acode,
+                                                    const AlnRes* __restrict__ res, const u32* __restrict__ op_off, u32* __restrict__ ops) {
+    const u32 r = blockIdx.x * 16u + (threadIdx.x >> 4), l = threadIdx.x & 15u;
+    if (r >= n) return;
+    const u32 task = sel_idx[r];
+    const int AL = max(res[task].aln, 0);
+    if (!AL) return;
+    const u32* src = acode + (size_t)aofs[task] * ALN_UNIT;
+    const u32 nwd = (u32)(AL + 15) / 16u;
+    const u32 o = op_off[r], nr = op_off[r + 1] - o;
+    u32* dst = ops + o;
+    auto op_of = [](u32 code) { return (0x60u >> (2u * code)) & 3u; };   // 1 -> M, 2 -> D, 3 -> I
+    u32 base = 0, last = 0;   // boundaries of the rounds done, and the last of them (0: none -- column 0 is no boundary)
+    for (u32 k0 = 0; k0 < nwd; k0 += 16u) {
+        const u32 k = k0 + l;
+        u32 w = 0, prev = 0, d = 0;
+        if (k < nwd) {
+            w = src[k], prev = k ? src[k - 1] >> 30 : 0u;
+            d = cigar_bounds(w, prev, AL - 16 * (int)k, k == 0);
+        }
+        const u32 c = (u32)__builtin_popcount(d);
+        u32 cs = c, ms = d ? 16u * k + ((31u - (u32)__builtin_clz(d)) >> 1) : 0u;   // inclusive over the lanes: boundaries, the last one's column
+        for (u32 s = 1; s < 16u; s <<= 1) {
+            const u32 tc = (u32)__shfl_up((int)cs, s, 16), tm = (u32)__shfl_up((int)ms, s, 16);
+            if (l >= s) cs += tc, ms = max(ms, tm);
+        }
+        const u32 mprev = (u32)__shfl_up((int)ms, 1u, 16);
+        u32 j = base + cs - c;                     // the run open where this lane's word begins (walk order) ...
+        u32 start = max(last, l ? mprev : 0u);     // ... and its first column
+        while (d) {
+            const u32 b = (u32)__builtin_ctz(d);
+            d &= d - 1u;
+            const u32 p = 16u * k + (b >> 1);
+            const u32 code = b ? (w >> (b - 2u)) & 3u : prev;   // of column p - 1: the run that ends here
+            if (j < nr) dst[nr - 1u - j] = (p - start) << 4 | op_of(code);
+            start = p, ++j;
+        }
+        base += (u32)__shfl((int)cs, 15, 16);
+        last = max(last, (u32)__shfl((int)ms, 15, 16));
+    }
+    if (l == 0 && base < nr) {
+        const u32 cc = (u32)AL - 1u;
+        dst[nr - 1u - base] = ((u32)AL - last) << 4 | op_of((src[cc >> 4] >> ((cc & 15u) << 1)) & 3u);
+    }
+}
+void launch_cigar_count(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const AlnRes* res, u32* runs, hipStream_t st) {
+    hipLaunchKernelGGL(k_cigar_count, dim3((n + 1 + 15) / 16), dim3(256), 0, st, sel_idx, n, aofs, acode, res, runs);
+}
+void launch_cigar_emit(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const AlnRes* res, const u32* op_off, u32* ops, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_cigar_emit, dim3((n + 15) / 16), dim3(256), 0, st, sel_idx, n, aofs, acode, res, op_off, ops);
+}

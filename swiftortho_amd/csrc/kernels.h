@@ -281,6 +281,10 @@ void launch_aln_units(const AlnTask* tasks, const u32* sel_idx, u32 n, const Aln
 void launch_aln_scatter(const u32* sel_idx, u32 n, const u32* rofs, u32* aofs /*per task*/, hipStream_t st);
 void launch_aln_words(const u32* sel_idx, u32 n, const AlnRes* res, u32* words /*n + 1*/, hipStream_t st);
 void launch_aln_compact(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const u32* cofs /*n + 1*/, u32* dst, hipStream_t st);
+// the reported rows' CIGARs, run-length coded from the walks' slots: runs per row (+ a 0 behind the last); scanned (op_off), every run as
+// length << 4 | op (0 M, 1 I, 2 D) in alignment order at ops[op_off[row] ...]
+void launch_cigar_count(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const AlnRes* res, u32* runs /*n + 1*/, hipStream_t st);
+void launch_cigar_emit(const u32* sel_idx, u32 n, const u32* aofs, const u32* acode, const AlnRes* res, const u32* op_off /*n + 1*/, u32* ops, hipStream_t st);
 void launch_stop_round_w(const AlnTask* tasks, const AlnRes* res, const u32* qcoff, const u32* ntask, const u32* ntile, const u32* roffc,
                          const u32* rk_slot, const u32* toff, const u32* rcnt, u32 nq, const u32* qoff, const u32* roff, const int* bittab,
                          int bittab_n, i64 D, double expect, double max_miss, i64 v, u32* sel, u32* st_state, int* bits,

@@ -8,6 +8,8 @@ Reference behaviour mirrored (bin/find_hit.py:194-358):
   * `-r aa9|aa20|custom`; chunk size = int(-c / number of '/'-separated alphabets) (273-274);
   * output rows in ascending query order (the reference concatenates its per-block part files in
     block order, 135-146).
+Addition: `-C T` appends every row's alignment path as a 17th column, a CIGAR (M both sides advance, I the query alone, D the
+subject alone), coded on the GPU; the default `-C F` writes the reference's 16 columns.
 Differences by design: `-a` is the number of GPUs (one process per GPU, queries sharded, hit
 records gathered over RCCL) instead of CPU worker processes; nothing is spilled to `-T`.
 The >= 4.2e9-byte reference split + `sort -m | awk` merge (303-351) is reproduced (reference_parts / merge_parts).
@@ -21,7 +23,7 @@ AA20 = 'A,S,T,C,F,I,L,M,V,Y,D,N,E,Q,G,H,K,R,P,W'
 
 DEFAULTS = {'-p': '', '-v': '500', '-s': '11111111', '-i': '', '-d': '', '-e': '1e-3', '-l': '-1', '-u': '-1', '-m': '1e-3',
             '-t': '-1', '-r': 'aa9', '-j': '1', '-F': 'T', '-o': '', '-D': '', '-O': 'wb', '-L': '-1', '-U': '-1',
-            '-M': '120000000', '-c': '50000', '-a': '1', '-T': ''}
+            '-M': '120000000', '-c': '50000', '-a': '1', '-T': '', '-C': 'F'}
 
 
 def manual_print(prog='find_hit.py'):
@@ -37,7 +39,9 @@ def manual_print(prog='find_hit.py'):
                  '-v: number of hits to show', '-e: expect value', '-m: max ratio of pseudo hits that will trigger stop',
                  '-j: distance between start sites of two neighbor seeds', '-t: filter high frequency kmers whose counts > t',
                  '-F: filter query sequence', '-M: bucket size of hash table', '-c: chunck size of reference',
-                 '-a: number of GPUs to use', '-T: tmpdir (accepted, unused)'):
+                 '-a: number of GPUs to use', '-T: tmpdir (accepted, unused)',
+                 '-C: T appends the alignment of every hit as a 17th column, a CIGAR (M: both advance, I: query alone, D: subject alone); '
+                 'F (default) writes the 16 columns. find_orth.py reads either file; nr2full.py and run_all_fast.py expect the 16 columns'):
         print('  ' + line)
 
 
@@ -54,7 +58,7 @@ def resolve(args):
         p = dict(qry=args['-i'], ref=args['-d'], exp=float(args['-e']), bv=int(args['-v']), start=int(args['-l']),
                  end=int(args['-u']), rstart=int(args['-L']), rend=int(args['-U']), miss=float(args['-m']), thr=int(args['-t']),
                  step=int(args['-j']), flt=args['-F'].upper(), outfile=args['-o'], wrt=args['-O'], ht=int(args['-M']),
-                 chk=int(args['-c']), ssd=args['-s'], nr=args['-r'], ngpu=int(args['-a']))
+                 chk=int(args['-c']), ssd=args['-s'], nr=args['-r'], ngpu=int(args['-a']), cigar=args['-C'].upper() == 'T')
     except ValueError:
         return None
     nr = p['nr'].strip()
@@ -105,7 +109,7 @@ def run_single(p, fast_exit=False):
         s.load_queries(p['qry'])
         lap('load_queries')
         st, ed = query_range(p['start'], p['end'], s.num_queries, p['ngpu'])
-        hits = s.search(st, ed)
+        hits = s.search(st, ed, cigar=True) if p['cigar'] else s.search(st, ed)   # (-C T: 17 columns)
         lap('index+search')
         hits.write(p['outfile'], 'w')
         lap('write')
@@ -153,7 +157,8 @@ def run_rank(p):
         # each rank writes a part file, the byte counts are exchanged (one all_gather of 8 bytes), rank 0 sizes the output file and
         # every rank copies its part to its offset -- find_hit.py's own scheme (block files + cat, find_hit.py:133-146) with the
         # copy done by all ranks at once.  The RCCL record gather stays the exchange of so_search_device / bench.py.
-        hits = s.search(lo, hi)   # hi == lo: no rows, still takes part in the exchange
+        # (-C T: the rank's rows carry their CIGARs and its part file the 17th column; the parts are placed as before)
+        hits = s.search(lo, hi, cigar=True) if p['cigar'] else s.search(lo, hi)   # hi == lo: no rows, still takes part in the exchange
         part = '%s.part%d' % (p['outfile'], rank)
         try:
             hits.write(part, 'w')

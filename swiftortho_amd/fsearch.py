@@ -105,11 +105,19 @@ class Searcher:
         return np.array([self.L.so_ref_len(self.h, i) for i in range(n)], dtype=np.int64)
 
     # search -----------------------------------------------------------------------------------
-    def search(self, st=-1, ed=-1, alignments=False):
+    def search(self, st=-1, ed=-1, alignments=False, cigar=False):
         """Queries [st, ed) of the loaded query file -> Hits (owning wrapper).  alignments=True: every row also carries its
-        aligned query and subject strings (Hits.alignment / Hits.alignment_buffer)."""
+        aligned query and subject strings (Hits.alignment / Hits.alignment_buffer).  cigar=True: every row carries its alignment
+        path as a CIGAR instead (Hits.cigar / Hits.cigar_ops; Hits.write then writes it as a 17th column) -- a few bytes per row,
+        coded on the GPU; cigar_to_strings() leads from it to the strings.  One search gives one of the two."""
+        if alignments and cigar:
+            raise ValueError("alignments=True and cigar=True in one search: ask for one of them")
         hits = C.POINTER(_lib.SoHit)()
         n = C.c_int64(0)
+        if cigar:
+            ops, off = C.c_void_p(), C.c_void_p()
+            self._chk(self.L.so_search_loaded_cigar(self.h, st, ed, C.byref(hits), C.byref(n), C.byref(ops), C.byref(off)))
+            return Hits(self, hits, n.value, cigar_ptrs=(ops.value, off.value))
         if not alignments:
             self._chk(self.L.so_search_loaded(self.h, st, ed, C.byref(hits), C.byref(n)))
             return Hits(self, hits, n.value)
@@ -185,10 +193,13 @@ class Searcher:
 
     ALIGN_DTYPE = [(f, "<i4") for f in ("maxscore", "aln", "matches", "gap", "qst", "qed", "sst", "sed", "cells", "wide")]
 
-    def align_pairs(self, tasks, kernel, order=None, alignments=False):
+    def align_pairs(self, tasks, kernel, order=None, alignments=False, cigar=False):
         """tests: the windows tasks[k] = (qidx, sidx, qi, qj, qe, se) aligned by ONE phase-2 aligner (so_align_pairs; qe / se = -1: the
         sequence's end) -> one record per task, fields ALIGN_DTYPE.  order: the launch list (None: 0 .. n-1).  alignments=True (traced
-        kernels 3 and 4, so_align_pairs_aln): (records, [(query string, subject string) per task]), built by the search's emission chain."""
+        kernels 3 and 4, so_align_pairs_aln): (records, [(query string, subject string) per task]), built by the search's emission chain.
+        cigar=True (kernels 3 and 4, so_align_pairs_cigar): (records, [uint32 runs per task]) -- format_cigar() gives their text."""
+        if alignments and cigar:
+            raise ValueError("alignments=True and cigar=True in one call: ask for one of them")
         t = np.ascontiguousarray(np.asarray(tasks, dtype=np.int64).reshape(-1, 6))
         n = len(t)
         out = np.zeros(max(n, 1), dtype=self.ALIGN_DTYPE)
@@ -197,6 +208,16 @@ class Searcher:
             o = np.ascontiguousarray(np.asarray(order, dtype=np.uint32))
             if len(o) != n:
                 raise ValueError("order must hold n positions")
+        if cigar:
+            ops, off = C.c_void_p(), C.c_void_p()
+            self._chk(self.L.so_align_pairs_cigar(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data,
+                                                  C.byref(ops), C.byref(off)))
+            try:
+                offs = np.frombuffer((C.c_int64 * (n + 1)).from_address(off.value), dtype=np.int64).copy()
+                runs = np.frombuffer((C.c_uint32 * max(int(offs[n]), 1)).from_address(ops.value), dtype=np.uint32)[:int(offs[n])].copy()
+            finally:
+                self.L.so_free_cigar(ops, off)
+            return out[:n], [runs[int(offs[k]):int(offs[k + 1])] for k in range(n)]
         if not alignments:
             self._chk(self.L.so_align_pairs(self.h, int(kernel), n, t.ctypes.data, None if o is None else o.ctypes.data, out.ctypes.data))
             return out[:n]
@@ -259,10 +280,12 @@ def hits_from_bytes(s, data):
 class Hits:
     """Result rows of one search; frees the library buffer on close."""
 
-    def __init__(self, s, ptr, n, aln_ptr=None, aln_bytes=0):
+    def __init__(self, s, ptr, n, aln_ptr=None, aln_bytes=0, cigar_ptrs=None):
         self.s, self.ptr, self.n = s, ptr, n
         self.aln_ptr, self.aln_bytes = aln_ptr, aln_bytes
         self._aln_off = None
+        self.cig_ptrs = cigar_ptrs   # (ops, op_off) of so_search_loaded_cigar
+        self._cig = None
 
     def __len__(self):
         return self.n
@@ -294,6 +317,29 @@ class Hits:
         mid = (a0 + a1) // 2
         return C.string_at(self.aln_ptr + a0, mid - a0), C.string_at(self.aln_ptr + mid, a1 - mid)
 
+    def cigar_buffer(self):
+        """(uint32 view of every row's runs -- no copy, valid until close() --, int64 offsets [n + 1]): row k's runs are
+        ops[off[k]:off[k + 1]], each length << 4 | op with op 0 = M, 1 = I, 2 = D, first column first."""
+        if self.cig_ptrs is None:
+            raise SohitError("this search was run without CIGARs: Searcher.search(..., cigar=True)")
+        if self._cig is None:
+            off = np.frombuffer((C.c_int64 * (self.n + 1)).from_address(self.cig_ptrs[1]), dtype=np.int64)
+            nops = int(off[self.n])
+            ops = np.frombuffer((C.c_uint32 * nops).from_address(self.cig_ptrs[0]), dtype=np.uint32) if nops else np.zeros(0, dtype=np.uint32)
+            self._cig = (ops, off)
+        return self._cig
+
+    def cigar_ops(self, k):
+        """row k's runs: a uint32 view, length << 4 | op (0 M, 1 I, 2 D)"""
+        ops, off = self.cigar_buffer()
+        if not 0 <= k < self.n:
+            raise IndexError(k)
+        return ops[int(off[k]):int(off[k + 1])]
+
+    def cigar(self, k):
+        """row k's CIGAR as text: M both sides advance, I the query alone, D the subject alone (35M2D10M)"""
+        return format_cigar(self.cigar_ops(k))
+
     def array(self):
         """numpy structured view (copy) of the so_hit records."""
         dt = np.dtype([(n, t) for n, t in (("qidx", "<i8"), ("sidx", "<i8"), ("identity", "<f8"), ("evalue", "<f8"), ("aln", "<i4"),
@@ -307,6 +353,10 @@ class Hits:
         return np.frombuffer(view, dtype=dt).copy()
 
     def write(self, path, mode="w"):
+        """the rows as text: 16 columns, or 17 -- the CIGAR last -- when the hits carry CIGARs"""
+        if self.cig_ptrs is not None:
+            self.s._chk(self.s.L.so_write_sc_cigar(self.s.h, self.ptr, self.n, self.cig_ptrs[0], self.cig_ptrs[1], os.fsencode(path), mode.encode()))
+            return
         self.s._chk(self.s.L.so_write_sc(self.s.h, self.ptr, self.n, os.fsencode(path), mode.encode()))
 
     def rows(self):
@@ -342,25 +392,29 @@ class Hits:
         if self.aln_ptr:
             self.s.L.so_free_aln(self.aln_ptr)
             self.aln_ptr = None
+        if self.cig_ptrs:
+            self._cig = None
+            self.s.L.so_free_cigar(self.cig_ptrs[0], self.cig_ptrs[1])
+            self.cig_ptrs = None
 
     __del__ = close
 
 
 def blastp(qry, ref, expect=1e-5, v=500, max_miss=1e-3, st=-1, ed=-1, rst=-1, red=-1, thr=-1, flt="T", ref_idx="", memory=True,
-           ssd="", nr="", step=4, ht=-1, chk=100000, tmpdir="./tmpdir", device=0, alignments=False):
+           ssd="", nr="", step=4, ht=-1, chk=100000, tmpdir="./tmpdir", device=0, alignments=False, cigar=False):
     """fsearch.py:2968 -- yields (i, j, li, lj, idy, aln, mis, gap, qst, qed, sst, sed, e, bit, seed) per reported row
     (query ordinal, subject ordinal, lengths, identity, ..., 1-based starts as printed, e-value, bit, ungapped score);
-    alignments=True: + (query string, subject string) as bytes."""
+    alignments=True: + (query string, subject string) as bytes; cigar=True: + the CIGAR text (one of the two per call)."""
     s = Searcher(ssd=ssd, nr=nr, ht=ht, chk=chk, step=step, v=v, thr=thr, expect=expect, max_miss=max_miss, flt=flt, device=device)
     try:
         s.load_ref(ref, rst, red)
         s.load_queries(qry)
-        hits = s.search(st, ed, alignments=alignments)
+        hits = s.search(st, ed, alignments=alignments, cigar=cigar)
         for k, r in enumerate(hits.array()):
             row = (int(r["qidx"]), int(r["sidx"]), int(r["qlen"]), int(r["slen"]), float(r["identity"]), int(r["aln"]), int(r["mis"]),
                    int(r["gap"]), int(r["qst"]), int(r["qed"]), int(r["sst"]), int(r["sed"]), float(r["evalue"]), int(r["bit"]),
                    int(r["ungapped"]))
-            yield row + hits.alignment(k) if alignments else row
+            yield row + hits.alignment(k) if alignments else row + (hits.cigar(k),) if cigar else row
         hits.close()
     finally:
         s.close()
@@ -399,6 +453,62 @@ def aln_stats(al0, al1):
     matches = AL - mis
     identity = idy * (100. / AL) if AL else float("nan")
     return matches, mis, gap, identity
+
+
+def format_cigar(ops):
+    """runs (uint32, length << 4 | op with op 0 = M, 1 = I, 2 = D) -> CIGAR text by the library's formatter (so_format_cigar; no device)"""
+    a = np.ascontiguousarray(np.asarray(ops, dtype=np.uint32))
+    L = _lib.load()
+    n = int(L.so_format_cigar(a.ctypes.data if len(a) else None, len(a), None, 0))
+    if n < 0:
+        raise ValueError("not a CIGAR: a run of length 0 or an unknown operation")
+    buf = C.create_string_buffer(n + 1)
+    L.so_format_cigar(a.ctypes.data if len(a) else None, len(a), buf, n + 1)
+    return buf.raw[:n].decode("ascii")
+
+
+def parse_cigar(cigar):
+    """CIGAR text -> [(length, op)] with op in 'MID'; runs of length 0 and repeated operations are accepted as written"""
+    if isinstance(cigar, bytes):
+        cigar = cigar.decode("ascii")
+    runs, n, digits = [], 0, False
+    for ch in cigar:
+        if ch.isdigit():
+            n, digits = 10 * n + int(ch), True
+            continue
+        if ch not in "MID" or not digits:
+            raise ValueError("not a CIGAR of M, I and D runs: %r" % cigar[:60])
+        runs.append((n, ch))
+        n, digits = 0, False
+    if digits:
+        raise ValueError("CIGAR ends inside a run: %r" % cigar[-60:])
+    return runs
+
+
+def cigar_to_strings(cigar, q, s, qst, sst):
+    """(query string, subject string) as bytes -- so_search_loaded_aln's strings -- from a row's CIGAR (text, or uint32 runs), the query
+    as the aligner saw it (Searcher.masked_query: SEG-masked under -F T), the subject, and the row's 1-based starts as printed: M
+    takes a residue of either, I one of the query opposite '-', D one of the subject opposite '-'.  Non-canonical CIGARs are accepted."""
+    if not isinstance(cigar, (str, bytes)):
+        cigar = [(int(v) >> 4, "MID"[int(v) & 15]) for v in cigar]
+    else:
+        cigar = parse_cigar(cigar)
+    q = q.encode("latin-1") if isinstance(q, str) else bytes(q)
+    s = s.encode("latin-1") if isinstance(s, str) else bytes(s)
+    a0, a1, qp, sp = [], [], qst - 1, sst - 1
+    if qst < 1 or sst < 1 or qp + sum(n for n, op in cigar if op != "D") > len(q) or sp + sum(n for n, op in cigar if op != "I") > len(s):
+        raise ValueError("the CIGAR runs past its sequences")
+    for n, op in cigar:
+        if op == "M":
+            a0.append(q[qp:qp + n]), a1.append(s[sp:sp + n])
+            qp, sp = qp + n, sp + n
+        elif op == "I":
+            a0.append(q[qp:qp + n]), a1.append(b"-" * n)
+            qp += n
+        else:
+            a0.append(b"-" * n), a1.append(s[sp:sp + n])
+            sp += n
+    return b"".join(a0), b"".join(a1)
 
 
 def makedb(ref, space='11111111', nr=AA9, step=1, ht=-1, chk=500000, device=0):

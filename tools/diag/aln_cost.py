@@ -1,10 +1,12 @@
 """What asking for the alignments costs on BASELINE config 3 (100k synthetic proteins x 300 aa, seed 11111011111, aa9):
-the same steps (index build + search) with alignments off and on, interleaved, best and median per mode.
+the same steps (index build + search) in three modes -- plain, with a CIGAR per row, with the aligned strings -- interleaved,
+best and median per mode.
 
-    python tools/diag/aln_cost.py [--steps K] [--warmup W] [--n N]
+    python tools/diag/aln_cost.py [--steps K] [--warmup W] [--n N] [--modes plain,cigar,strings]
 
-Prints one JSON line: ms per step for both modes, their ratio, rows and alignment bytes.  For the kernel table run it under
-rocprofv3 --kernel-trace --stats (k_traceback<false> is the counting walk, k_traceback<true> the emitting one).
+Prints one JSON line: ms per step for every mode, the ratios to the plain search, rows, the strings' bytes, the CIGARs' runs (total,
+mean and maximum per row) and the bytes their download takes.  For the kernel table run it under rocprofv3 --kernel-trace --stats
+(k_traceback<false> is the counting walk, k_traceback<true> the emitting one; k_cigar_count / k_cigar_emit code the runs).
 """
 import argparse
 import json
@@ -20,26 +22,40 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--n", type=int, default=100000)
+ap.add_argument("--modes", default="plain,cigar,strings")
 a = ap.parse_args()
+modes = [m for m in a.modes.split(",") if m]
+assert modes and set(modes) <= {"plain", "cigar", "strings"}, "--modes: plain, cigar, strings"
 fa = synthprot.synthprot(a.n, 300)
 s = fsearch.Searcher(ssd="11111011111", nr="AST,CFILMVY,DN,EQ,G,H,KR,P,W", ht=120000000, chk=50000, step=1, v=500, expect=1e-5, flt="T")
 s.load_ref_bytes(fa)
 s.load_queries_bytes(fa)
-ms = {False: [], True: []}
-rows = {}
+ms = {m: [] for m in modes}
+info = {}
 for it in range(a.warmup + a.steps):
-    for on in (False, True):
+    for m in modes:
         t = time.perf_counter()
         s.drop_index()
         s.build_index()
-        h = s.search(alignments=on)
+        h = s.search(alignments=m == "strings", cigar=m == "cigar")
         dt = (time.perf_counter() - t) * 1e3
-        rows[on] = (len(h), h.aln_bytes)
+        if m not in info:   # (outside the timed part of later steps)
+            info[m] = {"rows": len(h)}
+            if m == "strings":
+                info[m]["aln_bytes"] = h.aln_bytes
+            if m == "cigar":
+                ops, off = h.cigar_buffer()
+                per_row = off[1:] - off[:-1]
+                info[m].update(runs=int(len(ops)), runs_per_row_mean=round(float(per_row.mean()), 3) if len(per_row) else 0.,
+                               runs_per_row_max=int(per_row.max()) if len(per_row) else 0,
+                               download_bytes=int(4 * len(ops) + 4 * (len(h) + 1)), bytes_per_row=round(4. * len(ops) / max(len(h), 1), 2))
         h.close()
         if it >= a.warmup:
-            ms[on].append(dt)
+            ms[m].append(dt)
 s.close()
-off, on = statistics.median(ms[False]), statistics.median(ms[True])
-print(json.dumps({"workload": "config 3, %d proteins" % a.n, "steps": a.steps, "off_ms_median": round(off, 2), "on_ms_median": round(on, 2),
-                  "off_ms_best": round(min(ms[False]), 2), "on_ms_best": round(min(ms[True]), 2), "ratio_median": round(on / off, 3),
-                  "rows": rows[True][0], "rows_off": rows[False][0], "aln_bytes": rows[True][1]}))
+out = {"workload": "config 3, %d proteins" % a.n, "steps": a.steps}
+for m in modes:
+    out[m] = dict(info[m], ms_median=round(statistics.median(ms[m]), 2), ms_best=round(min(ms[m]), 2))
+    if "plain" in modes and m != "plain":
+        out[m]["ratio_median"] = round(statistics.median(ms[m]) / statistics.median(ms["plain"]), 3)
+print(json.dumps(out))
