@@ -265,6 +265,28 @@ int so_mcl(int device, int64_t n, const int64_t *indptr, const int32_t *indices,
 void so_mcl_free(so_mcl_result *result);
 const char *so_mcl_last_error(void);
 
+/* Affinity propagation on the edge list of the orthology graph.  Replaces: the loop of bin/find_cluster.py `apclust_blk` (404-513)
+ * with its passes `max_row`, `update_R`, `sum_col`, `update_A`, `get_change` (309-401), which `main` runs for `-a apc` with a batch
+ * size above zero -- in the reference's arithmetic order (csrc/apc.hip): float64 operations on float32-stored R and A, row maxima
+ * carried over all rounds, column sums added in entry order, the first maximum of a row gives its label; always `rounds` rounds
+ * (the reference's convergence counter never moves on this path).  Input: n_entries entries (row, col, score) in the reference's
+ * order (borrowed), gene numbers in 0 .. n_genes - 1; repeated entries are entries of their own.  n_genes above 2^24 is refused
+ * (the reference keeps gene numbers in float32 there).  `damp` is used as given.  Output: labels[n_genes] = the exemplar of every
+ * gene (a gene without entries keeps its own number), r / a[n_entries] = the float32 stores after the last round, in entry order;
+ * allocated by the library, released with so_apc_free().  Returns 0 / non-zero with a message in so_apc_last_error().  No so_ctx:
+ * the call owns a stream of `device` and queues all rounds on it. */
+typedef struct so_apc_result {
+    int64_t n_genes, n_entries;
+    int32_t rounds;
+    int64_t *labels;
+    float *r;
+    float *a;
+} so_apc_result;
+int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t *row, const int32_t *col, const float *score, double damp,
+           int32_t rounds, so_apc_result *out);
+void so_apc_free(so_apc_result *result);
+const char *so_apc_last_error(void);
+
 /* Host-side tokeniser of tab-separated text for the stages behind the search (csrc/tsv.hip; no device, no so_ctx).  Replaces: the
  * per-line `split('\t')` + `float()` loops of bin/find_orth.py (blastparse, 58-125) and bin/find_cluster.py (1425-1467) as the
  * numpy tokeniser of swiftortho_amd/find_orth.py restates them.

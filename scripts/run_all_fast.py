@@ -11,7 +11,8 @@ What is NOT the reference here: for `-A mcl` -- its default -- the reference wra
 (`mcl ... --abc -te N -I 1.5`; van Dongen's binary, not part of the reference repository and absent from this image).  This wrapper runs
 `bin/find_cluster.py -a mcl` (the reference's own Python implementation of the algorithm, SURVEY.md 8f-2, Markov loop on the GPU) on the
 same .xyz instead: the two implement the same algorithm with different pruning schemes, so the .clsr of `-A mcl` is not pinned against
-the reference wrapper's.  `-A apc` / `-A sap` are refused by find_cluster here (affinity propagation is outside 8f-2)."""
+the reference wrapper's.  `-A apc` is handed to find_cluster as `-a apc` (affinity propagation, loop on the GPU; ids without '|', so
+every gene counts as a taxon of its own in the preference, as in the reference wrapper); `-A sap` is refused by find_cluster."""
 import os
 import subprocess
 import sys
@@ -29,7 +30,7 @@ ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '
 def main(argv):
     a = parse_flags(argv, ARGS)
     if a['-i'] == '':
-        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl] [-I 1.5]' % argv[0])
+        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5]' % argv[0])
         raise SystemExit()
     fas, name = a['-i'], a['-i'].split(os.sep)[-1]
     t = time()

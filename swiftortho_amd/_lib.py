@@ -43,12 +43,18 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_align_pairs", "so_align_pairs_aln", "so_set_profile",
            "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
-           "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar"]
+           "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
+           "so_apc", "so_apc_free", "so_apc_last_error"]
 
 
 class SoMclResult(C.Structure):
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("rounds", C.c_int32), ("converged", C.c_int32), ("indptr", C.POINTER(C.c_int64)),
                 ("indices", C.POINTER(C.c_int32)), ("data", C.POINTER(C.c_float))]
+
+
+class SoApcResult(C.Structure):
+    _fields_ = [("n_genes", C.c_int64), ("n_entries", C.c_int64), ("rounds", C.c_int32), ("labels", C.POINTER(C.c_int64)),
+                ("r", C.POINTER(C.c_float)), ("a", C.POINTER(C.c_float))]
 
 _lib = None
 
@@ -156,6 +162,9 @@ def load():
     L.so_mcl.argtypes = [C.c_int, i64, vp, vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(SoMclResult)]
     L.so_mcl_free.argtypes = [C.POINTER(SoMclResult)]
     L.so_mcl_last_error.restype = cp
+    L.so_apc.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(SoApcResult)]
+    L.so_apc_free.argtypes = [C.POINTER(SoApcResult)]
+    L.so_apc_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

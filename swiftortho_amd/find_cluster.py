@@ -1,4 +1,4 @@
-"""find_cluster -- counterpart of SwiftOrtho's bin/find_cluster.py for `-a mcl`: from the orthology
+"""find_cluster -- counterpart of SwiftOrtho's bin/find_cluster.py for `-a mcl` and `-a apc`: from the orthology
 relations file (find_orth output) to ortholog groups, one tab-separated group per line, same flags,
 same stdout.
 
@@ -7,8 +7,11 @@ Last stage of BASELINE config 5 (find_hit -> find_orth -> find_cluster -a mcl -I
 sparse x sparse expansion, inflation, pruning on float32 CSR matrices -- runs on the GPU (libsohit `so_mcl`,
 csrc/mcl.hip) with scipy's arithmetic order, because the pruning decisions, and therefore the groups, depend
 on it; the graph bookkeeping around it (best-neighbour components, batching, the read-out) is host code.
-There is no CPU path for the loop: without the HIP library `-a mcl` fails.  Only `mcl` is provided; the
-reference's default `-a apc` and `-a sap` (affinity propagation) are refused with a message and exit code 2.
+So does the affinity-propagation loop of `-a apc` (libsohit `so_apc`, csrc/apc.hip), with the reference's own
+arithmetic order.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
+`-a apc` has to be named on the command line: a command without `-a` is still refused (exit code 2), as are `-a sap`
+(it needs pysapc), `-a apc` with a batch size `-b` of 0 or below (the reference's in-place float32 variant) and every
+other spelling that starts with `ap` (the reference then runs without preference entries).
 
 Reference behaviour reproduced (bin/find_cluster.py, `cnc` 1470-1673, `mcl_xyz` 1425-1467, `mcl`
 652-689, `normalize` 636-646), including its accidents, because they decide which genes appear:
@@ -27,6 +30,23 @@ Reference behaviour reproduced (bin/find_cluster.py, `cnc` 1470-1673, `mcl_xyz` 
     5th round against the normalised matrix of that round; groups = connected components of the
     entries > 1e-5 -- read, as the reference does, by zipping the coordinates of the non-zero entries
     with the raw data array (which still holds the pruned zeros when the round limit was hit).
+
+And for `-a apc` (`fc2mat` 767-858, `apclust_blk` 404-513 with its passes 309-401, `main` 1705-1723):
+  * rows with a > b are skipped before the genes are numbered; a gene is numbered by its first appearance even when
+    the row's weight then fails to parse (`float(w)`, then `float(w.split('rm')[0])`, else the row is dropped): such a
+    gene is a group of its own; a row of neither three nor four fields raises;
+  * every kept row gives the entries (a, b, w) and (b, a, w); repeated pairs and self pairs are entries of their own;
+    after all rows one preference entry (g, g, -20 x number of distinct `id.split('|')[0]`) per gene; gene numbers,
+    scores, responsibilities and availabilities are stored as float32, the arithmetic on them is float64;
+  * the two largest values of a row (R + A) are never reset between rounds: they start at 0 (the first at gene 0) and run
+    on over all rounds, and a displaced maximum is not demoted to second place;
+  * the responsibility of the diagonal enters the availabilities unrounded, the column sums add the rounded ones in
+    entry order;
+  * the convergence counter is handed to `get_change` by value, so the loop always runs its 100 rounds;
+  * a gene's exemplar is the first entry of its row that reaches the row's maximum of R + A; groups = connected
+    components of the gene -> exemplar graph, genes in number order;
+  * `-p` and `-t` are parsed and never used; the batch size `-b` (> 0) cannot change a result;
+  * the reference writes and removes `<input>.npy`; no file is written here.
 """
 import sys
 
@@ -40,11 +60,12 @@ def manual_print(prog='find_cluster.py'):
     print('    python %s -i foo.xyz -d 0.5' % prog)
     print('Parameters:')
     print('  -i: tab-delimited file which contain 3 columns')
-    print('  -d: damp (affinity propagation; not provided here)')
-    print('  -p: parameter of preference for apc (not provided here)')
+    print('  -d: damp for apc')
+    print('  -p: parameter of preference for apc')
     print('  -I: inflation parameter for mcl')
-    print('  -a: algorithm (mcl)')
+    print('  -a: algorithm (mcl or apc)')
     print('  -t: cpu number')
+    print('  -b: batch size for apc (above 0; no effect on the result)')
 
 
 class _Graph:
@@ -342,20 +363,27 @@ def _edge_columns_native(data):
     return names, cx[u], cy[u], z[u], ztext
 
 
-def _edge_columns(lines):
-    """relation rows ('[type\\t]x\\ty\\tweight\\n') -> (ids sorted bytewise, code of x, code of y, weight, weight text of row i) for the
-    rows with x <= y, in file order"""
-    data = None
+def _text_bytes(lines):
+    """an open file or a byte string as the bytes the reference's line loop sees; None for an iterable of lines"""
     if hasattr(lines, 'read'):
         data = lines.buffer.read() if hasattr(lines, 'buffer') else lines.read()
     elif isinstance(lines, (bytes, bytearray)):
         data = bytes(lines)
+    else:
+        return None
+    if isinstance(data, str):
+        data = data.encode('utf-8')
+    data = data.replace(b'\r\n', b'\n').replace(b'\r', b'\n')   # the reference reads in text mode (universal newlines)
+    if data and not data.endswith(b'\n'):
+        data = data[:-1] + b'\n'                                # ... and cuts the last character of every line, newline or not
+    return data
+
+
+def _edge_columns(lines):
+    """relation rows ('[type\\t]x\\ty\\tweight\\n') -> (ids sorted bytewise, code of x, code of y, weight, weight text of row i) for the
+    rows with x <= y, in file order"""
+    data = _text_bytes(lines)
     if data is not None:
-        if isinstance(data, str):
-            data = data.encode('utf-8')
-        data = data.replace(b'\r\n', b'\n').replace(b'\r', b'\n')   # the reference reads in text mode (universal newlines)
-        if data and not data.endswith(b'\n'):
-            data = data[:-1] + b'\n'                                # ... and cuts the last character of every line, newline or not
         cols = _edge_columns_native(data)
         if cols is not None:
             return cols
@@ -450,6 +478,117 @@ def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl):
     return out
 
 
+def _apc_rows_python(lines):
+    """fc2mat's line loop (find_cluster.py:779-808), literally: -> (ids by number, x numbers, y numbers, weights) of the kept rows"""
+    number, xs, ys, zs = {}, [], [], []
+    for i in lines:
+        j = i[:-1].split('\t')
+        if len(j) == 4:
+            x, y, z = j[1:4]
+        else:
+            x, y, z = j          # (neither three nor four fields: raises, as the reference does)
+        if x > y:
+            continue
+        if x not in number:
+            number[x] = len(number)
+        if y not in number:
+            number[y] = len(number)
+        try:
+            w = float(z)
+        except Exception:
+            try:
+                w = float(z.split('rm')[0])
+            except Exception:
+                continue         # (its genes stay numbered)
+        xs.append(number[x]), ys.append(number[y]), zs.append(w)
+    return list(number), np.array(xs, dtype=np.int64), np.array(ys, dtype=np.int64), np.array(zs, dtype=np.float64)
+
+
+def _rows_have_three_or_four_fields(data):
+    """every line of `data` holds two or three tabs (the tokeniser's fast path reads the first columns of a longer row, where the
+    reference raises)"""
+    tabs = np.frombuffer(data, dtype=np.uint8) == 9
+    ends = np.flatnonzero(np.frombuffer(data, dtype=np.uint8) == 10)
+    per_line = np.diff(np.concatenate([[0], np.cumsum(tabs)[ends]]))
+    return bool(np.all((per_line == 2) | (per_line == 3)))
+
+
+def apc_entries(lines):
+    """The entry list fc2mat (find_cluster.py:767-858) writes for `-a apc`: genes numbered by first appearance over the rows with
+    x <= y (x before y); per kept row (X, Y, w) then (Y, X, w); after all rows one preference entry (g, g, -20 * number of distinct
+    `id.split('|')[0]`) per gene.  `lines`: an open file, bytes or an iterable of lines.  Plain input goes through libsohit's
+    tokeniser, anything it does not take (a weight only Python can judge, a row of another shape, a tiny input) through the literal loop.
+    -> (ids by number, row int32, col int32, score float32, number of genes)"""
+    data = _text_bytes(lines)
+    cols = None
+    if data is not None:
+        if _rows_have_three_or_four_fields(data):
+            cols = _edge_columns_native(data)
+        lines = data.decode('utf-8').splitlines(True)
+    if cols is not None:
+        ids, cx, cy, z, _ = cols
+        seq = np.empty(2 * len(cx), dtype=np.int64)
+        seq[0::2], seq[1::2] = cx, cy
+        vals, first = np.unique(seq, return_index=True)
+        order = np.argsort(first, kind='stable')
+        number_of_code = np.zeros(len(ids), dtype=np.int64)
+        number_of_code[vals[order]] = np.arange(len(vals))
+        names, X, Y, Z = [ids[c] for c in vals[order].tolist()], number_of_code[cx], number_of_code[cy], z
+    else:
+        names, X, Y, Z = _apc_rows_python(lines)
+    n = len(names)
+    pref = len(set(g.split('|')[0] for g in names)) * -20.
+    row = np.empty(2 * len(X) + n, dtype=np.int32)
+    col = np.empty(2 * len(X) + n, dtype=np.int32)
+    score = np.empty(2 * len(X) + n, dtype=np.float32)
+    m = 2 * len(X)
+    row[0:m:2], row[1:m:2], col[0:m:2], col[1:m:2] = X, Y, Y, X
+    score[0:m:2] = score[1:m:2] = Z.astype(np.float32)
+    row[m:] = col[m:] = np.arange(n)
+    score[m:] = np.float32(pref)
+    return names, row, col, score, n
+
+
+def device_apc(row, col, score, n_genes, damp, rounds=100, device=0):
+    """the affinity-propagation loop on the GPU (libsohit so_apc, csrc/apc.hip) over the entries (row, col, score) in the reference's
+    order -> (labels int64[n_genes], r float32, a float32 in entry order) after `rounds` rounds.  No CPU path: raises when the HIP
+    library or a device is missing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoApcResult()
+    ri = np.ascontiguousarray(row, dtype=np.int32)
+    ci = np.ascontiguousarray(col, dtype=np.int32)
+    sv = np.ascontiguousarray(score, dtype=np.float32)
+    if not (len(ri) == len(ci) == len(sv)):
+        raise ValueError('device_apc: row, col and score differ in length')
+    n = len(ri)
+    rc = L.so_apc(device, int(n_genes), n, ri.ctypes.data if n else None, ci.ctypes.data if n else None, sv.ctypes.data if n else None, float(damp), int(rounds),
+                  C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_apc_last_error().decode())
+    try:
+        d = int(res.n_genes)
+        labels = np.ctypeslib.as_array(res.labels, shape=(max(d, 1),))[:d].copy()
+        r = np.ctypeslib.as_array(res.r, shape=(max(n, 1),))[:n].copy()
+        a = np.ctypeslib.as_array(res.a, shape=(max(n, 1),))[:n].copy()
+    finally:
+        L.so_apc_free(C.byref(res))
+    return labels, r, a
+
+
+def apc(lines, damp=0.5, loop=device_apc):
+    """`-a apc` (fc2mat, apclust_blk, main 1705-1723): relation rows -> groups (lists of gene ids) in the reference's output order: the
+    connected components of the graph after `add_edge(g, exemplar of g)` for the genes in number order.  `loop`: the affinity-propagation
+    loop over the entry list (the device implementation; the tests pass the literal numpy oracle to check this host bookkeeping on CPU)."""
+    names, row, col, score, n = apc_entries(lines)
+    if n == 0:
+        return []
+    labels = np.asarray(loop(row, col, score, n, damp)[0], dtype=np.int64)
+    g = _Graph.from_pairs((np.arange(n, dtype=np.int64), labels))
+    return [[names[e] for e in comp] for comp in g.components()]
+
+
 def parse(argv):
     from .fsearch import parse_flags
     return parse_flags(argv, DEFAULTS)
@@ -463,27 +602,44 @@ def main(argv=None):
         raise SystemExit()
     try:
         qry, ifl, alg = args['-i'], float(args['-I']), args['-a'].lower()
-        float(args['-d']), float(args['-p']), int(args['-t']), int(args['-b'])
+        dmp, bch = float(args['-d']), int(args['-b'])
+        float(args['-p']), int(args['-t'])
     except Exception:
         manual_print(argv[0] if argv else 'find_cluster.py')
         raise SystemExit()
-    if alg != 'mcl':
-        sys.stderr.write('find_cluster: only -a mcl is provided (the reference\'s affinity-propagation modes are not)\n')
+    named = any((t == '-a' and i + 2 < len(argv)) or (t[:2] == '-a' and len(t) > 2) for i, t in enumerate(argv[1:]))   # (the default is 'apc': only a named algorithm runs)
+    if alg == 'apc' and named and bch > 0:
+        run, warm_up = (lambda f: apc(f, dmp)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
+    elif alg == 'mcl':
+        run = lambda f: cnc(f, ifl)
+        warm_up = lambda: device_mcl(np.array([0, 1]), np.array([0]), np.array([1.], dtype=np.float32), ifl, rounds=1)
+    else:
+        if not named:
+            why = 'no algorithm named: say -a mcl or -a apc (the reference\'s default, apc, has to be asked for here)'
+        elif alg == 'apc':
+            why = '-a apc needs a batch size -b above 0 (the reference\'s in-place float32 variant of -b 0 is not provided; -a mcl is)'
+        elif alg == 'sap':
+            why = '-a sap is not provided (it needs pysapc); -a mcl and -a apc are'
+        elif alg.startswith('ap'):
+            why = '-a %s is not provided (the reference runs it as apc without preference entries); -a mcl and -a apc are' % args['-a']
+        else:
+            why = 'unknown algorithm -a %s: -a mcl and -a apc are provided' % args['-a']
+        sys.stderr.write('find_cluster: %s\n' % why)
         return 2
-    # the HIP runtime and the Markov kernels' code object take ~0.25 s to come up: a thread brings them up on a 1 x 1 matrix while
+    # the HIP runtime and the loop kernels' code object take ~0.25 s to come up: a thread brings them up on a 1 x 1 problem while
     # this one reads the edges and finds the components (failures there are left to the real call, which reports them)
     import threading
 
     def warm():
         try:
-            device_mcl(np.array([0, 1]), np.array([0]), np.array([1.], dtype=np.float32), ifl, rounds=1)
+            warm_up()
         except Exception:
             pass
     wt = threading.Thread(target=warm, daemon=True)
     wt.start()
     try:
         with open(qry, 'r') as f:
-            groups = cnc(f, ifl)
+            groups = run(f)
         w = sys.stdout.write
         for grp in groups:
             w('\t'.join(grp) + '\n')
