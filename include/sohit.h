@@ -251,7 +251,9 @@ int so_align_pairs_cigar(so_ctx *ctx, int kernel, int64_t n, const int64_t *task
  * every check_every-th round -- with scipy's arithmetic order (csrc/mcl.hip).  Input: an n x n CSR matrix (rows = indptr,
  * columns = indices, float32 data; inputs are borrowed).  Output: the matrix the loop ends with, in scipy's storage order and
  * with its explicitly stored zeros (the reference's read-out depends on both); arrays allocated by the library, released with
- * so_mcl_free().  Returns 0 / non-zero with a message in so_mcl_last_error().  No so_ctx: the call owns a stream of `device`. */
+ * so_mcl_free().  Returns 0 / non-zero with a message in so_mcl_last_error().  No so_ctx: the call owns a stream of `device`
+ * and reads the SOHIT_* switches itself (SOHIT_POISON, SOHIT_MCL_SCRATCH; so_apc: SOHIT_POISON).  check_every below 1 counts as 1;
+ * an empty block (n = 0) is served: nothing moves, so the first convergence test succeeds. */
 typedef struct so_mcl_result {
     int64_t n, nnz;
     int32_t rounds;    /* rounds executed                                  */

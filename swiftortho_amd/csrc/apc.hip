@@ -284,6 +284,9 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_apc: no HIP device available (libsohit has no CPU fallback)");
         if (device < 0 || device >= nd) throw SoError("so_apc: device index out of range");
         HIP_CHECK(hipSetDevice(device));
+        Tune tn;   // no context: the switches are read per call
+        tn.read();
+        const PoisonScope poison((int)tn.poison);
 
         // rows: the entries in row order; columns: positions (in row order) and rows of each column's entries, in entry order
         std::vector<u32> rptr, rorder, cptr, corder;

@@ -37,6 +37,14 @@ struct DevOom : SoError {
     } while (0)
 
 extern thread_local int g_poison;   // Tune::poison of the context whose call runs on this thread (-1: none)
+// ... for the duration of a call that has no context (so_mcl, so_apc)
+struct PoisonScope {
+    int before;
+    explicit PoisonScope(int v) : before(g_poison) { g_poison = v; }
+    ~PoisonScope() { g_poison = before; }
+    PoisonScope(const PoisonScope&) = delete;
+    PoisonScope& operator=(const PoisonScope&) = delete;
+};
 
 // Grow-only device buffer.
 template <class T>

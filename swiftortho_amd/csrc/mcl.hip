@@ -309,6 +309,7 @@ struct Mcl {
     DevBuf<u32> scan_tmp;
     std::vector<u32> hP;
     std::vector<u64> hoff;
+    size_t budget = (size_t)1 << 28;   // u32 words (1 GiB) of scratch per range of rows (SOHIT_MCL_SCRATCH: tests)
 
     void normalize(Csr& x) {
         if (!x.nnz) return;
@@ -354,12 +355,17 @@ struct Mcl {
         c.n = n;
         c.rp.ensure((size_t)n + 2);
         P.ensure((size_t)n + 2), ccnt.ensure((size_t)n + 2), soff.ensure((size_t)n + 2);
+        if (!n) {   // an empty block: nothing to launch (a grid of 0 blocks is an invalid configuration)
+            HIP_CHECK(hipMemsetAsync(c.rp.p, 0, sizeof(u32), st));
+            c.nnz = 0;
+            c.idx.ensure(2), c.val.ensure(2);
+            return;
+        }
         hipLaunchKernelGGL(k_mcl_products, dim3((n + 255) / 256), dim3(256), 0, st, x.rp.p, x.idx.p, n, P.p);
         hP.resize(n);
         HIP_CHECK(hipMemcpyAsync(hP.data(), P.p, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         std::vector<std::pair<u32, u32>> ranges;
-        const size_t budget = (size_t)1 << 28;   // 1 GiB of u32 scratch per range of rows
         plan(hP, 1, ranges, budget);
         size_t maxw = 0;
         for (auto& r : ranges) {
@@ -396,7 +402,7 @@ struct Mcl {
                 }
         }
         rows.ensure((size_t)n + 4);
-        if (n) HIP_CHECK(hipMemcpyAsync(rows.p, tier_rows.data(), (size_t)n * sizeof(u32), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(rows.p, tier_rows.data(), (size_t)n * sizeof(u32), hipMemcpyHostToDevice, st));
         auto launch_tiers = [&](bool write, size_t ri) {
             for (int t = 0; t < 3; ++t) {
                 const u32 first = tier_at[ri][t].first, cnt = tier_at[ri][t].second;
@@ -431,12 +437,13 @@ struct Mcl {
 
     bool converged(const Csr& x, const Csr& old, float rtol, float atol) {
         const u32 n = x.n;
+        if (!n) return 0.f <= atol;   // an empty block: no entry differs
         std::vector<u32> orp((size_t)n + 1), oc(n);
         HIP_CHECK(hipMemcpyAsync(orp.data(), old.rp.p, ((size_t)n + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         for (u32 i = 0; i < n; ++i) oc[i] = orp[i + 1] - orp[i];
         std::vector<std::pair<u32, u32>> ranges;
-        plan(oc, 0, ranges, (size_t)1 << 28);
+        plan(oc, 0, ranges, budget);
         if (ranges.size() != 1) throw SoError("so_mcl: convergence scratch exceeds the device budget");
         size_t maxw = 0;
         for (u32 i = 0; i < n; ++i)
@@ -497,7 +504,11 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
         const int64_t nnz0 = indptr[n];
         if (nnz0 < 0 || nnz0 > 0x7FFFFFF0ll) throw SoError("so_mcl: matrix too large for 32-bit positions");
         if (check_every < 1) check_every = 1;
+        Tune tn;   // no context: the switches are read per call
+        tn.read();
+        const PoisonScope poison((int)tn.poison);
         Mcl m;
+        if (tn.mcl_scratch >= 0) m.budget = (size_t)tn.mcl_scratch;
         HIP_CHECK(hipStreamCreate(&m.st));
         struct Guard {
             hipStream_t s;

@@ -1,5 +1,6 @@
 // tune.h -- every SOHIT_* switch of libsohit.so in ONE table.  The environment is read ONCE, by so_create (Tune::read), into the
 // context's Tune; the launch helpers in the k_*.hip files read the current context's copy through tune() -- no getenv() anywhere else.
+// (so_mcl and so_apc run without a context: each call reads the table into a Tune of its own at entry.)
 // None of the switches changes results, except the two ablation variants marked so.  tools/diag/README.md lists what they are for.
 #pragma once
 #include <cstdlib>
@@ -50,6 +51,7 @@
     X(B, hit_cache, "SOHIT_HIT_CACHE", 1, "one released result array is kept for the next search")                                                             \
     X(P, keep_cands, "SOHIT_KEEP_CANDS", 0, "tests: keep every query's candidate list (so_query_candidates)")                                                  \
     X(P, keep_masked, "SOHIT_KEEP_MASKED", 0, "tests: keep the masked queries (so_masked_query)")                                                              \
+    X(I, mcl_scratch, "SOHIT_MCL_SCRATCH", -1, "tests: u32 words of expansion / convergence scratch per range of rows (-1: 2^28)")                             \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \

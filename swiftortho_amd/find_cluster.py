@@ -213,9 +213,11 @@ def _block_matrix_sequential(X, Y, Z, dmx):
     return indptr, np.array([k[1] for k in keys], dtype=np.int32), np.array([cell[k] for k in keys], dtype=np.float32)
 
 
-def device_mcl(indptr, indices, data, inflation, device=0, rounds=100):
+def device_mcl(indptr, indices, data, inflation, device=0, rounds=100, check=5, prune=1e-5, rtol=1e-5, atol=1e-8, info=None):
     """the Markov loop on the GPU (libsohit so_mcl, csrc/mcl.hip) -> the final matrix as (indptr, indices, data) in the reference's
-    storage order, stored zeros included.  No CPU path: raises when the HIP library or a device is missing."""
+    storage order, stored zeros included.  `rounds`, `check`, `prune`, `rtol`, `atol`: the reference's own values by default (at most
+    100 rounds, convergence test every 5th, pruning below 1e-5); `info`: a dict that receives `rounds` (rounds begun) and `converged`
+    (0 / 1).  No CPU path: raises when the HIP library or a device is missing."""
     import ctypes as C
     from . import _lib
     L = _lib.load()
@@ -223,12 +225,14 @@ def device_mcl(indptr, indices, data, inflation, device=0, rounds=100):
     ip = np.ascontiguousarray(indptr, dtype=np.int64)
     ix = np.ascontiguousarray(indices, dtype=np.int32)
     dv = np.ascontiguousarray(data, dtype=np.float32)
-    rc = L.so_mcl(device, len(ip) - 1, ip.ctypes.data, ix.ctypes.data if len(ix) else None, dv.ctypes.data if len(dv) else None, float(inflation), int(rounds), 5,
-                  1e-5, 1e-5, 1e-8, C.byref(res))
+    rc = L.so_mcl(device, len(ip) - 1, ip.ctypes.data, ix.ctypes.data if len(ix) else None, dv.ctypes.data if len(dv) else None, float(inflation), int(rounds), int(check),
+                  float(prune), float(rtol), float(atol), C.byref(res))
     if rc != 0:
         raise RuntimeError(L.so_mcl_last_error().decode())
     try:
         n, nnz = int(res.n), int(res.nnz)
+        if isinstance(info, dict):
+            info.update(rounds=int(res.rounds), converged=int(res.converged))
         out_ip = np.ctypeslib.as_array(res.indptr, shape=(n + 1,)).copy()
         out_ix = np.ctypeslib.as_array(res.indices, shape=(max(nnz, 1),))[:nnz].copy()
         out_dv = np.ctypeslib.as_array(res.data, shape=(max(nnz, 1),))[:nnz].copy()

@@ -93,10 +93,16 @@ def test_device_mcl_random_graphs_vs_scipy(seed, nfam, famsize, inflation, round
     AVX512 SVML routine, which differs from libm's powf and from the correctly rounded value in ~20 % of inputs by one ulp; a hundred
     non-contracting rounds amplify that, so the reference itself does not reproduce such a run across CPU types.  For the same reason a
     run stopped where many entries sit AT the pruning threshold -- inflation 3.0 cut after two rounds, inflation 1.5 after six -- shows a
-    handful of flipped decisions against this host's numpy; such cases are not in the list.)"""
+    handful of flipped decisions against this host's numpy; such cases are not in the list.)
+    The round in which the loop stops and whether it converged (so_mcl_result.rounds, .converged) are the oracle's: in these runs the
+    maximum of the last check is exactly 0 and the one before it is far above atol, with numpy's power and with the exact one alike,
+    so the decision does not hang on the power routine.  (Short runs are compared bit for bit in tests/test_gpu_mcl.py.)"""
     from swiftortho_amd import find_cluster as fc
     names, ip, ix, dv = fc.block_matrix(_family_graph(seed, nfam, famsize))
-    a, b = fc.device_mcl(ip, ix, dv, inflation, rounds=rounds), scipy_mcl(ip, ix, dv, inflation, rounds=rounds)
+    got, want = {}, {}
+    a, b = fc.device_mcl(ip, ix, dv, inflation, rounds=rounds, info=got), scipy_mcl(ip, ix, dv, inflation, rounds=rounds, info=want)
+    assert got == {"rounds": want["rounds"], "converged": want["converged"]}
+    assert (want["rounds"] < 100 and want["converged"] == 1) if rounds == 100 else (want["rounds"], want["converged"]) == (rounds, 0)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     assert np.allclose(a[2], b[2], rtol=1e-6, atol=1e-12)
     assert fc.surviving_pairs(*a) == fc.surviving_pairs(*b)
@@ -234,8 +240,10 @@ def test_device_mcl_zero_sum_first_column(case, monkeypatch):
     monkeypatch.setattr(mo, "_normalize", spy)
     for rounds in (1, 2, 4, 100):
         seen.clear()
-        got = fc.device_mcl(ip, ix, dv.copy(), infl, rounds=rounds)
-        want = mo.scipy_mcl(ip.copy(), ix.copy(), dv.copy(), infl, rounds=rounds)   # (scipy normalises the data array it is handed in place)
+        ginfo, winfo = {}, {}
+        got = fc.device_mcl(ip, ix, dv.copy(), infl, rounds=rounds, info=ginfo)
+        want = mo.scipy_mcl(ip.copy(), ix.copy(), dv.copy(), infl, rounds=rounds, info=winfo)   # (scipy normalises the data array it is handed in place)
+        assert ginfo == {"rounds": winfo["rounds"], "converged": winfo["converged"]} == {"rounds": rounds, "converged": 0}, (name, rounds)
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (name, rounds)
         assert np.allclose(got[2], want[2], rtol=1e-6, atol=1e-12, equal_nan=True), (name, rounds)
         assert np.isnan(got[2]).sum() == np.isnan(want[2]).sum()
