@@ -289,6 +289,41 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t *row, c
 void so_apc_free(so_apc_result *result);
 const char *so_apc_last_error(void);
 
+/* The candidate stage of find_orth on the device (csrc/orth.hip).  Replaces: the row loop of bin/find_orth.py -- coverage / identity
+ * filter and -n normalisation (156-234), per query run the best hit per subject, the best score per subject taxon and out of the
+ * query's taxon, the in-paralog / ortholog / co-ortholog candidates (298-348) and "a pair is a relation iff proposed exactly twice"
+ * (351-377) -- as swiftortho_amd/find_orth.py `candidates()` restates it, bit for bit.
+ * Input: n hit rows in file order -- name codes q / s in 0 .. n_names - 1 and the six float64 columns (host arrays, borrowed), or
+ * so_hit records in DEVICE memory (d_hits: the pointer so_search_device hands out, or any device buffer of records such as the tensor
+ * gathered on rank 0) with the host maps query ordinal -> code (qmap, n_q) and subject ordinal -> code (smap, n_s); the identity
+ * column of a record is cut to the two decimals its text row carries.  tax[n_names]: taxon code of every name, in 0 .. n_taxa - 1.
+ * norm: 0 = no, 1 = bsr, 2 = bal.
+ * Output (allocated by the library, released with so_orth_free()): ot_* / ip_*: the ortholog / in-paralog pairs proposed exactly twice,
+ * ascending by (a, b), in-paralogs in both orientations, scored with the mean of the two proposals -- the last proposed pair of each
+ * list, when it is among them, with the larger one; co_key / co_best: the distinct keys a * max(n_names, 1) + b of the co-ortholog
+ * candidates, ascending, and their best scores; n_rows rows passed the filter, in n_runs runs of one query code, with n_groups distinct
+ * (run, subject).  n = 0 is served and launches nothing.
+ * Ordering: the records call reads d_hits on a stream of its own.  It first waits for ALL work queued on the device, so records
+ * written by any stream before the call are complete (so_search_device has synchronised its stream when it returns); work queued
+ * from another thread while the call runs is not ordered with it.  The records are only read.
+ * Refused with a message (so_orth_last_error): n >= 2^31, n_names * n_names >= 2^63, a name code outside 0 .. n_names - 1, a qidx /
+ * sidx outside its map, a taxon outside 0 .. n_taxa - 1, no HIP device.  No so_ctx: the call owns a stream of `device` and reads the
+ * SOHIT_* switches itself (SOHIT_POISON, SOHIT_ORTH_TIER). */
+typedef struct so_orth_cand {
+    int64_t n_ot, n_ip, n_co, n_rows, n_runs, n_groups;
+    int64_t *ot_a, *ot_b; double *ot_s;
+    int64_t *ip_a, *ip_b; double *ip_s;
+    int64_t *co_key;      double *co_best;
+} so_orth_cand;
+int so_orth_candidates_cols(int device, int64_t n, const int32_t *q, const int32_t *s, const double *idy, const double *aln,
+                            const double *qst, const double *qed, const double *score, const double *qlen, int64_t n_names,
+                            const int32_t *tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_cand *out);
+int so_orth_candidates_records(int device, const so_hit *d_hits, int64_t n, const int32_t *qmap, int64_t n_q, const int32_t *smap,
+                               int64_t n_s, int64_t n_names, const int32_t *tax, int64_t n_taxa, double coverage, double identity,
+                               int norm, so_orth_cand *out);
+void so_orth_free(so_orth_cand *result);
+const char *so_orth_last_error(void);
+
 /* Host-side tokeniser of tab-separated text for the stages behind the search (csrc/tsv.hip; no device, no so_ctx).  Replaces: the
  * per-line `split('\t')` + `float()` loops of bin/find_orth.py (blastparse, 58-125) and bin/find_cluster.py (1425-1467) as the
  * numpy tokeniser of swiftortho_amd/find_orth.py restates them.

@@ -526,6 +526,7 @@ int so_set_option(so_ctx* c, const char* name, const char* value) {
 #define X_I(f) c->tune.f = strtoll(value, nullptr, 0);
 #define X_D(f) c->tune.f = atof(value);
 #define X_P(f) c->tune.f = atoi(value) != 0;
+#define X_T(f) c->tune.f = orth_tier_of(value);
 #define X(kind, field, env, dflt, text) \
     if (!found && n == env) {           \
         X_##kind(field) found = true;   \
@@ -536,6 +537,7 @@ int so_set_option(so_ctx* c, const char* name, const char* value) {
 #undef X_I
 #undef X_D
 #undef X_P
+#undef X_T
         if (!found) throw SoError("so_set_option: unknown switch " + n);
         g_poison = (int)c->tune.poison;
     });

@@ -31,6 +31,19 @@ void sort_pairs_u64_u32(void* temp, size_t temp_bytes, const u64* kin, u64* kout
     HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, kin, kout, vin, vout, (int)n, 0, bits, st));
 }
 
+size_t sort_pairs_u64_u64_temp_bytes(size_t n, int bits) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, (const u64*)nullptr, (u64*)nullptr,
+                                       (int)n, 0, bits, (hipStream_t)0);
+    return bytes;
+}
+
+void sort_pairs_u64_u64(void* temp, size_t temp_bytes, const u64* kin, u64* kout, const u64* vin, u64* vout, size_t n, int bits,
+                        hipStream_t st) {
+    if (n == 0) return;
+    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, kin, kout, vin, vout, (int)n, 0, bits, st));
+}
+
 __global__ __launch_bounds__(256) void k_stride_gather(const u32* __restrict__ src, u32 stride, u32 n, u32* __restrict__ dst) {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) dst[i] = src[(size_t)i * stride];

@@ -26,6 +26,10 @@ void launch_stride_gather(const u32* src, u32 stride, u32 n, u32* dst, hipStream
 size_t sort_pairs_u64_u32_temp_bytes(size_t n, int bits);
 void sort_pairs_u64_u32(void* temp, size_t temp_bytes, const u64* kin, u64* kout, const u32* vin, u32* vout, size_t n, int bits,
                         hipStream_t st);
+// ... with 64-bit values (orth.hip: candidate keys a * M + b with their scores)
+size_t sort_pairs_u64_u64_temp_bytes(size_t n, int bits);
+void sort_pairs_u64_u64(void* temp, size_t temp_bytes, const u64* kin, u64* kout, const u64* vin, u64* vout, size_t n, int bits,
+                        hipStream_t st);
 
 // k_ixsort.hip: (bucket id, entry) pairs grouped by ascending bucket id, members of a bucket in no particular order.  plan:
 // ixsort_plan_elems(NC) u32, scan_tmp: scan_u32_temp_elems of that, (tk, tv): E pairs of scratch; (kin, vin) are scratch too when NC > 2^27

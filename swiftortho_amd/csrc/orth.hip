@@ -1,0 +1,600 @@
+// orth.hip -- the candidate stage of find_orth on the device: from the hit rows of a search (columns uploaded from the host, or the so_hit
+// records so_search_device left in HBM) to the three candidate tables swiftortho_amd/find_orth.py `candidates()` defines -- the ortholog
+// and in-paralog pairs proposed exactly twice, and the best score of every co-ortholog candidate pair.  It is the one part of that stage
+// that touches every row; the normalisers, the co-ortholog products and the text stay on the host, on tables several times smaller.
+//
+// The numpy function is the definition, and the tables are reproduced bit for bit:
+//   * a row is kept unless (1 + |qed - qst|) / qlen < coverage or idy < identity (a NaN coverage keeps the row); the score is the bit
+//     score, bit / aln (bal), or bit / (bit score of the first kept row of the same query CODE, anywhere in the input) (bsr) -- one IEEE
+//     division each;
+//   * a run = consecutive kept rows of one query code; per (run, subject) the largest score; per (run, subject taxon) and per run over
+//     the subjects of another taxon than the query's the largest of those, both starting from 0;
+//   * a (run, subject) group is an in-paralog candidate (same taxon, score >= the run's out-of-taxon maximum, not the query itself;
+//     emitted in both orientations), an ortholog candidate (other taxon, score >= its taxon's maximum) or a co-ortholog candidate (other
+//     taxon otherwise), keyed min(q, s) * M + max(q, s);
+//   * a key proposed exactly twice is a pair scored ((0 + s0) + s1) / 2 -- the LAST key of the sorted list, when it is one, max(s0, s1);
+//     co-ortholog candidates: distinct keys with their maximum.
+// Every maximum is exact whatever the order, so the order of a run's rows and of the candidates never reaches the output: scores are
+// compared through an order-preserving 64-bit code of the double (orth_enc) and reduced with integer atomic maxima.  A NaN is the largest
+// code, as numpy's maximum lets it win; its payload is not kept.  (Where +0 and -0 tie numpy keeps the one it met first; here +0 wins.
+// Bit scores are integers, and their quotients are zero only as +0.)
+//
+// Kernels.  k_orth_unpack (records -> columns), k_orth_rows (keep flags) -> scan -> k_orth_compact (kept rows, scores, first row per
+// code) -> k_orth_bsr -> k_orth_heads -> scan -> k_orth_starts (run bounds).  The host reads the run bounds and sorts the runs into three
+// lists by length (tune.h: ORTH_WAVE_ROWS, ORTH_LDS_ROWS, ORTH_LDS_TAXA; SOHIT_ORTH_TIER forces one tier wherever it can take the run):
+//   k_orth_run_wave     a run of up to 64 rows, a row per lane of one wave: dedupe and maxima with shuffles over the run's lanes;
+//   k_orth_run_table    one run per workgroup: an open-addressing table subject -> best score and a table taxon -> maximum, in LDS
+//                       (<false>) or, for longer runs and more taxa, in global scratch whose extents the host planned (<true>).
+// All three append their candidates to the three lists, one reservation per wave and list.  Then per list: library radix sort of
+// (key, score), k_orth_twice / k_orth_distinct flag the key groups, scan, k_orth_twice_emit / k_orth_distinct_emit write the tables.
+#include "common.h"
+#include "kernels.h"
+#include "../../include/sohit.h"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+#define ORTH_EMPTY 0xFFFFFFFFu                 // free slot of a subject table
+#define ORTH_ENC_ZERO 0x8000000000000000ull    // orth_enc(+0.)
+#define ORTH_LDS_SLOTS (2 * ORTH_LDS_ROWS)
+#define ORTH_MIN_SLOTS 256u                    // smallest table: one slot per thread of the workgroup (the passes over it stay wave-uniform)
+
+// order-preserving code of a double: a < b  <=>  enc(a) < enc(b) for everything but NaN, which is the largest code; 0 is no value's code
+__device__ __forceinline__ u64 orth_enc(double v) {
+    if (v != v) return ~0ull;
+    const u64 b = (u64)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | ORTH_ENC_ZERO);
+}
+__device__ __forceinline__ double orth_dec(u64 e) {
+    if (e == ~0ull) return __longlong_as_double(0x7FF8000000000000ll);
+    return __longlong_as_double((long long)((e >> 63) ? (e & ~ORTH_ENC_ZERO) : ~e));
+}
+__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
+
+struct OrthLists {   // candidate (key, score bits) lists and their fill counters: cnt[0] orthologs, [1] in-paralogs, [2] co-orthologs, [3] groups
+    u64 *ot_k, *ot_v, *ip_k, *ip_v, *co_k, *co_v;
+    u32* cnt;
+};
+
+// `per` list slots for every lane that wants them, one atomic per wave; called by all 64 lanes of the wave
+__device__ __forceinline__ u32 wave_reserve(u32* ctr, bool want, u32 per) {
+    const unsigned long long m = __ballot(want);
+    if (!m) return 0;
+    const u32 lane = threadIdx.x & 63u;
+    const int leader = __builtin_ctzll(m);
+    u32 base = 0;
+    if ((int)lane == leader) base = atomicAdd(ctr, per * (u32)__popcll(m));
+    base = __shfl(base, leader);
+    return base + per * (u32)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// one (run, subject) group: classified and appended; `have` false on lanes without a group (they only take part in the reservations)
+__device__ __forceinline__ void orth_emit(bool have, int q, int s, int qtx, int stx, u64 ebest, u64 etmax, u64 eomax, u64 M, const OrthLists& L) {
+    const double sco = orth_dec(ebest);
+    const bool same = qtx == stx;
+    const bool is_ip = have && same && sco >= orth_dec(eomax) && q != s;
+    const bool is_ot = have && !same && sco >= orth_dec(etmax);
+    const bool is_co = have && !same && !is_ot;
+    const u64 a = (u64)min(q, s), b = (u64)max(q, s);
+    const u64 v = (u64)__double_as_longlong(sco);
+    u32 p = wave_reserve(L.cnt + 0, is_ot, 1);
+    if (is_ot) L.ot_k[p] = a * M + b, L.ot_v[p] = v;
+    p = wave_reserve(L.cnt + 1, is_ip, 2);
+    if (is_ip) L.ip_k[p] = a * M + b, L.ip_v[p] = v, L.ip_k[p + 1] = b * M + a, L.ip_v[p + 1] = v;
+    p = wave_reserve(L.cnt + 2, is_co, 1);
+    if (is_co) L.co_k[p] = a * M + b, L.co_v[p] = v;
+    const unsigned long long g = __ballot(have);
+    if (g && (threadIdx.x & 63u) == 0) atomicAdd(L.cnt + 3, (u32)__popcll(g));
+}
+
+// ---- rows ----------------------------------------------------------------------------------------------------------------------------
+// so_hit records -> the columns columns_from_records() builds; err |= 1 / 2: a qidx / sidx outside its map
+__global__ __launch_bounds__(256) void k_orth_unpack(const so_hit* __restrict__ h, u32 n, const int* __restrict__ qmap, i64 nq, const int* __restrict__ smap, i64 ns,
+                                                     int* __restrict__ q, int* __restrict__ s, double* __restrict__ idy, double* __restrict__ aln,
+                                                     double* __restrict__ qst, double* __restrict__ qed, double* __restrict__ score, double* __restrict__ qlen,
+                                                     u32* __restrict__ err) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const so_hit r = h[i];
+    int qc = 0, sc = 0;
+    if (r.qidx < 0 || r.qidx >= nq) atomicOr(err, 1u);
+    else qc = qmap[r.qidx];
+    if (r.sidx < 0 || r.sidx >= ns) atomicOr(err, 2u);
+    else sc = smap[r.sidx];
+    q[i] = qc, s[i] = sc;
+    // numpy rounds to 6 decimals as rint(x * 1e6) / 1e6; then the two decimals the text row would carry
+    const double r6 = __ddiv_rn(rint(__dmul_rn(r.identity, 1e6)), 1e6);
+    idy[i] = __ddiv_rn(floor(__dadd_rn(__dmul_rn(r6, 100.), 1e-7)), 100.);
+    aln[i] = (double)r.aln, qst[i] = (double)r.qst, qed[i] = (double)r.qed, score[i] = (double)r.bit, qlen[i] = (double)r.qlen;
+}
+
+// keep[i] = the row passes the filter; err |= 4: a name code outside [0, n_names)
+__global__ __launch_bounds__(256) void k_orth_rows(u32 n, const int* __restrict__ q, const int* __restrict__ s, const double* __restrict__ idy,
+                                                   const double* __restrict__ qst, const double* __restrict__ qed, const double* __restrict__ qlen, i64 n_names,
+                                                   double coverage, double identity, u32* __restrict__ keep, u32* __restrict__ err) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (q[i] < 0 || q[i] >= n_names || s[i] < 0 || s[i] >= n_names) atomicOr(err, 4u);
+    const double qcv = __ddiv_rn(__dadd_rn(1., fabs(__dadd_rn(qed[i], -qst[i]))), qlen[i]);
+    keep[i] = ((qcv < coverage) | (idy[i] < identity)) ? 0u : 1u;
+}
+
+// the kept rows in order; norm 2 (bal): score = bit / aln; norm 1 (bsr): first[code] = the code's first kept row
+__global__ __launch_bounds__(256) void k_orth_compact(u32 n, const u32* __restrict__ keep, const u32* __restrict__ pos, const int* __restrict__ q, const int* __restrict__ s,
+                                                      const double* __restrict__ score, const double* __restrict__ aln, int norm, int* __restrict__ kq,
+                                                      int* __restrict__ ks, double* __restrict__ ksco, u32* __restrict__ first) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    const u32 j = pos[i];
+    kq[j] = q[i], ks[j] = s[i];
+    ksco[j] = norm == 2 ? __ddiv_rn(score[i], aln[i]) : score[i];
+    if (norm == 1) atomicMin(first + q[i], j);
+}
+
+__global__ __launch_bounds__(256) void k_orth_bsr(u32 nk, const int* __restrict__ kq, const double* __restrict__ bit, const u32* __restrict__ first, double* __restrict__ sco) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nk) sco[i] = __ddiv_rn(bit[i], bit[first[kq[i]]]);
+}
+
+__global__ __launch_bounds__(256) void k_orth_heads(u32 nk, const int* __restrict__ kq, u32* __restrict__ head) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nk) head[i] = (i == 0 || kq[i] != kq[i - 1]) ? 1u : 0u;
+}
+
+// rstart[r] = first row of run r; rstart[number of runs] = nk.  rid: inclusive scan of head
+__global__ __launch_bounds__(256) void k_orth_starts(u32 nk, const u32* __restrict__ head, const u32* __restrict__ rid, const u32* __restrict__ nruns, u32* __restrict__ rstart) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nk) return;
+    if (head[i]) rstart[rid[i] - 1u] = i;
+    if (i == 0) rstart[*nruns] = nk;
+}
+
+// ---- runs ----------------------------------------------------------------------------------------------------------------------------
+// a run of up to 64 rows per wave, a row per lane
+__global__ __launch_bounds__(256) void k_orth_run_wave(const u32* __restrict__ list, u32 nlist, const u32* __restrict__ rstart, const int* __restrict__ kq,
+                                                       const int* __restrict__ ks, const double* __restrict__ ksco, const int* __restrict__ tax, u64 M, OrthLists L) {
+    const u32 w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (w >= nlist) return;   // (a whole wave)
+    const u32 lane = threadIdx.x & 63u;
+    const u32 r = list[w];
+    const u32 b = rstart[r], len = rstart[r + 1] - b;   // 1 .. 64
+    const bool have = lane < len;
+    const int q = kq[b];
+    int s = -1;
+    u64 e = 0;
+    if (have) s = ks[b + lane], e = orth_enc(ksco[b + lane]);
+    // dedupe: the best score of this lane's subject over the run; the first lane of a subject stands for the group
+    u64 best = e;
+    bool rep = have;
+    for (u32 j = 0; j < len; ++j) {
+        const int sj = __shfl(s, (int)j);
+        const u64 ej = __shfl(e, (int)j);
+        if (have && sj == s) {
+            best = umax64(best, ej);
+            if (j < lane) rep = false;
+        }
+    }
+    const int qtx = tax[q];
+    const int stx = have ? tax[s] : -1;
+    u64 tm = ORTH_ENC_ZERO, om = ORTH_ENC_ZERO;
+    for (unsigned long long m = __ballot(rep); m; m &= m - 1ull) {
+        const int j = __builtin_ctzll(m);
+        const int tj = __shfl(stx, j);
+        const u64 bj = __shfl(best, j);
+        if (tj == stx) tm = umax64(tm, bj);
+        if (tj != qtx) om = umax64(om, bj);
+    }
+    orth_emit(rep, q, s, qtx, stx, best, tm, om, M, L);
+}
+
+template <class T>
+__device__ __forceinline__ T tab_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct OrthPlan {   // scratch tier: where run list[k] keeps its tables
+    u64 slot0;      // first slot of its subject table in hk / hv
+    u32 cap;        // slots (a power of two >= 2 * rows, >= ORTH_MIN_SLOTS)
+    u32 pad;
+};
+
+// one run per workgroup; GLOBAL: the subject table and the taxon maxima live in global scratch (plan), else in LDS
+template <bool GLOBAL>
+__global__ __launch_bounds__(256) void k_orth_run_table(const u32* __restrict__ list, u32 nlist, const OrthPlan* __restrict__ plan, u32* __restrict__ ghk, u64* __restrict__ ghv,
+                                                        u64* __restrict__ gtm, const u32* __restrict__ rstart, const int* __restrict__ kq, const int* __restrict__ ks,
+                                                        const double* __restrict__ ksco, const int* __restrict__ tax, u32 T, u64 M, OrthLists L) {
+    __shared__ u32 s_hk[GLOBAL ? 1 : ORTH_LDS_SLOTS];
+    __shared__ u64 s_hv[GLOBAL ? 1 : ORTH_LDS_SLOTS];
+    __shared__ u64 s_tm[GLOBAL ? 1 : ORTH_LDS_TAXA];
+    __shared__ u64 s_om;
+    const u32 k = blockIdx.x;
+    if (k >= nlist) return;
+    const u32 tid = threadIdx.x;
+    const u32 r = list[k];
+    const u32 b = rstart[r], len = rstart[r + 1] - b;
+    u32 cap;
+    u32* hk;
+    u64 *hv, *tm;
+    if (GLOBAL) {
+        cap = plan[k].cap;
+        hk = ghk + plan[k].slot0, hv = ghv + plan[k].slot0, tm = gtm + (size_t)k * T;
+    } else {
+        cap = ORTH_MIN_SLOTS;
+        while (cap < 2u * len && cap < ORTH_LDS_SLOTS) cap <<= 1;   // (the host sends only runs of up to ORTH_LDS_ROWS rows here)
+        hk = s_hk, hv = s_hv, tm = s_tm;
+    }
+    const u32 mask = cap - 1u;
+    for (u32 i = tid; i < cap; i += 256u) hk[i] = ORTH_EMPTY, hv[i] = 0;
+    for (u32 i = tid; i < T; i += 256u) tm[i] = ORTH_ENC_ZERO;
+    if (tid == 0) s_om = ORTH_ENC_ZERO;
+    // (plain stores, then atomics of other waves on the same words: the barrier waits for this workgroup's stores, which are written through
+    // to the L2 its atomics work in -- a release / acquire at workgroup scope -- so every atomic below meets the initial value, in LDS and
+    // in global scratch alike; no other workgroup touches a run's tables)
+    __syncthreads();
+    // dedupe: subject -> best score
+    for (u32 i = tid; i < len; i += 256u) {
+        const u32 s = (u32)ks[b + i];
+        const u64 e = orth_enc(ksco[b + i]);
+        u32 h = (s * 0x9E3779B1u) >> 7 & mask;
+        for (;;) {   // (the table is at most half full: a free slot is always met)
+            const u32 prev = atomicCAS(hk + h, ORTH_EMPTY, s);
+            if (prev == ORTH_EMPTY || prev == s) break;
+            h = (h + 1u) & mask;
+        }
+        atomicMax((unsigned long long*)hv + h, (unsigned long long)e);
+    }
+    __syncthreads();
+    const int q = kq[b];
+    const int qtx = tax[q];
+    // (the tables were written by atomics, which work in L2 when the tables are global: they are read back the same way)
+    for (u32 i = tid; i < cap; i += 256u) {
+        const u32 s = tab_load(hk + i);
+        if (s == ORTH_EMPTY) continue;
+        const int t = tax[s];
+        const u64 e = tab_load(hv + i);
+        atomicMax((unsigned long long*)tm + t, (unsigned long long)e);
+        if (t != qtx) atomicMax((unsigned long long*)&s_om, (unsigned long long)e);
+    }
+    __syncthreads();
+    const u64 om = tab_load(&s_om);
+    for (u32 i = tid; i < cap; i += 256u) {   // (cap is a multiple of 256: every wave makes the same number of turns, all lanes in it)
+        const u32 s = tab_load(hk + i);
+        const bool have = s != ORTH_EMPTY;
+        const int stx = have ? tax[s] : -1;
+        orth_emit(have, q, have ? (int)s : 0, qtx, stx, tab_load(hv + i), have ? tab_load(tm + stx) : 0, om, M, L);
+    }
+}
+
+// ---- pairs ---------------------------------------------------------------------------------------------------------------------------
+// flag[i] = 1 where a key group of exactly two members starts
+__global__ __launch_bounds__(256) void k_orth_twice(const u64* __restrict__ key, u32 n, u32* __restrict__ flag) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = key[i];
+    const bool head = i == 0 || key[i - 1] != k;
+    flag[i] = (head && i + 1 < n && key[i + 1] == k && (i + 2 >= n || key[i + 2] != k)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_orth_twice_emit(const u64* __restrict__ key, const u64* __restrict__ val, u32 n, const u32* __restrict__ flag, const u32* __restrict__ pos,
+                                                         u64 M, i64* __restrict__ oa, i64* __restrict__ ob, double* __restrict__ os) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const double s0 = __longlong_as_double((long long)val[i]), s1 = __longlong_as_double((long long)val[i + 1]);
+    const u32 p = pos[i];
+    const u64 k = key[i];
+    oa[p] = (i64)(k / M), ob[p] = (i64)(k % M);
+    // the last pair of the sorted list keeps the larger proposal, every other one the mean
+    os[p] = i + 2 == n ? (s1 > s0 ? s1 : s0) : __ddiv_rn(__dadd_rn(__dadd_rn(0., s0), s1), 2.);
+}
+
+__global__ __launch_bounds__(256) void k_orth_distinct(const u64* __restrict__ key, u32 n, u32* __restrict__ flag) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) flag[i] = (i == 0 || key[i - 1] != key[i]) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_orth_distinct_emit(const u64* __restrict__ key, const u64* __restrict__ val, u32 n, const u32* __restrict__ flag,
+                                                            const u32* __restrict__ pos, i64* __restrict__ okey, double* __restrict__ obest) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const u64 k = key[i];
+    double acc = -INFINITY;
+    for (u32 j = i; j < n && key[j] == k; ++j) {   // numpy's maximum: the accumulator stays unless the newcomer is larger; a NaN stays
+        const double v = __longlong_as_double((long long)val[j]);
+        if (!(acc >= v || acc != acc)) acc = v;
+    }
+    okey[pos[i]] = (i64)k, obest[pos[i]] = acc;
+}
+
+// (a synchronous copy: the host array may go away before the stream is waited for)
+template <class T>
+void upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t) {
+    d.ensure(n + 2);
+    if (n) HIP_CHECK(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
+}
+
+template <class T>
+T* host_copy(const T* d, size_t n, hipStream_t st) {
+    T* h = (T*)malloc((n ? n : 1) * sizeof(T));
+    if (!h) throw SoError("so_orth_candidates: out of host memory");
+    if (n) {
+        const hipError_t e = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            free(h);
+            HIP_CHECK(e);
+        }
+    }
+    return h;
+}
+
+inline dim3 grid256(size_t n) { return dim3((u32)((n + 255) / 256)); }
+
+thread_local std::string g_orth_err;
+
+struct OrthCols {   // device columns of n rows
+    const int *q, *s;
+    const double *idy, *aln, *qst, *qed, *score, *qlen;
+};
+
+// sorted (key, value) list -> its flags and their exclusive scan; returns the device word holding the number of flagged groups
+struct PairStage {
+    DevBuf<u64> sk, sv;
+    DevBuf<u32> flag, pos, tmp;
+    DevBuf<u8> sort_tmp;
+    const u32* total = nullptr;
+    void run(bool twice, const u64* k, const u64* v, u32 n, int bits, hipStream_t st) {
+        sk.ensure(n + 2), sv.ensure(n + 2), flag.ensure(n + 2), pos.ensure(n + 2), tmp.ensure(scan_u32_temp_elems(n) + 2);
+        const size_t tb = sort_pairs_u64_u64_temp_bytes(n, bits);
+        sort_tmp.ensure(tb + 16);
+        sort_pairs_u64_u64(sort_tmp.p, tb, k, sk.p, v, sv.p, n, bits, st);
+        if (n) {
+            if (twice) hipLaunchKernelGGL(k_orth_twice, grid256(n), dim3(256), 0, st, sk.p, n, flag.p);
+            else hipLaunchKernelGGL(k_orth_distinct, grid256(n), dim3(256), 0, st, sk.p, n, flag.p);
+        }
+        total = scan_u32(flag.p, pos.p, n, false, tmp.p, st);
+    }
+};
+
+void orth_run(int device, i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm,
+              const Tune& tn, u32* d_err, const char* who, so_orth_cand* out) {
+    const u64 M = (u64)(n_names > 0 ? n_names : 1);
+    const u32 T = (u32)(n_taxa > 0 ? n_taxa : 1);
+    const u32 N = (u32)n;
+    DevBuf<int> d_tax, kq, ks;
+    DevBuf<u32> keep, pos, tmp_a, tmp_b, first, head, rid, rstart;
+    DevBuf<double> kbit, ksco;
+    upload(d_tax, tax, (size_t)n_names, st);
+    keep.ensure(N + 2), pos.ensure(N + 2), tmp_a.ensure(scan_u32_temp_elems(N) + 2);
+    hipLaunchKernelGGL(k_orth_rows, grid256(N), dim3(256), 0, st, N, c.q, c.s, c.idy, c.qst, c.qed, c.qlen, n_names, coverage, identity, keep.p, d_err);
+    const u32* d_nk = scan_u32(keep.p, pos.p, N, false, tmp_a.p, st);
+    u32 nk = 0, err = 0;
+    HIP_CHECK(hipMemcpyAsync(&nk, d_nk, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&err, d_err, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (err & 1u) throw SoError(std::string(who) + ": a record's qidx lies outside the query map");
+    if (err & 2u) throw SoError(std::string(who) + ": a record's sidx lies outside the subject map");
+    if (err & 4u) throw SoError(std::string(who) + ": a name code lies outside 0 .. n_names - 1");
+    out->n_rows = nk;
+    if (!nk) return;   // every row filtered: all tables empty
+
+    // kept rows, scores, runs
+    kq.ensure(nk + 2), ks.ensure(nk + 2), kbit.ensure(nk + 2);
+    if (norm == 1) {
+        first.ensure((size_t)M + 2), ksco.ensure(nk + 2);
+        HIP_CHECK(hipMemsetAsync(first.p, 0xFF, (size_t)M * sizeof(u32), st));
+    }
+    hipLaunchKernelGGL(k_orth_compact, grid256(N), dim3(256), 0, st, N, keep.p, pos.p, c.q, c.s, c.score, c.aln, norm, kq.p, ks.p, kbit.p, first.p);
+    const double* sco = kbit.p;
+    if (norm == 1) {
+        hipLaunchKernelGGL(k_orth_bsr, grid256(nk), dim3(256), 0, st, nk, kq.p, kbit.p, first.p, ksco.p);
+        sco = ksco.p;
+    }
+    head.ensure(nk + 2), rid.ensure(nk + 2), rstart.ensure(nk + 3), tmp_b.ensure(scan_u32_temp_elems(nk) + 2);
+    hipLaunchKernelGGL(k_orth_heads, grid256(nk), dim3(256), 0, st, nk, kq.p, head.p);
+    const u32* d_nruns = scan_u32(head.p, rid.p, nk, true, tmp_b.p, st);
+    hipLaunchKernelGGL(k_orth_starts, grid256(nk), dim3(256), 0, st, nk, head.p, rid.p, d_nruns, rstart.p);
+    u32 nruns = 0;
+    HIP_CHECK(hipMemcpyAsync(&nruns, d_nruns, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<u32> rs((size_t)nruns + 1);
+    HIP_CHECK(hipMemcpyAsync(rs.data(), rstart.p, rs.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->n_runs = nruns;
+
+    // the runs by tier; the scratch tier's tables laid out one behind the other
+    std::vector<u32> l_wave, l_lds, l_scr;
+    std::vector<OrthPlan> plan;
+    u64 slots = 0;
+    const bool lds_taxa = T <= ORTH_LDS_TAXA;
+    for (u32 r = 0; r < nruns; ++r) {
+        const u32 len = rs[r + 1] - rs[r];
+        int tier = len <= ORTH_WAVE_ROWS ? ORTH_TIER_WAVE : (len <= ORTH_LDS_ROWS && lds_taxa) ? ORTH_TIER_LDS : ORTH_TIER_SCRATCH;
+        if (tn.orth_tier == ORTH_TIER_SCRATCH) tier = ORTH_TIER_SCRATCH;
+        if (tn.orth_tier == ORTH_TIER_LDS && len <= ORTH_LDS_ROWS && lds_taxa) tier = ORTH_TIER_LDS;
+        // (forcing the wave tier changes nothing: it already takes every run it can hold)
+        if (tier == ORTH_TIER_WAVE) l_wave.push_back(r);
+        else if (tier == ORTH_TIER_LDS) l_lds.push_back(r);
+        else {
+            u32 cap = ORTH_MIN_SLOTS;
+            while (cap < 2ull * len) cap <<= 1;   // len < 2^31 - but 2 * len may need 2^32 slots: refused below
+            if (cap < 2ull * len) throw SoError(std::string(who) + ": a run of 2^30 rows and more is not supported");
+            l_scr.push_back(r);
+            plan.push_back(OrthPlan{slots, cap, 0});
+            slots += cap;
+        }
+    }
+    DevBuf<u32> d_lw, d_ll, d_ls, ghk, cnt;
+    DevBuf<u64> ghv, gtm;
+    DevBuf<OrthPlan> d_plan;
+    upload(d_lw, l_wave.data(), l_wave.size(), st), upload(d_ll, l_lds.data(), l_lds.size(), st), upload(d_ls, l_scr.data(), l_scr.size(), st);
+    upload(d_plan, plan.data(), plan.size(), st);
+    if (!l_scr.empty()) ghk.ensure(slots + 2), ghv.ensure(slots + 2), gtm.ensure(l_scr.size() * (size_t)T + 2);
+
+    // candidate lists: at most one ortholog or co-ortholog candidate, or two in-paralog entries, per kept row
+    OrthLists L;
+    DevBuf<u64> ot_k, ot_v, ip_k, ip_v, co_k, co_v;
+    ot_k.ensure(nk + 2), ot_v.ensure(nk + 2), co_k.ensure(nk + 2), co_v.ensure(nk + 2), ip_k.ensure(2 * (size_t)nk + 2), ip_v.ensure(2 * (size_t)nk + 2);
+    cnt.ensure(8);
+    HIP_CHECK(hipMemsetAsync(cnt.p, 0, 8 * sizeof(u32), st));
+    L.ot_k = ot_k.p, L.ot_v = ot_v.p, L.ip_k = ip_k.p, L.ip_v = ip_v.p, L.co_k = co_k.p, L.co_v = co_v.p, L.cnt = cnt.p;
+    if (!l_wave.empty())
+        hipLaunchKernelGGL(k_orth_run_wave, dim3((u32)((l_wave.size() + 3) / 4)), dim3(256), 0, st, d_lw.p, (u32)l_wave.size(), rstart.p, kq.p, ks.p, sco, d_tax.p, M, L);
+    if (!l_lds.empty())
+        hipLaunchKernelGGL(k_orth_run_table<false>, dim3((u32)l_lds.size()), dim3(256), 0, st, d_ll.p, (u32)l_lds.size(), (const OrthPlan*)nullptr, (u32*)nullptr, (u64*)nullptr,
+                           (u64*)nullptr, rstart.p, kq.p, ks.p, sco, d_tax.p, T, M, L);
+    if (!l_scr.empty())
+        hipLaunchKernelGGL(k_orth_run_table<true>, dim3((u32)l_scr.size()), dim3(256), 0, st, d_ls.p, (u32)l_scr.size(), d_plan.p, ghk.p, ghv.p, gtm.p, rstart.p, kq.p, ks.p,
+                           sco, d_tax.p, T, M, L);
+    u32 hc[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->n_groups = hc[3];
+    if (hc[1] >= (1u << 31)) throw SoError(std::string(who) + ": 2^31 in-paralog candidates and more are not supported");
+    if (hc[0] > nk || hc[2] > nk || hc[1] > 2ull * nk) throw SoError(std::string(who) + ": internal error: a candidate list overflowed");
+
+    // pairs proposed exactly twice; distinct co-ortholog keys
+    const int bits = ceil_log2(M * M);
+    PairStage p_ot, p_ip, p_co;
+    p_ot.run(true, ot_k.p, ot_v.p, hc[0], bits, st);
+    p_ip.run(true, ip_k.p, ip_v.p, hc[1], bits, st);
+    p_co.run(false, co_k.p, co_v.p, hc[2], bits, st);
+    u32 tot[3] = {0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(tot + 0, p_ot.total, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(tot + 1, p_ip.total, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(tot + 2, p_co.total, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    DevBuf<i64> o_ota, o_otb, o_ipa, o_ipb, o_cok;
+    DevBuf<double> o_ots, o_ips, o_cob;
+    o_ota.ensure(tot[0] + 2), o_otb.ensure(tot[0] + 2), o_ots.ensure(tot[0] + 2), o_ipa.ensure(tot[1] + 2), o_ipb.ensure(tot[1] + 2), o_ips.ensure(tot[1] + 2);
+    o_cok.ensure(tot[2] + 2), o_cob.ensure(tot[2] + 2);
+    if (hc[0]) hipLaunchKernelGGL(k_orth_twice_emit, grid256(hc[0]), dim3(256), 0, st, p_ot.sk.p, p_ot.sv.p, hc[0], p_ot.flag.p, p_ot.pos.p, M, o_ota.p, o_otb.p, o_ots.p);
+    if (hc[1]) hipLaunchKernelGGL(k_orth_twice_emit, grid256(hc[1]), dim3(256), 0, st, p_ip.sk.p, p_ip.sv.p, hc[1], p_ip.flag.p, p_ip.pos.p, M, o_ipa.p, o_ipb.p, o_ips.p);
+    if (hc[2]) hipLaunchKernelGGL(k_orth_distinct_emit, grid256(hc[2]), dim3(256), 0, st, p_co.sk.p, p_co.sv.p, hc[2], p_co.flag.p, p_co.pos.p, o_cok.p, o_cob.p);
+    HIP_CHECK(hipGetLastError());
+    out->n_ot = tot[0], out->n_ip = tot[1], out->n_co = tot[2];
+    out->ot_a = host_copy(o_ota.p, tot[0], st), out->ot_b = host_copy(o_otb.p, tot[0], st), out->ot_s = host_copy(o_ots.p, tot[0], st);
+    out->ip_a = host_copy(o_ipa.p, tot[1], st), out->ip_b = host_copy(o_ipb.p, tot[1], st), out->ip_s = host_copy(o_ips.p, tot[1], st);
+    out->co_key = host_copy(o_cok.p, tot[2], st), out->co_best = host_copy(o_cob.p, tot[2], st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    (void)device;
+}
+
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() {
+        if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
+    }
+};
+
+// what both entry points check before anything touches the device
+void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, so_orth_cand* out) {
+    if (!out) throw SoError(std::string(who) + ": result pointer is NULL");
+    memset(out, 0, sizeof *out);
+    if (n < 0 || n_names < 0 || n_taxa < 0 || (n_names > 0 && !tax) || norm < 0 || norm > 2) throw SoError(std::string(who) + ": bad arguments");
+    if (n >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 rows and more are not supported (32-bit row numbers)");
+    if (n_names > 3037000499ll) throw SoError(std::string(who) + ": n_names * n_names reaches 2^63 (pair keys a * n_names + b are 63-bit)");
+    for (i64 i = 0; i < n_names; ++i)
+        if (tax[i] < 0 || tax[i] >= n_taxa) throw SoError(std::string(who) + ": name " + std::to_string(i) + " has a taxon outside 0 .. n_taxa - 1");
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError(std::string(who) + ": no HIP device available (libsohit has no CPU fallback)");
+    if (device < 0 || device >= nd) throw SoError(std::string(who) + ": device index out of range");
+}
+
+// an output of no rows still hands out arrays that so_orth_free can release
+void orth_fill_empty(so_orth_cand* out) {
+    void** slots[8] = {(void**)&out->ot_a, (void**)&out->ot_b, (void**)&out->ot_s, (void**)&out->ip_a, (void**)&out->ip_b, (void**)&out->ip_s, (void**)&out->co_key,
+                       (void**)&out->co_best};
+    for (void** p : slots)
+        if (!*p) *p = calloc(1, 8);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* so_orth_last_error(void) { return g_orth_err.c_str(); }
+
+void so_orth_free(so_orth_cand* r) {
+    if (!r) return;
+    free(r->ot_a), free(r->ot_b), free(r->ot_s), free(r->ip_a), free(r->ip_b), free(r->ip_s), free(r->co_key), free(r->co_best);
+    memset(r, 0, sizeof *r);
+}
+
+int so_orth_candidates_cols(int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
+                            const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm,
+                            so_orth_cand* out) {
+    const char* who = "so_orth_candidates_cols";
+    try {
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
+        if (n > 0 && (!q || !s || !idy || !aln || !qst || !qed || !score || !qlen)) throw SoError(std::string(who) + ": a column is NULL");
+        if (n > 0) {
+            HIP_CHECK(hipSetDevice(device));
+            Tune tn;   // no context: the switches are read per call
+            tn.read();
+            const PoisonScope poison((int)tn.poison);
+            StreamGuard g;
+            HIP_CHECK(hipStreamCreate(&g.s));
+            DevBuf<int> dq, ds;
+            DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
+            DevBuf<u32> d_err;
+            const size_t N = (size_t)n;
+            upload(dq, q, N, g.s), upload(ds, s, N, g.s), upload(d_idy, idy, N, g.s), upload(d_aln, aln, N, g.s), upload(d_qst, qst, N, g.s), upload(d_qed, qed, N, g.s);
+            upload(d_score, score, N, g.s), upload(d_qlen, qlen, N, g.s);
+            d_err.ensure(4);
+            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
+            const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
+            orth_run(device, n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, out);
+        }
+        orth_fill_empty(out);
+        g_orth_err.clear();
+        return 0;
+    } catch (const std::exception& e) {
+        if (out) so_orth_free(out);
+        g_orth_err = e.what();
+        return 1;
+    }
+}
+
+int so_orth_candidates_records(int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
+                               const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_cand* out) {
+    const char* who = "so_orth_candidates_records";
+    try {
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
+        if (n_q < 0 || n_s < 0 || (n_q > 0 && !qmap) || (n_s > 0 && !smap)) throw SoError(std::string(who) + ": bad arguments");
+        if (n > 0 && !d_hits) throw SoError(std::string(who) + ": the record pointer is NULL");
+        if (n > 0) {
+            HIP_CHECK(hipSetDevice(device));
+            // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
+            // (so_search_device has synchronised its stream when it returns; a torch tensor's producer is on torch's stream)
+            HIP_CHECK(hipDeviceSynchronize());
+            Tune tn;
+            tn.read();
+            const PoisonScope poison((int)tn.poison);
+            StreamGuard g;
+            HIP_CHECK(hipStreamCreate(&g.s));
+            DevBuf<int> dq, ds, d_qmap, d_smap;
+            DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
+            DevBuf<u32> d_err;
+            const size_t N = (size_t)n;
+            upload(d_qmap, qmap, (size_t)n_q, g.s), upload(d_smap, smap, (size_t)n_s, g.s);
+            dq.ensure(N + 2), ds.ensure(N + 2), d_idy.ensure(N + 2), d_aln.ensure(N + 2), d_qst.ensure(N + 2), d_qed.ensure(N + 2), d_score.ensure(N + 2), d_qlen.ensure(N + 2);
+            d_err.ensure(4);
+            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
+            hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, g.s, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
+                               d_qed.p, d_score.p, d_qlen.p, d_err.p);
+            const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
+            orth_run(device, n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, out);
+        }
+        orth_fill_empty(out);
+        g_orth_err.clear();
+        return 0;
+    } catch (const std::exception& e) {
+        if (out) so_orth_free(out);
+        g_orth_err = e.what();
+        return 1;
+    }
+}
+
+}  // extern "C"

@@ -6,7 +6,8 @@
 #include <cstdlib>
 
 //   kind  field            environment variable      default   meaning
-//   B = boolean (unset: default, else atoi != 0), I = integer (atoll), D = double (atof), P = presence (set to anything)
+//   B = boolean (unset: default, else atoi != 0), I = integer (atoll), D = double (atof), P = presence (set to anything),
+//   T = tier of k_orth_run (auto | wave | lds | scratch, or 0 .. 3)
 #define SOHIT_TUNE_TABLE(X)                                                                                                                                     \
     /* ---- ungapped extension ---- */                                                                                                                          \
     X(B, ug1, "SOHIT_UG1", 1, "bucketed passes: singleton groups to k_ungap1 (0: everything to k_ungap)")                                                     \
@@ -52,6 +53,8 @@
     X(P, keep_cands, "SOHIT_KEEP_CANDS", 0, "tests: keep every query's candidate list (so_query_candidates)")                                                  \
     X(P, keep_masked, "SOHIT_KEEP_MASKED", 0, "tests: keep the masked queries (so_masked_query)")                                                              \
     X(I, mcl_scratch, "SOHIT_MCL_SCRATCH", -1, "tests: u32 words of expansion / convergence scratch per range of rows (-1: 2^28)")                             \
+    /* ---- find_orth candidates (so_orth_candidates_*: read per call) ---- */                                                                                  \
+    X(T, orth_tier, "SOHIT_ORTH_TIER", 0, "tests: every run of query rows through one tier of k_orth_run wherever that tier can take it (0 = auto: by run length)") \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
@@ -59,11 +62,26 @@
     X(P, debug, "SOHIT_DEBUG", 0, "per-pass lines on stderr")                                                                                                  \
     X(P, debug_index, "SOHIT_DEBUG_INDEX", 0, "wall laps of the index build on stderr")
 
+// ---- find_orth candidates (orth.hip): which tier of k_orth_run takes a run of query rows ----
+#define ORTH_WAVE_ROWS 64     // longest run one wave holds in registers, a row per lane
+#define ORTH_LDS_ROWS 1024    // longest run whose subjects fit the LDS table (2 slots per row) ...
+#define ORTH_LDS_TAXA 512     // ... when the taxa fit the per-taxon LDS table; beyond either: tables in global scratch
+enum { ORTH_TIER_AUTO = 0, ORTH_TIER_WAVE = 1, ORTH_TIER_LDS = 2, ORTH_TIER_SCRATCH = 3 };
+static inline int orth_tier_of(const char* v) {
+    switch (v[0]) {
+        case 'w': case '1': return ORTH_TIER_WAVE;
+        case 'l': case '2': return ORTH_TIER_LDS;
+        case 's': case '3': return ORTH_TIER_SCRATCH;
+        default: return ORTH_TIER_AUTO;
+    }
+}
+
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;
 #define X_I(f, d) long long f = (d);
 #define X_D(f, d) double f = (d);
 #define X_P(f, d) bool f = false;
+#define X_T(f, d) int f = (d);
 #define X(kind, field, env, dflt, text) X_##kind(field, dflt)
     SOHIT_TUNE_TABLE(X)
 #undef X
@@ -71,11 +89,13 @@ struct Tune {
 #undef X_I
 #undef X_D
 #undef X_P
+#undef X_T
     void read() {
 #define X_B(f, e) if (const char* v = getenv(e)) f = atoi(v) != 0;
 #define X_I(f, e) if (const char* v = getenv(e)) f = strtoll(v, nullptr, 0);
 #define X_D(f, e) if (const char* v = getenv(e)) f = atof(v);
 #define X_P(f, e) f = getenv(e) != nullptr;
+#define X_T(f, e) if (const char* v = getenv(e)) f = orth_tier_of(v);
 #define X(kind, field, env, dflt, text) X_##kind(field, env)
         SOHIT_TUNE_TABLE(X)
 #undef X
@@ -83,6 +103,7 @@ struct Tune {
 #undef X_I
 #undef X_D
 #undef X_P
+#undef X_T
     }
 };
 

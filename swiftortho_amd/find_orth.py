@@ -35,7 +35,7 @@ import sys
 
 import numpy as np
 
-DEFAULTS = {'-i': '', '-c': .5, '-y': 0, '-n': 'no', '-t': 'n', '-a': '4', '-T': './tmp/', '-s': '|'}
+DEFAULTS = {'-i': '', '-c': .5, '-y': 0, '-n': 'no', '-t': 'n', '-a': '4', '-T': './tmp/', '-s': '|', '-G': 'F'}
 
 
 def manual_print(prog='find_orth.py'):
@@ -50,6 +50,7 @@ def manual_print(prog='find_orth.py'):
     print('  -t: keep tmpdir[y|n]. Default: n (accepted, unused)')
     print('  -T: tmpdir for sort command. Default: ./tmp/ (accepted, unused)')
     print('  -s: separator between taxa and sequence id. Default is |.')
+    print('  -G: candidate stage on the GPU [T|F]. Default: F (T needs libsohit.so and a HIP device; same output)')
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -304,8 +305,31 @@ def _taxa(names, sep):
 # ---------------------------------------------------------------------------------------------------------
 # the stage
 # ---------------------------------------------------------------------------------------------------------
-def relations(cols, coverage=.5, identity=0., norm='no', sep='|'):
-    """HitColumns -> output lines (bytes, no newline) in the reference's order: IP, then OT, then CO"""
+class Candidates:
+    """What the candidate stage hands to the rest of relations(): the pairs proposed exactly twice -- orthologs (ot_*) and in-paralogs (ip_*,
+    both orientations), each ascending by (a, b) -- the sorted distinct keys a * M + b of the co-ortholog candidates with their best scores
+    (M = max(len(names), 1)), and three counters: rows kept by the filter, runs of one query id, distinct (run, subject).
+    `tax`, `taxa`: what _taxa() gave the stage for the names, kept so that relations() need not derive them again (None: not kept)."""
+    FIELDS = ('ot_a', 'ot_b', 'ot_s', 'ip_a', 'ip_b', 'ip_s', 'co_key', 'co_best')
+
+    def __init__(self, ot_a, ot_b, ot_s, ip_a, ip_b, ip_s, co_key, co_best, n_rows, n_runs, n_groups, tax=None, taxa=None):
+        self.ot_a, self.ot_b, self.ot_s = ot_a, ot_b, ot_s
+        self.ip_a, self.ip_b, self.ip_s = ip_a, ip_b, ip_s
+        self.co_key, self.co_best = co_key, co_best
+        self.n_rows, self.n_runs, self.n_groups = int(n_rows), int(n_runs), int(n_groups)
+        self.tax, self.taxa = tax, taxa
+
+    @classmethod
+    def empty(cls, tax=None, taxa=None):
+        i, f = (lambda: np.zeros(0, dtype=np.int64)), (lambda: np.zeros(0, dtype=np.float64))
+        return cls(i(), i(), f(), i(), i(), f(), i(), f(), 0, 0, 0, tax, taxa)
+
+
+NORMS = {'no': 0, 'bsr': 1, 'bal': 2}   # (every other -n counts as 'no', as in the reference)
+
+
+def candidates(cols, coverage=.5, identity=0., norm='no', sep='|'):
+    """HitColumns -> Candidates: the only part of the stage that touches every row (numpy; device_candidates() is the same on the GPU)"""
     names = cols.names
     M = max(len(names), 1)
     tax, taxa = _taxa(names, sep)
@@ -327,7 +351,7 @@ def relations(cols, coverage=.5, identity=0., norm='no', sep='|'):
     # ---- groups = runs of one query id; per (group, subject) the best score at the subject's first row -------------
     n = len(q)
     if n == 0:
-        return []
+        return Candidates.empty(tax, taxa)
     run = np.cumsum(np.concatenate([[0], q[1:] != q[:-1]]).astype(np.int64))
     key = run * M + s
     uk, first, inv = np.unique(key, return_index=True, return_inverse=True)
@@ -352,6 +376,22 @@ def relations(cols, coverage=.5, identity=0., norm='no', sep='|'):
     ip_s = np.concatenate([g_sco[is_ip], g_sco[is_ip]])
     ot_a, ot_b, ot_s = _pairs_proposed_twice(a[is_ot], b[is_ot], g_sco[is_ot])
     ip_a, ip_b, ip_s = _pairs_proposed_twice(ip_a, ip_b, ip_s)
+    cu, cinv = np.unique(a[is_co] * M + b[is_co], return_inverse=True)
+    cbest = np.full(len(cu), -np.inf)
+    np.maximum.at(cbest, cinv, g_sco[is_co])
+    return Candidates(ot_a, ot_b, ot_s, ip_a, ip_b, ip_s, cu, cbest, n, nrun, len(uk), tax, taxa)
+
+
+_numpy_candidates = candidates   # (relations() has a keyword of the same name)
+
+
+def relations_from_candidates(names, tax, taxa, cand):
+    """the rest of the stage -- normalisers, co-orthologs, text -- on the candidate tables -> output lines (bytes, no newline)"""
+    if cand.n_rows == 0:
+        return []
+    M = max(len(names), 1)
+    T = max(len(taxa), 1)
+    ot_a, ot_b, ot_s, ip_a, ip_b, ip_s, cu, cbest = (getattr(cand, k) for k in Candidates.FIELDS)
     # ---- in-paralog normalisers ---------------------------------------------------------------------------------
     has_ot = np.zeros(M, dtype=bool)
     has_ot[ot_a] = True
@@ -368,11 +408,7 @@ def relations(cols, coverage=.5, identity=0., norm='no', sep='|'):
     # ---- co-orthologs -------------------------------------------------------------------------------------------
     co_a = np.zeros(0, dtype=np.int64)
     co_b, co_s = co_a, np.zeros(0, dtype=np.float64)
-    if len(ip_a) and is_co.any() and len(ot_a):
-        ck = a[is_co] * M + b[is_co]
-        cu, cinv = np.unique(ck, return_inverse=True)
-        cbest = np.full(len(cu), -np.inf)
-        np.maximum.at(cbest, cinv, g_sco[is_co])
+    if len(ip_a) and len(cu) and len(ot_a):
         lo_q, hi_q = np.searchsorted(ip_a, ot_a, 'left'), np.searchsorted(ip_a, ot_a, 'right')
         lo_s, hi_s = np.searchsorted(ip_a, ot_b, 'left'), np.searchsorted(ip_a, ot_b, 'right')
         nq, ns = hi_q - lo_q, hi_s - lo_s
@@ -422,6 +458,102 @@ def relations(cols, coverage=.5, identity=0., norm='no', sep='|'):
         val = ps / (gsum / gcnt)[ginv]
         lines.extend(fmt.lines(kind, pa, pb, val))
     return lines
+
+
+def relations(cols, coverage=.5, identity=0., norm='no', sep='|', candidates=None):
+    """HitColumns -> output lines (bytes, no newline) in the reference's order: IP, then OT, then CO.
+    `candidates`: the function of the candidate stage -- None: the numpy one; device_candidates: the HIP kernels of csrc/orth.hip."""
+    stage = _numpy_candidates if candidates is None else candidates
+    cand = stage(cols, coverage, identity, norm, sep)
+    tax, taxa = (cand.tax, cand.taxa) if getattr(cand, 'tax', None) is not None else _taxa(cols.names, sep)
+    return relations_from_candidates(cols.names, tax, taxa, cand)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the candidate stage on the GPU (include/sohit.h so_orth_*, csrc/orth.hip).  No fallback: without the library or a device these raise.
+# ---------------------------------------------------------------------------------------------------------
+def _orth_call(fn, tail_of, names, tax, taxa, coverage, identity, norm):
+    """shared tail of the two entry points: the call, the result tables copied out of the library's arrays"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    tax32 = np.ascontiguousarray(tax, dtype=np.int32)
+    out = _lib.SoOrthCand()
+    rc = fn(L, *tail_of(len(names), C.c_void_p(tax32.ctypes.data), len(taxa), float(coverage), float(identity), NORMS.get(norm, 0), C.byref(out)))
+    if rc != 0:
+        raise RuntimeError(L.so_orth_last_error().decode())
+    try:
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+        i, f = np.int64, np.float64
+        return Candidates(arr(out.ot_a, out.n_ot, i), arr(out.ot_b, out.n_ot, i), arr(out.ot_s, out.n_ot, f),
+                          arr(out.ip_a, out.n_ip, i), arr(out.ip_b, out.n_ip, i), arr(out.ip_s, out.n_ip, f),
+                          arr(out.co_key, out.n_co, i), arr(out.co_best, out.n_co, f), out.n_rows, out.n_runs, out.n_groups, tax, taxa)
+    finally:
+        L.so_orth_free(C.byref(out))
+
+
+def device_candidates(cols, coverage=.5, identity=0., norm='no', sep='|', device=0):
+    """candidates() on the GPU from host columns (so_orth_candidates_cols): the same tables, bit for bit"""
+    import ctypes as C
+    n = len(cols.q)
+    if n >= 1 << 31:
+        raise RuntimeError('so_orth_candidates: 2^31 rows and more are not supported')
+    q32 = np.ascontiguousarray(cols.q, dtype=np.int32)
+    s32 = np.ascontiguousarray(cols.s, dtype=np.int32)
+    if n and not (np.array_equal(q32, cols.q) and np.array_equal(s32, cols.s)):
+        raise RuntimeError('so_orth_candidates: a name code does not fit 32 bits')
+    dbl = [np.ascontiguousarray(getattr(cols, k), dtype=np.float64) for k in ('idy', 'aln', 'qst', 'qed', 'score', 'qlen')]
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    head = [int(device), n, ptr(q32), ptr(s32)] + [ptr(a) for a in dbl]
+    tax, taxa = _taxa(cols.names, sep)
+    return _orth_call(lambda L, *a: L.so_orth_candidates_cols(*a), lambda *tail: head + list(tail), cols.names, tax, taxa, coverage, identity, norm)
+
+
+def _record_maps(query_ids, subject_ids):
+    qn = np.asarray(query_ids, dtype=np.bytes_)
+    sn = np.asarray(subject_ids, dtype=np.bytes_)
+    names, qmap, smap = _codes(qn, sn)
+    return names, np.ascontiguousarray(qmap, dtype=np.int32), np.ascontiguousarray(smap, dtype=np.int32)
+
+
+def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep):
+    """-> (names, tax, taxa, Candidates) of the records `dev` holds"""
+    import ctypes as C
+    from . import _lib
+    rec = C.sizeof(_lib.SoHit)
+    keep_alive = dev
+    if hasattr(dev, 'device_pointer'):
+        d_ptr, n, device = dev.device_pointer(), len(dev), dev.s.device
+    else:
+        import torch
+        if not (isinstance(dev, torch.Tensor) and dev.is_cuda and dev.dtype == torch.uint8):
+            raise TypeError('device_candidates_from_records: a DeviceHits or a CUDA uint8 tensor of so_hit records is needed')
+        if dev.numel() % rec:
+            raise ValueError('device_candidates_from_records: the tensor does not hold whole so_hit records')
+        keep_alive = dev = dev.contiguous()
+        # the records were written on torch's stream; the library works on a stream of its own
+        torch.cuda.current_stream(dev.device).synchronize()
+        d_ptr, n, device = dev.data_ptr(), dev.numel() // rec, dev.device.index or 0
+    names, qmap, smap = _record_maps(query_ids, subject_ids)
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    head = [int(device), C.c_void_p(d_ptr), n, ptr(qmap), len(qmap), ptr(smap), len(smap)]
+    tax, taxa = _taxa(names, sep)
+    cand = _orth_call(lambda L, *a: L.so_orth_candidates_records(*a), lambda *tail: head + list(tail), names, tax, taxa, coverage, identity, norm)
+    del keep_alive
+    return names, tax, taxa, cand
+
+
+def device_candidates_from_records(dev, query_ids, subject_ids, coverage=.5, identity=0., norm='no', sep='|'):
+    """candidates() of columns_from_records() without the download: `dev` is a fsearch.DeviceHits (the records so_search_device left in
+    HBM) or a CUDA uint8 torch tensor of so_hit records (e.g. the tensor gathered on rank 0) -> Candidates"""
+    return _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep)[3]
+
+
+def relations_from_device(dev, query_ids, subject_ids, coverage=.5, identity=0., norm='no', sep='|'):
+    """relations_from_records() on records that stay on the device: only the candidate tables come to the host"""
+    names, tax, taxa, cand = _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep)
+    return relations_from_candidates(names, tax, taxa, cand)
 
 
 class _PairFormatter:
@@ -491,11 +623,12 @@ def main(argv=None):
     try:
         qry, coverage, identity, norm, sep = args['-i'], float(args['-c']), float(args['-y']), args['-n'], args['-s']
         int(args['-a'])
+        stage = device_candidates if str(args['-G']).upper().startswith('T') else None
     except Exception:
         manual_print(argv[0] if argv else 'find_orth.py')
         raise SystemExit()
     with open(qry, 'rb') as f:
-        lines = relations(columns_from_text(f.read()), coverage, identity, norm, sep)
+        lines = relations(columns_from_text(f.read()), coverage, identity, norm, sep, candidates=stage)
     out = sys.stdout.buffer
     if lines:
         out.write(b'\n'.join(lines) + b'\n')

@@ -47,6 +47,7 @@ class Searcher:
         self._keep = (ssd.encode(), nr.encode())
         p = _lib.SoParams(self._keep[0], self._keep[1], int(ht), int(chk), int(step), int(v), int(thr), float(expect),
                           float(max_miss), 1 if flt == "T" else 0, 1 if profile else 0)
+        self.device = int(device)
         self.h = self.L.so_create(int(device), C.byref(p))
         if not self.h:
             raise SohitError(self.L.so_last_error(None).decode())
@@ -131,7 +132,7 @@ class Searcher:
         n = C.c_int64(0)
         ptr = C.c_void_p()
         self._chk(self.L.so_search_device(self.h, st, ed, C.byref(ptr), C.byref(n)))
-        return DeviceHits(self, n.value)
+        return DeviceHits(self, n.value, ptr.value)
 
     def query_work(self, st=-1, ed=-1):
         """Index entries each query of [st, ed) visits over all chunks (pre-pass, no search): the shard-balancing weight."""
@@ -242,8 +243,13 @@ class DeviceHits:
     """so_hit records of one so_search_device() call, resident in the ctx's device memory until its next search."""
     record_bytes = C.sizeof(_lib.SoHit)
 
-    def __init__(self, s, n):
-        self.s, self.n = s, n
+    def __init__(self, s, n, ptr=None):
+        self.s, self.n, self.ptr = s, n, ptr
+
+    def device_pointer(self):
+        """address of the records in the ctx's device memory (so_search_device's d_hits; 0 when there are none): for device-side consumers
+        such as find_orth.relations_from_device, until the searcher's next search"""
+        return int(self.ptr or 0)
 
     def __len__(self):
         return self.n

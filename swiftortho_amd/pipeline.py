@@ -4,12 +4,15 @@ The reference pipeline writes the 16-column .sc file and bin/find_orth.py parses
 search produced (fixed-width so_hit structs, `Hits.array()`; on several GPUs the records gathered over RCCL) are handed
 to the columnar find_orth stage directly; the .sc file is still written when asked for (it is the drop-in artefact), but
 nothing reads it.  `orthology_from_search()` is what `bin/find_hit.py ... && bin/find_orth.py -i x.sc` computes."""
+import os
 import time
 
 
-def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., norm='no', sep='|', device=0, **search_kw):
+def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage=False, **search_kw):
     """self-search of one proteome on the GPU, then IP / OT / CO relations from the hit RECORDS.
-    -> (relation lines as bytes, dict of stage wall times in seconds)"""
+    device_stage=True: the records stay in HBM (search_device) and the candidate stage of find_orth runs on them there
+    (find_orth.relations_from_device); they are downloaded only when `sc_path` asks for the file.
+    -> (relation lines as bytes, dict of stage wall times in seconds; with device_stage also 'orth_candidates')"""
     from . import find_orth, fsearch
     t = {}
     t0 = time.time()
@@ -21,6 +24,8 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
         s.load_queries_bytes(data)
         t['load'] = time.time() - t0
         t0 = time.time()
+        if device_stage:
+            return _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0)
         hits = s.search()
         t['search'] = time.time() - t0
         t0 = time.time()
@@ -35,4 +40,25 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
     lines = find_orth.relations_from_records(rec, ids, ids, coverage, identity, norm, sep)
     t['find_orth'] = time.time() - t0
     t['rows'] = len(rec)
+    return lines, t
+
+
+def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0):
+    """orthology_from_search() from the search on, with the records left on the device (the caller closes the searcher)"""
+    import numpy as np
+    from . import find_orth, fsearch
+    dev = s.search_device()
+    t['search'] = time.time() - t0
+    t0 = time.time()
+    if sc_path:
+        raw = dev.tensor().cpu().numpy() if len(dev) else np.zeros(0, dtype=np.uint8)
+        arr, n = fsearch.hits_from_bytes(s, raw)
+        s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(sc_path), b'w'))
+        t['write_sc'] = time.time() - t0
+        t0 = time.time()
+    names, tax, taxa, cand = find_orth._device_records(dev, ids, ids, coverage, identity, norm, sep)
+    t['orth_candidates'] = time.time() - t0
+    lines = find_orth.relations_from_candidates(names, tax, taxa, cand)
+    t['find_orth'] = time.time() - t0
+    t['rows'] = len(dev)
     return lines, t

@@ -4,7 +4,7 @@
 import os, re
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = open(os.path.join(ROOT, "swiftortho_amd", "csrc", "tune.h")).read()
-kinds = {"B": "0 / 1", "I": "integer", "D": "number", "P": "set = on"}
+kinds = {"B": "0 / 1", "I": "integer", "D": "number", "P": "set = on", "T": "auto / wave / lds / scratch"}
 print("| variable | values | default | effect |\n|---|---|---|---|")
 for line in src.splitlines():
     m = re.match(r'\s*X\((\w), (\w+), "(\w+)", ([^,]+), "(.*)"\)\s*\\?$', line)
