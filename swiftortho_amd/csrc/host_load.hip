@@ -394,4 +394,5 @@ void load_queries_common(so_ctx* c, bool parsed) {
     HIP_CHECK(hipStreamSynchronize(c->st));
     c->qry_loaded = true;
     c->lt["load.qry_parse"] = (t1 - t0) * 1e3, c->lt["load.qry_h2d"] = (wall() - t1) * 1e3;
+    c->lt["load.seg_on_device"] = c->seg_on_device ? 1. : 0.;   // (not a time: which SEG implementation the loaded queries get)
 }

@@ -70,7 +70,7 @@ void search_loaded(so_ctx* c, i64 q_lo, i64 q_hi, HitBuf& out) {
             c->cnt.n_queries += b.nq;
             c->cnt.query_aa += b.h_off[b.nq];
             if (tune().keep_masked) {
-                if (c->masked.empty()) c->masked_lo = st;
+                c->masked_lo = st;   // (of the search, not of the batch: c->masked grows batch by batch)
                 if (b.h_res.empty() && b.h_off[b.nq]) {
                     b.h_res.resize(b.h_off[b.nq] + 16);
                     HIP_CHECK(hipMemcpy(b.h_res.data(), b.dev.d_res.p, b.h_off[b.nq], hipMemcpyDeviceToHost));

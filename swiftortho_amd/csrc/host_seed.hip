@@ -97,7 +97,6 @@ void prepare_batch(so_ctx* c, Batch& b, i64 q_lo, i64 q_hi) {
         d_qid = b.d_qid.p;
     }
     const size_t nres_b = b.h_off[b.nq];
-    c->masked_lo = q_lo;
     if (c->seg_on_device || !c->filter) {
         // residues never leave the device: SEG kernel (or plain copy) from the resident raw queries
         b.dev.d_res.ensure(nres_b + 64);

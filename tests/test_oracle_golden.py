@@ -224,3 +224,46 @@ def test_index_files_golden(oracle):
         trailer = "%d;%d;%d;%d;%d;%s;%s" % (st, ed + 1, mw, ix.threshold, a["ht"], a["space"], a["nr"])
         want = ix.start().astype("<i4").tobytes() + trailer.encode() + bytes([len(trailer)])
         assert want == open(os.path.join(GOLD, "idx_toy.%d.bin" % k), "rb").read()
+
+
+def test_seg_at_the_mask_kernels_edges(oracle):
+    """tests/golden/seg_edges.json: the REAL reference's seg() on mosaics of low- and high-complexity segments, plain and with odd
+    bytes, from 1 to 33 293 residues (kat.json's longest seg input is 148) -- the oracle's mask equals it byte for byte."""
+    import seg_fixture
+    for name, _, s, want in seg_fixture.cases():
+        got = oracle.seg(s)
+        assert got == want, "%s: %s" % (name, seg_fixture.first_difference(got, want))
+
+
+def test_seg_fixture_holds_what_it_promises():
+    """the lengths at every instance / tile / window edge, a quarter of all residues masked, a mask edge strictly inside every case of 75
+    residues or more, and 64 / 65 distinct upper-cased bytes in the two alphabet groups"""
+    import seg_fixture
+    d, cs = seg_fixture.document(), seg_fixture.cases()
+    both = [1, 2, 11, 12, 13, 14, 23, 24, 25, 75, 76, 77, 139, 140, 141, 268, 269, 1023, 1024, 1025, 1035, 1036, 1037, 1547, 1548, 1549,
+            4095, 4096, 4097, 4107, 4108, 4109, 4620, 4621]
+    plain_only = [32767, 32768, 32769, 33293]
+    by_name = {name: (s, out) for name, _, s, out in cs}
+    assert len(by_name) == len(cs) == 2 * len(both) + len(plain_only) + 10
+    for n in both + plain_only:
+        assert len(by_name["plain_%d" % n][0]) == n
+        assert set(by_name["plain_%d" % n][0]) <= set(b"ACDEFGHIKLMNPQRSTVWY")
+    for n in both:
+        assert len(by_name["odd_%d" % n][0]) == n
+    assert sum(bool(set(by_name["odd_%d" % n][0]) & set(b"-*.UJOBZxXak")) for n in both if n >= 75) >= 20
+    total = sum(len(s) for s, _ in by_name.values())
+    masked = sum(out.count(b"x") for _, out in by_name.values())
+    edges = sum(seg_fixture.inner_edges(out) for _, out in by_name.values())
+    assert (total, masked, edges) == (d["residues"], d["masked"], d["inner_edges"])
+    assert masked >= 0.25 * total and edges > 5000
+    for name, _, s, out in cs:
+        assert len(out) == len(s) and all(o == 120 or o == u for o, u in zip(out, s.upper())), name
+        assert all(b < 128 for b in s), name
+        if len(s) >= 75:
+            assert seg_fixture.inner_edges(out) > 0, name
+    for nsym in (64, 65):
+        grp = [s for name, g, s, _ in cs if g == "alphabet%d" % nsym]
+        assert len(grp) == 5 and all(60 <= len(s) <= 300 for s in grp)
+        assert len(set(b"".join(grp).upper())) == nsym
+        assert all(32 < b < 127 and b != ord(">") for s in grp for b in s)
+    assert os.path.getsize(os.path.join(GOLD, "seg_edges.json")) < 300 * 1024
