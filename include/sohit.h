@@ -323,6 +323,32 @@ int so_orth_candidates_records(int device, const so_hit *d_hits, int64_t n, cons
                                int norm, so_orth_cand *out);
 void so_orth_free(so_orth_cand *result);
 const char *so_orth_last_error(void);
+/* The rest of find_orth but the text, on the candidate tables above while they are still on the device (csrc/orth.hip).  Replaces: the
+ * in-paralog normalisers of bin/find_orth.py (507-543), the co-ortholog cross products (547-617) and the normalisation of the ortholog
+ * and co-ortholog lines inside runs of one query taxon with its "repeats inside a run are dropped, one repeat of the run's first pair
+ * survives" rule (681-762) -- as swiftortho_amd/find_orth.py `relation_tables()` restates them, bit for bit: every float64 sum is one
+ * chain over its group's rows in table order, as numpy's bincount adds them.
+ * Input, ordering, stream ownership and refusals: those of so_orth_candidates_cols / so_orth_candidates_records, argument for argument.
+ * Output (allocated by the library, released with so_orth_rel_free()), in output order: ip_*: the forward in-paralog pairs (a < b) whose
+ * taxon normaliser is not zero, with score / normaliser; ot_* / co_*: the ortholog / co-ortholog rows that survive the repeat rule, with
+ * score / (mean score of their (run of one taxon of a, taxon of b) group); n_rows, n_runs, n_groups as above.  Only these tables come to
+ * the host.  n = 0 and inputs whose every row is filtered are served and launch nothing for this stage.
+ * Refused with a message (so_orth_last_error), never truncated: what the candidates calls refuse, and an input whose ortholog pairs expand
+ * to 2^31 co-ortholog products ((in-paralogs of a + 1) * (in-paralogs of b + 1), summed in 64 bits) or more.  Scores are expected to be
+ * numbers: a NaN score (-n bsr with a zero reference score) is outside what the call defines. */
+typedef struct so_orth_rel {
+    int64_t n_ip, n_ot, n_co, n_rows, n_runs, n_groups;
+    int64_t *ip_a, *ip_b; double *ip_v;
+    int64_t *ot_a, *ot_b; double *ot_v;
+    int64_t *co_a, *co_b; double *co_v;
+} so_orth_rel;
+int so_orth_relations_cols(int device, int64_t n, const int32_t *q, const int32_t *s, const double *idy, const double *aln,
+                           const double *qst, const double *qed, const double *score, const double *qlen, int64_t n_names,
+                           const int32_t *tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_rel *out);
+int so_orth_relations_records(int device, const so_hit *d_hits, int64_t n, const int32_t *qmap, int64_t n_q, const int32_t *smap,
+                              int64_t n_s, int64_t n_names, const int32_t *tax, int64_t n_taxa, double coverage, double identity,
+                              int norm, so_orth_rel *out);
+void so_orth_rel_free(so_orth_rel *result);
 
 /* Host-side tokeniser of tab-separated text for the stages behind the search (csrc/tsv.hip; no device, no so_ctx).  Replaces: the
  * per-line `split('\t')` + `float()` loops of bin/find_orth.py (blastparse, 58-125) and bin/find_cluster.py (1425-1467) as the

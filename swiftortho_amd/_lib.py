@@ -13,6 +13,13 @@ class SoParams(C.Structure):
                 ("filter", C.c_int32), ("profile", C.c_int32)]
 
 
+class SoOrthRel(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_ip", "n_ot", "n_co", "n_rows", "n_runs", "n_groups")] + \
+               [("ip_a", C.POINTER(C.c_int64)), ("ip_b", C.POINTER(C.c_int64)), ("ip_v", C.POINTER(C.c_double)),
+                ("ot_a", C.POINTER(C.c_int64)), ("ot_b", C.POINTER(C.c_int64)), ("ot_v", C.POINTER(C.c_double)),
+                ("co_a", C.POINTER(C.c_int64)), ("co_b", C.POINTER(C.c_int64)), ("co_v", C.POINTER(C.c_double))]
+
+
 class SoHit(C.Structure):
     _fields_ = [("qidx", C.c_int64), ("sidx", C.c_int64), ("identity", C.c_double), ("evalue", C.c_double), ("aln", C.c_int32),
                 ("mis", C.c_int32), ("gap", C.c_int32), ("qst", C.c_int32), ("qed", C.c_int32), ("sst", C.c_int32),
@@ -45,7 +52,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
            "so_apc", "so_apc_free", "so_apc_last_error",
-           "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error"]
+           "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
+           "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free"]
 
 
 class SoMclResult(C.Structure):
@@ -178,6 +186,9 @@ def load():
     L.so_orth_candidates_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, C.c_double, C.c_double, C.c_int, C.POINTER(SoOrthCand)]
     L.so_orth_free.argtypes = [C.POINTER(SoOrthCand)]
     L.so_orth_last_error.restype = cp
+    L.so_orth_relations_cols.argtypes = L.so_orth_candidates_cols.argtypes[:-1] + [C.POINTER(SoOrthRel)]
+    L.so_orth_relations_records.argtypes = L.so_orth_candidates_records.argtypes[:-1] + [C.POINTER(SoOrthRel)]
+    L.so_orth_rel_free.argtypes = [C.POINTER(SoOrthRel)]
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

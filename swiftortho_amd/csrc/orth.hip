@@ -1,7 +1,9 @@
 // orth.hip -- the candidate stage of find_orth on the device: from the hit rows of a search (columns uploaded from the host, or the so_hit
 // records so_search_device left in HBM) to the three candidate tables swiftortho_amd/find_orth.py `candidates()` defines -- the ortholog
 // and in-paralog pairs proposed exactly twice, and the best score of every co-ortholog candidate pair.  It is the one part of that stage
-// that touches every row; the normalisers, the co-ortholog products and the text stay on the host, on tables several times smaller.
+// that touches every row.  so_orth_candidates_* hand those tables to the host; so_orth_relations_* go on from them on the device (the
+// relations part below: normalisers, co-ortholog products, repeat rule, normalisation) and hand out the relation tables -- the text stays
+// on the host.
 //
 // The numpy function is the definition, and the tables are reproduced bit for bit:
 //   * a row is kept unless (1 + |qed - qst|) / qlen < coverage or idy < identity (a NaN coverage keeps the row); the score is the bit
@@ -356,12 +358,25 @@ struct PairStage {
     }
 };
 
-void orth_run(int device, i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm,
-              const Tune& tn, u32* d_err, const char* who, so_orth_cand* out) {
+// the candidate tables of one call, left on the device: what so_orth_candidates_* download and so_orth_relations_* work on
+struct OrthDev {
+    DevBuf<int> tax;                  // taxon code of every name
+    DevBuf<i64> ot_a, ot_b, ip_a, ip_b, co_key;
+    DevBuf<double> ot_s, ip_s, co_best;
+    u32 n_ot = 0, n_ip = 0, n_co = 0;
+    i64 n_rows = 0, n_runs = 0, n_groups = 0;
+    u64 M = 1;
+    u32 T = 1;
+};
+
+void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm, const Tune& tn,
+              u32* d_err, const char* who, OrthDev* out) {
     const u64 M = (u64)(n_names > 0 ? n_names : 1);
     const u32 T = (u32)(n_taxa > 0 ? n_taxa : 1);
     const u32 N = (u32)n;
-    DevBuf<int> d_tax, kq, ks;
+    out->M = M, out->T = T;
+    DevBuf<int>& d_tax = out->tax;
+    DevBuf<int> kq, ks;
     DevBuf<u32> keep, pos, tmp_a, tmp_b, first, head, rid, rstart;
     DevBuf<double> kbit, ksco;
     upload(d_tax, tax, (size_t)n_names, st);
@@ -465,8 +480,8 @@ void orth_run(int device, i64 n, const OrthCols& c, hipStream_t st, i64 n_names,
     HIP_CHECK(hipMemcpyAsync(tot + 1, p_ip.total, sizeof(u32), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(tot + 2, p_co.total, sizeof(u32), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    DevBuf<i64> o_ota, o_otb, o_ipa, o_ipb, o_cok;
-    DevBuf<double> o_ots, o_ips, o_cob;
+    DevBuf<i64>&o_ota = out->ot_a, &o_otb = out->ot_b, &o_ipa = out->ip_a, &o_ipb = out->ip_b, &o_cok = out->co_key;
+    DevBuf<double>&o_ots = out->ot_s, &o_ips = out->ip_s, &o_cob = out->co_best;
     o_ota.ensure(tot[0] + 2), o_otb.ensure(tot[0] + 2), o_ots.ensure(tot[0] + 2), o_ipa.ensure(tot[1] + 2), o_ipb.ensure(tot[1] + 2), o_ips.ensure(tot[1] + 2);
     o_cok.ensure(tot[2] + 2), o_cob.ensure(tot[2] + 2);
     if (hc[0]) hipLaunchKernelGGL(k_orth_twice_emit, grid256(hc[0]), dim3(256), 0, st, p_ot.sk.p, p_ot.sv.p, hc[0], p_ot.flag.p, p_ot.pos.p, M, o_ota.p, o_otb.p, o_ots.p);
@@ -474,12 +489,394 @@ void orth_run(int device, i64 n, const OrthCols& c, hipStream_t st, i64 n_names,
     if (hc[2]) hipLaunchKernelGGL(k_orth_distinct_emit, grid256(hc[2]), dim3(256), 0, st, p_co.sk.p, p_co.sv.p, hc[2], p_co.flag.p, p_co.pos.p, o_cok.p, o_cob.p);
     HIP_CHECK(hipGetLastError());
     out->n_ot = tot[0], out->n_ip = tot[1], out->n_co = tot[2];
-    out->ot_a = host_copy(o_ota.p, tot[0], st), out->ot_b = host_copy(o_otb.p, tot[0], st), out->ot_s = host_copy(o_ots.p, tot[0], st);
-    out->ip_a = host_copy(o_ipa.p, tot[1], st), out->ip_b = host_copy(o_ipb.p, tot[1], st), out->ip_s = host_copy(o_ips.p, tot[1], st);
-    out->co_key = host_copy(o_cok.p, tot[2], st), out->co_best = host_copy(o_cob.p, tot[2], st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    (void)device;
 }
+
+// so_orth_candidates_*: the tables come to the host
+void orth_finish(OrthDev& D, hipStream_t st, const char*, so_orth_cand* out) {
+    out->n_rows = D.n_rows, out->n_runs = D.n_runs, out->n_groups = D.n_groups;
+    out->n_ot = D.n_ot, out->n_ip = D.n_ip, out->n_co = D.n_co;
+    out->ot_a = host_copy(D.ot_a.p, D.n_ot, st), out->ot_b = host_copy(D.ot_b.p, D.n_ot, st), out->ot_s = host_copy(D.ot_s.p, D.n_ot, st);
+    out->ip_a = host_copy(D.ip_a.p, D.n_ip, st), out->ip_b = host_copy(D.ip_b.p, D.n_ip, st), out->ip_s = host_copy(D.ip_s.p, D.n_ip, st);
+    out->co_key = host_copy(D.co_key.p, D.n_co, st), out->co_best = host_copy(D.co_best.p, D.n_co, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// ---- relations -----------------------------------------------------------------------------------------------------------------------
+// so_orth_relations_*: find_orth.py `relation_tables()` on the tables above, which never leave the device -- the in-paralog normalisers,
+// the co-ortholog products, the repeat rule and the per-(block, subject taxon) normalisation; bit for bit.
+// What that rests on: numpy's bincount(weights=) adds a group's rows in array order, so every float64 sum here is ONE chain
+// ((0 + x0) + x1) + ... over the group's rows in table order: the rows are grouped by a STABLE radix sort of (group key, row), and one wave
+// per group loads 64 rows at a time, coalesced, and adds them one after the other (k_rel_ip_avg, k_rel_group_norm: the same kernel shape
+// for a group of one row and of a million -- no size tiers).  No float atomics, no tree or wave reductions, nothing to contract (the sums
+// and quotients are single __dadd_rn / __ddiv_rn).  Positions come from count -> scan -> emit throughout; the one atomic (the 64-bit total
+// of the co-ortholog products) decides no position.
+//   k_rel_has_ot -> k_rel_fwd_flag / scan / k_rel_fwd_emit (forward in-paralog pairs, keyed by the taxon of a) -> sort -> segments ->
+//   k_rel_ip_avg -> k_rel_ip_flag / scan / k_rel_ip_emit;  k_rel_co_count / scan / k_rel_co_probe / scan / k_rel_co_emit;
+//   per section (OT, CO): k_rel_blk_heads / scan / k_rel_starts, [sort by pair, k_rel_occ], scan, k_rel_keep_emit, sort by group,
+//   segments, k_rel_group_norm.
+__device__ __forceinline__ u32 lower_i64(const i64* __restrict__ a, u32 n, i64 x) {   // first position with a[p] >= x
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (a[m] < x) lo = m + 1u;
+        else hi = m;
+    }
+    return lo;
+}
+__device__ __forceinline__ u32 upper_i64(const i64* __restrict__ a, u32 n, i64 x) {   // first position with a[p] > x
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (a[m] <= x) lo = m + 1u;
+        else hi = m;
+    }
+    return lo;
+}
+static_assert(ORTH_WAVE_ROWS == 64, "the group kernels walk a group one wave-wide chunk of rows at a time");
+// the value lane j holds (j the same in all lanes)
+__device__ __forceinline__ double lane_get(double v, int j) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+    return __hiloint2double(hi, lo);
+}
+
+__global__ __launch_bounds__(256) void k_rel_has_ot(const i64* __restrict__ ot_a, const i64* __restrict__ ot_b, u32 n, u32* __restrict__ has) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) has[ot_a[i]] = 1u, has[ot_b[i]] = 1u;
+}
+
+__global__ __launch_bounds__(256) void k_rel_fwd_flag(const i64* __restrict__ ip_a, const i64* __restrict__ ip_b, u32 n, u32* __restrict__ flag) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) flag[i] = ip_a[i] < ip_b[i] ? 1u : 0u;
+}
+
+// the forward pairs in table order: fidx = row of the in-paralog table, fkey = taxon of its a
+__global__ __launch_bounds__(256) void k_rel_fwd_emit(const i64* __restrict__ ip_a, u32 n, const u32* __restrict__ flag, const u32* __restrict__ pos,
+                                                      const int* __restrict__ tax, u32* __restrict__ fidx, u64* __restrict__ fkey) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const u32 p = pos[i];
+    fidx[p] = i, fkey[p] = (u64)tax[ip_a[i]];
+}
+
+// segments of a sorted key list: head flags, and (after their inclusive scan) the segment starts; start[nseg] = n
+__global__ __launch_bounds__(256) void k_rel_heads(const u64* __restrict__ key, u32 n, u32* __restrict__ head) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rel_starts(u32 n, const u32* __restrict__ head, const u32* __restrict__ rid, u32 nseg, u32* __restrict__ start) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (head[i]) start[rid[i] - 1u] = i;
+    if (i == 0) start[nseg] = n;
+}
+
+// one wave per taxon that has forward pairs: the sum over all its pairs and over those with an ortholog on either side, each one chain in
+// table order (sidx ascends inside a segment: the sort is stable) -> avg[taxon]
+__global__ __launch_bounds__(256) void k_rel_ip_avg(const u32* __restrict__ start, u32 nseg, const u64* __restrict__ skey, const u32* __restrict__ sidx,
+                                                    const i64* __restrict__ ip_a, const i64* __restrict__ ip_b, const double* __restrict__ ip_s,
+                                                    const u32* __restrict__ has, double* __restrict__ avg) {
+    const u32 w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (w >= nseg) return;   // (a whole wave)
+    const u32 lane = threadIdx.x & 63u;
+    const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)start[w]), hi = (u32)__builtin_amdgcn_readfirstlane((int)start[w + 1]);
+    double all = 0., near = 0.;
+    u32 ncnt = 0;
+    for (u32 base = lo; base < hi; base += ORTH_WAVE_ROWS) {
+        const u32 i = base + lane;
+        double v = 0.;
+        bool nr = false;
+        if (i < hi) {
+            const u32 r = sidx[i];
+            v = ip_s[r];
+            nr = (has[ip_a[r]] | has[ip_b[r]]) != 0u;
+        }
+        const unsigned long long m = __ballot(nr);
+        const int cnt = (int)min((u32)ORTH_WAVE_ROWS, hi - base);
+        ncnt += (u32)__popcll(m);
+        for (int j = 0; j < cnt; ++j) {
+            const double x = lane_get(v, j);
+            all = __dadd_rn(all, x);
+            if ((m >> j) & 1ull) near = __dadd_rn(near, x);
+        }
+    }
+    if (lane == 0) avg[skey[lo]] = ncnt > 0 ? __ddiv_rn(near, (double)ncnt) : __ddiv_rn(all, (double)(hi - lo));
+}
+
+// a forward pair is a row unless its taxon's normaliser is zero (a NaN normaliser keeps it, as numpy's != does)
+__global__ __launch_bounds__(256) void k_rel_ip_flag(const u32* __restrict__ fidx, u32 nf, const i64* __restrict__ ip_a, const int* __restrict__ tax,
+                                                     const double* __restrict__ avg, u32* __restrict__ flag) {
+    const u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p < nf) flag[p] = avg[tax[ip_a[fidx[p]]]] != 0. ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rel_ip_emit(const u32* __restrict__ fidx, u32 nf, const u32* __restrict__ flag, const u32* __restrict__ pos,
+                                                     const i64* __restrict__ ip_a, const i64* __restrict__ ip_b, const double* __restrict__ ip_s,
+                                                     const int* __restrict__ tax, const double* __restrict__ avg, i64* __restrict__ oa, i64* __restrict__ ob,
+                                                     double* __restrict__ ov) {
+    const u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= nf || !flag[p]) return;
+    const u32 r = fidx[p], o = pos[p];
+    oa[o] = ip_a[r], ob[o] = ip_b[r], ov[o] = __ddiv_rn(ip_s[r], avg[tax[ip_a[r]]]);
+}
+
+// per ortholog pair: where the in-paralogs of its two genes lie in the table, and how many products it expands to; the products' 64-bit
+// total (an integer: any order); err |= 8: one pair alone has 2^32 products or more
+__global__ __launch_bounds__(256) void k_rel_co_count(const i64* __restrict__ ot_a, const i64* __restrict__ ot_b, u32 n, const i64* __restrict__ ip_a, u32 n_ip,
+                                                      u32* __restrict__ lo_q, u32* __restrict__ nq, u32* __restrict__ lo_s, u32* __restrict__ ns,
+                                                      u32* __restrict__ cnt, unsigned long long* __restrict__ total, u32* __restrict__ err) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long c = 0;
+    if (i < n) {
+        const i64 a = ot_a[i], b = ot_b[i];
+        const u32 lq = lower_i64(ip_a, n_ip, a), cq = upper_i64(ip_a, n_ip, a) - lq;
+        const u32 ls = lower_i64(ip_a, n_ip, b), cs = upper_i64(ip_a, n_ip, b) - ls;
+        lo_q[i] = lq, nq[i] = cq, lo_s[i] = ls, ns[i] = cs;
+        if (cq > 0 || cs > 0) c = ((unsigned long long)cq + 1ull) * ((unsigned long long)cs + 1ull);
+        if (c > 0xFFFFFFFFull) atomicOr(err, 8u);
+        cnt[i] = (u32)c;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(total, c);
+}
+
+// one thread per product, in (pair, qi-major, si-minor) order: partners in table order, the gene itself last; hit = the product is a
+// co-ortholog candidate in this orientation (cpos: where)
+__global__ __launch_bounds__(256) void k_rel_co_probe(u32 P, const u32* __restrict__ base, u32 n_ot, const u32* __restrict__ lo_q, const u32* __restrict__ nq,
+                                                      const u32* __restrict__ lo_s, const u32* __restrict__ ns, const i64* __restrict__ ot_a,
+                                                      const i64* __restrict__ ot_b, const i64* __restrict__ ip_b, const i64* __restrict__ co_key, u32 n_co, u64 M,
+                                                      u32* __restrict__ hit, u32* __restrict__ cpos) {
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= P) return;
+    u32 lo = 0, hi = n_ot;   // the last pair whose first product is <= t (pairs without products share their successor's base)
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (base[m] <= t) lo = m + 1u;
+        else hi = m;
+    }
+    const u32 u = lo - 1u;
+    const u32 local = t - base[u];
+    const u32 cs = ns[u] + 1u;
+    const u32 qi = local / cs, si = local % cs;
+    const i64 qip = qi < nq[u] ? ip_b[lo_q[u] + qi] : ot_a[u];
+    const i64 sip = si < ns[u] ? ip_b[lo_s[u] + si] : ot_b[u];
+    const i64 k = (i64)((u64)qip * M + (u64)sip);
+    const u32 p = lower_i64(co_key, n_co, k);
+    const bool h = p < n_co && co_key[p] == k;
+    hit[t] = h ? 1u : 0u, cpos[t] = p;
+}
+__global__ __launch_bounds__(256) void k_rel_co_emit(u32 P, const u32* __restrict__ hit, const u32* __restrict__ pos, const u32* __restrict__ cpos,
+                                                     const i64* __restrict__ co_key, const double* __restrict__ co_best, u64 M, i64* __restrict__ oa,
+                                                     i64* __restrict__ ob, double* __restrict__ os) {
+    const u32 t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= P || !hit[t]) return;
+    const u32 c = cpos[t], o = pos[t];
+    const u64 k = (u64)co_key[c];
+    oa[o] = (i64)(k / M), ob[o] = (i64)(k % M), os[o] = co_best[c];
+}
+
+// blocks of a section: runs of consecutive rows whose a has one taxon
+__global__ __launch_bounds__(256) void k_rel_blk_heads(const i64* __restrict__ pa, const int* __restrict__ tax, u32 n, u32* __restrict__ head) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) head[i] = (i == 0 || tax[pa[i]] != tax[pa[i - 1]]) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rel_pair_keys(const i64* __restrict__ pa, const i64* __restrict__ pb, u32 n, u64 M, u64* __restrict__ key, u32* __restrict__ idx) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) key[i] = (u64)pa[i] * M + (u64)pb[i], idx[i] = i;
+}
+// rows sorted by pair (stable: rows of one pair ascend, and so do their blocks): a row stays when it is the first of its (pair, block), or the
+// second and the pair is its block's first pair.  bid: block number + 1; bstart: first row of every block
+__global__ __launch_bounds__(256) void k_rel_occ(const u64* __restrict__ skey, const u32* __restrict__ sidx, u32 n, const u32* __restrict__ bid,
+                                                 const u32* __restrict__ bstart, const i64* __restrict__ pa, const i64* __restrict__ pb, u64 M, u32* __restrict__ keep) {
+    const u32 j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const u32 r = sidx[j];
+    const u32 b = bid[r];
+    const u64 k = skey[j];
+    const bool same1 = j >= 1u && skey[j - 1] == k && bid[sidx[j - 1]] == b;
+    const bool same2 = same1 && j >= 2u && skey[j - 2] == k && bid[sidx[j - 2]] == b;
+    const u32 f = bstart[b - 1u];
+    const bool first_pair = k == (u64)pa[f] * M + (u64)pb[f];
+    keep[r] = (!same1 || (!same2 && first_pair)) ? 1u : 0u;
+}
+// the kept rows in order, with their group key block * T + taxon of b
+__global__ __launch_bounds__(256) void k_rel_keep_emit(u32 n, const u32* __restrict__ keep, const u32* __restrict__ pos, const i64* __restrict__ pa,
+                                                       const i64* __restrict__ pb, const double* __restrict__ ps, const u32* __restrict__ bid,
+                                                       const int* __restrict__ tax, u32 T, i64* __restrict__ oa, i64* __restrict__ ob, double* __restrict__ os,
+                                                       u64* __restrict__ gkey, u32* __restrict__ gidx) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    const u32 p = pos[i];
+    oa[p] = pa[i], ob[p] = pb[i], os[p] = ps[i];
+    gkey[p] = (u64)(bid[i] - 1u) * T + (u64)tax[pb[i]], gidx[p] = p;
+}
+// one wave per (block, subject taxon) group: the sum of its rows' scores as one chain in kept order, then v = s / (sum / count)
+__global__ __launch_bounds__(256) void k_rel_group_norm(const u32* __restrict__ start, u32 nseg, const u32* __restrict__ sidx, const double* __restrict__ s,
+                                                        double* __restrict__ v) {
+    const u32 w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (w >= nseg) return;   // (a whole wave)
+    const u32 lane = threadIdx.x & 63u;
+    const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)start[w]), hi = (u32)__builtin_amdgcn_readfirstlane((int)start[w + 1]);
+    double sum = 0.;
+    for (u32 base = lo; base < hi; base += ORTH_WAVE_ROWS) {
+        const u32 i = base + lane;
+        const double x = i < hi ? s[sidx[i]] : 0.;
+        const int cnt = (int)min((u32)ORTH_WAVE_ROWS, hi - base);
+        for (int j = 0; j < cnt; ++j) sum = __dadd_rn(sum, lane_get(x, j));
+    }
+    const double mean = __ddiv_rn(sum, (double)(hi - lo));
+    for (u32 i = lo + lane; i < hi; i += ORTH_WAVE_ROWS) {
+        const u32 r = sidx[i];
+        v[r] = __ddiv_rn(s[r], mean);
+    }
+}
+
+// scan + its total on the host (the stage sizes its next buffers by it)
+struct RelScan {
+    DevBuf<u32> tmp;
+    u32 run(const u32* in, u32* out, u32 n, bool inclusive, hipStream_t st) {
+        tmp.ensure(scan_u32_temp_elems(n) + 2);
+        const u32* d = scan_u32(in, out, n, inclusive, tmp.p, st);
+        u32 tot = 0;
+        HIP_CHECK(hipMemcpyAsync(&tot, d, sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        return tot;
+    }
+};
+
+// (key, row) pairs -> sorted by key, rows of one key in their order, and the bounds of the key groups
+struct RelGroups {
+    DevBuf<u64> skey;
+    DevBuf<u32> sidx, head, rid, start;
+    DevBuf<u8> sort_tmp;
+    RelScan sc;
+    u32 nseg = 0;
+    void sort(const u64* key, const u32* idx, u32 n, int bits, hipStream_t st) {
+        skey.ensure(n + 2), sidx.ensure(n + 2);
+        const size_t tb = sort_pairs_u64_u32_temp_bytes(n, bits);
+        sort_tmp.ensure(tb + 16);
+        sort_pairs_u64_u32(sort_tmp.p, tb, key, skey.p, idx, sidx.p, n, bits, st);
+    }
+    void segments(u32 n, hipStream_t st) {
+        head.ensure(n + 2), rid.ensure(n + 2);
+        hipLaunchKernelGGL(k_rel_heads, grid256(n), dim3(256), 0, st, skey.p, n, head.p);
+        nseg = sc.run(head.p, rid.p, n, true, st);
+        start.ensure((size_t)nseg + 3);
+        hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, st, n, head.p, rid.p, nseg, start.p);
+    }
+};
+
+struct RelSection {   // one output section on the device
+    DevBuf<i64> a, b;
+    DevBuf<double> v;
+    u32 n = 0;
+};
+
+// the repeat rule and the normalisation of one section (n > 0 rows pa, pb, ps); distinct: no pair occurs twice (the ortholog table: one row
+// per key that was proposed twice), so every row stays
+void rel_section(const i64* pa, const i64* pb, const double* ps, u32 n, bool distinct, const OrthDev& D, hipStream_t st, RelSection* out) {
+    DevBuf<u32> head, bid, bstart, keep, pos, idx, gidx;
+    DevBuf<u64> key, gkey;
+    DevBuf<double> ks;
+    RelScan sc;
+    head.ensure(n + 2), bid.ensure(n + 2), keep.ensure(n + 2), pos.ensure(n + 2);
+    hipLaunchKernelGGL(k_rel_blk_heads, grid256(n), dim3(256), 0, st, pa, D.tax.p, n, head.p);
+    const u32 nblk = sc.run(head.p, bid.p, n, true, st);
+    if (distinct) fill_u32(keep.p, n, 1u, st);
+    else {
+        bstart.ensure((size_t)nblk + 3), key.ensure(n + 2), idx.ensure(n + 2);
+        hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, st, n, head.p, bid.p, nblk, bstart.p);
+        hipLaunchKernelGGL(k_rel_pair_keys, grid256(n), dim3(256), 0, st, pa, pb, n, D.M, key.p, idx.p);
+        RelGroups g;
+        g.sort(key.p, idx.p, n, ceil_log2(D.M * D.M), st);
+        hipLaunchKernelGGL(k_rel_occ, grid256(n), dim3(256), 0, st, g.skey.p, g.sidx.p, n, bid.p, bstart.p, pa, pb, D.M, keep.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));   // (g's buffers go away here)
+    }
+    const u32 nk = sc.run(keep.p, pos.p, n, false, st);
+    out->n = nk;
+    out->a.ensure(nk + 2), out->b.ensure(nk + 2), out->v.ensure(nk + 2), ks.ensure(nk + 2), gkey.ensure(nk + 2), gidx.ensure(nk + 2);
+    hipLaunchKernelGGL(k_rel_keep_emit, grid256(n), dim3(256), 0, st, n, keep.p, pos.p, pa, pb, ps, bid.p, D.tax.p, D.T, out->a.p, out->b.p, ks.p, gkey.p, gidx.p);
+    RelGroups g;
+    g.sort(gkey.p, gidx.p, nk, ceil_log2((u64)nblk * D.T), st);
+    g.segments(nk, st);
+    hipLaunchKernelGGL(k_rel_group_norm, dim3((g.nseg + 3u) / 4u), dim3(256), 0, st, g.start.p, g.nseg, g.sidx.p, ks.p, out->v.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// so_orth_relations_*: the relation tables are computed where the candidate tables are; only they come to the host
+void orth_finish(OrthDev& D, hipStream_t st, const char* who, so_orth_rel* out) {
+    out->n_rows = D.n_rows, out->n_runs = D.n_runs, out->n_groups = D.n_groups;
+    RelSection ip, ot, co;
+    RelScan sc;
+    DevBuf<i64> c_a, c_b;   // the co-ortholog rows before the repeat rule
+    DevBuf<double> c_s;
+    u32 n_c = 0;
+    if (D.n_ip) {
+        // ---- in-paralog normalisers and values
+        const u32 n = D.n_ip;
+        DevBuf<u32> has, flag, pos, fidx, flag2, pos2;
+        DevBuf<u64> fkey;
+        DevBuf<double> avg;
+        has.ensure((size_t)D.M + 2), flag.ensure(n + 2), pos.ensure(n + 2);
+        HIP_CHECK(hipMemsetAsync(has.p, 0, (size_t)D.M * sizeof(u32), st));
+        if (D.n_ot) hipLaunchKernelGGL(k_rel_has_ot, grid256(D.n_ot), dim3(256), 0, st, D.ot_a.p, D.ot_b.p, D.n_ot, has.p);
+        hipLaunchKernelGGL(k_rel_fwd_flag, grid256(n), dim3(256), 0, st, D.ip_a.p, D.ip_b.p, n, flag.p);
+        const u32 nf = sc.run(flag.p, pos.p, n, false, st);
+        if (nf) {
+            fidx.ensure(nf + 2), fkey.ensure(nf + 2), flag2.ensure(nf + 2), pos2.ensure(nf + 2), avg.ensure((size_t)D.T + 2);
+            hipLaunchKernelGGL(k_rel_fwd_emit, grid256(n), dim3(256), 0, st, D.ip_a.p, n, flag.p, pos.p, D.tax.p, fidx.p, fkey.p);
+            RelGroups g;
+            g.sort(fkey.p, fidx.p, nf, ceil_log2(D.T), st);
+            g.segments(nf, st);
+            hipLaunchKernelGGL(k_rel_ip_avg, dim3((g.nseg + 3u) / 4u), dim3(256), 0, st, g.start.p, g.nseg, g.skey.p, g.sidx.p, D.ip_a.p, D.ip_b.p, D.ip_s.p, has.p, avg.p);
+            hipLaunchKernelGGL(k_rel_ip_flag, grid256(nf), dim3(256), 0, st, fidx.p, nf, D.ip_a.p, D.tax.p, avg.p, flag2.p);
+            ip.n = sc.run(flag2.p, pos2.p, nf, false, st);
+            ip.a.ensure(ip.n + 2), ip.b.ensure(ip.n + 2), ip.v.ensure(ip.n + 2);
+            hipLaunchKernelGGL(k_rel_ip_emit, grid256(nf), dim3(256), 0, st, fidx.p, nf, flag2.p, pos2.p, D.ip_a.p, D.ip_b.p, D.ip_s.p, D.tax.p, avg.p, ip.a.p, ip.b.p, ip.v.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    }
+    if (D.n_ip && D.n_co && D.n_ot) {
+        // ---- co-orthologs: count -> scan -> probe -> scan -> emit
+        const u32 n = D.n_ot;
+        DevBuf<u32> lo_q, nq, lo_s, ns, cnt, base, err, hit, hpos, cpos;
+        DevBuf<unsigned long long> total;
+        lo_q.ensure(n + 2), nq.ensure(n + 2), lo_s.ensure(n + 2), ns.ensure(n + 2), cnt.ensure(n + 2), base.ensure(n + 2), err.ensure(4), total.ensure(2);
+        HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(u32), st));
+        HIP_CHECK(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_rel_co_count, grid256(n), dim3(256), 0, st, D.ot_a.p, D.ot_b.p, n, D.ip_a.p, D.n_ip, lo_q.p, nq.p, lo_s.p, ns.p, cnt.p, total.p, err.p);
+        unsigned long long tot = 0;
+        u32 e = 0;
+        HIP_CHECK(hipMemcpyAsync(&tot, total.p, sizeof tot, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&e, err.p, sizeof e, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (e || tot >= (1ull << 31)) throw SoError(std::string(who) + ": 2^31 co-ortholog products and more are not supported (32-bit product numbers)");
+        if (tot) {
+            const u32 P = (u32)tot;
+            if (sc.run(cnt.p, base.p, n, false, st) != P) throw SoError(std::string(who) + ": internal error: the co-ortholog products do not add up");
+            hit.ensure((size_t)P + 2), hpos.ensure((size_t)P + 2), cpos.ensure((size_t)P + 2);
+            hipLaunchKernelGGL(k_rel_co_probe, grid256(P), dim3(256), 0, st, P, base.p, n, lo_q.p, nq.p, lo_s.p, ns.p, D.ot_a.p, D.ot_b.p, D.ip_b.p, D.co_key.p, D.n_co, D.M,
+                               hit.p, cpos.p);
+            n_c = sc.run(hit.p, hpos.p, P, false, st);
+            c_a.ensure(n_c + 2), c_b.ensure(n_c + 2), c_s.ensure(n_c + 2);
+            hipLaunchKernelGGL(k_rel_co_emit, grid256(P), dim3(256), 0, st, P, hit.p, hpos.p, cpos.p, D.co_key.p, D.co_best.p, D.M, c_a.p, c_b.p, c_s.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    }
+    // ---- the repeat rule and the normalisation
+    if (D.n_ot) rel_section(D.ot_a.p, D.ot_b.p, D.ot_s.p, D.n_ot, true, D, st, &ot);
+    if (n_c) rel_section(c_a.p, c_b.p, c_s.p, n_c, false, D, st, &co);
+    out->n_ip = ip.n, out->n_ot = ot.n, out->n_co = co.n;
+    out->ip_a = host_copy(ip.a.p, ip.n, st), out->ip_b = host_copy(ip.b.p, ip.n, st), out->ip_v = host_copy(ip.v.p, ip.n, st);
+    out->ot_a = host_copy(ot.a.p, ot.n, st), out->ot_b = host_copy(ot.b.p, ot.n, st), out->ot_v = host_copy(ot.v.p, ot.n, st);
+    out->co_a = host_copy(co.a.p, co.n, st), out->co_b = host_copy(co.b.p, co.n, st), out->co_v = host_copy(co.v.p, co.n, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
 
 struct StreamGuard {
     hipStream_t s = nullptr;
@@ -488,10 +885,10 @@ struct StreamGuard {
     }
 };
 
-// what both entry points check before anything touches the device
-void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, so_orth_cand* out) {
+// what every entry point checks before anything touches the device
+void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, void* out, size_t out_bytes) {
     if (!out) throw SoError(std::string(who) + ": result pointer is NULL");
-    memset(out, 0, sizeof *out);
+    memset(out, 0, out_bytes);
     if (n < 0 || n_names < 0 || n_taxa < 0 || (n_names > 0 && !tax) || norm < 0 || norm > 2) throw SoError(std::string(who) + ": bad arguments");
     if (n >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 rows and more are not supported (32-bit row numbers)");
     if (n_names > 3037000499ll) throw SoError(std::string(who) + ": n_names * n_names reaches 2^63 (pair keys a * n_names + b are 63-bit)");
@@ -502,32 +899,34 @@ void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* 
     if (device < 0 || device >= nd) throw SoError(std::string(who) + ": device index out of range");
 }
 
-// an output of no rows still hands out arrays that so_orth_free can release
+// an output of no rows still hands out arrays that its free function can release
 void orth_fill_empty(so_orth_cand* out) {
     void** slots[8] = {(void**)&out->ot_a, (void**)&out->ot_b, (void**)&out->ot_s, (void**)&out->ip_a, (void**)&out->ip_b, (void**)&out->ip_s, (void**)&out->co_key,
                        (void**)&out->co_best};
     for (void** p : slots)
         if (!*p) *p = calloc(1, 8);
 }
-
-}  // namespace
-
-extern "C" {
-
-const char* so_orth_last_error(void) { return g_orth_err.c_str(); }
-
-void so_orth_free(so_orth_cand* r) {
-    if (!r) return;
+void orth_fill_empty(so_orth_rel* out) {
+    void** slots[9] = {(void**)&out->ip_a, (void**)&out->ip_b, (void**)&out->ip_v, (void**)&out->ot_a, (void**)&out->ot_b, (void**)&out->ot_v, (void**)&out->co_a,
+                       (void**)&out->co_b, (void**)&out->co_v};
+    for (void** p : slots)
+        if (!*p) *p = calloc(1, 8);
+}
+void orth_release(so_orth_cand* r) {
     free(r->ot_a), free(r->ot_b), free(r->ot_s), free(r->ip_a), free(r->ip_b), free(r->ip_s), free(r->co_key), free(r->co_best);
     memset(r, 0, sizeof *r);
 }
+void orth_release(so_orth_rel* r) {
+    free(r->ip_a), free(r->ip_b), free(r->ip_v), free(r->ot_a), free(r->ot_b), free(r->ot_v), free(r->co_a), free(r->co_b), free(r->co_v);
+    memset(r, 0, sizeof *r);
+}
 
-int so_orth_candidates_cols(int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
-                            const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm,
-                            so_orth_cand* out) {
-    const char* who = "so_orth_candidates_cols";
+// the two entry families: the candidate tables from host columns / device records, then orth_finish for the kind of result asked for
+template <class Out>
+int orth_from_cols(const char* who, int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
+                   const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, Out* out) {
     try {
-        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out, sizeof *out);
         if (n > 0 && (!q || !s || !idy || !aln || !qst || !qed || !score || !qlen)) throw SoError(std::string(who) + ": a column is NULL");
         if (n > 0) {
             HIP_CHECK(hipSetDevice(device));
@@ -536,32 +935,37 @@ int so_orth_candidates_cols(int device, int64_t n, const int32_t* q, const int32
             const PoisonScope poison((int)tn.poison);
             StreamGuard g;
             HIP_CHECK(hipStreamCreate(&g.s));
-            DevBuf<int> dq, ds;
-            DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
-            DevBuf<u32> d_err;
-            const size_t N = (size_t)n;
-            upload(dq, q, N, g.s), upload(ds, s, N, g.s), upload(d_idy, idy, N, g.s), upload(d_aln, aln, N, g.s), upload(d_qst, qst, N, g.s), upload(d_qed, qed, N, g.s);
-            upload(d_score, score, N, g.s), upload(d_qlen, qlen, N, g.s);
-            d_err.ensure(4);
-            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
-            const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-            orth_run(device, n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, out);
+            OrthDev D;
+            {
+                DevBuf<int> dq, ds;
+                DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
+                DevBuf<u32> d_err;
+                const size_t N = (size_t)n;
+                upload(dq, q, N, g.s), upload(ds, s, N, g.s), upload(d_idy, idy, N, g.s), upload(d_aln, aln, N, g.s), upload(d_qst, qst, N, g.s), upload(d_qed, qed, N, g.s);
+                upload(d_score, score, N, g.s), upload(d_qlen, qlen, N, g.s);
+                d_err.ensure(4);
+                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
+                const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
+                orth_run(n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, &D);
+                HIP_CHECK(hipStreamSynchronize(g.s));   // (the columns go away here)
+            }
+            orth_finish(D, g.s, who, out);
         }
         orth_fill_empty(out);
         g_orth_err.clear();
         return 0;
     } catch (const std::exception& e) {
-        if (out) so_orth_free(out);
+        if (out) orth_release(out);
         g_orth_err = e.what();
         return 1;
     }
 }
 
-int so_orth_candidates_records(int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
-                               const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_cand* out) {
-    const char* who = "so_orth_candidates_records";
+template <class Out>
+int orth_from_records(const char* who, int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
+                      const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, Out* out) {
     try {
-        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out, sizeof *out);
         if (n_q < 0 || n_s < 0 || (n_q > 0 && !qmap) || (n_s > 0 && !smap)) throw SoError(std::string(who) + ": bad arguments");
         if (n > 0 && !d_hits) throw SoError(std::string(who) + ": the record pointer is NULL");
         if (n > 0) {
@@ -574,27 +978,68 @@ int so_orth_candidates_records(int device, const so_hit* d_hits, int64_t n, cons
             const PoisonScope poison((int)tn.poison);
             StreamGuard g;
             HIP_CHECK(hipStreamCreate(&g.s));
-            DevBuf<int> dq, ds, d_qmap, d_smap;
-            DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
-            DevBuf<u32> d_err;
-            const size_t N = (size_t)n;
-            upload(d_qmap, qmap, (size_t)n_q, g.s), upload(d_smap, smap, (size_t)n_s, g.s);
-            dq.ensure(N + 2), ds.ensure(N + 2), d_idy.ensure(N + 2), d_aln.ensure(N + 2), d_qst.ensure(N + 2), d_qed.ensure(N + 2), d_score.ensure(N + 2), d_qlen.ensure(N + 2);
-            d_err.ensure(4);
-            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
-            hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, g.s, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
-                               d_qed.p, d_score.p, d_qlen.p, d_err.p);
-            const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-            orth_run(device, n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, out);
+            OrthDev D;
+            {
+                DevBuf<int> dq, ds, d_qmap, d_smap;
+                DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
+                DevBuf<u32> d_err;
+                const size_t N = (size_t)n;
+                upload(d_qmap, qmap, (size_t)n_q, g.s), upload(d_smap, smap, (size_t)n_s, g.s);
+                dq.ensure(N + 2), ds.ensure(N + 2), d_idy.ensure(N + 2), d_aln.ensure(N + 2), d_qst.ensure(N + 2), d_qed.ensure(N + 2), d_score.ensure(N + 2), d_qlen.ensure(N + 2);
+                d_err.ensure(4);
+                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
+                hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, g.s, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
+                                   d_qed.p, d_score.p, d_qlen.p, d_err.p);
+                const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
+                orth_run(n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, &D);
+                HIP_CHECK(hipStreamSynchronize(g.s));
+            }
+            orth_finish(D, g.s, who, out);
         }
         orth_fill_empty(out);
         g_orth_err.clear();
         return 0;
     } catch (const std::exception& e) {
-        if (out) so_orth_free(out);
+        if (out) orth_release(out);
         g_orth_err = e.what();
         return 1;
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* so_orth_last_error(void) { return g_orth_err.c_str(); }
+
+void so_orth_free(so_orth_cand* r) {
+    if (r) orth_release(r);
+}
+
+void so_orth_rel_free(so_orth_rel* r) {
+    if (r) orth_release(r);
+}
+
+int so_orth_candidates_cols(int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
+                            const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm,
+                            so_orth_cand* out) {
+    return orth_from_cols("so_orth_candidates_cols", device, n, q, s, idy, aln, qst, qed, score, qlen, n_names, tax, n_taxa, coverage, identity, norm, out);
+}
+
+int so_orth_candidates_records(int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
+                               const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_cand* out) {
+    return orth_from_records("so_orth_candidates_records", device, d_hits, n, qmap, n_q, smap, n_s, n_names, tax, n_taxa, coverage, identity, norm, out);
+}
+
+int so_orth_relations_cols(int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
+                           const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm,
+                           so_orth_rel* out) {
+    return orth_from_cols("so_orth_relations_cols", device, n, q, s, idy, aln, qst, qed, score, qlen, n_names, tax, n_taxa, coverage, identity, norm, out);
+}
+
+int so_orth_relations_records(int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
+                              const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, so_orth_rel* out) {
+    return orth_from_records("so_orth_relations_records", device, d_hits, n, qmap, n_q, smap, n_s, n_names, tax, n_taxa, coverage, identity, norm, out);
 }
 
 }  // extern "C"

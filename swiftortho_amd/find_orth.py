@@ -50,7 +50,7 @@ def manual_print(prog='find_orth.py'):
     print('  -t: keep tmpdir[y|n]. Default: n (accepted, unused)')
     print('  -T: tmpdir for sort command. Default: ./tmp/ (accepted, unused)')
     print('  -s: separator between taxa and sequence id. Default is |.')
-    print('  -G: candidate stage on the GPU [T|F]. Default: F (T needs libsohit.so and a HIP device; same output)')
+    print('  -G: stages on the GPU [T|R|F]. T: the candidate stage; R: candidates and relations (the host only writes the text). Default: F (T and R need libsohit.so and a HIP device; same output)')
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -385,10 +385,29 @@ def candidates(cols, coverage=.5, identity=0., norm='no', sep='|'):
 _numpy_candidates = candidates   # (relations() has a keyword of the same name)
 
 
-def relations_from_candidates(names, tax, taxa, cand):
-    """the rest of the stage -- normalisers, co-orthologs, text -- on the candidate tables -> output lines (bytes, no newline)"""
+class RelationTables:
+    """The relations as arrays, in output order: ip_* the forward in-paralog pairs (a < b) whose taxon normaliser is not zero, ot_* / co_* the
+    ortholog / co-ortholog rows that survive the repeat rule; *_a, *_b: name codes (int64), *_v: the normalised scores (float64).
+    n_rows / n_runs / n_groups: the counters of the Candidates they came from."""
+    FIELDS = ('ip_a', 'ip_b', 'ip_v', 'ot_a', 'ot_b', 'ot_v', 'co_a', 'co_b', 'co_v')
+
+    def __init__(self, ip_a, ip_b, ip_v, ot_a, ot_b, ot_v, co_a, co_b, co_v, n_rows=0, n_runs=0, n_groups=0):
+        self.ip_a, self.ip_b, self.ip_v = ip_a, ip_b, ip_v
+        self.ot_a, self.ot_b, self.ot_v = ot_a, ot_b, ot_v
+        self.co_a, self.co_b, self.co_v = co_a, co_b, co_v
+        self.n_rows, self.n_runs, self.n_groups = int(n_rows), int(n_runs), int(n_groups)
+
+    @classmethod
+    def empty(cls):
+        i, f = (lambda: np.zeros(0, dtype=np.int64)), (lambda: np.zeros(0, dtype=np.float64))
+        return cls(i(), i(), f(), i(), i(), f(), i(), i(), f())
+
+
+def relation_tables(names, tax, taxa, cand):
+    """the rest of the stage but the text -- normalisers, co-orthologs, the repeat rule -- on the candidate tables -> RelationTables
+    (numpy; device_relation_tables() is the same on the GPU)"""
     if cand.n_rows == 0:
-        return []
+        return RelationTables.empty()
     M = max(len(names), 1)
     T = max(len(taxa), 1)
     ot_a, ot_b, ot_s, ip_a, ip_b, ip_s, cu, cbest = (getattr(cand, k) for k in Candidates.FIELDS)
@@ -426,17 +445,16 @@ def relations_from_candidates(names, tax, taxa, cand):
             pos = np.minimum(np.searchsorted(cu, k), len(cu) - 1)
             hit = cu[pos] == k
             co_a, co_b, co_s = qip[hit], sip[hit], cbest[pos[hit]]
-    # ---- text ----------------------------------------------------------------------------------------------------
-    lines = []
-    nm = names.tolist()
-    fmt = _PairFormatter(nm)
+    # ---- in-paralog values ----------------------------------------------------------------------------------------
     avg = ip_avg[tax[ip_a[fwd]]]
     with np.errstate(divide='ignore', invalid='ignore'):
         val = ip_s[fwd] / avg
     ok = avg != 0    # the reference's division raises there and the line is skipped
-    lines.extend(fmt.lines(b'IP', ip_a[fwd][ok], ip_b[fwd][ok], val[ok]))
-    for kind, (pa, pb, ps) in ((b'OT', (ot_a, ot_b, ot_s)), (b'CO', (co_a, co_b, co_s))):
+    out = [ip_a[fwd][ok], ip_b[fwd][ok], val[ok]]
+    # ---- repeat rule and normalisation of the ortholog and co-ortholog rows ---------------------------------------
+    for pa, pb, ps in ((ot_a, ot_b, ot_s), (co_a, co_b, co_s)):
         if len(pa) == 0:
+            out += [np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)]
             continue
         blk = np.cumsum(np.concatenate([[0], tax[pa][1:] != tax[pa][:-1]]).astype(np.int64))
         # occurrence number of every pair inside its block
@@ -456,8 +474,25 @@ def relations_from_candidates(names, tax, taxa, cand):
         gsum = np.bincount(ginv, weights=ps, minlength=len(gu))
         gcnt = np.bincount(ginv, minlength=len(gu)).astype(np.float64)
         val = ps / (gsum / gcnt)[ginv]
-        lines.extend(fmt.lines(kind, pa, pb, val))
+        out += [pa, pb, val]
+    return RelationTables(*[np.asarray(x, dtype=np.float64 if k % 3 == 2 else np.int64) for k, x in enumerate(out)],
+                          n_rows=cand.n_rows, n_runs=cand.n_runs, n_groups=cand.n_groups)
+
+
+def lines_from_tables(names, tables):
+    """RelationTables -> output lines (bytes, no newline): the IP, the OT, then the CO section"""
+    fmt = _PairFormatter(names.tolist())
+    lines = []
+    for kind, k in ((b'IP', 'ip'), (b'OT', 'ot'), (b'CO', 'co')):
+        lines.extend(fmt.lines(kind, getattr(tables, k + '_a'), getattr(tables, k + '_b'), getattr(tables, k + '_v')))
     return lines
+
+
+def relations_from_candidates(names, tax, taxa, cand):
+    """the rest of the stage -- normalisers, co-orthologs, text -- on the candidate tables -> output lines (bytes, no newline)"""
+    if cand.n_rows == 0:
+        return []
+    return lines_from_tables(names, relation_tables(names, tax, taxa, cand))
 
 
 def relations(cols, coverage=.5, identity=0., norm='no', sep='|', candidates=None):
@@ -472,29 +507,46 @@ def relations(cols, coverage=.5, identity=0., norm='no', sep='|', candidates=Non
 # ---------------------------------------------------------------------------------------------------------
 # the candidate stage on the GPU (include/sohit.h so_orth_*, csrc/orth.hip).  No fallback: without the library or a device these raise.
 # ---------------------------------------------------------------------------------------------------------
-def _orth_call(fn, tail_of, names, tax, taxa, coverage, identity, norm):
-    """shared tail of the two entry points: the call, the result tables copied out of the library's arrays"""
+def _orth_call(fn, tail_of, names, tax, taxa, coverage, identity, norm, stage='candidates'):
+    """shared tail of the entry points: the call, the result tables copied out of the library's arrays.  `fn`: the name of the library call
+    without its so_orth_ prefix and stage ('cols' | 'records'); stage 'candidates' -> Candidates, 'relations' -> RelationTables"""
     import ctypes as C
     from . import _lib
     L = _lib.load()
     tax32 = np.ascontiguousarray(tax, dtype=np.int32)
-    out = _lib.SoOrthCand()
-    rc = fn(L, *tail_of(len(names), C.c_void_p(tax32.ctypes.data), len(taxa), float(coverage), float(identity), NORMS.get(norm, 0), C.byref(out)))
+    rel = stage == 'relations'
+    out = _lib.SoOrthRel() if rel else _lib.SoOrthCand()
+    call = getattr(L, 'so_orth_%s_%s' % (stage, fn))
+    rc = call(*tail_of(len(names), C.c_void_p(tax32.ctypes.data), len(taxa), float(coverage), float(identity), NORMS.get(norm, 0), C.byref(out)))
     if rc != 0:
         raise RuntimeError(L.so_orth_last_error().decode())
     try:
         def arr(p, n, dt):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
         i, f = np.int64, np.float64
+        if rel:
+            return RelationTables(arr(out.ip_a, out.n_ip, i), arr(out.ip_b, out.n_ip, i), arr(out.ip_v, out.n_ip, f),
+                                  arr(out.ot_a, out.n_ot, i), arr(out.ot_b, out.n_ot, i), arr(out.ot_v, out.n_ot, f),
+                                  arr(out.co_a, out.n_co, i), arr(out.co_b, out.n_co, i), arr(out.co_v, out.n_co, f), out.n_rows, out.n_runs, out.n_groups)
         return Candidates(arr(out.ot_a, out.n_ot, i), arr(out.ot_b, out.n_ot, i), arr(out.ot_s, out.n_ot, f),
                           arr(out.ip_a, out.n_ip, i), arr(out.ip_b, out.n_ip, i), arr(out.ip_s, out.n_ip, f),
                           arr(out.co_key, out.n_co, i), arr(out.co_best, out.n_co, f), out.n_rows, out.n_runs, out.n_groups, tax, taxa)
     finally:
-        L.so_orth_free(C.byref(out))
+        (L.so_orth_rel_free if rel else L.so_orth_free)(C.byref(out))
 
 
 def device_candidates(cols, coverage=.5, identity=0., norm='no', sep='|', device=0):
     """candidates() on the GPU from host columns (so_orth_candidates_cols): the same tables, bit for bit"""
+    return _device_cols(cols, coverage, identity, norm, sep, device, 'candidates')
+
+
+def device_relation_tables(cols, coverage=.5, identity=0., norm='no', sep='|', device=0):
+    """relation_tables(candidates()) on the GPU from host columns (so_orth_relations_cols): the candidate tables stay on the device, the
+    relation tables come back, bit for bit those of the numpy stage"""
+    return _device_cols(cols, coverage, identity, norm, sep, device, 'relations')
+
+
+def _device_cols(cols, coverage, identity, norm, sep, device, stage):
     import ctypes as C
     n = len(cols.q)
     if n >= 1 << 31:
@@ -507,7 +559,7 @@ def device_candidates(cols, coverage=.5, identity=0., norm='no', sep='|', device
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     head = [int(device), n, ptr(q32), ptr(s32)] + [ptr(a) for a in dbl]
     tax, taxa = _taxa(cols.names, sep)
-    return _orth_call(lambda L, *a: L.so_orth_candidates_cols(*a), lambda *tail: head + list(tail), cols.names, tax, taxa, coverage, identity, norm)
+    return _orth_call('cols', lambda *tail: head + list(tail), cols.names, tax, taxa, coverage, identity, norm, stage)
 
 
 def _record_maps(query_ids, subject_ids):
@@ -517,8 +569,8 @@ def _record_maps(query_ids, subject_ids):
     return names, np.ascontiguousarray(qmap, dtype=np.int32), np.ascontiguousarray(smap, dtype=np.int32)
 
 
-def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep):
-    """-> (names, tax, taxa, Candidates) of the records `dev` holds"""
+def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep, stage='candidates'):
+    """-> (names, tax, taxa, Candidates | RelationTables) of the records `dev` holds"""
     import ctypes as C
     from . import _lib
     rec = C.sizeof(_lib.SoHit)
@@ -539,7 +591,7 @@ def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep):
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     head = [int(device), C.c_void_p(d_ptr), n, ptr(qmap), len(qmap), ptr(smap), len(smap)]
     tax, taxa = _taxa(names, sep)
-    cand = _orth_call(lambda L, *a: L.so_orth_candidates_records(*a), lambda *tail: head + list(tail), names, tax, taxa, coverage, identity, norm)
+    cand = _orth_call('records', lambda *tail: head + list(tail), names, tax, taxa, coverage, identity, norm, stage)
     del keep_alive
     return names, tax, taxa, cand
 
@@ -550,8 +602,20 @@ def device_candidates_from_records(dev, query_ids, subject_ids, coverage=.5, ide
     return _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep)[3]
 
 
-def relations_from_device(dev, query_ids, subject_ids, coverage=.5, identity=0., norm='no', sep='|'):
-    """relations_from_records() on records that stay on the device: only the candidate tables come to the host"""
+def device_relation_tables_from_records(dev, query_ids, subject_ids, coverage=.5, identity=0., norm='no', sep='|'):
+    """relation_tables() of the records `dev` holds (see device_candidates_from_records) without the candidate tables ever leaving the
+    device (so_orth_relations_records) -> (names, RelationTables)"""
+    names, _, _, tables = _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep, 'relations')
+    return names, tables
+
+
+def relations_from_device(dev, query_ids, subject_ids, coverage=.5, identity=0., norm='no', sep='|', stage='candidates'):
+    """relations_from_records() on records that stay on the device.  stage 'candidates': the candidate tables come to the host, numpy does
+    the rest; 'relations': the relation tables are computed on the device too and the host only writes the text"""
+    if stage == 'relations':
+        return lines_from_tables(*device_relation_tables_from_records(dev, query_ids, subject_ids, coverage, identity, norm, sep))
+    if stage != 'candidates':
+        raise ValueError("relations_from_device: stage is 'candidates' or 'relations'")
     names, tax, taxa, cand = _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep)
     return relations_from_candidates(names, tax, taxa, cand)
 
@@ -623,12 +687,17 @@ def main(argv=None):
     try:
         qry, coverage, identity, norm, sep = args['-i'], float(args['-c']), float(args['-y']), args['-n'], args['-s']
         int(args['-a'])
-        stage = device_candidates if str(args['-G']).upper().startswith('T') else None
+        gpu = str(args['-G']).upper()[:1]
+        stage = device_candidates if gpu == 'T' else None
     except Exception:
         manual_print(argv[0] if argv else 'find_orth.py')
         raise SystemExit()
     with open(qry, 'rb') as f:
-        lines = relations(columns_from_text(f.read()), coverage, identity, norm, sep, candidates=stage)
+        cols = columns_from_text(f.read())
+    if gpu == 'R':
+        lines = lines_from_tables(cols.names, device_relation_tables(cols, coverage, identity, norm, sep))
+    else:
+        lines = relations(cols, coverage, identity, norm, sep, candidates=stage)
     out = sys.stdout.buffer
     if lines:
         out.write(b'\n'.join(lines) + b'\n')

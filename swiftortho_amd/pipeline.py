@@ -12,7 +12,9 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
     """self-search of one proteome on the GPU, then IP / OT / CO relations from the hit RECORDS.
     device_stage=True: the records stay in HBM (search_device) and the candidate stage of find_orth runs on them there
     (find_orth.relations_from_device); they are downloaded only when `sc_path` asks for the file.
-    -> (relation lines as bytes, dict of stage wall times in seconds; with device_stage also 'orth_candidates')"""
+    device_stage='relations': the relation tables are computed on the device as well (find_orth.device_relation_tables_from_records)
+    and the host only writes the text.
+    -> (relation lines as bytes, dict of stage wall times in seconds; with device_stage also 'orth_candidates', or 'orth_relations')"""
     from . import find_orth, fsearch
     t = {}
     t0 = time.time()
@@ -25,7 +27,7 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
         t['load'] = time.time() - t0
         t0 = time.time()
         if device_stage:
-            return _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0)
+            return _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=device_stage == 'relations')
         hits = s.search()
         t['search'] = time.time() - t0
         t0 = time.time()
@@ -43,7 +45,7 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
     return lines, t
 
 
-def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0):
+def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=False):
     """orthology_from_search() from the search on, with the records left on the device (the caller closes the searcher)"""
     import numpy as np
     from . import find_orth, fsearch
@@ -56,9 +58,14 @@ def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0):
         s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(sc_path), b'w'))
         t['write_sc'] = time.time() - t0
         t0 = time.time()
-    names, tax, taxa, cand = find_orth._device_records(dev, ids, ids, coverage, identity, norm, sep)
-    t['orth_candidates'] = time.time() - t0
-    lines = find_orth.relations_from_candidates(names, tax, taxa, cand)
+    if relations:
+        names, tables = find_orth.device_relation_tables_from_records(dev, ids, ids, coverage, identity, norm, sep)
+        t['orth_relations'] = time.time() - t0
+        lines = find_orth.lines_from_tables(names, tables)
+    else:
+        names, tax, taxa, cand = find_orth._device_records(dev, ids, ids, coverage, identity, norm, sep)
+        t['orth_candidates'] = time.time() - t0
+        lines = find_orth.relations_from_candidates(names, tax, taxa, cand)
     t['find_orth'] = time.time() - t0
     t['rows'] = len(dev)
     return lines, t
