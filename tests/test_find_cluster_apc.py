@@ -34,11 +34,14 @@ CASES = apc_cases()
 
 def test_the_goldens_are_all_there():
     names = {n for n, _ in CASES}
-    assert names == {"odd_rows", "taxa3_dense", "taxa4_colon", "taxa5", "taxa8_big", "toy_default"}
+    assert names == {"hub_edges", "odd_rows", "taxa3_dense", "taxa4_colon", "taxa5", "taxa8_big", "toy_default"}
     assert {v for n, v in CASES if n == "taxa8_big"} == {"default", "d0.95", "b1000"}
     big = lambda v: open(os.path.join(GOLD, "apc_taxa8_big.%s.apc" % v)).read()
     assert big("b1000") == big("default")            # the batch size cannot change a result
     assert big("d0.95") != big("default")            # the damping factor can
+    assert {v for n, v in CASES if n == "hub_edges"} == {"default", "d0.9"}
+    hub = lambda v: open(os.path.join(GOLD, "apc_hub_edges.%s.apc" % v)).read()
+    assert hub("d0.9") != hub("default") and hub("d0.9").count("\n") >= 3 and hub("default").count("\n") >= 3
 
 
 def as_sets(text):

@@ -4,13 +4,15 @@
 
 Runs the REAL reference script bin/find_cluster.py -a apc (numpy + networkx; tools/refharness/fcshim/ stands in for its numba
 and cffi imports, so the loop runs as plain Python: ~30 s for the largest input) on .orth files and stores its stdout.
-Fixtures: tests/golden/apc_<name>.<variant>.apc (expected stdout), apc_<name>.json (input file name, flags per variant), and
-apc_odd_rows.orth, a small input written here that holds the rows fc2mat treats specially.
+Fixtures: tests/golden/apc_<name>.<variant>.apc (expected stdout), apc_<name>.json (input file name, flags per variant),
+apc_odd_rows.orth, a small input written here that holds the rows fc2mat treats specially, and apc_hub_edges.orth, the two-hub graph
+of tests/apc_edge_inputs.py at the hub degrees that give rows of APC_LANE_MAX + 1 and 64 + 1 entries.
 """
 import json
 import os
+import sys
 
-from make_cluster_goldens import FORCE, GOLD, run_ref_find_cluster
+from make_cluster_goldens import FORCE, GOLD, ROOT, run_ref_find_cluster
 
 # a repeated pair with two weights, a self pair, an x > y row, three-column rows, an id without '|', a weight of the form 1.5rm3 and an
 # unparsable weight whose genes appear nowhere else (they are numbered all the same, and end as groups of their own)
@@ -30,6 +32,17 @@ ODD_ROWS = [
     "CO\tt2|g\tt3|e\t7.5",
     "OT\tt1|c\tt2|g\t0.25",
 ]
+
+
+def hub_edges_rows(seed=2, taxa=2):
+    """two hubs sharing most leaves, tied weights, pairs in a seeded order (tests/apc_edge_inputs.py two_hub_pairs): after fc2mat's
+    doubling and preference entries the hubs' rows hold LM + 1 and W + 1 entries -- one past the lane / wave split of so_apc, one past
+    a full chunk"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import apc_edge_inputs as X
+    pairs, _ = X.two_hub_pairs(X.LM + 1, X.W + 1, seed)
+    name = lambda g: "t%d|g%03d" % (g % taxa, g)
+    return ["OT\t%s\t%s\t%r" % (tuple(sorted((name(x), name(y)))) + (w,)) for x, y, w in pairs]
 
 
 def make(name, orth_file, variants):
@@ -54,6 +67,10 @@ def main():
     if FORCE or not os.path.isfile(odd):
         open(odd, "w").write("".join(l + "\n" for l in ODD_ROWS))
     make("odd_rows", odd, default)
+    hub = os.path.join(GOLD, "apc_hub_edges.orth")
+    if FORCE or not os.path.isfile(hub):
+        open(hub, "w").write("".join(l + "\n" for l in hub_edges_rows()))
+    make("hub_edges", hub, {"default": ["-a", "apc"], "d0.9": ["-a", "apc", "-d", "0.9"]})
     make("taxa8_big", os.path.join(GOLD, "clu_taxa8_big.orth"),
          {"default": ["-a", "apc"], "d0.95": ["-a", "apc", "-d", "0.95"], "b1000": ["-a", "apc", "-b", "1000"]})
 
