@@ -289,6 +289,35 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t *row, c
 void so_apc_free(so_apc_result *result);
 const char *so_apc_last_error(void);
 
+/* The component stage of `find_cluster -a mcl` on the device (csrc/cnc.hip).  Replaces: the first half of bin/find_cluster.py `cnc`
+ * (1470-1590) -- every gene linked to its best-scoring neighbours, the connected components of those links numbered (level 1), the
+ * components joined by a row whose two component numbers are non-zero merged and numbered (level 2), the rows inside one level-2
+ * group other than group 0 kept -- as swiftortho_amd/find_cluster.py `group_numbers()` restates it, number for number.
+ * Input: n_rows rows in file order (host arrays, borrowed): gene numbers x / y in 0 .. n_genes - 1, genes numbered by first
+ * appearance (x of a row before its y), so every gene occurs in some row; float64 weights z.  -0.0 ties with +0.0, +inf and -inf are
+ * ordinary weights.
+ * Output (allocated by the library, released with so_cnc_free()): comp1[n_genes] = the number of level-1 components whose largest gene
+ * exceeds that of the gene's own (component 0 holds gene n_genes - 1); grp[n_genes] = the rank, in file order, of the first row with
+ * two non-zero component numbers that touches the gene's level-2 component, -1 for the genes of component 0 and of components no such
+ * row touches; keep[n_rows] = 1 where grp[x] == grp[y] and that number is not 0.  n_comp1 / n_grp: level-1 components / level-2
+ * groups; n_keep: rows kept; sweeps1 / sweeps2: label sweeps of the two levels, the confirming one included (diagnostic: they may
+ * differ between two runs of one input, the arrays may not).  n_genes = 0 or n_rows = 0 is served and launches nothing (comp1 0,
+ * grp -1); so is level 2 of an input with a single level-1 component (sweeps2 = 0).
+ * Refused with a message (so_cnc_last_error), nothing launched and nothing left allocated: negative counts, n_genes or n_rows >= 2^31,
+ * a gene number outside 0 .. n_genes - 1, a gene without a row, a NaN weight (numpy's answer to it has no integer order: the caller
+ * keeps the host stage), no HIP device.  Labels that still move after nodes + 2 sweeps are an error, never a truncated answer.  No
+ * so_ctx: the call owns a stream of `device` and reads the SOHIT_* switches itself (SOHIT_POISON). */
+typedef struct so_cnc_result {
+    int64_t n_genes, n_rows, n_comp1, n_grp, n_keep;
+    int32_t sweeps1, sweeps2;
+    int64_t *comp1, *grp;
+    uint8_t *keep;        /* one byte per row */
+} so_cnc_result;
+int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t *x, const int32_t *y, const double *z,
+                  so_cnc_result *out);
+void so_cnc_free(so_cnc_result *result);
+const char *so_cnc_last_error(void);
+
 /* The candidate stage of find_orth on the device (csrc/orth.hip).  Replaces: the row loop of bin/find_orth.py -- coverage / identity
  * filter and -n normalisation (156-234), per query run the best hit per subject, the best score per subject taxon and out of the
  * query's taxon, the in-paralog / ortholog / co-ortholog candidates (298-348) and "a pair is a relation iff proposed exactly twice"

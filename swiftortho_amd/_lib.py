@@ -51,7 +51,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
-           "so_apc", "so_apc_free", "so_apc_last_error",
+           "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free"]
 
@@ -64,6 +64,12 @@ class SoMclResult(C.Structure):
 class SoApcResult(C.Structure):
     _fields_ = [("n_genes", C.c_int64), ("n_entries", C.c_int64), ("rounds", C.c_int32), ("labels", C.POINTER(C.c_int64)),
                 ("r", C.POINTER(C.c_float)), ("a", C.POINTER(C.c_float))]
+
+
+class SoCncResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_genes", "n_rows", "n_comp1", "n_grp", "n_keep")] + \
+               [("sweeps1", C.c_int32), ("sweeps2", C.c_int32), ("comp1", C.POINTER(C.c_int64)), ("grp", C.POINTER(C.c_int64)),
+                ("keep", C.POINTER(C.c_uint8))]
 
 
 class SoOrthCand(C.Structure):
@@ -182,6 +188,9 @@ def load():
     L.so_apc.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(SoApcResult)]
     L.so_apc_free.argtypes = [C.POINTER(SoApcResult)]
     L.so_apc_last_error.restype = cp
+    L.so_cnc_groups.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.POINTER(SoCncResult)]
+    L.so_cnc_free.argtypes = [C.POINTER(SoCncResult)]
+    L.so_cnc_last_error.restype = cp
     L.so_orth_candidates_cols.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int, C.POINTER(SoOrthCand)]
     L.so_orth_candidates_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, C.c_double, C.c_double, C.c_int, C.POINTER(SoOrthCand)]
     L.so_orth_free.argtypes = [C.POINTER(SoOrthCand)]

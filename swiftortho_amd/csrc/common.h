@@ -37,7 +37,7 @@ struct DevOom : SoError {
     } while (0)
 
 extern thread_local int g_poison;   // Tune::poison of the context whose call runs on this thread (-1: none)
-// ... for the duration of a call that has no context (so_mcl, so_apc)
+// ... for the duration of a call that has no context (so_mcl, so_apc, so_cnc_groups)
 struct PoisonScope {
     int before;
     explicit PoisonScope(int v) : before(g_poison) { g_poison = v; }

@@ -1,6 +1,6 @@
 // tune.h -- every SOHIT_* switch of libsohit.so in ONE table.  The environment is read ONCE, by so_create (Tune::read), into the
 // context's Tune; the launch helpers in the k_*.hip files read the current context's copy through tune() -- no getenv() anywhere else.
-// (so_mcl and so_apc run without a context: each call reads the table into a Tune of its own at entry.)
+// (so_mcl, so_apc and so_cnc_groups run without a context: each call reads the table into a Tune of its own at entry.)
 // None of the switches changes results, except the two ablation variants marked so.  tools/diag/README.md lists what they are for.
 #pragma once
 #include <cstdlib>

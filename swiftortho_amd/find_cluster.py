@@ -6,7 +6,9 @@ Last stage of BASELINE config 5 (find_hit -> find_orth -> find_cluster -a mcl -I
 "next" row.  The Markov-cluster iteration -- the one data-parallel part of this stage: column normalisation,
 sparse x sparse expansion, inflation, pruning on float32 CSR matrices -- runs on the GPU (libsohit `so_mcl`,
 csrc/mcl.hip) with scipy's arithmetic order, because the pruning decisions, and therefore the groups, depend
-on it; the graph bookkeeping around it (best-neighbour components, batching, the read-out) is host code.
+on it; the graph bookkeeping around it (best-neighbour components, batching, the read-out) is host code.  With `-G T`
+(`cnc(device_stage=True)`) the first half of that bookkeeping -- best-neighbour components, level-2 groups, the rows to keep --
+runs on the GPU too (libsohit `so_cnc_groups`, csrc/cnc.hip), pinned number for number to `group_numbers()`; default off, same output.
 So does the affinity-propagation loop of `-a apc` (libsohit `so_apc`, csrc/apc.hip), with the reference's own
 arithmetic order.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
 `-a apc` has to be named on the command line: a command without `-a` is still refused (exit code 2), as are `-a sap`
@@ -52,7 +54,7 @@ import sys
 
 import numpy as np
 
-DEFAULTS = {'-i': '', '-d': '0.5', '-p': '-10000', '-I': '1.5', '-a': 'apc', '-t': '2', '-b': '25000000'}
+DEFAULTS = {'-i': '', '-d': '0.5', '-p': '-10000', '-I': '1.5', '-a': 'apc', '-t': '2', '-b': '25000000', '-G': 'F'}
 
 
 def manual_print(prog='find_cluster.py'):
@@ -66,6 +68,7 @@ def manual_print(prog='find_cluster.py'):
     print('  -a: algorithm (mcl or apc)')
     print('  -t: cpu number')
     print('  -b: batch size for apc (above 0; no effect on the result)')
+    print('  -G: component stage of mcl on the GPU [T|F]. Default: F (same output; no effect with -a apc)')
 
 
 class _Graph:
@@ -401,29 +404,13 @@ def _edge_columns(lines):
     return [g.decode('utf-8') for g in names.tolist()], inv[:len(rows)], inv[len(rows):], z, (lambda i: zs[i].encode('utf-8'))
 
 
-def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl):
-    """cnc (1470-1673): relation rows -> groups (lists of gene ids), in the reference's output order.  `lines`: an open file, bytes or an
-    iterable of lines.  `mcl`: the Markov loop on a CSR block (the device implementation; the tests pass the scipy oracle to check this host
-    bookkeeping on CPU).
-    The reference keeps Python dictionaries and networkx graphs and moves the edges between its stages as sorted text files; here the
-    rows are columns from the start (ids coded by their byte order, which is also the order `sort` compares them in), genes are integers
-    numbered by first appearance (the insertion order of the reference's best-neighbour dictionary), and each of its orders --
-    `popitem()` = last gene first, a graph's node order = first appearance in the `add_edge` sequence, components numbered by their
-    first node, `LC_ALL=C sort -n` of the group-tagged edge lines -- is reproduced as index arithmetic."""
-    names, cx, cy, Z, ztext = _edge_columns(lines)
-    nrow = len(cx)
-    if nrow == 0:
-        return []
-    # genes numbered by first appearance (x of a row before its y)
-    seq = np.empty(2 * nrow, dtype=np.int64)
-    seq[0::2], seq[1::2] = cx, cy
-    vals, first = np.unique(seq, return_index=True)
-    order = np.argsort(first, kind='stable')
-    number_of_code = np.zeros(len(names), dtype=np.int64)
-    number_of_code[vals[order]] = np.arange(len(vals))
-    X, Y = number_of_code[cx], number_of_code[cy]
-    gene_names = [names[c] for c in vals[order].tolist()]
-    n = len(vals)
+def group_numbers(X, Y, Z, n):
+    """The component stage of cnc (1470-1590) -- the DEFINITION the device stage (so_cnc_groups, csrc/cnc.hip) is pinned to.  X, Y: gene
+    numbers of the rows with x <= y in file order, genes numbered 0 .. n-1 by first appearance (x of a row before its y), Z: their float64
+    weights.  -> (comp1, grp), int64[n]: a gene's level-1 component number and its level-2 group number (-1: in no level-2 group)."""
+    nrow = len(X)
+    if nrow == 0:                                         # (cnc never gets here without a row)
+        return np.zeros(n, dtype=np.int64), np.full(n, -1, dtype=np.int64)
     # level 1: every gene linked to its best-scoring neighbour(s); the dictionary is emptied last gene first, a gene's ties in file order
     best = np.full(n, -np.inf)
     np.maximum.at(best, X, Z)
@@ -449,9 +436,81 @@ def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl):
     group_of_comp = np.full(nc, -1, dtype=np.int64)
     group_of_comp[nodes2] = comp2_of_node
     grp = group_of_comp[comp1]
+    return comp1, grp
+
+
+def device_group_numbers(X, Y, Z, n, device=0, info=None):
+    """group_numbers on the GPU (libsohit so_cnc_groups, csrc/cnc.hip) -> (comp1 int64[n], grp int64[n], keep bool[rows]); keep[i] =
+    grp[X[i]] == grp[Y[i]] != 0, the rows cnc hands on.  `info`: a dict that receives n_comp1, n_grp, n_keep, sweeps1 and sweeps2 (the
+    label sweeps of the two levels, the confirming one included).  A NaN weight, a gene number outside 0 .. n-1 and a gene without a
+    row are refused.  No CPU path: raises when the HIP library or a device is missing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoCncResult()
+    xi = np.ascontiguousarray(X, dtype=np.int64)
+    yi = np.ascontiguousarray(Y, dtype=np.int64)
+    zv = np.ascontiguousarray(Z, dtype=np.float64)
+    if not (len(xi) == len(yi) == len(zv)):
+        raise ValueError('device_group_numbers: X, Y and Z differ in length')
+    for v in (xi, yi):
+        if len(v) and (int(v.min()) < -2 ** 31 or int(v.max()) >= 2 ** 31):
+            raise RuntimeError('so_cnc_groups: a gene number does not fit 32 bits')
+    xi, yi = xi.astype(np.int32), yi.astype(np.int32)
+    nr = len(xi)
+    rc = L.so_cnc_groups(device, int(n), nr, xi.ctypes.data if nr else None, yi.ctypes.data if nr else None, zv.ctypes.data if nr else None, C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_cnc_last_error().decode())
+    try:
+        d = int(res.n_genes)
+        if isinstance(info, dict):
+            info.update(n_comp1=int(res.n_comp1), n_grp=int(res.n_grp), n_keep=int(res.n_keep), sweeps1=int(res.sweeps1), sweeps2=int(res.sweeps2))
+        comp1 = np.ctypeslib.as_array(res.comp1, shape=(max(d, 1),))[:d].copy()
+        grp = np.ctypeslib.as_array(res.grp, shape=(max(d, 1),))[:d].copy()
+        keep = np.ctypeslib.as_array(res.keep, shape=(max(nr, 1),))[:nr].astype(bool)
+    finally:
+        L.so_cnc_free(C.byref(res))
+    return comp1, grp, keep
+
+
+def _device_stage(X, Y, Z, n):
+    """cnc's component stage with `device_stage=True`: a NaN weight has no place in the device's integer order, and numpy's answer to
+    it is what the bytes hang on: such an input keeps the numpy stage"""
+    if np.isnan(Z).any():
+        return group_numbers(X, Y, Z, n)
+    return device_group_numbers(X, Y, Z, n)
+
+
+def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_stage=False):
+    """cnc (1470-1673): relation rows -> groups (lists of gene ids), in the reference's output order.  `lines`: an open file, bytes or an
+    iterable of lines.  `mcl`: the Markov loop on a CSR block (the device implementation; the tests pass the scipy oracle to check this host
+    bookkeeping on CPU).  `groups`: the component stage, (X, Y, Z, n) -> (comp1, grp) or (comp1, grp, keep flag per row): group_numbers by
+    default, the device stage (device_group_numbers; the numpy one when a weight is NaN) with `device_stage=True`.
+    The reference keeps Python dictionaries and networkx graphs and moves the edges between its stages as sorted text files; here the
+    rows are columns from the start (ids coded by their byte order, which is also the order `sort` compares them in), genes are integers
+    numbered by first appearance (the insertion order of the reference's best-neighbour dictionary), and each of its orders --
+    `popitem()` = last gene first, a graph's node order = first appearance in the `add_edge` sequence, components numbered by their
+    first node, `LC_ALL=C sort -n` of the group-tagged edge lines -- is reproduced as index arithmetic."""
+    names, cx, cy, Z, ztext = _edge_columns(lines)
+    nrow = len(cx)
+    if nrow == 0:
+        return []
+    # genes numbered by first appearance (x of a row before its y)
+    seq = np.empty(2 * nrow, dtype=np.int64)
+    seq[0::2], seq[1::2] = cx, cy
+    vals, first = np.unique(seq, return_index=True)
+    order = np.argsort(first, kind='stable')
+    number_of_code = np.zeros(len(names), dtype=np.int64)
+    number_of_code[vals[order]] = np.arange(len(vals))
+    X, Y = number_of_code[cx], number_of_code[cy]
+    gene_names = [names[c] for c in vals[order].tolist()]
+    n = len(vals)
+    stage = groups if groups is not None else (_device_stage if device_stage else group_numbers)
+    res = stage(X, Y, Z, n)
+    grp = res[1]
     # edges inside one level-2 group whose number is non-zero (-1, the pool of unmerged components, included)
     gx, gy = grp[X], grp[Y]
-    keep = np.flatnonzero((gx != 0) & (gy != 0) & (gx == gy))
+    keep = np.flatnonzero(res[2]) if len(res) > 2 else np.flatnonzero((gx != 0) & (gy != 0) & (gx == gy))
     if len(keep) == 0:
         return []
     # LC_ALL=C sort -n of the lines 'group\tx\ty\tweight': the leading number, then the whole line bytewise = (x, y, weight text)
@@ -615,7 +674,8 @@ def main(argv=None):
     if alg == 'apc' and named and bch > 0:
         run, warm_up = (lambda f: apc(f, dmp)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
     elif alg == 'mcl':
-        run = lambda f: cnc(f, ifl)
+        gpu = str(args['-G']).upper()[:1] == 'T'
+        run = lambda f: cnc(f, ifl, device_stage=gpu)
         warm_up = lambda: device_mcl(np.array([0, 1]), np.array([0]), np.array([1.], dtype=np.float32), ifl, rounds=1)
     else:
         if not named:
