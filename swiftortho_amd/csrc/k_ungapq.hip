@@ -7,9 +7,17 @@
 // (subject, diagonal): they need no order at all, only the knowledge that they ARE alone.  This kernel finds that out without a sort:
 //
 //   * a wave takes a query (work counter), puts its score classes into an LDS slot (k_ungap1's, sentinel-bounded) and walks the query's
-//     seeds TWICE, 64 seeds at a time, every lane the entries of its own seed: pass 1 marks  hash(G)  of every hit's banded diagonal id
-//     G = addend + qpos  in a table of 4096 two-bit counters (seen once / seen again), pass 2 regenerates the hits (the entries are in
-//     L1 / L2 by then) and looks them up: "seen once" is PROOF that no other hit of this query shares the diagonal;
+//     hits TWICE, 64 hit ordinals at a time, in tiles of 256: pass 1 marks  hash(G)  of every hit's banded diagonal id
+//     G = addend + qpos  in a table of 4096 two-bit counters (seen once / seen again), pass 2 looks every hit up there: "seen once" is
+//     PROOF that no other hit of this query shares the diagonal;
+//   * an index entry is read ONCE: pass 1 has the (up to four) index loads of a tile in flight together -- owners first, then the loads,
+//     then the counters: one trip to memory per tile -- and keeps the entry and the query position of the first UQ_CACHE ordinals of the
+//     query in registers (16 + 8 of them); pass 2 takes those from there, without seed marks and without a load.  Only the ordinals
+//     beyond the cache are regenerated as in pass 1 (seed marks of the tile, index load: L1 / L2 by then).  SOHIT_UQ_CACHE moves that
+//     boundary (0: every entry read twice), it changes no result;
+//   * pass 2 is one step AHEAD of the ring: when a refill turn has put a step's singletons into the ring it classifies the next step and
+//     asks for its singletons' subject offsets (roff); that trip runs beside the extension steps that follow, and the next turn finds
+//     the offsets there;
 //   * such a hit goes straight into k_ungap1's ring and is extended by the next free lane with k_ungap1's step (both passes at once in the
 //     two 16-bit halves, 16 residues per step, lane-private score table) -- no key is written, sorted or read for it;
 //   * every other hit (the diagonals with two and more hits, plus the few singletons that share a counter with another diagonal) is written
@@ -26,6 +34,9 @@
 // per wave: query slot, counters, ring (subject byte, diagonal id, query position)
 #define UQ_TILE 256                       // hit ordinals per tile of the owner marks (mark, slot base, query position: 8 bytes per ordinal)
 #define UQ_WAVE_BYTES (UQ_QSLOT + (1 << UQ_TBITS) / 4 + UQ_RING * 4 + UQ_RING * 4 + UQ_RING * 2 + UQ_TILE * 8)
+#define UQ_CACHE 1024                     // hit ordinals per query whose index entry and query position stay in registers between the two walks
+#define UQ_CSTEPS (UQ_CACHE / 64)         // ... as 64-ordinal steps: one register per step for the entries, one per two steps for the positions
+static_assert(UQ_CACHE % UQ_TILE == 0 && UQ_CACHE > 0, "whole tiles");
 
 __device__ __forceinline__ u32 bk_scan_max16(u32 x) {  // inclusive max-scan over the wave (DPP)
     x = max(x, (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true));
@@ -36,6 +47,10 @@ __device__ __forceinline__ u32 bk_scan_max16(u32 x) {  // inclusive max-scan ove
     x = max(x, (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false));
     return x;
 }
+
+// the cache: vectors, not arrays -- an element at a wave-uniform index is an indexed register move, where an array would go to scratch
+typedef u32 uq_vc __attribute__((ext_vector_type(UQ_CSTEPS)));
+typedef u32 uq_vq __attribute__((ext_vector_type(UQ_CSTEPS / 2)));
 
 __device__ __forceinline__ u32 uq_slot(u32 g) { return (g * 2654435761u) >> (32 - UQ_TBITS); }
 
@@ -57,7 +72,7 @@ template <bool BANDS, bool COUNT>
 __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96))) void k_ungapq(
     const u32* __restrict__ qseg /*first hit ordinal of every pass query, + end*/, u32 nqp, u32 qa, const u32* __restrict__ qk, const u32* __restrict__ cs_hoff,
     const u32* __restrict__ cs_base, const u64* __restrict__ cs_kbase, const u32* __restrict__ dk32, int bp, int bd, int sh_q, int sh_qpos, int sh_diag, int diag_off, int rbs,
-    int rsh_subj, int rsh_diag, int rdoff, const uint2* __restrict__ btab, u32 wait_n, const u8* __restrict__ q_scls, const u32* __restrict__ qoff,
+    int rsh_subj, int rsh_diag, int rdoff, const uint2* __restrict__ btab, u32 wait_n, u32 csteps /*steps of 64 ordinals kept in registers, <= UQ_CSTEPS*/, const u8* __restrict__ q_scls, const u32* __restrict__ qoff,
     const u8* __restrict__ r_ug, const u32* __restrict__ roff, const signed char* __restrict__ b62g, u32* __restrict__ work_ctr, u32* __restrict__ shard_cnt,
     u64* __restrict__ p_qs, u64* __restrict__ p_sd, u64* __restrict__ p_ft, unsigned long long* __restrict__ group_count, u64* __restrict__ keys,
     u64* __restrict__ keys_sorted, u32* __restrict__ seg_end, unsigned long long* __restrict__ stat /*COUNT: [0] += b62 lookups, [1] += groups*/) {
@@ -159,27 +174,53 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
             }
             u1_wave_sync();
         };
-        // one step: the ordinals tb + 64 st + lane -> (valid, addend, query position, ordinal); ONE trip to memory per step (the index entry)
-        auto gen_step = [&](u32 tb, u32 st, u32& c, u32& qpos, u32& o) -> bool {
-            o = tb + 64u * st + (u32)lane;
+        // the owner of every ordinal of step st of the marked tile: its slot base and query position (no trip to memory); carries the owner on
+        auto owner = [&](u32 st, u32& base, u32& qpos) {
             const u32 p1 = bk_scan_max16((u32)marks[64u * st + (u32)lane]);   // first ordinal (+ 1) of the owner inside this step's part of the tile, 0: before it
-            u32 base = c_base;
+            base = c_base;
             qpos = c_qpos;
             if (p1) base = mbase[p1 - 1u], qpos = (u32)mqpos[p1 - 1u];
             c_base = (u32)__builtin_amdgcn_readlane((int)base, 63), c_qpos = (u32)__builtin_amdgcn_readlane((int)qpos, 63);
-            c = 0xFFFFFFFFu;
-            if (o >= n) return false;
-            c = dk32[base + o];
-            return (int)c >= 0;
         };
-        // ---- pass 1: the two-bit counters ----
+        // one step: the ordinals tb + 64 st + lane -> (index entry, query position); ONE trip to memory per step (the index entry), not waited
+        // for here.  An entry with the top bit set is no hit (so is a lane beyond the query's last ordinal).
+        auto gen_step = [&](u32 tb, u32 st, u32& c, u32& qpos) {
+            const u32 o = tb + 64u * st + (u32)lane;
+            u32 base;
+            owner(st, base, qpos);
+            c = 0xFFFFFFFFu;
+            if (o < n) c = dk32[base + o];
+        };
+        // ---- pass 1: the two-bit counters; the entries and positions of the first csteps steps stay in cc / cq ----
+        uq_vc cc = 0xFFFFFFFFu;
+        uq_vq cq = 0;   // (step 2 i in the low half of element i, step 2 i + 1 in the high half)
+        const u32 nsteps = (n + 63u) / 64u;
+        const u32 ncs = min(csteps, nsteps);            // steps pass 2 takes from the registers
+        const u32 rg_tb = (csteps * 64u) & ~(u32)(UQ_TILE - 1);   // tile in which pass 2 starts to regenerate (when nsteps > csteps) ...
+        u32 rg_tnext = k0, rg_base = 0, rg_qpos = 0;    // ... and the walk's state in front of that tile
         for (u32 tb = 0; tb < n; tb += UQ_TILE) {
+            if (tb == rg_tb) rg_tnext = t_next, rg_base = c_base, rg_qpos = c_qpos;
             tile_marks(tb);
             const u32 nst = (min(n - tb, (u32)UQ_TILE) + 63u) / 64u;
-            for (u32 st = 0; st < nst; ++st) {
-                u32 c, qpos, o;
-                if (gen_step(tb, st, c, qpos, o)) {
-                    const u32 t = uq_slot(c + qpos), sh = (t & 15u) * 2u;
+            // the tile's (up to) four steps: all owners, then all index loads in flight together, then the counters: one trip per tile
+            u32 c4[4], q4[4];
+#pragma unroll
+            for (u32 st = 0; st < 4; ++st) {
+                c4[st] = 0xFFFFFFFFu, q4[st] = 0;
+                if (st < nst) gen_step(tb, st, c4[st], q4[st]);
+            }
+#pragma unroll
+            for (u32 t = 0; t < UQ_CSTEPS / 4; ++t) {   // (steps at and beyond csteps are kept too and never read)
+                if (tb == t * UQ_TILE) {
+#pragma unroll
+                    for (u32 st = 0; st < 4; ++st) cc[4 * t + st] = c4[st];
+                    cq[2 * t] = q4[0] | (q4[1] << 16), cq[2 * t + 1] = q4[2] | (q4[3] << 16);
+                }
+            }
+#pragma unroll
+            for (u32 st = 0; st < 4; ++st) {
+                if ((int)c4[st] >= 0) {
+                    const u32 t = uq_slot(c4[st] + q4[st]), sh = (t & 15u) * 2u;
                     const u32 old = atomicOr(&tab[t >> 4], 1u << sh);
                     if ((old >> sh) & 1u) atomicOr(&tab[t >> 4], 2u << sh);
                 }
@@ -209,9 +250,52 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
             }
             npb = 0;
         };
-        t_next = k0, c_base = 0, c_qpos = 0;
-        u32 g_tb = 0, g_st = 0, g_nst = (min(n, (u32)UQ_TILE) + 63u) / 64u;
-        tile_marks(0);
+        // Step gs made ready for the ring one refill turn ahead: its hits from the registers (gs < ncs) or regenerated as in pass 1 (beyond the
+        // cache: tile marks + index load), looked up in the counters, and the subject offsets of the singletons ASKED FOR -- the turn that
+        // takes the step finds them there, the trip having run beside the extension steps in between.
+        u32 p_c = 0xFFFFFFFFu, p_qpos = 0, p_ro = 0, p_ad = 0;   // (p_ro: the subject's offset as loaded -- added up only by the turn that takes it)
+        bool p_sing = false;
+        auto prepare = [&](u32 gs) {
+            u32 c, qpos;
+            if (gs < ncs) {
+                c = cc[gs];
+                const u32 w2 = cq[gs >> 1];
+                qpos = (gs & 1u) ? (w2 >> 16) : (w2 & 0xFFFFu);
+            } else {
+                const u32 st = gs & 3u, tb = (gs >> 2) * (u32)UQ_TILE;
+                if (st == 0 || gs == ncs) {
+                    if (gs == ncs) t_next = rg_tnext, c_base = rg_base, c_qpos = rg_qpos;   // (ncs == csteps here: rg_tb is this tile)
+                    tile_marks(tb);
+                    for (u32 s0 = 0; s0 < st; ++s0) {   // the tile's steps that came from the registers: their owners carried on
+                        u32 b_, q_;
+                        owner(s0, b_, q_);
+                    }
+                }
+                gen_step(tb, st, c, qpos);
+            }
+            bool sing = false;
+            u32 ro = 0, ad = 0;
+            if ((int)c >= 0) {
+                const u32 G = c + qpos, t = uq_slot(G);
+                sing = ((tab[t >> 4] >> ((t & 15u) * 2u)) & 3u) == 1u;
+                if (sing) {
+                    u32 gsubj;
+                    int dlt;
+                    if (BANDS) {
+                        const uint2 be = btab[G >> bd];
+                        gsubj = be.x;
+                        dlt = (int)(be.y - G);   // sst - qpos
+                    } else {
+                        gsubj = G >> bd;
+                        dlt = diag_off - (int)(G & dmask);
+                    }
+                    ro = roff[gsubj], ad = (u32)((int)qpos + dlt);   // ro + ad: byte of (subject, sst) in r_ug
+                }
+            }
+            p_c = c, p_qpos = qpos, p_ro = ro, p_ad = ad, p_sing = sing;
+        };
+        u32 g_s = 0;        // the prepared step
+        prepare(0);
         bool more = true;   // the generator has hits left
         u32 ns = 0;         // hits left to the sorted path so far (they sit at the front of the query's part of the key array)
         u32 rfront = 0, rback = 0;
@@ -226,44 +310,23 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
             if (idleb && ((u32)__popcll(idleb) >= wait_n || idleb == ~0ull)) {
                 // ---- refill the ring: 64 hit ordinals per turn ----
                 while (rback - rfront <= UQ_RING - 64u && more) {
-                    u32 c, qpos, o;
-                    const bool valid = gen_step(g_tb, g_st, c, qpos, o);
-                    bool sing = false;
-                    u32 G = 0;
-                    if (valid) {
-                        G = c + qpos;
-                        const u32 t = uq_slot(G);
-                        sing = ((tab[t >> 4] >> ((t & 15u) * 2u)) & 3u) == 1u;
-                    }
+                    const u32 c = p_c, qpos = p_qpos, G = c + qpos;
+                    const bool valid = (int)c >= 0, sing = p_sing;
                     const unsigned long long sb_ = __ballot(sing), kb_ = __ballot(valid && !sing);
-                    if (valid && !sing) keys[h0 + ns + (u32)__popcll(kb_ & lt)] = kq + ((u64)qpos << sh_diag) + ((u64)qpos << sh_qpos) + ((u64)c << sh_diag);   // k_lookup's key
-                    ns += (u32)__popcll(kb_);
                     if (sing) {
-                        u32 gsubj;
-                        int dlt;
-                        if (BANDS) {
-                            const uint2 be = btab[G >> bd];
-                            gsubj = be.x;
-                            dlt = (int)(be.y - G);   // sst - qpos
-                        } else {
-                            gsubj = G >> bd;
-                            dlt = diag_off - (int)(G & dmask);
-                        }
                         const u32 slot = (rback + (u32)__popcll(sb_ & lt)) & (UQ_RING - 1);
-                        ring_s[slot] = roff[gsubj] + (u32)((int)qpos + dlt);   // byte of (subject, sst) in r_ug
+                        ring_s[slot] = p_ro + p_ad;
                         ring_g[slot] = G;
                         ring_q[slot] = (u16)qpos;
                     }
                     rback += (u32)__popcll(sb_);
-                    if (++g_st >= g_nst) {
-                        g_st = 0, g_tb += UQ_TILE;
-                        if (g_tb < n) {
-                            g_nst = (min(n - g_tb, (u32)UQ_TILE) + 63u) / 64u;
-                            tile_marks(g_tb);
-                        } else {
-                            more = false;
-                        }
-                    }
+                    // The next step is made ready between this step's ring entries and its keys: after the entries, so that the offsets asked
+                    // for land in the registers this step has just emptied (no copy that would have to wait for them); before the keys, so
+                    // that what it waits for itself (index entries beyond the cache) is not queued behind the key stores.
+                    if (++g_s < nsteps) prepare(g_s);
+                    else more = false;
+                    if (valid && !sing) keys[h0 + ns + (u32)__popcll(kb_ & lt)] = kq + ((u64)qpos << sh_diag) + ((u64)qpos << sh_qpos) + ((u64)c << sh_diag);   // k_lookup's key
+                    ns += (u32)__popcll(kb_);
                 }
                 u1_wave_sync();
                 // ---- hand out ----
@@ -352,9 +415,11 @@ void launch_ungapq(u32 ncu, const u32* qseg, u32 nqp, u32 qa, u32* qk, const u32
     hipLaunchKernelGGL(k_uq_first, dim3((nqp + 1 + 255) / 256), dim3(256), 0, st, qseg, nqp, cs_hoff, K, qk);
     static_assert(((size_t)U1_ROWS << 11) + (size_t)UQ_WAVES * UQ_WAVE_BYTES <= 160 * 1024, "LDS of a CU");
     const dim3 g(std::min<u32>(ncu, (nqp + UQ_WAVES - 1) / UQ_WAVES)), bl(64 * UQ_WAVES);
+    const long long uqc = tune().uq_cache;
+    const u32 csteps = uqc < 0 ? (u32)UQ_CSTEPS : (u32)std::min<long long>(uqc / 64, UQ_CSTEPS);
 #define UQ_GO(B, CT)                                                                                                                                              \
     hipLaunchKernelGGL((k_ungapq<B, CT>), g, bl, 0, st, qseg, nqp, qa, qk, cs_hoff, cs_base, cs_kbase, dk32, kl.bp, kl.bd, kl.sh_q, kl.sh_qpos, kl.sh_diag, (int)kl.diag_off, klr.bs,  \
-                       klr.sh_subj, klr.sh_diag, (int)klr.diag_off, (const uint2*)btab, U1_WAIT, q_scls, qoff, r_ug, roff, b62g, work_ctr, shard_cnt, p_qs, p_sd, p_ft,      \
+                       klr.sh_subj, klr.sh_diag, (int)klr.diag_off, (const uint2*)btab, U1_WAIT, csteps, q_scls, qoff, r_ug, roff, b62g, work_ctr, shard_cnt, p_qs, p_sd, p_ft,      \
                        group_count, keys, keys_sorted, seg_end, stat)
     if (stat) {
         if (btab) UQ_GO(true, true);
