@@ -267,6 +267,48 @@ int so_mcl(int device, int64_t n, const int64_t *indptr, const int32_t *indices,
 void so_mcl_free(so_mcl_result *result);
 const char *so_mcl_last_error(void);
 
+/* One batch of `find_cluster -a mcl` from its rows to its surviving pairs on the device (csrc/mcl.hip): the matrix never exists on the
+ * host.  Replaces: the matrix `mcl_xyz` of bin/find_cluster.py (1425-1467) builds for a batch, as swiftortho_amd/find_cluster.py
+ * `block_matrix_arrays()` restates it bit for bit, the upload, the loop of so_mcl, the download of the final matrix and the read-out
+ * of `mcl` (686-689) as `surviving_pair_columns()` restates it, shifted pairing included.
+ * Input: n_rows rows in batch order (host arrays, borrowed): gene labels gx / gy in 0 .. n_labels - 1 (any labelling; labels may be
+ * unused), float64 weights z; the loop's parameters as so_mcl takes them (max_rounds = 0 skips the loop); flags & 1: the assembled matrix
+ * comes back too.
+ * Assembly: genes numbered by first appearance in x0, y0, x1, y1, ...; a (n_genes + 1)^2 matrix with an empty last row; weights rounded
+ * to float32 once (nearest even, overflow = +-inf, denormals kept); per ordered pair the LAST row wins, (x, y) and (y, x) both stored;
+ * the diagonal of a gene = the largest positive weight of any of its rows, overwritten repeats included, stored only where it is above
+ * 0 (a denormal is, -0.0 is not); zeros of either sign are not stored; canonical CSR, columns ascending.
+ * Read-out: the k-th non-zero entry in storage order gives the k-th coordinate, kept when the k-th RAW stored value exceeds
+ * (float)prune; a NaN is non-zero and exceeds nothing, -0.0 is a zero.
+ * Output (allocated by the library, released with so_mcl_rows_free()): gene[n_genes] = the label of matrix row k; rounds / converged
+ * as so_mcl reports them; pair_r / pair_c[n_pairs] in read-out order; with flags & 1 the matrix as it entered the loop: indptr[n_genes + 2],
+ * indices / data[nnz].  n_rows = 0 is served without a launch (no gene, no round, no pair, indptr = {0, 0}).
+ * Refused with a message (so_mcl_last_error), nothing further launched and nothing left allocated: negative counts, n_labels or n_rows
+ * >= 2^31, a label outside 0 .. n_labels - 1, a NaN weight, a row with x == y (the reference overwrites the diagonal in line order: the
+ * host's sequential builder is the only implementation), no HIP device -- all before a device is touched -- and, found on the device
+ * as equal neighbours of the sorted entries, a batch in which both (a, b) and (b, a) occur (numpy stores the coordinate twice); a
+ * matrix of more than 2^31 - 16 entries.  No so_ctx: the call owns a stream of `device` and reads the SOHIT_* switches itself
+ * (SOHIT_POISON, SOHIT_MCL_SCRATCH).
+ * so_mcl_readout: the read-out kernels alone on an n x n host CSR (borrowed; stored zeros and any column order allowed) -> n_pairs,
+ * pair_r, pair_c of the same structure, everything else 0.  Refused: n < 0, row pointers that do not start at 0 or that fall, more
+ * than 2^31 - 16 entries, no HIP device. */
+typedef struct so_mcl_rows_result {
+    int64_t n_genes, n_pairs, nnz;
+    int32_t rounds;    /* rounds executed                                  */
+    int32_t converged; /* 1 = left the loop through the convergence test   */
+    int64_t *gene;     /* n_genes                                          */
+    int64_t *pair_r;   /* n_pairs                                          */
+    int64_t *pair_c;
+    int64_t *indptr;   /* flags & 1: n_genes + 2, else NULL                */
+    int32_t *indices;  /* flags & 1: nnz                                   */
+    float *data;       /* flags & 1: nnz                                   */
+} so_mcl_rows_result;
+int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t *gx, const int64_t *gy, const double *z, double inflation,
+                int32_t max_rounds, int32_t check_every, double prune, double rtol, double atol, int32_t flags, so_mcl_rows_result *out);
+int so_mcl_readout(int device, int64_t n, const int64_t *indptr, const int32_t *indices, const float *data, double prune,
+                   so_mcl_rows_result *out_pairs);
+void so_mcl_rows_free(so_mcl_rows_result *result);
+
 /* Affinity propagation on the edge list of the orthology graph.  Replaces: the loop of bin/find_cluster.py `apclust_blk` (404-513)
  * with its passes `max_row`, `update_R`, `sum_col`, `update_A`, `get_change` (309-401), which `main` runs for `-a apc` with a batch
  * size above zero -- in the reference's arithmetic order (csrc/apc.hip): float64 operations on float32-stored R and A, row maxima

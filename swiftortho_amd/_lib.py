@@ -53,12 +53,18 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
-           "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free"]
+           "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free"]
 
 
 class SoMclResult(C.Structure):
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("rounds", C.c_int32), ("converged", C.c_int32), ("indptr", C.POINTER(C.c_int64)),
                 ("indices", C.POINTER(C.c_int32)), ("data", C.POINTER(C.c_float))]
+
+
+class SoMclRowsResult(C.Structure):
+    _fields_ = [("n_genes", C.c_int64), ("n_pairs", C.c_int64), ("nnz", C.c_int64), ("rounds", C.c_int32), ("converged", C.c_int32),
+                ("gene", C.POINTER(C.c_int64)), ("pair_r", C.POINTER(C.c_int64)), ("pair_c", C.POINTER(C.c_int64)),
+                ("indptr", C.POINTER(C.c_int64)), ("indices", C.POINTER(C.c_int32)), ("data", C.POINTER(C.c_float))]
 
 
 class SoApcResult(C.Structure):
@@ -185,6 +191,9 @@ def load():
     L.so_mcl.argtypes = [C.c_int, i64, vp, vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(SoMclResult)]
     L.so_mcl_free.argtypes = [C.POINTER(SoMclResult)]
     L.so_mcl_last_error.restype = cp
+    L.so_mcl_rows.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.POINTER(SoMclRowsResult)]
+    L.so_mcl_readout.argtypes = [C.c_int, i64, vp, vp, vp, C.c_double, C.POINTER(SoMclRowsResult)]
+    L.so_mcl_rows_free.argtypes = [C.POINTER(SoMclRowsResult)]
     L.so_apc.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(SoApcResult)]
     L.so_apc_free.argtypes = [C.POINTER(SoApcResult)]
     L.so_apc_last_error.restype = cp

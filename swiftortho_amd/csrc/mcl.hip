@@ -20,6 +20,8 @@
 //   * pruning keeps the entry and stores 0 (the reference assigns into .data), so the matrix structure -- which the reference's
 //     final read-out zips against -- is scipy's.
 // Product code behind the C ABI (so_mcl); the scipy loop survives only in tests/ as the oracle.
+// so_mcl_rows runs the same rounds on a matrix it assembles on the device from a batch's rows, and reads the result out there
+// (k_rows_*, k_ro_* below); so_mcl_readout is that read-out alone.
 #include "common.h"
 #include "kernels.h"
 #include "../../include/sohit.h"
@@ -477,6 +479,285 @@ void copy_csr(const Csr& a, Csr& b, hipStream_t st) {
     }
 }
 
+// ---- a batch's matrix from its rows, and the read-out, on the device (so_mcl_rows, so_mcl_readout) ------------------------------
+// find_cluster.py `block_matrix_arrays` and `surviving_pair_columns` are the definitions, bit for bit.  Assembly: genes numbered by
+// first appearance in x0, y0, x1, y1, ... (atomicMin of the position per label, flag the positions that are a first appearance, scan);
+// weights rounded to float32 once; per ordered pair (X, Y) the LAST line wins (stable radix sort of X << 32 | Y with the line index as
+// payload: the winner is the last of its run); the diagonal = the largest positive weight of ANY line at the gene (atomicMax on the bit
+// patterns: positive floats, denormals and +inf included, order like their patterns); zeros of either sign are not stored; a second
+// radix sort of row << 32 | column with the value bits as payload gives canonical CSR, and equal neighbours there mean that both
+// (a, b) and (b, a) were rows (refused: numpy emits the coordinate twice).  Read-out: flag the non-zero entries, scan, compact their
+// coordinates; then flag the first M RAW values above the threshold, scan, compact.  Every comparison of values is one of bit
+// patterns, so nothing hangs on the kernels' denormal mode.  All stores are vector stores, all atomics integer min / max.
+#define ROWS_NONE 0xFFFFFFFFu
+
+// float64 -> float32, round to nearest even, in integer arithmetic (numpy's astype on the host: overflow -> +-inf, results below the
+// normal range are denormals, below half the smallest of them zero)
+__host__ __device__ inline u32 f64_to_f32_bits(u64 b) {
+    const u32 sign = (u32)(b >> 63) << 31;
+    const int e = (int)((b >> 52) & 0x7FF);
+    const u64 m = b & 0xFFFFFFFFFFFFFull;
+    if (e == 0x7FF) return sign | 0x7F800000u | (m ? 0x400000u : 0u);
+    if (e == 0) return sign;   // zero or a float64 denormal
+    const int E = e - 1023 + 127;
+    if (E >= 255) return sign | 0x7F800000u;
+    if (E >= 1) {
+        u32 r = ((u32)E << 23) | (u32)(m >> 29);
+        const u64 rest = m & 0x1FFFFFFFull, half = 0x10000000ull;
+        if (rest > half || (rest == half && (r & 1u))) ++r;   // (a carry runs into the exponent, up to the pattern of inf)
+        return sign | r;
+    }
+    const int shift = 30 - E;   // 29 + (1 - E)
+    if (shift >= 64) return sign;
+    const u64 full = m | 0x10000000000000ull;
+    u32 r = (u32)(full >> shift);
+    const u64 rest = full & ((1ull << shift) - 1ull), half = 1ull << (shift - 1);
+    if (rest > half || (rest == half && (r & 1u))) ++r;
+    return sign | r;
+}
+// float32 patterns (no NaN) -> u32 that order like the values; -0.0 and +0.0 share one image
+__host__ __device__ inline u32 f32_image(u32 b) {
+    if (!(b & 0x7FFFFFFFu)) b = 0;
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+
+inline dim3 rows_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+#define ROWS_TID ((size_t)blockIdx.x * 256u + threadIdx.x)
+
+__global__ __launch_bounds__(256) void k_rows_first(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, u32* __restrict__ first) {
+    const size_t i = ROWS_TID;
+    if (i >= nr) return;
+    atomicMin(&first[gx[i]], (u32)(2 * i));
+    atomicMin(&first[gy[i]], (u32)(2 * i + 1));
+}
+__global__ __launch_bounds__(256) void k_rows_firstflag(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, const u32* __restrict__ first,
+                                                        u32* __restrict__ flag) {
+    const size_t p = ROWS_TID;
+    if (p >= 2 * (size_t)nr) return;
+    const u32 label = (p & 1) ? gy[p >> 1] : gx[p >> 1];
+    flag[p] = first[label] == (u32)p ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rows_number(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, const u32* __restrict__ flag,
+                                                     const u32* __restrict__ rank, u32* __restrict__ num /*by label*/, u32* __restrict__ gene /*by number*/) {
+    const size_t p = ROWS_TID;
+    if (p >= 2 * (size_t)nr || !flag[p]) return;
+    const u32 label = (p & 1) ? gy[p >> 1] : gx[p >> 1];
+    num[label] = rank[p];
+    gene[rank[p]] = label;
+}
+__global__ __launch_bounds__(256) void k_rows_keys(const u32* __restrict__ gx, const u32* __restrict__ gy, const double* __restrict__ z, u32 nr,
+                                                   const u32* __restrict__ num, u64* __restrict__ key, u32* __restrict__ line, u32* __restrict__ zbits,
+                                                   u32* __restrict__ diag /*zeroed*/) {
+    const size_t i = ROWS_TID;
+    if (i >= nr) return;
+    const u32 X = num[gx[i]], Y = num[gy[i]];
+    const u32 zb = f64_to_f32_bits((u64)__double_as_longlong(z[i]));
+    key[i] = ((u64)X << 32) | Y, line[i] = (u32)i, zbits[i] = zb;
+    if (zb - 1u < 0x7F800000u) atomicMax(&diag[X], zb), atomicMax(&diag[Y], zb);   // 0 < weight <= +inf
+}
+// the sorted lines that are the last of their pair and whose weight is not a zero
+__global__ __launch_bounds__(256) void k_rows_winflag(const u64* __restrict__ skey, const u32* __restrict__ sline, const u32* __restrict__ zbits, u32 nr,
+                                                      u32* __restrict__ flag) {
+    const size_t k = ROWS_TID;
+    if (k >= nr) return;
+    const bool win = k + 1 == nr || skey[k + 1] != skey[k];
+    flag[k] = (win && (zbits[sline[k]] & 0x7FFFFFFFu)) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rows_diagflag(const u32* __restrict__ diag, u32 D, u32* __restrict__ flag) {
+    const size_t g = ROWS_TID;
+    if (g < D) flag[g] = diag[g] ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rows_emit_pairs(const u64* __restrict__ skey, const u32* __restrict__ sline, const u32* __restrict__ zbits, u32 nr,
+                                                         const u32* __restrict__ flag, const u32* __restrict__ off, u64* __restrict__ ekey,
+                                                         u32* __restrict__ eval) {
+    const size_t k = ROWS_TID;
+    if (k >= nr || !flag[k]) return;
+    const size_t o = 2 * (size_t)off[k];
+    const u64 xy = skey[k];
+    const u32 v = zbits[sline[k]];
+    ekey[o] = xy, eval[o] = v;
+    ekey[o + 1] = (xy << 32) | (xy >> 32), eval[o + 1] = v;
+}
+__global__ __launch_bounds__(256) void k_rows_emit_diag(const u32* __restrict__ diag, u32 D, const u32* __restrict__ flag, const u32* __restrict__ off,
+                                                        size_t base, u64* __restrict__ ekey, u32* __restrict__ eval) {
+    const size_t g = ROWS_TID;
+    if (g >= D || !flag[g]) return;
+    ekey[base + off[g]] = ((u64)g << 32) | g, eval[base + off[g]] = diag[g];
+}
+__global__ __launch_bounds__(256) void k_rows_split(const u64* __restrict__ skey, const u32* __restrict__ sval, u32 nnz, u32* __restrict__ idx,
+                                                    u32* __restrict__ val /*float32 patterns*/, u32* __restrict__ dup /*zeroed*/) {
+    const size_t k = ROWS_TID;
+    if (k >= nnz) return;
+    idx[k] = (u32)skey[k], val[k] = sval[k];
+    if (k + 1 < nnz && skey[k + 1] == skey[k]) *dup = 1u;
+}
+// rp[r] = entries in front of row r, r = 0 .. n (keys are row << 32 | column, ascending)
+__global__ __launch_bounds__(256) void k_rows_rowptr(const u64* __restrict__ skey, u32 nnz, u32 n, u32* __restrict__ rp) {
+    const size_t r = ROWS_TID;
+    if (r > n) return;
+    const u64 want = (u64)r << 32;
+    u32 lo = 0, hi = nnz;
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (skey[m] < want) lo = m + 1;
+        else hi = m;
+    }
+    rp[r] = lo;
+}
+
+__global__ __launch_bounds__(256) void k_ro_nzflag(const u32* __restrict__ val /*float32 patterns*/, u32 nnz, u32* __restrict__ flag) {
+    const size_t k = ROWS_TID;
+    if (k < nnz) flag[k] = (val[k] & 0x7FFFFFFFu) ? 1u : 0u;   // (a NaN is not zero, -0.0 is)
+}
+__global__ __launch_bounds__(256) void k_ro_coords(const u32* __restrict__ rp, u32 n, const u32* __restrict__ idx, u32 nnz, const u32* __restrict__ flag,
+                                                   const u32* __restrict__ pos, u32* __restrict__ cr, u32* __restrict__ cc) {
+    const size_t k = ROWS_TID;
+    if (k >= nnz || !flag[k]) return;
+    u32 lo = 0, hi = n - 1;   // the row r with rp[r] <= k < rp[r + 1]
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (rp[m + 1] <= k) lo = m + 1;
+        else hi = m;
+    }
+    cr[pos[k]] = lo, cc[pos[k]] = idx[k];
+}
+// the k-th coordinate is kept when the k-th RAW value exceeds the threshold
+__global__ __launch_bounds__(256) void k_ro_keepflag(const u32* __restrict__ val, u32 m, u32 prune_image, u32* __restrict__ flag) {
+    const size_t j = ROWS_TID;
+    if (j >= m) return;
+    const u32 b = val[j];
+    flag[j] = ((b & 0x7FFFFFFFu) <= 0x7F800000u && f32_image(b) > prune_image) ? 1u : 0u;   // (a NaN exceeds nothing)
+}
+__global__ __launch_bounds__(256) void k_ro_compact(const u32* __restrict__ cr, const u32* __restrict__ cc, u32 m, const u32* __restrict__ flag,
+                                                    const u32* __restrict__ pos, u32* __restrict__ pr, u32* __restrict__ pc) {
+    const size_t j = ROWS_TID;
+    if (j >= m || !flag[j]) return;
+    pr[pos[j]] = cr[j], pc[pos[j]] = cc[j];
+}
+
+u32 read_u32(const u32* d, hipStream_t st) {
+    u32 v = 0;
+    HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return v;
+}
+
+// the read-out of a device-resident matrix -> the surviving pairs on the host
+void read_out(const Csr& x, double prune, hipStream_t st, std::vector<u32>& pr, std::vector<u32>& pc) {
+    pr.clear(), pc.clear();
+    const float prunef = (float)prune;
+    u32 pb;
+    memcpy(&pb, &prunef, 4);
+    if (!x.n || !x.nnz || prunef != prunef) return;   // (nothing exceeds a NaN threshold)
+    const u32 nnz = x.nnz;
+    DevBuf<u32> flag, pos, cr, cc, dr, dc, tmp;
+    flag.ensure((size_t)nnz + 2), pos.ensure((size_t)nnz + 2), tmp.ensure(scan_u32_temp_elems(nnz) + 8);
+    hipLaunchKernelGGL(k_ro_nzflag, rows_grid(nnz), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), nnz, flag.p);
+    const u32 m = read_u32(scan_u32(flag.p, pos.p, nnz, false, tmp.p, st), st);
+    if (!m) return;
+    cr.ensure((size_t)m + 2), cc.ensure((size_t)m + 2);
+    hipLaunchKernelGGL(k_ro_coords, rows_grid(nnz), dim3(256), 0, st, x.rp.p, x.n, x.idx.p, nnz, flag.p, pos.p, cr.p, cc.p);
+    hipLaunchKernelGGL(k_ro_keepflag, rows_grid(m), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), m, f32_image(pb), flag.p);
+    const u32 np = read_u32(scan_u32(flag.p, pos.p, m, false, tmp.p, st), st);
+    if (!np) return;
+    dr.ensure((size_t)np + 2), dc.ensure((size_t)np + 2);
+    hipLaunchKernelGGL(k_ro_compact, rows_grid(m), dim3(256), 0, st, cr.p, cc.p, m, flag.p, pos.p, dr.p, dc.p);
+    pr.resize(np), pc.resize(np);
+    HIP_CHECK(hipMemcpyAsync(pr.data(), dr.p, (size_t)np * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(pc.data(), dc.p, (size_t)np * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// a batch's rows (labels below n_labels, checked; nr > 0) -> its matrix in x (n = genes + 1) and the label of every matrix row
+void assemble(const std::vector<u32>& hx, const std::vector<u32>& hy, const double* z, u32 n_labels, Mcl& m, Csr& x, std::vector<u32>& gene) {
+    hipStream_t st = m.st;
+    const u32 nr = (u32)hx.size();
+    const size_t N = nr, N2 = 2 * N;
+    DevBuf<u32> gx, gy, first, flag, rank, num, dgene, line, sline, zbits, diag, off, eval, sval, dup;
+    DevBuf<double> dz;
+    DevBuf<u64> key, skey, ekey, sekey;
+    gx.ensure(N + 2), gy.ensure(N + 2), dz.ensure(N + 2), first.ensure((size_t)n_labels + 2), num.ensure((size_t)n_labels + 2);
+    flag.ensure(N2 + 2), rank.ensure(N2 + 2), m.scan_tmp.ensure(scan_u32_temp_elems(N2) + 8);
+    HIP_CHECK(hipMemcpyAsync(gx.p, hx.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(gy.p, hy.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(dz.p, z, N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(first.p, 0xFF, (size_t)n_labels * sizeof(u32), st));   // ROWS_NONE
+    hipLaunchKernelGGL(k_rows_first, rows_grid(N), dim3(256), 0, st, gx.p, gy.p, nr, first.p);
+    hipLaunchKernelGGL(k_rows_firstflag, rows_grid(N2), dim3(256), 0, st, gx.p, gy.p, nr, first.p, flag.p);
+    const u32 D = read_u32(scan_u32(flag.p, rank.p, N2, false, m.scan_tmp.p, st), st);
+    if (D < 1 || D > n_labels || D > N2) throw SoError("so_mcl_rows: internal error: " + std::to_string(D) + " genes in " + std::to_string(nr) + " rows");
+    dgene.ensure((size_t)D + 2), diag.ensure((size_t)D + 2);
+    key.ensure(N + 2), skey.ensure(N + 2), line.ensure(N + 2), sline.ensure(N + 2), zbits.ensure(N + 2), off.ensure(std::max<size_t>(N, D) + 2);
+    hipLaunchKernelGGL(k_rows_number, rows_grid(N2), dim3(256), 0, st, gx.p, gy.p, nr, flag.p, rank.p, num.p, dgene.p);
+    HIP_CHECK(hipMemsetAsync(diag.p, 0, ((size_t)D + 1) * sizeof(u32), st));
+    hipLaunchKernelGGL(k_rows_keys, rows_grid(N), dim3(256), 0, st, gx.p, gy.p, dz.p, nr, num.p, key.p, line.p, zbits.p, diag.p);
+    const int gbits = ceil_log2((u64)D + 1);
+    m.sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(N, 32 + gbits) + 256);
+    sort_pairs_u64_u32(m.sort_tmp.p, m.sort_tmp.cap, key.p, skey.p, line.p, sline.p, N, 32 + gbits, st);   // stable: lines ascend inside a pair
+    hipLaunchKernelGGL(k_rows_winflag, rows_grid(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p);
+    const u32 K = read_u32(scan_u32(flag.p, off.p, N, false, m.scan_tmp.p, st), st);
+    if ((size_t)2 * K + D > 0x7FFFFFF0ull) throw SoError("so_mcl_rows: matrix too large for 32-bit positions");
+    ekey.ensure((size_t)2 * K + D + 2), eval.ensure((size_t)2 * K + D + 2);
+    if (K) hipLaunchKernelGGL(k_rows_emit_pairs, rows_grid(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p, off.p, ekey.p, eval.p);
+    hipLaunchKernelGGL(k_rows_diagflag, rows_grid(D), dim3(256), 0, st, diag.p, D, flag.p);   // (D <= 2 nr: the flags fit)
+    const u32 Kd = read_u32(scan_u32(flag.p, off.p, D, false, m.scan_tmp.p, st), st);
+    if (Kd) hipLaunchKernelGGL(k_rows_emit_diag, rows_grid(D), dim3(256), 0, st, diag.p, D, flag.p, off.p, (size_t)2 * K, ekey.p, eval.p);
+    const u32 nnz = 2 * K + Kd;
+    x.n = D + 1, x.nnz = nnz;
+    x.rp.ensure((size_t)x.n + 2), x.idx.ensure((size_t)nnz + 2), x.val.ensure((size_t)nnz + 2);
+    sekey.ensure((size_t)nnz + 2), sval.ensure((size_t)nnz + 2), dup.ensure(4);
+    HIP_CHECK(hipMemsetAsync(dup.p, 0, sizeof(u32), st));
+    if (nnz) {
+        m.sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(nnz, 32 + gbits) + 256);
+        sort_pairs_u64_u32(m.sort_tmp.p, m.sort_tmp.cap, ekey.p, sekey.p, eval.p, sval.p, nnz, 32 + gbits, st);
+        hipLaunchKernelGGL(k_rows_split, rows_grid(nnz), dim3(256), 0, st, sekey.p, sval.p, nnz, x.idx.p, reinterpret_cast<u32*>(x.val.p), dup.p);
+    }
+    hipLaunchKernelGGL(k_rows_rowptr, rows_grid((size_t)x.n + 1), dim3(256), 0, st, sekey.p, nnz, x.n, x.rp.p);
+    gene.resize(D);
+    HIP_CHECK(hipMemcpyAsync(gene.data(), dgene.p, (size_t)D * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (read_u32(dup.p, st)) throw SoError("so_mcl_rows: some pair occurs as (a, b) and as (b, a) (the reference stores its coordinate twice; not served)");
+    HIP_CHECK(hipGetLastError());
+}
+
+// what every call without a context begins with: the device, or the refusal
+void need_device(int device, const char* who) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError(std::string(who) + ": no HIP device available (libsohit has no CPU fallback)");
+    if (device < 0 || device >= nd) throw SoError(std::string(who) + ": device index out of range");
+    HIP_CHECK(hipSetDevice(device));
+}
+
+int64_t* widen(const std::vector<u32>& v) {
+    int64_t* p = (int64_t*)malloc(std::max<size_t>(1, v.size()) * sizeof(int64_t));
+    if (!p) throw SoError("so_mcl_rows: out of host memory");
+    for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
+    return p;
+}
+
+// The rounds of the loop on a device-resident matrix x (old and c: its two work matrices) -> the matrix the loop ends with, x or c;
+// everything is queued on m.st, the convergence tests wait for it.  max_rounds = 0: x as it is.
+Csr* run_rounds(Mcl& m, Csr& x, Csr& old, Csr& c, double inflation, int max_rounds, int check_every, double prune, double rtol, double atol, int& rounds,
+                int& conv) {
+    const float prunef = (float)prune, rtolf = (float)rtol, atolf = (float)atol;
+    const double pw = (double)(float)inflation;   // numpy raises the float32 data to a float32 exponent
+    rounds = 0, conv = 0;
+    Csr *px = &x, *pc = &c;
+    for (int i = 0; i < max_rounds; ++i) {
+        ++rounds;
+        m.normalize(*px);
+        if (i % check_every == 0) copy_csr(*px, old, m.st);
+        m.expand(*px, *pc);
+        if (pc->nnz) hipLaunchKernelGGL(k_mcl_pow, dim3((pc->nnz + 255) / 256), dim3(256), 0, m.st, pc->val.p, pc->nnz, pw);
+        std::swap(px, pc);
+        if (i % check_every == 0 && i > 0 && m.converged(*px, old, rtolf, atolf)) {
+            conv = 1;
+            break;
+        }
+        if (px->nnz) hipLaunchKernelGGL(k_mcl_prune, dim3((px->nnz + 255) / 256), dim3(256), 0, m.st, px->val.p, px->nnz, prunef);
+    }
+    return px;
+}
+
 thread_local std::string g_mcl_err;
 
 }  // namespace
@@ -526,23 +807,8 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
                 HIP_CHECK(hipMemcpy(x.val.p, data, (size_t)nnz0 * sizeof(float), hipMemcpyHostToDevice));
             }
         }
-        const float prunef = (float)prune, rtolf = (float)rtol, atolf = (float)atol;
-        const double pw = (double)(float)inflation;   // numpy raises the float32 data to a float32 exponent
         int rounds = 0, conv = 0;
-        Csr *px = &x, *pc = &c;
-        for (int i = 0; i < max_rounds; ++i) {
-            ++rounds;
-            m.normalize(*px);
-            if (i % check_every == 0) copy_csr(*px, old, m.st);
-            m.expand(*px, *pc);
-            if (pc->nnz) hipLaunchKernelGGL(k_mcl_pow, dim3((pc->nnz + 255) / 256), dim3(256), 0, m.st, pc->val.p, pc->nnz, pw);
-            std::swap(px, pc);
-            if (i % check_every == 0 && i > 0 && m.converged(*px, old, rtolf, atolf)) {
-                conv = 1;
-                break;
-            }
-            if (px->nnz) hipLaunchKernelGGL(k_mcl_prune, dim3((px->nnz + 255) / 256), dim3(256), 0, m.st, px->val.p, px->nnz, prunef);
-        }
+        Csr* px = run_rounds(m, x, old, c, inflation, max_rounds, check_every, prune, rtol, atol, rounds, conv);
         HIP_CHECK(hipStreamSynchronize(m.st));
         HIP_CHECK(hipGetLastError());
         out->n = n, out->nnz = px->nnz, out->rounds = rounds, out->converged = conv;
@@ -563,6 +829,128 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
         g_mcl_err.clear();
         return 0;
     } catch (const std::exception& e) {
+        g_mcl_err = e.what();
+        return 1;
+    }
+}
+
+void so_mcl_rows_free(so_mcl_rows_result* r) {
+    if (!r) return;
+    free(r->gene), free(r->pair_r), free(r->pair_c), free(r->indptr), free(r->indices), free(r->data);
+    memset(r, 0, sizeof *r);
+}
+
+int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx, const int64_t* gy, const double* z, double inflation,
+                int32_t max_rounds, int32_t check_every, double prune, double rtol, double atol, int32_t flags, so_mcl_rows_result* out) {
+    try {
+        if (!out) throw SoError("so_mcl_rows: result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (n_labels < 0 || n_rows < 0 || (n_rows > 0 && (!gx || !gy || !z))) throw SoError("so_mcl_rows: bad arguments");
+        if (n_labels >= (1ll << 31) || n_rows >= (1ll << 31)) throw SoError("so_mcl_rows: 2^31 labels or rows and more are not served (32-bit numbers and positions)");
+        const size_t N = (size_t)n_rows;
+        std::vector<u32> hx(N), hy(N);
+        for (size_t i = 0; i < N; ++i) {
+            if (gx[i] < 0 || gx[i] >= n_labels || gy[i] < 0 || gy[i] >= n_labels)
+                throw SoError("so_mcl_rows: row " + std::to_string(i) + " names a gene outside 0 .. n_labels - 1");
+            if (z[i] != z[i]) throw SoError("so_mcl_rows: row " + std::to_string(i) + " has a NaN weight (not served: the caller keeps the host path)");
+            if (gx[i] == gy[i])
+                throw SoError("so_mcl_rows: row " + std::to_string(i) + " is a self pair (the reference overwrites the diagonal in line order; not served)");
+            hx[i] = (u32)gx[i], hy[i] = (u32)gy[i];
+        }
+        need_device(device, "so_mcl_rows");
+        const bool want_matrix = flags & 1;
+        std::vector<u32> gene, pr, pc, hrp, hidx;
+        std::vector<float> hval;
+        int rounds = 0, conv = 0;
+        if (N) {   // (no row: no gene, a 1 x 1 matrix without entries, no round, no pair -- and no launch)
+            if (check_every < 1) check_every = 1;
+            Tune tn;   // no context: the switches are read per call
+            tn.read();
+            const PoisonScope poison((int)tn.poison);
+            Mcl m;
+            if (tn.mcl_scratch >= 0) m.budget = (size_t)tn.mcl_scratch;
+            HIP_CHECK(hipStreamCreate(&m.st));
+            struct Guard {
+                hipStream_t s;
+                ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
+            } guard{m.st};
+            Csr x, old, c;
+            assemble(hx, hy, z, (u32)n_labels, m, x, gene);
+            if (want_matrix) {
+                hrp.resize((size_t)x.n + 1), hidx.resize(x.nnz), hval.resize(x.nnz);
+                HIP_CHECK(hipMemcpyAsync(hrp.data(), x.rp.p, hrp.size() * sizeof(u32), hipMemcpyDeviceToHost, m.st));
+                if (x.nnz) {
+                    HIP_CHECK(hipMemcpyAsync(hidx.data(), x.idx.p, (size_t)x.nnz * sizeof(u32), hipMemcpyDeviceToHost, m.st));
+                    HIP_CHECK(hipMemcpyAsync(hval.data(), x.val.p, (size_t)x.nnz * sizeof(float), hipMemcpyDeviceToHost, m.st));
+                }
+                HIP_CHECK(hipStreamSynchronize(m.st));
+            }
+            const Csr* px = run_rounds(m, x, old, c, inflation, max_rounds, check_every, prune, rtol, atol, rounds, conv);
+            read_out(*px, prune, m.st, pr, pc);
+            HIP_CHECK(hipStreamSynchronize(m.st));
+            HIP_CHECK(hipGetLastError());
+        } else if (want_matrix) {
+            hrp.assign(2, 0);
+        }
+        out->gene = widen(gene), out->pair_r = widen(pr), out->pair_c = widen(pc);
+        if (want_matrix) {
+            out->indptr = widen(hrp);
+            out->indices = (int32_t*)malloc(std::max<size_t>(1, hidx.size()) * sizeof(int32_t));
+            out->data = (float*)malloc(std::max<size_t>(1, hval.size()) * sizeof(float));
+            if (!out->indices || !out->data) throw SoError("so_mcl_rows: out of host memory");
+            if (!hidx.empty()) memcpy(out->indices, hidx.data(), hidx.size() * sizeof(u32)), memcpy(out->data, hval.data(), hval.size() * sizeof(float));
+            out->nnz = (int64_t)hidx.size();
+        }
+        out->n_genes = (int64_t)gene.size(), out->n_pairs = (int64_t)pr.size(), out->rounds = rounds, out->converged = conv;
+        g_mcl_err.clear();
+        return 0;
+    } catch (const std::exception& e) {
+        if (out) so_mcl_rows_free(out);
+        g_mcl_err = e.what();
+        return 1;
+    }
+}
+
+int so_mcl_readout(int device, int64_t n, const int64_t* indptr, const int32_t* indices, const float* data, double prune, so_mcl_rows_result* out) {
+    try {
+        if (!out) throw SoError("so_mcl_readout: result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (n < 0 || n > 0x7FFFFFF0ll || !indptr || indptr[0] != 0) throw SoError("so_mcl_readout: bad matrix");
+        for (int64_t i = 0; i < n; ++i)
+            if (indptr[i + 1] < indptr[i]) throw SoError("so_mcl_readout: bad matrix (row pointers fall)");
+        const int64_t nnz = indptr[n];
+        if (nnz > 0x7FFFFFF0ll) throw SoError("so_mcl_readout: matrix too large for 32-bit positions");
+        if (nnz > 0 && (!indices || !data)) throw SoError("so_mcl_readout: bad matrix");
+        need_device(device, "so_mcl_readout");
+        std::vector<u32> pr, pc;
+        if (n && nnz) {
+            Tune tn;
+            tn.read();
+            const PoisonScope poison((int)tn.poison);
+            hipStream_t st = nullptr;
+            HIP_CHECK(hipStreamCreate(&st));
+            struct Guard {
+                hipStream_t s;
+                ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
+            } guard{st};
+            Csr x;
+            x.n = (u32)n, x.nnz = (u32)nnz;
+            x.rp.ensure((size_t)n + 2), x.idx.ensure((size_t)nnz + 2), x.val.ensure((size_t)nnz + 2);
+            std::vector<u32> rp((size_t)n + 1);
+            for (int64_t i = 0; i <= n; ++i) rp[(size_t)i] = (u32)indptr[i];
+            HIP_CHECK(hipMemcpyAsync(x.rp.p, rp.data(), rp.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(x.idx.p, indices, (size_t)nnz * sizeof(u32), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(x.val.p, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
+            read_out(x, prune, st, pr, pc);
+            HIP_CHECK(hipStreamSynchronize(st));
+            HIP_CHECK(hipGetLastError());
+        }
+        out->pair_r = widen(pr), out->pair_c = widen(pc);
+        out->n_pairs = (int64_t)pr.size();
+        g_mcl_err.clear();
+        return 0;
+    } catch (const std::exception& e) {
+        if (out) so_mcl_rows_free(out);
         g_mcl_err = e.what();
         return 1;
     }

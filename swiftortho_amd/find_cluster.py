@@ -9,6 +9,9 @@ csrc/mcl.hip) with scipy's arithmetic order, because the pruning decisions, and 
 on it; the graph bookkeeping around it (best-neighbour components, batching, the read-out) is host code.  With `-G T`
 (`cnc(device_stage=True)`) the first half of that bookkeeping -- best-neighbour components, level-2 groups, the rows to keep --
 runs on the GPU too (libsohit `so_cnc_groups`, csrc/cnc.hip), pinned number for number to `group_numbers()`; default off, same output.
+With `-G M` (`cnc(device_stage='matrix')`) every batch also goes from its rows to its surviving pairs in one device call (libsohit
+`so_mcl_rows`, csrc/mcl.hip): the matrix is assembled, iterated and read out on the GPU, pinned bit for bit to `block_matrix_arrays()` and
+`surviving_pair_columns()`; default off, same output.
 So does the affinity-propagation loop of `-a apc` (libsohit `so_apc`, csrc/apc.hip), with the reference's own
 arithmetic order.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
 `-a apc` has to be named on the command line: a command without `-a` is still refused (exit code 2), as are `-a sap`
@@ -68,7 +71,8 @@ def manual_print(prog='find_cluster.py'):
     print('  -a: algorithm (mcl or apc)')
     print('  -t: cpu number')
     print('  -b: batch size for apc (above 0; no effect on the result)')
-    print('  -G: component stage of mcl on the GPU [T|F]. Default: F (same output; no effect with -a apc)')
+    print('  -G: stages of mcl on the GPU beside the loop [T|M|F]: T = the component stage, M = that and every batch from its rows to')
+    print('      its surviving pairs (matrix assembly and read-out). Default: F (same output; no effect with -a apc)')
 
 
 class _Graph:
@@ -244,6 +248,67 @@ def device_mcl(indptr, indices, data, inflation, device=0, rounds=100, check=5, 
     return out_ip, out_ix, out_dv
 
 
+def device_mcl_rows(gx, gy, z, n_labels, inflation, device=0, rounds=100, check=5, prune=1e-5, rtol=1e-5, atol=1e-8, want_matrix=False, info=None):
+    """one batch from its rows to its surviving pairs on the GPU (libsohit so_mcl_rows, csrc/mcl.hip): block_matrix_arrays, the loop of
+    device_mcl and surviving_pair_columns without the matrix ever existing on the host.  gx / gy: gene labels in 0 .. n_labels - 1 of the
+    batch's rows in batch order, z: their float64 weights.  -> (gene, pair_r, pair_c), all int64: gene[k] = the label of matrix row k, the
+    pairs in read-out order over matrix rows; with `want_matrix` also (indptr, indices, data), the matrix as it entered the loop.
+    `rounds` = 0 skips the loop.  `info`: a dict that receives `rounds` and `converged`.  A NaN weight, a row with x == y, a label outside
+    its range and a batch that holds both (a, b) and (b, a) are refused (RuntimeError).  No CPU path: raises when the HIP library or a
+    device is missing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoMclRowsResult()
+    xi = np.ascontiguousarray(gx, dtype=np.int64)
+    yi = np.ascontiguousarray(gy, dtype=np.int64)
+    zv = np.ascontiguousarray(z, dtype=np.float64)
+    if not (len(xi) == len(yi) == len(zv)):
+        raise ValueError('device_mcl_rows: gx, gy and z differ in length')
+    nr = len(xi)
+    rc = L.so_mcl_rows(device, int(n_labels), nr, xi.ctypes.data if nr else None, yi.ctypes.data if nr else None, zv.ctypes.data if nr else None, float(inflation),
+                       int(rounds), int(check), float(prune), float(rtol), float(atol), 1 if want_matrix else 0, C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_mcl_last_error().decode())
+    try:
+        d, npair, nnz = int(res.n_genes), int(res.n_pairs), int(res.nnz)
+        if isinstance(info, dict):
+            info.update(rounds=int(res.rounds), converged=int(res.converged))
+        out = (np.ctypeslib.as_array(res.gene, shape=(max(d, 1),))[:d].copy(),
+               np.ctypeslib.as_array(res.pair_r, shape=(max(npair, 1),))[:npair].copy(),
+               np.ctypeslib.as_array(res.pair_c, shape=(max(npair, 1),))[:npair].copy())
+        if want_matrix:
+            out += (np.ctypeslib.as_array(res.indptr, shape=(d + 2,)).copy(),
+                    np.ctypeslib.as_array(res.indices, shape=(max(nnz, 1),))[:nnz].copy(),
+                    np.ctypeslib.as_array(res.data, shape=(max(nnz, 1),))[:nnz].copy())
+    finally:
+        L.so_mcl_rows_free(C.byref(res))
+    return out
+
+
+def device_readout(indptr, indices, data, prune=1e-5, device=0):
+    """surviving_pair_columns on the GPU (libsohit so_mcl_readout: the read-out kernels of device_mcl_rows alone, on a host matrix)"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoMclRowsResult()
+    ip = np.ascontiguousarray(indptr, dtype=np.int64)
+    ix = np.ascontiguousarray(indices, dtype=np.int32)
+    dv = np.ascontiguousarray(data, dtype=np.float32)
+    if len(ip) < 1 or len(ix) != len(dv):
+        raise ValueError('device_readout: not a CSR matrix')
+    rc = L.so_mcl_readout(device, len(ip) - 1, ip.ctypes.data, ix.ctypes.data if len(ix) else None, dv.ctypes.data if len(dv) else None, float(prune), C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_mcl_last_error().decode())
+    try:
+        npair = int(res.n_pairs)
+        r = np.ctypeslib.as_array(res.pair_r, shape=(max(npair, 1),))[:npair].copy()
+        c = np.ctypeslib.as_array(res.pair_c, shape=(max(npair, 1),))[:npair].copy()
+    finally:
+        L.so_mcl_rows_free(C.byref(res))
+    return r, c
+
+
 def surviving_pairs(indptr, indices, data, prune=1e-5):
     """The reference's read-out of the final matrix (find_cluster.py:686-689): the coordinates of the entries that are not zero, paired
     IN ORDER with the raw data array -- which still holds the pruned zeros when the loop ran out of rounds, so the pairing can be
@@ -275,6 +340,26 @@ def mcl_block_arrays(gx, gy, z, gene_names, inflation, mcl=device_mcl):
         return
     names, indptr, indices, data = block_matrix_arrays(gx, gy, z, gene_names)
     g = _Graph.from_pairs(surviving_pair_columns(*mcl(indptr, indices, data, inflation)))
+    for comp in g.components():
+        yield [names[e] for e in comp]
+
+
+def _device_block(gx, gy, z, n_labels, inflation):
+    """cnc's batch with `device_stage='matrix'`: (device_mcl_rows is looked up per call)"""
+    return device_mcl_rows(gx, gy, z, n_labels, inflation)
+
+
+def mcl_block_rows(gx, gy, z, gene_names, inflation, mcl=device_mcl, block=_device_block):
+    """mcl_block_arrays with the batch handed to `block` as rows: (gx, gy, z, number of labels, inflation) -> (gene labels in matrix
+    order, pair_r, pair_c).  What the device call refuses -- a NaN weight, a self pair -- is a batch for mcl_block_arrays and `mcl`."""
+    if len(gx) == 0:
+        return
+    if np.isnan(z).any() or np.any(gx == gy):
+        yield from mcl_block_arrays(gx, gy, z, gene_names, inflation, mcl)
+        return
+    gene, pair_r, pair_c = block(gx, gy, z, len(gene_names), inflation)
+    names = [gene_names[g] for g in np.asarray(gene).tolist()]
+    g = _Graph.from_pairs((np.asarray(pair_r, dtype=np.int64), np.asarray(pair_c, dtype=np.int64)))
     for comp in g.components():
         yield [names[e] for e in comp]
 
@@ -481,11 +566,14 @@ def _device_stage(X, Y, Z, n):
     return device_group_numbers(X, Y, Z, n)
 
 
-def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_stage=False):
+def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_stage=False, block=None):
     """cnc (1470-1673): relation rows -> groups (lists of gene ids), in the reference's output order.  `lines`: an open file, bytes or an
     iterable of lines.  `mcl`: the Markov loop on a CSR block (the device implementation; the tests pass the scipy oracle to check this host
     bookkeeping on CPU).  `groups`: the component stage, (X, Y, Z, n) -> (comp1, grp) or (comp1, grp, keep flag per row): group_numbers by
     default, the device stage (device_group_numbers; the numpy one when a weight is NaN) with `device_stage=True`.
+    `device_stage='matrix'`: the device stage, and every batch goes from its rows to its surviving pairs in one device call (`block`:
+    (gx, gy, z, number of labels, inflation) -> (gene labels in matrix order, pair_r, pair_c); device_mcl_rows by default, the tests plug in
+    a numpy restatement) -- but for a batch with a NaN weight or a self pair, which keeps the host matrix and `mcl`.
     The reference keeps Python dictionaries and networkx graphs and moves the edges between its stages as sorted text files; here the
     rows are columns from the start (ids coded by their byte order, which is also the order `sort` compares them in), genes are integers
     numbered by first appearance (the insertion order of the reference's best-neighbour dictionary), and each of its orders --
@@ -532,12 +620,16 @@ def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_s
     kcls = kg[order]
     # batches: a new one starts where the group changes once the running batch holds more than chk rows
     change = np.concatenate([[0], np.flatnonzero(kcls[1:] != kcls[:-1]) + 1, [len(kcls)]])
+    if device_stage == 'matrix' or block is not None:
+        batch = lambda r: mcl_block_rows(X[r], Y[r], Z[r], gene_names, inflation, mcl, block if block is not None else _device_block)
+    else:
+        batch = lambda r: mcl_block_arrays(X[r], Y[r], Z[r], gene_names, inflation, mcl)
     out, start = [], 0
     for c in change[1:-1].tolist():
         if c - start > chk:
-            out.extend(mcl_block_arrays(X[rows_sorted[start:c]], Y[rows_sorted[start:c]], Z[rows_sorted[start:c]], gene_names, inflation, mcl))
+            out.extend(batch(rows_sorted[start:c]))
             start = c
-    out.extend(mcl_block_arrays(X[rows_sorted[start:]], Y[rows_sorted[start:]], Z[rows_sorted[start:]], gene_names, inflation, mcl))
+    out.extend(batch(rows_sorted[start:]))
     return out
 
 
@@ -674,7 +766,7 @@ def main(argv=None):
     if alg == 'apc' and named and bch > 0:
         run, warm_up = (lambda f: apc(f, dmp)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
     elif alg == 'mcl':
-        gpu = str(args['-G']).upper()[:1] == 'T'
+        gpu = {'T': True, 'M': 'matrix'}.get(str(args['-G']).upper()[:1], False)
         run = lambda f: cnc(f, ifl, device_stage=gpu)
         warm_up = lambda: device_mcl(np.array([0, 1]), np.array([0]), np.array([1.], dtype=np.float32), ifl, rounds=1)
     else:
