@@ -360,6 +360,39 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t *x,
 void so_cnc_free(so_cnc_result *result);
 const char *so_cnc_last_error(void);
 
+/* The row plan of `find_cluster -a mcl` on the device (csrc/cnc.hip): one call from the id codes of the rows to everything cnc needs
+ * before its batches.  Replaces: the part of bin/find_cluster.py `cnc` between reading the rows and `mcl_xyz` -- the gene dictionary
+ * (numbered by first appearance), the component stage of so_cnc_groups, the selection of the kept rows and the `LC_ALL=C sort -n` of
+ * the group-tagged lines (1590-1640) -- as swiftortho_amd/find_cluster.py `row_plan()` restates it, number for number.
+ * Input: n_rows rows in file order (host arrays, borrowed) with cx <= cy: id codes in 0 .. n_codes - 1 whose order is the byte order of
+ * the ids (codes may be unused), float64 weights z.  flags & 1: the order is made by two stable sort passes -- (cx, cy), then the group
+ * -- also where the three fields fit one 64-bit key (bits(n_grp + 1) + 2 bits(n_codes) <= 64), which otherwise takes one pass.
+ * Output (allocated by the library, released with so_cnc_plan_free()): gene_code[n_genes] = the codes in order of first appearance in
+ * cx0, cy0, cx1, ...; x / y[n_rows] = the gene numbers of the rows; comp1 / grp[n_genes] as so_cnc_groups defines them; order[n_keep] =
+ * the rows with grp[x] == grp[y] != 0, sorted by (grp as a signed number: the pool -1 first, cx, cy), rows with an equal triple in file
+ * order; cut[n_cut] = the positions p >= 1 of `order` whose grp differs from that of p - 1; tied[n_tied] = the positions p >= 1 whose
+ * (grp, cx, cy) equals that of p - 1.  sort_passes: 1 or 2 (0: no row kept); waits: host waits of the call -- one each for the number
+ * of genes, of level-1 roots, of kept rows (with the number of groups), of cuts and ties (the arrays up to `order` arrive with it) and
+ * one for cut / tied when there are any, plus one per label sweep (sweeps1 + sweeps2; level 2 is skipped when there is one level-1
+ * component).  n_rows = 0 is served without a launch (nothing numbered, nothing kept).
+ * Refused with a message (so_cnc_last_error), nothing launched and nothing left allocated: negative counts, n_codes or n_rows >= 2^31,
+ * a code outside 0 .. n_codes - 1, a row with cx > cy, a NaN weight (the caller keeps the numpy plan), no HIP device.  Integer atomics
+ * only: no value depends on scheduling.  No so_ctx: the call owns a stream of `device` and reads the SOHIT_* switches itself
+ * (SOHIT_POISON). */
+typedef struct so_cnc_plan_result {
+    int64_t n_codes, n_rows, n_genes, n_comp1, n_grp, n_keep, n_cut, n_tied;
+    int32_t sweeps1, sweeps2, sort_passes, waits;
+    int32_t *gene_code;   /* n_genes */
+    int32_t *x, *y;       /* n_rows  */
+    int32_t *comp1, *grp; /* n_genes */
+    int32_t *order;       /* n_keep  */
+    int32_t *cut;         /* n_cut   */
+    int32_t *tied;        /* n_tied  */
+} so_cnc_plan_result;
+int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t *cx, const int32_t *cy, const double *z, int32_t flags,
+                so_cnc_plan_result *out);
+void so_cnc_plan_free(so_cnc_plan_result *result);
+
 /* The candidate stage of find_orth on the device (csrc/orth.hip).  Replaces: the row loop of bin/find_orth.py -- coverage / identity
  * filter and -n normalisation (156-234), per query run the best hit per subject, the best score per subject taxon and out of the
  * query's taxon, the in-paralog / ortholog / co-ortholog candidates (298-348) and "a pair is a relation iff proposed exactly twice"

@@ -53,7 +53,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
-           "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free"]
+           "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
+           "so_cnc_plan", "so_cnc_plan_free"]
 
 
 class SoMclResult(C.Structure):
@@ -76,6 +77,12 @@ class SoCncResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_genes", "n_rows", "n_comp1", "n_grp", "n_keep")] + \
                [("sweeps1", C.c_int32), ("sweeps2", C.c_int32), ("comp1", C.POINTER(C.c_int64)), ("grp", C.POINTER(C.c_int64)),
                 ("keep", C.POINTER(C.c_uint8))]
+
+
+class SoCncPlanResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_codes", "n_rows", "n_genes", "n_comp1", "n_grp", "n_keep", "n_cut", "n_tied")] + \
+               [(n, C.c_int32) for n in ("sweeps1", "sweeps2", "sort_passes", "waits")] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("gene_code", "x", "y", "comp1", "grp", "order", "cut", "tied")]
 
 
 class SoOrthCand(C.Structure):
@@ -200,6 +207,8 @@ def load():
     L.so_cnc_groups.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.POINTER(SoCncResult)]
     L.so_cnc_free.argtypes = [C.POINTER(SoCncResult)]
     L.so_cnc_last_error.restype = cp
+    L.so_cnc_plan.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_int32, C.POINTER(SoCncPlanResult)]
+    L.so_cnc_plan_free.argtypes = [C.POINTER(SoCncPlanResult)]
     L.so_orth_candidates_cols.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, C.c_double, C.c_double, C.c_int, C.POINTER(SoOrthCand)]
     L.so_orth_candidates_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, C.c_double, C.c_double, C.c_int, C.POINTER(SoOrthCand)]
     L.so_orth_free.argtypes = [C.POINTER(SoOrthCand)]

@@ -12,6 +12,11 @@ runs on the GPU too (libsohit `so_cnc_groups`, csrc/cnc.hip), pinned number for 
 With `-G M` (`cnc(device_stage='matrix')`) every batch also goes from its rows to its surviving pairs in one device call (libsohit
 `so_mcl_rows`, csrc/mcl.hip): the matrix is assembled, iterated and read out on the GPU, pinned bit for bit to `block_matrix_arrays()` and
 `surviving_pair_columns()`; default off, same output.
+With `-G A` (`cnc(device_stage='all')`) the front of cnc between the tokeniser and the batches is one device call as well (libsohit
+`so_cnc_plan`, csrc/cnc.hip): genes numbered by first appearance, the component stage, the kept rows, their `sort -n` order and the
+batch cuts, pinned field for field to `row_plan()`; the rest is `-G M`; default off, same output.  `cnc_columns()` is cnc behind its
+tokeniser and `groups_from_tables()` feeds it find_orth's relation tables, so that `pipeline.groups_from_search()` goes from a FASTA
+file to the groups in one process without relation text.
 So does the affinity-propagation loop of `-a apc` (libsohit `so_apc`, csrc/apc.hip), with the reference's own
 arithmetic order.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
 `-a apc` has to be named on the command line: a command without `-a` is still refused (exit code 2), as are `-a sap`
@@ -71,8 +76,9 @@ def manual_print(prog='find_cluster.py'):
     print('  -a: algorithm (mcl or apc)')
     print('  -t: cpu number')
     print('  -b: batch size for apc (above 0; no effect on the result)')
-    print('  -G: stages of mcl on the GPU beside the loop [T|M|F]: T = the component stage, M = that and every batch from its rows to')
-    print('      its surviving pairs (matrix assembly and read-out). Default: F (same output; no effect with -a apc)')
+    print('  -G: stages of mcl on the GPU beside the loop [A|T|M|F]: T = the component stage, M = that and every batch from its rows to')
+    print('      its surviving pairs (matrix assembly and read-out), A = M and the whole row plan in front of the batches (gene numbers,')
+    print('      kept rows, their order). Default: F (same output; no effect with -a apc)')
 
 
 class _Graph:
@@ -566,6 +572,98 @@ def _device_stage(X, Y, Z, n):
     return device_group_numbers(X, Y, Z, n)
 
 
+class RowPlan:
+    """What cnc knows of its rows before the batches (row_plan() is the definition, device_row_plan() the same from the GPU); all int64.
+    gene_code[n_genes]: the id codes in order of first appearance (the x of a row before its y); X, Y[rows]: the rows' gene numbers;
+    comp1, grp[n_genes]: as group_numbers() gives them; order[n_keep]: the kept rows (grp[X] == grp[Y] != 0) sorted by (grp as a signed
+    number, cx, cy), rows with an equal triple in file order; cut: the positions p >= 1 of `order` whose grp differs from that of p - 1;
+    tied: the positions p >= 1 whose (grp, cx, cy) equals that of p - 1."""
+    FIELDS = ('gene_code', 'X', 'Y', 'comp1', 'grp', 'order', 'cut', 'tied')
+
+    def __init__(self, gene_code, X, Y, comp1, grp, order, cut, tied):
+        self.gene_code, self.X, self.Y, self.comp1, self.grp, self.order, self.cut, self.tied = gene_code, X, Y, comp1, grp, order, cut, tied
+
+    @classmethod
+    def empty(cls):
+        return cls(*[np.zeros(0, dtype=np.int64) for _ in cls.FIELDS])
+
+
+def row_plan(cx, cy, Z, n_codes, groups=None):
+    """The front of cnc between the rows and the batches -- the DEFINITION the device plan (so_cnc_plan, csrc/cnc.hip) is pinned to.
+    cx, cy: id codes of the rows with x <= y in file order (code order = the byte order of the ids), Z: their float64 weights, n_codes:
+    the number of codes (it may exceed the number that occur).  `groups`: the component stage, (X, Y, Z, n) -> (comp1, grp) or
+    (comp1, grp, keep flag per row); group_numbers by default.  -> RowPlan"""
+    cx, cy = np.asarray(cx, dtype=np.int64), np.asarray(cy, dtype=np.int64)
+    nrow = len(cx)
+    if nrow == 0:
+        return RowPlan.empty()
+    # genes numbered by first appearance (x of a row before its y)
+    seq = np.empty(2 * nrow, dtype=np.int64)
+    seq[0::2], seq[1::2] = cx, cy
+    vals, first = np.unique(seq, return_index=True)
+    gene_code = vals[np.argsort(first, kind='stable')]
+    number_of_code = np.zeros(int(n_codes), dtype=np.int64)
+    number_of_code[gene_code] = np.arange(len(vals))
+    X, Y = number_of_code[cx], number_of_code[cy]
+    res = (groups if groups is not None else group_numbers)(X, Y, Z, len(vals))
+    comp1, grp = np.asarray(res[0], dtype=np.int64), np.asarray(res[1], dtype=np.int64)
+    # edges inside one level-2 group whose number is non-zero (-1, the pool of unmerged components, included)
+    gx, gy = grp[X], grp[Y]
+    keep = np.flatnonzero(res[2]) if len(res) > 2 else np.flatnonzero((gx != 0) & (gy != 0) & (gx == gy))
+    # LC_ALL=C sort -n of the lines 'group\tx\ty\tweight': the leading number, then the whole line bytewise = (x, y, weight text)
+    # bytewise (ids hold no byte below the tab, so a shorter id sorts before its extensions, like its code does)
+    kg, kx, ky = gx[keep], cx[keep], cy[keep]
+    o = np.lexsort((ky, kx, kg))
+    sg, sx, sy = kg[o], kx[o], ky[o]
+    new_grp = sg[1:] != sg[:-1]
+    cut = np.flatnonzero(new_grp) + 1
+    tied = np.flatnonzero(~new_grp & (sx[1:] == sx[:-1]) & (sy[1:] == sy[:-1])) + 1
+    return RowPlan(gene_code, X, Y, comp1, grp, keep[o], cut, tied)
+
+
+def device_row_plan(cx, cy, Z, n_codes, device=0, info=None, two_pass=False):
+    """row_plan on the GPU (libsohit so_cnc_plan, csrc/cnc.hip): one device call from the code columns to every field of RowPlan.
+    `two_pass`: the order by two stable sort passes, (cx, cy) then the group, also where one 64-bit key would do.  `info`: a dict that
+    receives n_genes, n_comp1, n_grp, n_keep, sweeps1, sweeps2, sort_passes and waits (host waits of the call).  A NaN weight, a code
+    outside 0 .. n_codes - 1 and a row with cx > cy are refused (RuntimeError).  No CPU path: raises when the HIP library or a device
+    is missing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoCncPlanResult()
+    xi = np.ascontiguousarray(cx, dtype=np.int64)
+    yi = np.ascontiguousarray(cy, dtype=np.int64)
+    zv = np.ascontiguousarray(Z, dtype=np.float64)
+    if not (len(xi) == len(yi) == len(zv)):
+        raise ValueError('device_row_plan: cx, cy and Z differ in length')
+    for v in (xi, yi):
+        if len(v) and (int(v.min()) < -2 ** 31 or int(v.max()) >= 2 ** 31):
+            raise RuntimeError('so_cnc_plan: a code does not fit 32 bits')
+    xi, yi = xi.astype(np.int32), yi.astype(np.int32)
+    nr = len(xi)
+    rc = L.so_cnc_plan(device, int(n_codes), nr, xi.ctypes.data if nr else None, yi.ctypes.data if nr else None, zv.ctypes.data if nr else None,
+                       1 if two_pass else 0, C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_cnc_last_error().decode())
+    try:
+        if isinstance(info, dict):
+            info.update({k: int(getattr(res, k)) for k in ('n_genes', 'n_comp1', 'n_grp', 'n_keep', 'sweeps1', 'sweeps2', 'sort_passes', 'waits')})
+        col = lambda p, n: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(np.int64)
+        d, k = int(res.n_genes), int(res.n_keep)
+        plan = RowPlan(col(res.gene_code, d), col(res.x, nr), col(res.y, nr), col(res.comp1, d), col(res.grp, d), col(res.order, k),
+                       col(res.cut, int(res.n_cut)), col(res.tied, int(res.n_tied)))
+    finally:
+        L.so_cnc_plan_free(C.byref(res))
+    return plan
+
+
+def _device_plan(cx, cy, Z, n_codes):
+    """cnc's plan with `device_stage='all'`: an input with a NaN weight keeps the numpy plan, as _device_stage keeps the numpy stage"""
+    if np.isnan(Z).any():
+        return row_plan(cx, cy, Z, n_codes)
+    return device_row_plan(cx, cy, Z, n_codes)
+
+
 def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_stage=False, block=None):
     """cnc (1470-1673): relation rows -> groups (lists of gene ids), in the reference's output order.  `lines`: an open file, bytes or an
     iterable of lines.  `mcl`: the Markov loop on a CSR block (the device implementation; the tests pass the scipy oracle to check this host
@@ -574,63 +672,69 @@ def cnc(lines, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_s
     `device_stage='matrix'`: the device stage, and every batch goes from its rows to its surviving pairs in one device call (`block`:
     (gx, gy, z, number of labels, inflation) -> (gene labels in matrix order, pair_r, pair_c); device_mcl_rows by default, the tests plug in
     a numpy restatement) -- but for a batch with a NaN weight or a self pair, which keeps the host matrix and `mcl`.
+    `device_stage='all'`: as 'matrix', and the whole plan in front of the batches -- gene numbers, component stage, kept rows, their order,
+    the cuts -- comes from one device call (device_row_plan; the numpy plan when a weight is NaN or `groups` is given).
     The reference keeps Python dictionaries and networkx graphs and moves the edges between its stages as sorted text files; here the
     rows are columns from the start (ids coded by their byte order, which is also the order `sort` compares them in), genes are integers
     numbered by first appearance (the insertion order of the reference's best-neighbour dictionary), and each of its orders --
     `popitem()` = last gene first, a graph's node order = first appearance in the `add_edge` sequence, components numbered by their
-    first node, `LC_ALL=C sort -n` of the group-tagged edge lines -- is reproduced as index arithmetic."""
+    first node, `LC_ALL=C sort -n` of the group-tagged edge lines -- is reproduced as index arithmetic (row_plan)."""
     names, cx, cy, Z, ztext = _edge_columns(lines)
-    nrow = len(cx)
-    if nrow == 0:
+    return cnc_columns(names, cx, cy, Z, ztext, inflation, chk, mcl, groups, device_stage, block)
+
+
+def cnc_columns(names, cx, cy, Z, ztext, inflation=1.5, chk=10 ** 7, mcl=device_mcl, groups=None, device_stage=False, block=None, plan=None):
+    """cnc behind its tokeniser: rows that are columns already -> groups.  names: the ids by code (code order = their byte order); cx, cy:
+    the codes of the rows with x <= y in file order; Z: their float64 weights; ztext(i): the weight of row i as the bytes a file would
+    hold (asked for only where one pair occurs twice in a group: those lines are ordered by that text).  `plan`: (cx, cy, Z, number of
+    codes) -> RowPlan, instead of what `groups` and `device_stage` select.  The other arguments: see cnc."""
+    if len(cx) == 0:
         return []
-    # genes numbered by first appearance (x of a row before its y)
-    seq = np.empty(2 * nrow, dtype=np.int64)
-    seq[0::2], seq[1::2] = cx, cy
-    vals, first = np.unique(seq, return_index=True)
-    order = np.argsort(first, kind='stable')
-    number_of_code = np.zeros(len(names), dtype=np.int64)
-    number_of_code[vals[order]] = np.arange(len(vals))
-    X, Y = number_of_code[cx], number_of_code[cy]
-    gene_names = [names[c] for c in vals[order].tolist()]
-    n = len(vals)
-    stage = groups if groups is not None else (_device_stage if device_stage else group_numbers)
-    res = stage(X, Y, Z, n)
-    grp = res[1]
-    # edges inside one level-2 group whose number is non-zero (-1, the pool of unmerged components, included)
-    gx, gy = grp[X], grp[Y]
-    keep = np.flatnonzero(res[2]) if len(res) > 2 else np.flatnonzero((gx != 0) & (gy != 0) & (gx == gy))
-    if len(keep) == 0:
+    if plan is not None:
+        P = plan(cx, cy, Z, len(names))
+    elif device_stage == 'all' and groups is None:
+        P = _device_plan(cx, cy, Z, len(names))
+    else:
+        P = row_plan(cx, cy, Z, len(names), groups if groups is not None else (_device_stage if device_stage else group_numbers))
+    X, Y = P.X, P.Y
+    if len(P.order) == 0:
         return []
-    # LC_ALL=C sort -n of the lines 'group\tx\ty\tweight': the leading number, then the whole line bytewise = (x, y, weight text)
-    # bytewise (ids hold no byte below the tab, so a shorter id sorts before its extensions, like its code does)
-    kg, kx, ky = gx[keep], cx[keep], cy[keep]
-    order = np.lexsort((ky, kx, kg))
-    sg, sx, sy = kg[order], kx[order], ky[order]
-    dup = np.flatnonzero((sg[1:] == sg[:-1]) & (sx[1:] == sx[:-1]) & (sy[1:] == sy[:-1]))
-    if len(dup):                                          # the same pair twice in a group: its lines are ordered by the weight's text
-        run_start = dup[np.concatenate([[True], np.diff(dup) > 1])]
-        for s0 in run_start.tolist():
-            e0 = s0 + 1
-            while e0 < len(order) and sg[e0] == sg[s0] and sx[e0] == sx[s0] and sy[e0] == sy[s0]:
-                e0 += 1
-            seg = order[s0:e0].tolist()
-            seg.sort(key=lambda r: ztext(int(keep[r])) + b'\n')
-            order[s0:e0] = seg
-    rows_sorted = keep[order]
-    kcls = kg[order]
+    gene_names = [names[c] for c in P.gene_code.tolist()]
+    rows_sorted = P.order.copy()
+    if len(P.tied):                                       # the same pair twice in a group: its lines are ordered by the weight's text
+        first = np.concatenate([[True], np.diff(P.tied) > 1])
+        last = np.concatenate([first[1:], [True]])
+        for s0, e0 in zip((P.tied[first] - 1).tolist(), (P.tied[last] + 1).tolist()):
+            seg = rows_sorted[s0:e0].tolist()
+            seg.sort(key=lambda r: ztext(int(r)) + b'\n')
+            rows_sorted[s0:e0] = seg
     # batches: a new one starts where the group changes once the running batch holds more than chk rows
-    change = np.concatenate([[0], np.flatnonzero(kcls[1:] != kcls[:-1]) + 1, [len(kcls)]])
-    if device_stage == 'matrix' or block is not None:
+    if device_stage in ('matrix', 'all') or block is not None:
         batch = lambda r: mcl_block_rows(X[r], Y[r], Z[r], gene_names, inflation, mcl, block if block is not None else _device_block)
     else:
         batch = lambda r: mcl_block_arrays(X[r], Y[r], Z[r], gene_names, inflation, mcl)
     out, start = [], 0
-    for c in change[1:-1].tolist():
+    for c in P.cut.tolist():
         if c - start > chk:
             out.extend(batch(rows_sorted[start:c]))
             start = c
     out.extend(batch(rows_sorted[start:]))
     return out
+
+
+def groups_from_tables(names, tables, inflation=1.5, device_stage=False, chk=10 ** 7, mcl=device_mcl, block=None, groups=None, plan=None):
+    """find_orth's RelationTables -> ortholog groups (lists of ids, str) without the relation text: what cnc() returns for the lines
+    find_orth.lines_from_tables() writes.  names: the ids by code as find_orth numbers them (np.unique: byte order); rows = the IP, OT and
+    CO sections in output order, kept where a <= b; a weight is the table's value (repr round-trips: the number the tokeniser would read
+    back) and its text, needed for tied runs only, repr(v).  `device_stage`, `chk`, `mcl`, `block`, `groups`, `plan`: see cnc_columns
+    (a NaN value takes the numpy plan)."""
+    a = np.concatenate([np.asarray(getattr(tables, k + '_a'), dtype=np.int64) for k in ('ip', 'ot', 'co')])
+    b = np.concatenate([np.asarray(getattr(tables, k + '_b'), dtype=np.int64) for k in ('ip', 'ot', 'co')])
+    v = np.concatenate([np.asarray(getattr(tables, k + '_v'), dtype=np.float64) for k in ('ip', 'ot', 'co')])
+    use = a <= b
+    cx, cy, Z = a[use], b[use], v[use]
+    ids = [t.decode('utf-8') if isinstance(t, bytes) else str(t) for t in (names.tolist() if hasattr(names, 'tolist') else names)]
+    return cnc_columns(ids, cx, cy, Z, (lambda i: repr(float(Z[i])).encode()), inflation, chk, mcl, groups, device_stage, block, plan)
 
 
 def _apc_rows_python(lines):
@@ -766,7 +870,7 @@ def main(argv=None):
     if alg == 'apc' and named and bch > 0:
         run, warm_up = (lambda f: apc(f, dmp)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
     elif alg == 'mcl':
-        gpu = {'T': True, 'M': 'matrix'}.get(str(args['-G']).upper()[:1], False)
+        gpu = {'T': True, 'M': 'matrix', 'A': 'all'}.get(str(args['-G']).upper()[:1], False)
         run = lambda f: cnc(f, ifl, device_stage=gpu)
         warm_up = lambda: device_mcl(np.array([0, 1]), np.array([0]), np.array([1.], dtype=np.float32), ifl, rounds=1)
     else:
