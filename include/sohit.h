@@ -218,6 +218,10 @@ int64_t so_masked_query(so_ctx *ctx, int64_t qidx, char *buf, int64_t cap);
 /* candidates [subject, ungapped score, qi, qj] x uint32 of query qidx from the last
  * so_search_loaded() call, in the order the reference's spill file holds them (chunk-major) */
 int64_t so_query_candidates(so_ctx *ctx, int64_t qidx, uint32_t *out4, int64_t cap);
+/* tests (kept under the same switch as the candidates, SOHIT_KEEP_CANDS): query qidx's phase-2 state behind the alignment rounds of the
+ * last so_search_loaded() call -- out[0..4] = next rank, consecutive misses, passing tiles, selected tiles, stopped; out[5] = ranks
+ * considered (top vmax), out[6] = their alignment tasks, out[7] = band cells of the tasks aligned.  0, or -1 without a kept state. */
+int so_query_phase2(so_ctx *ctx, int64_t qidx, int64_t out[8]);
 /* tests: align explicit windows with ONE phase-2 aligner (not used by the search).  Queries are the loaded query file (raw residues, no
  * masking), subjects the loaded reference.
  * task6: n x {qidx, sidx, qi, qj, qe, se}: windows [qi, qe) of the query and [qj, se) of the subject, aligned from (qi, qj) as kswat_st does;

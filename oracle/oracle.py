@@ -80,6 +80,11 @@ def lib():
         L.oc_result_aln_bytes.restype = i64
         L.oc_result_aln_bytes.argtypes = [C.c_void_p]
         L.oc_result_alns.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+        L.oc_blastp_walk.restype = C.c_void_p
+        L.oc_blastp_walk.argtypes = L.oc_blastp.argtypes + [i64]
+        L.oc_result_walk_head.restype = i64
+        L.oc_result_walk_head.argtypes = [C.c_void_p, i64, C.c_void_p, C.POINTER(C.c_double)]
+        L.oc_result_walk.argtypes = [C.c_void_p, i64, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -270,6 +275,28 @@ class Result:
             lib().oc_result_cands(self.h, qrel, out.ctypes.data)
         return out[:n]
 
+    def walk(self, qrel):
+        """blastp(walk=True): the phase-2 loop's walk over query qrel's sorted candidates, as a dict --
+        ncand, mmiss, walked (ranks the loop visited) and ranks: one dict per rank of the top-vmax list in visiting order with subj,
+        tasks (1, or kswat_st_long's tile count), passed (tiles within expect) and bits / cells / hits per tile (None for a rank behind
+        the stop that shadow did not reach)."""
+        head = np.zeros(4, dtype=np.int64)
+        mm = C.c_double()
+        if lib().oc_result_walk_head(self.h, qrel, head.ctypes.data, C.byref(mm)) != 0:
+            raise ValueError("this Result was computed without walk=True")
+        nr, nt = int(head[0]), int(head[3])
+        rk = np.zeros((max(nr, 1), 5), dtype=np.int64)
+        tl = np.zeros((max(nt, 1), 3), dtype=np.int64)
+        lib().oc_result_walk(self.h, qrel, rk.ctypes.data, tl.ctypes.data)
+        ranks = []
+        for i in range(nr):
+            subj, tasks, npass, t0, n = (int(x) for x in rk[i])
+            have = n > 0 or tasks == 0 or i < int(head[1])
+            ranks.append(dict(subj=subj, tasks=tasks, passed=npass if have else None,
+                              bits=tl[t0:t0 + n, 0].tolist() if have else None, cells=tl[t0:t0 + n, 1].tolist() if have else None,
+                              hits=tl[t0:t0 + n, 2].tolist() if have else None))
+        return dict(ncand=int(head[2]), mmiss=float(mm.value), walked=int(head[1]), ranks=ranks)
+
     @property
     def nqueries(self):
         return int(lib().oc_result_nqueries(self.h))
@@ -297,6 +324,10 @@ class MergedResult:
     def cands(self, qrel):
         k = int(np.searchsorted(self._first, qrel, side="right")) - 1
         return self.parts[k].cands(qrel - int(self._first[k]))
+
+    def walk(self, qrel):
+        k = int(np.searchsorted(self._first, qrel, side="right")) - 1
+        return self.parts[k].walk(qrel - int(self._first[k]))
 
     @property
     def nqueries(self):
@@ -335,11 +366,17 @@ def blastp_parallel(qry, ref, out_path="", threads=0, st=-1, ed=-1, min_piece=64
 
 
 def blastp(qry, ref, out_path="", ssd="111111", nr=AA9, expect=1e-3, v=500, max_miss=1e-3, st=-1, ed=-1, rst=-1, red=-1,
-           thr=-1, step=1, flt="T", ht=120000000, chk=50000, mode="w", alignments=False):
+           thr=-1, step=1, flt="T", ht=120000000, chk=50000, mode="w", alignments=False, walk=False, shadow=0):
     """End-to-end reference path for queries [st, ed) (fsearch.py blastp + entry_point).  alignments=True: Result.alignments holds
-    every row's (query string, subject string) in row order (a tile row: its own tile's)"""
-    h = (lib().oc_blastp_aln if alignments else lib().oc_blastp)(_b(qry), _b(ref), _b(ssd), _b(nr), expect, v, max_miss, st, ed, rst, red, thr, step, _b(flt), ht, chk,
-                        _b(out_path), _b(mode))
+    every row's (query string, subject string) in row order (a tile row: its own tile's).  walk=True: Result.walk(qrel) gives every
+    query's walk over its sorted candidates (lengths and the loop's own alignments: no extra work); shadow=N also aligns up to N
+    ranks behind each query's stop, for the walk alone (rows and stats are those of walk=False)."""
+    args = (_b(qry), _b(ref), _b(ssd), _b(nr), expect, v, max_miss, st, ed, rst, red, thr, step, _b(flt), ht, chk, _b(out_path), _b(mode))
+    if walk:
+        assert not alignments
+        h = lib().oc_blastp_walk(*args, shadow)
+    else:
+        h = (lib().oc_blastp_aln if alignments else lib().oc_blastp)(*args)
     if not h:
         raise IOError("oracle blastp failed (cannot read %s / %s)" % (qry, ref))
     return Result(h)

@@ -921,9 +921,28 @@ struct HitRec {  // one reported alignment (fixed-width; mirrors include/sohit.h
     i64 aln, mis, gap, qst, qed, sst, sed, bit, qlen, slen, ungapped;
 };
 
+// The phase-2 loop's walk over one query's sorted candidates (tests: Result.walk): every rank of the top-vmax list in visiting
+// order.  A rank the loop visited carries the bit score, the band cells and the e-value verdict of each of its tiles; a rank behind the
+// loop's stop carries its subject and its tile count alone (lengths only), unless it is one of the first `shadow` such ranks, which are
+// aligned as well -- counted in no statistic and never emitted.
+struct WalkTile {
+    i64 bit, cells, pass;
+};
+struct WalkRank {
+    i64 subj, ntask, npass, tile0, ntile;   // tiles [tile0, tile0 + ntile) of the query's tile list (ntile = 0: not aligned)
+};
+struct Walk {
+    i64 ncand = 0, walked = 0;   // candidates of the query; ranks the loop visited
+    double mmiss = 0;
+    std::vector<WalkRank> ranks;
+    std::vector<WalkTile> tiles;
+};
+
 // alns (optional, with recs): every reported row's (query string, subject string), in row order
+// walks (optional): one Walk per query; shadow: ranks aligned behind each query's stop (walks only)
 int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats& stt, std::vector<HitRec>* recs = nullptr,
-           std::vector<std::vector<Cand>>* cand_dump = nullptr, std::vector<std::pair<std::string, std::string>>* alns = nullptr) {
+           std::vector<std::vector<Cand>>* cand_dump = nullptr, std::vector<std::pair<std::string, std::string>>* alns = nullptr,
+           std::vector<Walk>* walks = nullptr, i64 shadow = 0) {
     init_b62();
     Params p = p0;
     p.max_miss = std::max(p.max_miss, 1e-3);
@@ -972,6 +991,7 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
     double t2 = now();
     std::vector<Aln> longres;
     std::vector<std::pair<std::string, std::string>> longstr;
+    std::vector<i64> dblen(walks ? (size_t)D : 0, -1);   // (walks) subject lengths seen behind a stop
     for (i64 i = st; i < ed; ++i) {
         auto& H = KDB[i - st];
         stt.cands += (i64)H.size();
@@ -995,7 +1015,14 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
         std::vector<M8> m8s;
         std::string hi = hd.substr(0, hd.find(' '));
         const i64 lim = std::min<i64>((i64)perm.size(), vmax);
-        for (i64 h = 0; h < lim; ++h) {
+        Walk* W = nullptr;
+        if (walks) {
+            walks->emplace_back();
+            W = &walks->back();
+            W->ncand = (i64)H.size(), W->mmiss = mmiss;
+        }
+        i64 h = 0;
+        for (; h < lim; ++h) {
             const Cand& c = H[perm[h]];
             i64 j = c.subj;
             DB.get(j, hdj, sqj);
@@ -1013,6 +1040,10 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
                 Aln a = kswat_st(sqi, sqj, c.qi, c.qj, *mats, alns ? &al.first : nullptr, alns ? &al.second : nullptr);
                 stt.alignments += 1, stt.cells += a.cells;
                 double e = bit2e(D, li, lj, a.bit);
+                if (W) {
+                    W->ranks.push_back({j, 1, e <= p.expect ? 1 : 0, (i64)W->tiles.size(), 1});
+                    W->tiles.push_back({a.bit, a.cells, e <= p.expect ? 1 : 0});
+                }
                 if (e <= p.expect) {
                     emit(a, e, alns ? &al : nullptr);
                     unmch = 0;
@@ -1023,10 +1054,15 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
             } else {
                 int flag = 1;
                 kswat_st_long(sqi, sqj, c.qi, c.qj, *mats, longres, alns ? &longstr : nullptr);
+                if (W) W->ranks.push_back({j, (i64)longres.size(), 0, (i64)W->tiles.size(), (i64)longres.size()});
                 for (size_t t = 0; t < longres.size(); ++t) {
                     const Aln& a = longres[t];
                     stt.alignments += 1, stt.cells += a.cells;
                     double e = bit2e(D, li, lj, a.bit);
+                    if (W) {
+                        W->tiles.push_back({a.bit, a.cells, e <= p.expect ? 1 : 0});
+                        W->ranks.back().npass += e <= p.expect ? 1 : 0;
+                    }
                     if (e <= p.expect) {
                         emit(a, e, alns ? &longstr[t] : nullptr);
                         flag = 0;
@@ -1037,6 +1073,36 @@ int blastp(const char* qry, const char* ref, const Params& p0, FILE* out, Stats&
                 else unmch = 0;
             }
             if ((double)unmch >= mmiss || (double)bv >= (double)p.v + mmiss) break;
+        }
+        if (W) {
+            W->walked = std::min<i64>(h + 1, lim);
+            // behind the stop: subject and tile count (range(qi, li, 4096), 1487), and the alignments of the first `shadow` ranks
+            for (i64 g = W->walked, left = shadow; g < lim; ++g) {
+                const Cand& c = H[perm[g]];
+                i64& known = dblen[(size_t)c.subj];   // (a subject is read for its length once per call, and again only to be aligned)
+                if (known < 0 || left > 0) {
+                    DB.get((i64)c.subj, hdj, sqj);
+                    known = (i64)sqj.size();
+                }
+                const i64 lj = known;
+                const bool lng = !(li < 4096 && lj < 4096);
+                const i64 nt = !lng ? 1 : ((i64)c.qi < li ? (li - (i64)c.qi + 4095) / 4096 : 0);
+                W->ranks.push_back({(i64)c.subj, nt, 0, (i64)W->tiles.size(), 0});
+                if (left <= 0) continue;
+                --left;
+                if (!lng) {
+                    longres.assign(1, kswat_st(sqi, sqj, c.qi, c.qj, *mats));
+                } else {
+                    kswat_st_long(sqi, sqj, c.qi, c.qj, *mats, longres);
+                }
+                WalkRank& wr = W->ranks.back();
+                wr.ntile = (i64)longres.size();
+                for (const Aln& a : longres) {
+                    const i64 ok = bit2e(D, li, lj, a.bit) <= p.expect ? 1 : 0;
+                    W->tiles.push_back({a.bit, a.cells, ok});
+                    wr.npass += ok;
+                }
+            }
         }
         std::vector<int> pm(m8s.size());
         for (size_t k = 0; k < pm.size(); ++k) pm[k] = (int)k;
@@ -1198,18 +1264,21 @@ struct OcResult {
     std::vector<std::vector<Cand>> cands;
     Stats st;
     std::vector<std::pair<std::string, std::string>> alns;   // (oc_blastp_aln) per record: query string, subject string
+    std::vector<Walk> walks;                                 // (oc_blastp_walk) per query
+    bool has_walks = false;
 };
 
 static void* blastp_result(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
                            i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
-                           const char* mode, bool with_alns) {
+                           const char* mode, bool with_alns, i64 shadow = -1 /*>= 0: keep the walks*/) {
     Params p;
     p.ssd = ssd, p.nr = nr, p.expect = expect, p.v = v, p.max_miss = max_miss, p.st = st, p.ed = ed, p.rst = rst, p.red = red,
     p.thr = thr, p.step = step, p.flt = flt, p.ht = ht, p.chk = chk;
     OcResult* r = new OcResult();
     FILE* f = nullptr;
     if (out_path && out_path[0]) f = fopen(out_path, (mode && mode[0] == 'a') ? "ab" : "wb");
-    int rc = blastp(qry, ref, p, f, r->st, &r->recs, &r->cands, with_alns ? &r->alns : nullptr);
+    r->has_walks = shadow >= 0;
+    int rc = blastp(qry, ref, p, f, r->st, &r->recs, &r->cands, with_alns ? &r->alns : nullptr, shadow >= 0 ? &r->walks : nullptr, shadow);
     if (f) fclose(f);
     if (rc) {
         delete r;
@@ -1230,6 +1299,33 @@ void* oc_blastp_aln(const char* qry, const char* ref, const char* ssd, const cha
                     i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
                     const char* mode) {
     return blastp_result(qry, ref, ssd, nr, expect, v, max_miss, st, ed, rst, red, thr, step, flt, ht, chk, out_path, mode, true);
+}
+
+// oc_blastp that also keeps every query's walk (oc_result_walk), with `shadow` >= 0 ranks aligned behind each query's stop
+void* oc_blastp_walk(const char* qry, const char* ref, const char* ssd, const char* nr, double expect, i64 v, double max_miss, i64 st,
+                     i64 ed, i64 rst, i64 red, i64 thr, i64 step, const char* flt, i64 ht, i64 chk, const char* out_path,
+                     const char* mode, i64 shadow) {
+    return blastp_result(qry, ref, ssd, nr, expect, v, max_miss, st, ed, rst, red, thr, step, flt, ht, chk, out_path, mode, false,
+                         std::max<i64>(0, shadow));
+}
+// head4: ranks listed, ranks the loop visited, candidates, tiles listed; -1 without walks
+i64 oc_result_walk_head(void* h, i64 qrel, i64* head4, double* mmiss) {
+    OcResult* r = (OcResult*)h;
+    if (!r->has_walks || qrel < 0 || qrel >= (i64)r->walks.size()) return -1;
+    const Walk& w = r->walks[(size_t)qrel];
+    head4[0] = (i64)w.ranks.size(), head4[1] = w.walked, head4[2] = w.ncand, head4[3] = (i64)w.tiles.size();
+    *mmiss = w.mmiss;
+    return 0;
+}
+// ranks5: subj, tasks, passing tiles, first tile, tiles listed per rank; tiles3: bit, cells, pass per tile
+void oc_result_walk(void* h, i64 qrel, i64* ranks5, i64* tiles3) {
+    const Walk& w = ((OcResult*)h)->walks[(size_t)qrel];
+    for (size_t i = 0; i < w.ranks.size(); ++i) {
+        const WalkRank& k = w.ranks[i];
+        i64* o = ranks5 + 5 * i;
+        o[0] = k.subj, o[1] = k.ntask, o[2] = k.npass, o[3] = k.tile0, o[4] = k.ntile;
+    }
+    for (size_t i = 0; i < w.tiles.size(); ++i) tiles3[3 * i] = w.tiles[i].bit, tiles3[3 * i + 1] = w.tiles[i].cells, tiles3[3 * i + 2] = w.tiles[i].pass;
 }
 
 // bytes of all rows' strings (both sides), or -1 without them

@@ -47,7 +47,7 @@ class SoCounters(C.Structure):
 EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_last_error", "so_load_ref", "so_load_ref_mem", "so_build_index", "so_drop_index", "so_load_index",
            "so_load_queries", "so_load_queries_mem", "so_num_queries", "so_num_refs", "so_query_len", "so_search_loaded",
            "so_search", "so_free_hits", "so_search_loaded_aln", "so_free_aln", "so_write_sc", "so_format_hit", "so_get_counters", "so_reset_counters", "so_timing_report",
-           "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_align_pairs", "so_align_pairs_aln", "so_set_profile",
+           "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_query_phase2", "so_align_pairs", "so_align_pairs_aln", "so_set_profile",
            "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
@@ -193,6 +193,8 @@ def load():
     L.so_masked_query.argtypes = [vp, i64, cp, i64]
     L.so_query_candidates.restype = i64
     L.so_query_candidates.argtypes = [vp, i64, vp, i64]
+    L.so_query_phase2.restype = C.c_int
+    L.so_query_phase2.argtypes = [vp, i64, vp]
     L.so_align_pairs.argtypes = [vp, C.c_int, i64, vp, vp, vp]
     L.so_align_pairs_aln.argtypes = [vp, C.c_int, i64, vp, vp, vp, C.POINTER(C.c_void_p), C.POINTER(i64)]
     L.so_mcl.argtypes = [C.c_int, i64, vp, vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(SoMclResult)]

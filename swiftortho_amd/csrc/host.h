@@ -225,6 +225,7 @@ struct so_ctx {
     std::vector<std::string> masked;     // indexed by qidx - masked_lo
     i64 masked_lo = 0;
     std::vector<std::vector<u32>> last_cands;  // per query of last search: 4 x u32 per cand
+    std::vector<std::array<int64_t, 8>> last_p2;  // per query of last search: phase-2 state behind the rounds (so_query_phase2)
     u64 qry_gen = 0;                           // bumped by every query load: what a batch's cached slot layout is good for
     i64 last_q_lo = 0;
     so_counters cnt;

@@ -631,6 +631,14 @@ int64_t so_query_candidates(so_ctx* c, int64_t q, uint32_t* out4, int64_t cap) {
     return n;
 }
 
+int so_query_phase2(so_ctx* c, int64_t q, int64_t out[8]) {
+    if (!c || !out) return -1;
+    i64 k = q - c->last_q_lo;
+    if (k < 0 || k >= (i64)c->last_p2.size()) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = c->last_p2[(size_t)k][i];
+    return 0;
+}
+
 int so_align_pairs(so_ctx* c, int kernel, int64_t n, const int64_t* task6, const uint32_t* order, int32_t* out) {
     return guarded(c, [&] { align_pairs(c, kernel, n, task6, order, out); });
 }

@@ -398,6 +398,21 @@ static void align_rounds(so_ctx* c, Batch& b, P2& p) {
         aligned_total += NR + NS;
     }
     launch_sum_u64(b.qcells.p, nq, b.ucount.p + 1, c->st);
+    // state dump for so_query_phase2 (tests only)
+    if (tune().keep_cands) {
+        std::vector<u32> state(5 * (size_t)nq), ntask(nq), ntile(nq);
+        std::vector<unsigned long long> qcells(nq);
+        HIP_CHECK(hipMemcpyAsync(state.data(), b.st_state.p, 5 * (size_t)nq * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipMemcpyAsync(ntask.data(), b.ntask.p, (size_t)nq * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipMemcpyAsync(ntile.data(), b.ntile.p, (size_t)nq * sizeof(u32), hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipMemcpyAsync(qcells.data(), b.qcells.p, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipStreamSynchronize(c->st));
+        for (u32 q = 0; q < nq; ++q) {
+            auto& dst = c->last_p2[(size_t)(b.q_lo - c->last_q_lo) + b.qid[q]];
+            for (int k = 0; k < 5; ++k) dst[k] = (int64_t)state[5 * (size_t)q + k];
+            dst[5] = (int64_t)ntask[q], dst[6] = (int64_t)ntile[q], dst[7] = (int64_t)qcells[q];
+        }
+    }
     p.sc.lap("phase2.align_rounds");
     c->cnt.alignments += aligned_total;
 }

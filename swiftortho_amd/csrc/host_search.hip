@@ -27,6 +27,8 @@ void search_loaded(so_ctx* c, i64 q_lo, i64 q_hi, HitBuf& out) {
     c->last_q_lo = st;
     if (tune().keep_cands) c->last_cands.assign((size_t)(ed - st), std::vector<u32>());   // (tests: so_query_candidates)
     else c->last_cands.clear();
+    if (tune().keep_cands) c->last_p2.assign((size_t)(ed - st), std::array<int64_t, 8>{});   // (tests: so_query_phase2; a batch without candidates leaves zeros)
+    else c->last_p2.clear();
     c->masked.clear();
     const int nchunks = (int)c->chunks.size();
     if (tune().batch > 0) c->max_batch = (u32)tune().batch;

@@ -192,6 +192,17 @@ class Searcher:
         self.L.so_query_candidates(self.h, q, out.ctypes.data, n)
         return out[:n]
 
+    P2_FIELDS = ("next", "unmch", "bv", "nsel", "done", "ntask", "ntile", "qcells")
+
+    def query_phase2(self, q):
+        """tests (SOHIT_KEEP_CANDS=1): query q's phase-2 state behind the alignment rounds of the last search, a dict of P2_FIELDS --
+        the stop rule's next rank, consecutive misses, passing tiles, selected tiles and stopped flag, the ranks considered, their
+        alignment tasks and the band cells of the tasks aligned (None without a kept state)"""
+        out = np.zeros(8, dtype=np.int64)
+        if self.L.so_query_phase2(self.h, q, out.ctypes.data) != 0:
+            return None
+        return dict(zip(self.P2_FIELDS, (int(x) for x in out)))
+
     ALIGN_DTYPE = [(f, "<i4") for f in ("maxscore", "aln", "matches", "gap", "qst", "qed", "sst", "sed", "cells", "wide")]
 
     def align_pairs(self, tasks, kernel, order=None, alignments=False, cigar=False):

@@ -109,33 +109,43 @@ def check_index(s, ix, NC, A, S):
 _ORACLE_RUNS = {}
 
 
-def oracle_run(oracle, fasta, kw, st, ed, tmp_path):
+def oracle_run(oracle, fasta, kw, st, ed, tmp_path, qry=None, shadow=0):
+    """qry: a query file of its own (default: the reference searched against itself); shadow: ranks aligned behind each query's stop
+    for Result.walk() (the designed sets of tests/stop_rule_inputs.py; 0 adds no alignment to the oracle's run)"""
     import hashlib
-    key = (hashlib.sha1(fasta).hexdigest(), kw["ssd"], kw["nr"], kw["expect"], kw["v"], kw["step"], kw["flt"], kw["ht"], kw["chk"], st, ed,
+    key = (hashlib.sha1(fasta).hexdigest(), hashlib.sha1(qry).hexdigest() if qry is not None else None, shadow, kw["ssd"], kw["nr"], kw["expect"], kw["v"], kw["step"], kw["flt"], kw["ht"], kw["chk"], st, ed,
            kw.get("thr", -1), kw.get("max_miss", 1e-3))
     hit = _ORACLE_RUNS.get(key)
     if hit is None:
         fa = str(tmp_path / "x.fsa")
         open(fa, "wb").write(fasta)
         out = str(tmp_path / "o.oracle.sc")
+        fq = fa
+        if qry is not None:
+            fq = str(tmp_path / "xq.fsa")
+            open(fq, "wb").write(qry)
         # (query ranges side by side on the host's cores: identical to one call, tests/test_oracle_golden.py checks that)
-        r = oracle.blastp_parallel(fa, fa, out, ssd=kw["ssd"], nr=kw["nr"], expect=kw["expect"], v=kw["v"], step=kw["step"], flt=kw["flt"],
+        r = oracle.blastp_parallel(fq, fa, out, walk=True, shadow=shadow, ssd=kw["ssd"], nr=kw["nr"], expect=kw["expect"], v=kw["v"], step=kw["step"], flt=kw["flt"],
                                    ht=kw["ht"], chk=kw["chk"], st=st, ed=ed, thr=kw.get("thr", -1), max_miss=kw.get("max_miss", 1e-3))
         hit = _ORACLE_RUNS[key] = (r, open(out, "rb").read())
     return hit
 
 
-def oracle_vs_gpu(fs, oracle, fasta, kw, tmp_path, sub=None):
+def oracle_vs_gpu(fs, oracle, fasta, kw, tmp_path, sub=None, qry=None, shadow=0, stage=None):
+    """stage(searcher, oracle Result): a caller's own comparison of a stage in front of the rows, run behind the candidates' -- a stage
+    that went wrong is then named before the rows it spoilt"""
     st, ed = sub if sub else (-1, -1)
-    r, want = oracle_run(oracle, fasta, kw, st, ed, tmp_path)
+    r, want = oracle_run(oracle, fasta, kw, st, ed, tmp_path, qry, shadow)
     open(str(tmp_path / "o.sc"), "wb").write(want)   # (some callers read the oracle's text back)
-    s, hits, rows = gpu_rows(fs, fasta, fasta, kw, st, ed, keep=True)
+    s, hits, rows = gpu_rows(fs, fasta, fasta if qry is None else qry, kw, st, ed, keep=True)
     # stage: candidates of every query, in the reference's spill order
     lo = 0 if st < 0 else st
     for qrel in range(r.nqueries):
         got = s.query_candidates(lo + qrel)
         exp = r.cands(qrel)
         assert np.array_equal(got, exp), "candidates of query %d differ:\n gpu %s\n ora %s" % (lo + qrel, got[:8], exp[:8])
+    if stage is not None:
+        stage(s, r)
     a, b = rows.split(b"\n"), want.split(b"\n")
     for i in range(max(len(a), len(b))):
         x = a[i] if i < len(a) else b"<none>"
@@ -158,6 +168,15 @@ def oracle_vs_gpu(fs, oracle, fasta, kw, tmp_path, sub=None):
         assert c["ungap_steps"] == r.stats["ungap_steps"], (c["ungap_steps"], r.stats["ungap_steps"])
     # the oracle also counts the never-scoring "subject -1" groups (offset 0 of a chunk's first sequence)
     assert 0 <= r.stats["groups"] - c["groups"] <= 64 * c["n_chunks"] * max(1, r.nqueries // 50)
+    # work: the device aligns at least what the reference's sequential loop aligns, and exactly the tasks its round
+    # policy asks for -- rounds of max(minr, ceil(mmiss) - unmch) ranks, minr = 8, 16 ... 256 (tests/stop_rule_model.py on the oracle's
+    # walk; no switch changes that policy).  SOHIT_TEST_OOM_PHASE2 aligns a batch twice: it belongs to child processes only.
+    assert os.environ.get("SOHIT_TEST_OOM_PHASE2", "0") in ("", "0"), "SOHIT_TEST_OOM_PHASE2 is set: the work counters below cannot hold"
+    assert c["alignments"] >= r.stats["alignments"], (c["alignments"], r.stats["alignments"])
+    assert c["cells"] >= r.stats["cells"], (c["cells"], r.stats["cells"])
+    from stop_rule_model import model_rounds
+    tasks = [model_rounds(r.walk(qrel), kw["v"])["tasks"] for qrel in range(r.nqueries)]
+    assert c["alignments"] == sum(tasks), "alignments: device %d, round policy %d, reference %d" % (c["alignments"], sum(tasks), r.stats["alignments"])
     hits.close()
     s.close()
     return c, r.stats
