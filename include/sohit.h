@@ -335,6 +335,37 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t *row, c
 void so_apc_free(so_apc_result *result);
 const char *so_apc_last_error(void);
 
+/* `find_cluster -a apc` from id-coded rows to exemplar labels in one device call (csrc/apc.hip).  Replaces: the column half of
+ * fc2mat (767-858) -- gene numbers, the mirrored entries, the preference entries -- as swiftortho_amd/find_cluster.py
+ * `apc_entry_columns()` restates it, field for field, and then the loop of so_apc on those entries, bit for bit.
+ * Input: n_rows rows in file order (host arrays, borrowed): id codes cx <= cy in 0 .. n_codes - 1 (code order = the ids' byte order;
+ * codes may be unused), float64 weights z (a NaN or an infinite weight is served: the loop defines what it does with them),
+ * taxon_of_code[n_codes] = a code in 0 .. n_taxa - 1 of the id's text before its first '|'.  Genes are numbered by first appearance
+ * in cx0, cy0, cx1, cy1, ...; entry 2r = (X_r, Y_r, float32(z_r)), entry 2r + 1 = (Y_r, X_r, float32(z_r)), entry 2 n_rows + g =
+ * (g, g, float32(-20.0 * n_taxa_used)), n_taxa_used = the distinct taxon codes of the numbered genes.  The entry list never exists:
+ * the row / column layout of the loop is built from the rows on the device.
+ * Output: gene_code[n_genes] = the code of gene g, labels[n_genes] = its exemplar; R and A stay on the device.  With flags & 1 also
+ * row, col, score, r, a [n_entries] in ENTRY order (the tests' view; otherwise NULL).  Arrays allocated by the library, released with
+ * so_apc_rows_free().  `waits` = host waits of the call (the number of genes, the list lengths, the end: none per round).
+ * n_rows = 0 is served without a launch (no gene, no entry, n_taxa_used = 0).  Refused before a device is touched: negative counts,
+ * n_codes / n_rows / n_taxa of 2^31 and more, a code or a taxon code out of range, a row with cx > cy, 2 n_rows + n_codes above
+ * 0x7FFFFFF0, no HIP device; after numbering: more than 2^24 genes (so_apc's rule).  Returns 0 / non-zero with a message in
+ * so_apc_last_error().  No so_ctx: the call owns a stream of `device` and reads SOHIT_POISON itself. */
+typedef struct so_apc_rows_result {
+    int64_t n_codes, n_rows, n_genes, n_entries, n_taxa_used;
+    int32_t rounds, waits;
+    int32_t *gene_code; /* n_genes                                          */
+    int64_t *labels;    /* n_genes                                          */
+    int32_t *row;       /* n_entries, flags & 1 only (as col, score, r, a)  */
+    int32_t *col;
+    float *score;
+    float *r;
+    float *a;
+} so_apc_rows_result;
+int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t *cx, const int32_t *cy, const double *z,
+                const int32_t *taxon_of_code, int64_t n_taxa, double damp, int32_t rounds, int32_t flags, so_apc_rows_result *out);
+void so_apc_rows_free(so_apc_rows_result *result);
+
 /* The component stage of `find_cluster -a mcl` on the device (csrc/cnc.hip).  Replaces: the first half of bin/find_cluster.py `cnc`
  * (1470-1590) -- every gene linked to its best-scoring neighbours, the connected components of those links numbered (level 1), the
  * components joined by a row whose two component numbers are non-zero merged and numbered (level 2), the rows inside one level-2

@@ -54,7 +54,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
-           "so_cnc_plan", "so_cnc_plan_free"]
+           "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free"]
 
 
 class SoMclResult(C.Structure):
@@ -71,6 +71,13 @@ class SoMclRowsResult(C.Structure):
 class SoApcResult(C.Structure):
     _fields_ = [("n_genes", C.c_int64), ("n_entries", C.c_int64), ("rounds", C.c_int32), ("labels", C.POINTER(C.c_int64)),
                 ("r", C.POINTER(C.c_float)), ("a", C.POINTER(C.c_float))]
+
+
+class SoApcRowsResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_codes", "n_rows", "n_genes", "n_entries", "n_taxa_used")] + \
+               [("rounds", C.c_int32), ("waits", C.c_int32), ("gene_code", C.POINTER(C.c_int32)), ("labels", C.POINTER(C.c_int64)),
+                ("row", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)), ("score", C.POINTER(C.c_float)), ("r", C.POINTER(C.c_float)),
+                ("a", C.POINTER(C.c_float))]
 
 
 class SoCncResult(C.Structure):
@@ -206,6 +213,8 @@ def load():
     L.so_apc.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(SoApcResult)]
     L.so_apc_free.argtypes = [C.POINTER(SoApcResult)]
     L.so_apc_last_error.restype = cp
+    L.so_apc_rows.argtypes = [C.c_int, i64, i64, vp, vp, vp, vp, i64, C.c_double, C.c_int32, C.c_int32, C.POINTER(SoApcRowsResult)]
+    L.so_apc_rows_free.argtypes = [C.POINTER(SoApcRowsResult)]
     L.so_cnc_groups.argtypes = [C.c_int, i64, i64, vp, vp, vp, C.POINTER(SoCncResult)]
     L.so_cnc_free.argtypes = [C.POINTER(SoCncResult)]
     L.so_cnc_last_error.restype = cp

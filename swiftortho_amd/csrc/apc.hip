@@ -25,7 +25,15 @@
 // -inf never passes either strict compare, so both count as -inf in the scans.  The column sum of a wave is loaded 64 values at a
 // time and added one after the other, in entry order, by every lane alike.
 // All rounds are queued on one stream; the host waits once, at the end.
+//
+// so_apc_rows: the same loop from id-coded rows (cx <= cy, float64 weights, a taxon code per id code) -- `find_cluster -a apc -G A`.  The
+// layout above is built on the device, without the entry list ever being written (its definition: find_cluster.apc_entry_columns()): genes
+// numbered by first appearance, the taxa in use counted for the preference, pointers from the occurrences per gene, the entries in row
+// order and the columns' entries in entry order from two stable radix sorts, short / long lists by flag / scan / compact; see "the layout
+// from id-coded rows" below.  so_apc (layout prepared on the host) and so_apc_rows (on the device) feed one function, apc_queue_loop, which
+// queues the four kernels above.  Only gene codes and labels are downloaded; the host waits three times (number of genes, list lengths, end).
 #include "common.h"
+#include "kernels.h"
 #include "../../include/sohit.h"
 
 #include <cmath>
@@ -36,6 +44,7 @@
 namespace {
 
 #define APC_LANE_MAX 32u   // longest row / column one lane walks alone
+#define APC_TOO_MANY_GENES ": more than 2^24 genes (the reference keeps gene numbers in float32 and merges genes beyond that; not reproduced)"
 
 struct ApcRowState {   // per gene, carried over all rounds
     double* m1;
@@ -229,6 +238,48 @@ __global__ __launch_bounds__(256) void k_apc_iota(int* __restrict__ lab, u32 n) 
     if (i < n) lab[i] = (int)i;
 }
 
+// the row / column layout of one call, on the device: what the host prepares in so_apc and the device in so_apc_rows
+struct ApcLayout {
+    const u32 *rptr, *cptr, *cpos, *rshort, *rlong, *cshort, *clong;
+    const int *kcol, *crow;
+    const float* s;
+    u32 nrs, nrl, ncs, ncl;   // lengths of the four lists
+};
+struct ApcLoop {   // R, A (row order) and the per-gene state of the loop
+    DevBuf<int> k1, lab;
+    DevBuf<float> R, A;
+    DevBuf<double> m1, m2, d5;
+};
+
+// all rounds of the loop over a prepared layout of D genes and N entries, queued on `st` (no host wait)
+void apc_queue_loop(const ApcLayout& l, size_t D, size_t N, ApcLoop& b, double damp, int rounds, hipStream_t st) {
+    b.R.ensure(N + 2), b.A.ensure(N + 2), b.m1.ensure(D + 2), b.m2.ensure(D + 2), b.d5.ensure(D + 2), b.k1.ensure(D + 2), b.lab.ensure(D + 2);
+    HIP_CHECK(hipMemsetAsync(b.R.p, 0, (N + 2) * sizeof(float), st));
+    HIP_CHECK(hipMemsetAsync(b.A.p, 0, (N + 2) * sizeof(float), st));
+    HIP_CHECK(hipMemsetAsync(b.m1.p, 0, (D + 2) * sizeof(double), st));
+    HIP_CHECK(hipMemsetAsync(b.m2.p, 0, (D + 2) * sizeof(double), st));
+    HIP_CHECK(hipMemsetAsync(b.d5.p, 0, (D + 2) * sizeof(double), st));
+    HIP_CHECK(hipMemsetAsync(b.k1.p, 0, (D + 2) * sizeof(int), st));
+    if (D) hipLaunchKernelGGL(k_apc_iota, dim3((u32)((D + 255) / 256)), dim3(256), 0, st, b.lab.p, (u32)D);
+
+    const ApcRowState g{b.m1.p, b.m2.p, b.d5.p, b.k1.p, b.lab.p};
+    const double beta = 1. - damp;
+    auto row_pass = [&](int do_change, int do_update) {
+        if (l.nrs)
+            hipLaunchKernelGGL(k_apc_row_lane, dim3((l.nrs + 255) / 256), dim3(256), 0, st, l.rshort, l.nrs, l.rptr, l.kcol, l.s, b.R.p, b.A.p, g, damp, beta, do_change,
+                               do_update);
+        if (l.nrl)
+            hipLaunchKernelGGL(k_apc_row_wave, dim3(l.nrl), dim3(64), 0, st, l.rlong, l.nrl, l.rptr, l.kcol, l.s, b.R.p, b.A.p, g, damp, beta, do_change, do_update);
+    };
+    for (int it = 0; it < rounds; ++it) {
+        row_pass(it > 0, 1);
+        if (l.ncs) hipLaunchKernelGGL(k_apc_col_lane, dim3((l.ncs + 255) / 256), dim3(256), 0, st, l.cshort, l.ncs, l.cptr, l.cpos, l.crow, b.R.p, b.A.p, b.d5.p, damp, beta);
+        if (l.ncl) hipLaunchKernelGGL(k_apc_col_wave, dim3(l.ncl), dim3(64), 0, st, l.clong, l.ncl, l.cptr, l.cpos, l.crow, b.R.p, b.A.p, b.d5.p, damp, beta);
+    }
+    if (rounds > 0) row_pass(1, 0);   // get_change of the last round
+    HIP_CHECK(hipGetLastError());
+}
+
 // stable grouping of the entries by `key`: ptr[g] .. ptr[g + 1] = the entries of group g in entry order
 void group_stable(const int32_t* key, size_t n, size_t groups, std::vector<u32>& ptr, std::vector<u32>& order) {
     ptr.assign(groups + 1, 0);
@@ -254,6 +305,122 @@ void upload(DevBuf<T>& d, const std::vector<T>& h) {
     if (!h.empty()) HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 
+// ---- the layout from id-coded rows, on the device (so_apc_rows) ----------------------------------------------------------------------
+// Rows come as id CODES (cx <= cy).  Genes are numbered by first appearance in cx0, cy0, cx1, ... as cnc.hip's plan numbers them
+// (atomicMin of the position per code, flag the positions that are a code's first, scan: the scan value at a code's first position is its
+// number); the taxa of the first positions are flagged and counted for the preference.  The entry list is never written: entry e is
+// (X_r, Y_r) for e = 2r, (Y_r, X_r) for e = 2r + 1 and (g, g) for e = 2 * rows + g, and every kernel below derives it from e.  A row of
+// the layout holds one entry per occurrence of its gene in the rows and its preference entry, and so does its column: ONE array of
+// pointers serves as rptr and cptr, one pair of lists as the short / long rows and columns.  A stable radix sort of (row of e, e) gives
+// the entries in row order, a second one of (column of e, e) the columns' entries in entry order.  Integer atomics only.
+inline dim3 rows_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+#define ROWS_TID ((size_t)blockIdx.x * 256u + threadIdx.x)
+#define ROWS_NONE 0xFFFFFFFFu
+
+__global__ __launch_bounds__(256) void k_apcr_first(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, u32* __restrict__ first) {
+    const size_t i = ROWS_TID;
+    if (i >= nr) return;
+    atomicMin(&first[cx[i]], (u32)(2 * i));
+    atomicMin(&first[cy[i]], (u32)(2 * i + 1));
+}
+// flag[p] = position p is its code's first; the taxon of such a code is in use
+__global__ __launch_bounds__(256) void k_apcr_firstflag(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
+                                                        const int* __restrict__ taxon_of_code, u32* __restrict__ flag, u32* __restrict__ taxflag) {
+    const size_t p = ROWS_TID;
+    if (p >= 2 * (size_t)nr) return;
+    const int code = (p & 1) ? cy[p >> 1] : cx[p >> 1];
+    const u32 f = first[code] == (u32)p ? 1u : 0u;
+    flag[p] = f;
+    if (f) atomicOr(&taxflag[taxon_of_code[code]], 1u);
+}
+// a code's number = the scan value at its first position; cnt[g] = the occurrences of gene g in the rows
+__global__ __launch_bounds__(256) void k_apcr_number(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
+                                                     const u32* __restrict__ flag, const u32* __restrict__ rank, int* __restrict__ X, int* __restrict__ Y,
+                                                     int* __restrict__ gene_code, u32* __restrict__ cnt) {
+    const size_t i = ROWS_TID;
+    if (i >= nr) return;
+    const int a = cx[i], b = cy[i];
+    const u32 x = rank[first[a]], y = rank[first[b]];
+    X[i] = (int)x, Y[i] = (int)y;
+    if (flag[2 * i]) gene_code[rank[2 * i]] = a;
+    if (flag[2 * i + 1]) gene_code[rank[2 * i + 1]] = b;
+    atomicAdd(&cnt[x], 1u);
+    atomicAdd(&cnt[y], 1u);
+}
+// len[g] = cnt[g] + 1 (the preference entry), len[D] = 0 for the scan that ends the pointers; which list gene g goes to
+__global__ __launch_bounds__(256) void k_apcr_len(const u32* __restrict__ cnt, u32 D, u32* __restrict__ len, u32* __restrict__ sflag, u32* __restrict__ lflag) {
+    const size_t g = ROWS_TID;
+    if (g > D) return;
+    if (g == D) {
+        len[g] = 0;
+        return;
+    }
+    const u32 l = cnt[g] + 1u;
+    len[g] = l, sflag[g] = l <= APC_LANE_MAX ? 1u : 0u, lflag[g] = l <= APC_LANE_MAX ? 0u : 1u;
+}
+__global__ __launch_bounds__(256) void k_apcr_lists(const u32* __restrict__ sflag, const u32* __restrict__ spos, const u32* __restrict__ lflag,
+                                                    const u32* __restrict__ lpos, u32 D, u32* __restrict__ shorts, u32* __restrict__ longs) {
+    const size_t g = ROWS_TID;
+    if (g >= D) return;
+    if (sflag[g]) shorts[spos[g]] = (u32)g;
+    if (lflag[g]) longs[lpos[g]] = (u32)g;
+}
+// entry e of the list that is never written: its row and its column
+__device__ __forceinline__ void apcr_entry(u32 e, u32 nr2, const int* __restrict__ X, const int* __restrict__ Y, int& row, int& col) {
+    if (e < nr2) {
+        const int x = X[e >> 1], y = Y[e >> 1];
+        row = (e & 1) ? y : x, col = (e & 1) ? x : y;
+    } else {
+        row = col = (int)(e - nr2);
+    }
+}
+template <bool BYCOL>
+__global__ __launch_bounds__(256) void k_apcr_keys(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, u64* __restrict__ key, u32* __restrict__ val) {
+    const size_t e = ROWS_TID;
+    if (e >= N) return;
+    int row, col;
+    apcr_entry((u32)e, nr2, X, Y, row, col);
+    key[e] = (u64)(u32)(BYCOL ? col : row), val[e] = (u32)e;
+}
+// position p of the row order holds entry rorder[p]: its column, its score (one rounding of the float64 weight), and where the entry went
+__global__ __launch_bounds__(256) void k_apcr_place(const int* __restrict__ X, const int* __restrict__ Y, const double* __restrict__ z, u32 nr2, u32 N,
+                                                    const u32* __restrict__ rorder, float pref, u32* __restrict__ place, int* __restrict__ kcol,
+                                                    float* __restrict__ s) {
+    const size_t p = ROWS_TID;
+    if (p >= N) return;
+    const u32 e = rorder[p];
+    int row, col;
+    apcr_entry(e, nr2, X, Y, row, col);
+    place[e] = (u32)p, kcol[p] = col, s[p] = e < nr2 ? (float)z[e >> 1] : pref;
+}
+__global__ __launch_bounds__(256) void k_apcr_cols(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, const u32* __restrict__ corder,
+                                                   const u32* __restrict__ place, u32* __restrict__ cpos, int* __restrict__ crow) {
+    const size_t q = ROWS_TID;
+    if (q >= N) return;
+    const u32 e = corder[q];
+    int row, col;
+    apcr_entry(e, nr2, X, Y, row, col);
+    cpos[q] = place[e], crow[q] = row;
+}
+// the tests' view: the entry list and the stores of the loop in ENTRY order
+__global__ __launch_bounds__(256) void k_apcr_entries(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, const u32* __restrict__ place,
+                                                      const float* __restrict__ s, const float* __restrict__ R, const float* __restrict__ A, int* __restrict__ orow,
+                                                      int* __restrict__ ocol, float* __restrict__ os, float* __restrict__ o_r, float* __restrict__ o_a) {
+    const size_t e = ROWS_TID;
+    if (e >= N) return;
+    int row, col;
+    apcr_entry((u32)e, nr2, X, Y, row, col);
+    const u32 p = place[e];
+    orow[e] = row, ocol[e] = col, os[e] = s[p], o_r[e] = R[p], o_a[e] = A[p];
+}
+
+template <class T>
+T* rows_alloc(size_t n) {
+    T* p = (T*)malloc((n ? n : 1) * sizeof(T));
+    if (!p) throw SoError("so_apc_rows: out of host memory");
+    return p;
+}
+
 thread_local std::string g_apc_err;
 
 }  // namespace
@@ -275,7 +442,7 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         memset(out, 0, sizeof *out);
         if (n_genes < 0 || n_entries < 0 || rounds < 0 || (n_entries > 0 && (!row || !col || !score))) throw SoError("so_apc: bad arguments");
         if (n_genes > (1ll << 24))
-            throw SoError("so_apc: more than 2^24 genes (the reference keeps gene numbers in float32 and merges genes beyond that; not reproduced)");
+            throw SoError("so_apc" APC_TOO_MANY_GENES);
         if (n_entries > 0x7FFFFFF0ll) throw SoError("so_apc: edge list too large for 32-bit positions");
         const size_t D = (size_t)n_genes, N = (size_t)n_entries;
         for (size_t e = 0; e < N; ++e)
@@ -308,46 +475,22 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
             ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
         } guard{st};
         DevBuf<u32> d_rptr, d_cptr, d_cpos, d_rshort, d_rlong, d_cshort, d_clong;
-        DevBuf<int> d_kcol, d_crow, d_k1, d_lab;
-        DevBuf<float> d_s, d_R, d_A;
-        DevBuf<double> d_m1, d_m2, d_d5;
+        DevBuf<int> d_kcol, d_crow;
+        DevBuf<float> d_s;
         upload(d_rptr, rptr), upload(d_cptr, cptr), upload(d_cpos, cpos), upload(d_kcol, kcol), upload(d_crow, crow), upload(d_s, sc);
         upload(d_rshort, rshort), upload(d_rlong, rlong), upload(d_cshort, cshort), upload(d_clong, clong);
-        d_R.ensure(N + 2), d_A.ensure(N + 2), d_m1.ensure(D + 2), d_m2.ensure(D + 2), d_d5.ensure(D + 2), d_k1.ensure(D + 2), d_lab.ensure(D + 2);
-        HIP_CHECK(hipMemsetAsync(d_R.p, 0, (N + 2) * sizeof(float), st));
-        HIP_CHECK(hipMemsetAsync(d_A.p, 0, (N + 2) * sizeof(float), st));
-        HIP_CHECK(hipMemsetAsync(d_m1.p, 0, (D + 2) * sizeof(double), st));
-        HIP_CHECK(hipMemsetAsync(d_m2.p, 0, (D + 2) * sizeof(double), st));
-        HIP_CHECK(hipMemsetAsync(d_d5.p, 0, (D + 2) * sizeof(double), st));
-        HIP_CHECK(hipMemsetAsync(d_k1.p, 0, (D + 2) * sizeof(int), st));
-        if (D) hipLaunchKernelGGL(k_apc_iota, dim3((u32)((D + 255) / 256)), dim3(256), 0, st, d_lab.p, (u32)D);
-
-        const ApcRowState g{d_m1.p, d_m2.p, d_d5.p, d_k1.p, d_lab.p};
-        const double beta = 1. - damp;
-        const u32 nrs = (u32)rshort.size(), nrl = (u32)rlong.size(), ncs = (u32)cshort.size(), ncl = (u32)clong.size();
-        auto row_pass = [&](int do_change, int do_update) {
-            if (nrs)
-                hipLaunchKernelGGL(k_apc_row_lane, dim3((nrs + 255) / 256), dim3(256), 0, st, d_rshort.p, nrs, d_rptr.p, d_kcol.p, d_s.p, d_R.p, d_A.p, g, damp, beta,
-                                   do_change, do_update);
-            if (nrl)
-                hipLaunchKernelGGL(k_apc_row_wave, dim3(nrl), dim3(64), 0, st, d_rlong.p, nrl, d_rptr.p, d_kcol.p, d_s.p, d_R.p, d_A.p, g, damp, beta, do_change,
-                                   do_update);
-        };
-        for (int it = 0; it < rounds; ++it) {
-            row_pass(it > 0, 1);
-            if (ncs) hipLaunchKernelGGL(k_apc_col_lane, dim3((ncs + 255) / 256), dim3(256), 0, st, d_cshort.p, ncs, d_cptr.p, d_cpos.p, d_crow.p, d_R.p, d_A.p, d_d5.p, damp, beta);
-            if (ncl) hipLaunchKernelGGL(k_apc_col_wave, dim3(ncl), dim3(64), 0, st, d_clong.p, ncl, d_cptr.p, d_cpos.p, d_crow.p, d_R.p, d_A.p, d_d5.p, damp, beta);
-        }
-        if (rounds > 0) row_pass(1, 0);   // get_change of the last round
-        HIP_CHECK(hipGetLastError());
+        const ApcLayout lay{d_rptr.p, d_cptr.p, d_cpos.p, d_rshort.p, d_rlong.p, d_cshort.p, d_clong.p, d_kcol.p, d_crow.p, d_s.p,
+                            (u32)rshort.size(), (u32)rlong.size(), (u32)cshort.size(), (u32)clong.size()};
+        ApcLoop lp;
+        apc_queue_loop(lay, D, N, lp, damp, rounds, st);
         HIP_CHECK(hipStreamSynchronize(st));
 
         std::vector<int> lab(D);
         std::vector<float> hr(N), ha(N);
-        if (D) HIP_CHECK(hipMemcpy(lab.data(), d_lab.p, D * sizeof(int), hipMemcpyDeviceToHost));
+        if (D) HIP_CHECK(hipMemcpy(lab.data(), lp.lab.p, D * sizeof(int), hipMemcpyDeviceToHost));
         if (N) {
-            HIP_CHECK(hipMemcpy(hr.data(), d_R.p, N * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(ha.data(), d_A.p, N * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(hr.data(), lp.R.p, N * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(ha.data(), lp.A.p, N * sizeof(float), hipMemcpyDeviceToHost));
         }
         out->n_genes = n_genes, out->n_entries = n_entries, out->rounds = rounds;
         out->labels = (int64_t*)malloc((D ? D : 1) * sizeof(int64_t));
@@ -362,6 +505,160 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         g_apc_err.clear();
         return 0;
     } catch (const std::exception& e) {
+        g_apc_err = e.what();
+        return 1;
+    }
+}
+
+void so_apc_rows_free(so_apc_rows_result* r) {
+    if (!r) return;
+    free(r->gene_code), free(r->labels), free(r->row), free(r->col), free(r->score), free(r->r), free(r->a);
+    memset(r, 0, sizeof *r);
+}
+
+int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, const int32_t* cy, const double* z, const int32_t* taxon_of_code,
+                int64_t n_taxa, double damp, int32_t rounds, int32_t flags, so_apc_rows_result* out) {
+    try {
+        if (!out) throw SoError("so_apc_rows: result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (n_codes < 0 || n_rows < 0 || n_taxa < 0 || rounds < 0 || (n_rows > 0 && (!cx || !cy || !z)) || (n_codes > 0 && !taxon_of_code))
+            throw SoError("so_apc_rows: bad arguments");
+        if (n_codes >= (1ll << 31) || n_rows >= (1ll << 31) || n_taxa >= (1ll << 31))
+            throw SoError("so_apc_rows: 2^31 codes, rows or taxa and more are not served (32-bit codes and row indices)");
+        if (2 * n_rows + n_codes > 0x7FFFFFF0ll) throw SoError("so_apc_rows: edge list too large for 32-bit positions");
+        const size_t N1 = (size_t)n_rows, C = (size_t)n_codes;
+        for (size_t c = 0; c < C; ++c)
+            if (taxon_of_code[c] < 0 || taxon_of_code[c] >= n_taxa) throw SoError("so_apc_rows: code " + std::to_string(c) + " names a taxon outside 0 .. n_taxa - 1");
+        for (size_t i = 0; i < N1; ++i) {
+            if (cx[i] < 0 || cx[i] >= n_codes || cy[i] < 0 || cy[i] >= n_codes)
+                throw SoError("so_apc_rows: row " + std::to_string(i) + " names a code outside 0 .. n_codes - 1");
+            if (cx[i] > cy[i]) throw SoError("so_apc_rows: row " + std::to_string(i) + " has cx > cy (fc2mat drops such rows before anything is numbered)");
+        }
+        int nd = 0;
+        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_apc_rows: no HIP device available (libsohit has no CPU fallback)");
+        if (device < 0 || device >= nd) throw SoError("so_apc_rows: device index out of range");
+        out->n_codes = n_codes, out->n_rows = n_rows, out->rounds = rounds;
+        const bool want_entries = (flags & 1) != 0;
+        if (!N1) {   // no row: no gene, no entry, nothing to launch
+            out->gene_code = rows_alloc<int32_t>(0), out->labels = rows_alloc<int64_t>(0);
+            if (want_entries)
+                out->row = rows_alloc<int32_t>(0), out->col = rows_alloc<int32_t>(0), out->score = rows_alloc<float>(0), out->r = rows_alloc<float>(0),
+                out->a = rows_alloc<float>(0);
+            g_apc_err.clear();
+            return 0;
+        }
+
+        HIP_CHECK(hipSetDevice(device));
+        Tune tn;   // no context: the switches are read per call
+        tn.read();
+        const PoisonScope poison((int)tn.poison);
+        hipStream_t st = nullptr;
+        HIP_CHECK(hipStreamCreate(&st));
+        struct Guard {
+            hipStream_t s;
+            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
+        } guard{st};
+        const u32 nr = (u32)N1, nr2 = 2 * nr;
+        const size_t N2 = 2 * N1, T = (size_t)n_taxa, Dmax = std::min(C, N2);
+        int waits = 0;
+        auto read2 = [&](const u32* a, u32& va, const u32* b, u32& vb) {   // one host wait for two device words
+            HIP_CHECK(hipMemcpyAsync(&va, a, sizeof(u32), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(&vb, b, sizeof(u32), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++waits;
+        };
+
+        // genes numbered by first appearance, the taxa in use, the occurrences of every gene
+        DevBuf<int> d_cx, d_cy, d_tax, d_x, d_y, d_gene;
+        DevBuf<double> d_z;
+        DevBuf<u32> d_first, d_flag, d_rank, d_taxflag, d_taxpos, d_cnt, d_tmp_a, d_tmp_b, d_tmp_c;
+        d_cx.ensure(N1 + 2), d_cy.ensure(N1 + 2), d_z.ensure(N1 + 2), d_tax.ensure(C + 2), d_x.ensure(N1 + 2), d_y.ensure(N1 + 2), d_first.ensure(C + 2);
+        d_flag.ensure(N2 + 2), d_rank.ensure(N2 + 2), d_taxflag.ensure(T + 2), d_taxpos.ensure(T + 2), d_gene.ensure(Dmax + 2), d_cnt.ensure(Dmax + 2);
+        const size_t tmp_elems = scan_u32_temp_elems(std::max(N2, T) + 1) + 8;
+        d_tmp_a.ensure(tmp_elems), d_tmp_b.ensure(tmp_elems), d_tmp_c.ensure(tmp_elems);
+        HIP_CHECK(hipMemcpyAsync(d_cx.p, cx, N1 * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_cy.p, cy, N1 * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_z.p, z, N1 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_tax.p, taxon_of_code, C * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(d_first.p, 0xFF, C * sizeof(u32), st));   // ROWS_NONE (positions stay below 2^32 - 1)
+        HIP_CHECK(hipMemsetAsync(d_taxflag.p, 0, T * sizeof(u32), st));
+        HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (Dmax + 2) * sizeof(u32), st));
+        hipLaunchKernelGGL(k_apcr_first, rows_grid(N1), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p);
+        hipLaunchKernelGGL(k_apcr_firstflag, rows_grid(N2), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_tax.p, d_flag.p, d_taxflag.p);
+        const u32* d_ngenes = scan_u32(d_flag.p, d_rank.p, N2, false, d_tmp_a.p, st);
+        const u32* d_ntaxa = scan_u32(d_taxflag.p, d_taxpos.p, T, false, d_tmp_b.p, st);
+        hipLaunchKernelGGL(k_apcr_number, rows_grid(N1), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_flag.p, d_rank.p, d_x.p, d_y.p, d_gene.p, d_cnt.p);
+        HIP_CHECK(hipGetLastError());
+        u32 n = 0, ntax = 0;
+        read2(d_ngenes, n, d_ntaxa, ntax);
+        if (n < 1 || n > Dmax || ntax < 1 || ntax > T || ntax > n)
+            throw SoError("so_apc_rows: internal error: " + std::to_string(n) + " genes of " + std::to_string(ntax) + " taxa in " + std::to_string(nr) + " rows");
+        if (n > (1u << 24)) throw SoError("so_apc_rows" APC_TOO_MANY_GENES);
+        const size_t D = n, N = N2 + D;
+        const u32 ne = (u32)N;
+        const float pref = (float)(-20.0 * (double)ntax);
+
+        // pointers (rows and columns alike) and the short / long lists
+        DevBuf<u32> d_len, d_ptr, d_sflag, d_lflag, d_spos, d_lpos, d_short, d_long;
+        d_len.ensure(D + 3), d_ptr.ensure(D + 3), d_sflag.ensure(D + 2), d_lflag.ensure(D + 2), d_spos.ensure(D + 2), d_lpos.ensure(D + 2), d_short.ensure(D + 2),
+            d_long.ensure(D + 2);
+        hipLaunchKernelGGL(k_apcr_len, rows_grid(D + 1), dim3(256), 0, st, d_cnt.p, n, d_len.p, d_sflag.p, d_lflag.p);
+        scan_u32(d_len.p, d_ptr.p, D + 1, false, d_tmp_a.p, st);
+        const u32* d_nshort = scan_u32(d_sflag.p, d_spos.p, D, false, d_tmp_b.p, st);
+        const u32* d_nlong = scan_u32(d_lflag.p, d_lpos.p, D, false, d_tmp_c.p, st);
+        hipLaunchKernelGGL(k_apcr_lists, rows_grid(D), dim3(256), 0, st, d_sflag.p, d_spos.p, d_lflag.p, d_lpos.p, n, d_short.p, d_long.p);
+
+        // the entries in row order, the columns' entries in entry order
+        const int bits = ceil_log2((u64)D);
+        DevBuf<u64> d_key, d_skey;
+        DevBuf<u32> d_val, d_order, d_place, d_cpos;
+        DevBuf<int> d_kcol, d_crow;
+        DevBuf<float> d_s;
+        DevBuf<u8> d_sort_tmp;
+        d_key.ensure(N + 2), d_skey.ensure(N + 2), d_val.ensure(N + 2), d_order.ensure(N + 2), d_place.ensure(N + 2), d_cpos.ensure(N + 2), d_kcol.ensure(N + 2);
+        d_crow.ensure(N + 2), d_s.ensure(N + 2), d_sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(N, bits) + 256);
+        hipLaunchKernelGGL(k_apcr_keys<false>, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
+        sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_val.p, d_order.p, N, bits, st);   // stable: entry order inside a row
+        hipLaunchKernelGGL(k_apcr_place, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, d_z.p, nr2, ne, d_order.p, pref, d_place.p, d_kcol.p, d_s.p);
+        hipLaunchKernelGGL(k_apcr_keys<true>, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
+        sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_val.p, d_order.p, N, bits, st);   // stable: entry order inside a column
+        hipLaunchKernelGGL(k_apcr_cols, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_order.p, d_place.p, d_cpos.p, d_crow.p);
+        HIP_CHECK(hipGetLastError());
+        u32 nshort = 0, nlong = 0;
+        read2(d_nshort, nshort, d_nlong, nlong);
+        if ((size_t)nshort + nlong != D) throw SoError("so_apc_rows: internal error: " + std::to_string(nshort) + " short and " + std::to_string(nlong) + " long rows of " + std::to_string(n));
+
+        const ApcLayout lay{d_ptr.p, d_ptr.p, d_cpos.p, d_short.p, d_long.p, d_short.p, d_long.p, d_kcol.p, d_crow.p, d_s.p, nshort, nlong, nshort, nlong};
+        ApcLoop lp;
+        apc_queue_loop(lay, D, N, lp, damp, rounds, st);
+
+        out->n_genes = n, out->n_entries = (int64_t)N, out->n_taxa_used = ntax;
+        out->gene_code = rows_alloc<int32_t>(D), out->labels = rows_alloc<int64_t>(D);
+        std::vector<int> lab(D);
+        HIP_CHECK(hipMemcpyAsync(out->gene_code, d_gene.p, D * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(lab.data(), lp.lab.p, D * sizeof(int), hipMemcpyDeviceToHost, st));
+        DevBuf<int> d_orow, d_ocol;
+        DevBuf<float> d_os, d_or, d_oa;
+        if (want_entries) {
+            out->row = rows_alloc<int32_t>(N), out->col = rows_alloc<int32_t>(N), out->score = rows_alloc<float>(N), out->r = rows_alloc<float>(N), out->a = rows_alloc<float>(N);
+            d_orow.ensure(N + 2), d_ocol.ensure(N + 2), d_os.ensure(N + 2), d_or.ensure(N + 2), d_oa.ensure(N + 2);
+            hipLaunchKernelGGL(k_apcr_entries, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_place.p, d_s.p, lp.R.p, lp.A.p, d_orow.p, d_ocol.p, d_os.p, d_or.p,
+                               d_oa.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out->row, d_orow.p, N * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(out->col, d_ocol.p, N * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(out->score, d_os.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(out->r, d_or.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(out->a, d_oa.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        ++waits;
+        for (size_t i = 0; i < D; ++i) out->labels[i] = lab[i];
+        out->waits = waits;
+        g_apc_err.clear();
+        return 0;
+    } catch (const std::exception& e) {
+        if (out) so_apc_rows_free(out);
         g_apc_err = e.what();
         return 1;
     }

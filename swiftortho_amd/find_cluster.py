@@ -18,7 +18,10 @@ batch cuts, pinned field for field to `row_plan()`; the rest is `-G M`; default 
 tokeniser and `groups_from_tables()` feeds it find_orth's relation tables, so that `pipeline.groups_from_search()` goes from a FASTA
 file to the groups in one process without relation text.
 So does the affinity-propagation loop of `-a apc` (libsohit `so_apc`, csrc/apc.hip), with the reference's own
-arithmetic order.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
+arithmetic order.  With `-a apc -G A` (`apc(device_stage=True)`) the rows go from their id codes to the exemplar labels in one device call
+(libsohit `so_apc_rows`, the same file): gene numbers, preference, the entry layout and the loop, pinned field for field to
+`apc_entry_columns()` and bit for bit to `so_apc`; `apc_columns()` is apc behind its tokeniser and `apc_from_tables()` feeds it find_orth's
+relation tables; the read-out stays on the host; default off, same output.  There is no CPU path for either loop: without the HIP library `-a mcl` and `-a apc` fail.
 `-a apc` has to be named on the command line: a command without `-a` is still refused (exit code 2), as are `-a sap`
 (it needs pysapc), `-a apc` with a batch size `-b` of 0 or below (the reference's in-place float32 variant) and every
 other spelling that starts with `ap` (the reference then runs without preference entries).
@@ -78,7 +81,8 @@ def manual_print(prog='find_cluster.py'):
     print('  -b: batch size for apc (above 0; no effect on the result)')
     print('  -G: stages of mcl on the GPU beside the loop [A|T|M|F]: T = the component stage, M = that and every batch from its rows to')
     print('      its surviving pairs (matrix assembly and read-out), A = M and the whole row plan in front of the batches (gene numbers,')
-    print('      kept rows, their order). Default: F (same output; no effect with -a apc)')
+    print('      kept rows, their order). Default: F (same output).  With -a apc: A = the rows go from their id codes to the exemplar labels')
+    print('      in one device call (numbering, entry layout, loop); T, M and F have no effect')
 
 
 class _Graph:
@@ -772,12 +776,50 @@ def _rows_have_three_or_four_fields(data):
     return bool(np.all((per_line == 2) | (per_line == 3)))
 
 
-def apc_entries(lines):
-    """The entry list fc2mat (find_cluster.py:767-858) writes for `-a apc`: genes numbered by first appearance over the rows with
-    x <= y (x before y); per kept row (X, Y, w) then (Y, X, w); after all rows one preference entry (g, g, -20 * number of distinct
-    `id.split('|')[0]`) per gene.  `lines`: an open file, bytes or an iterable of lines.  Plain input goes through libsohit's
-    tokeniser, anything it does not take (a weight only Python can judge, a row of another shape, a tiny input) through the literal loop.
-    -> (ids by number, row int32, col int32, score float32, number of genes)"""
+def _taxon_codes(ids):
+    """ids by code -> (int32 code of `id.split('|')[0]` per id, number of distinct prefixes)"""
+    number = {}
+    tax = np.fromiter((number.setdefault(g.split('|')[0], len(number)) for g in ids), dtype=np.int32, count=len(ids))
+    return tax, len(number)
+
+
+def apc_entry_columns(cx, cy, Z, n_codes, taxon_of_code):
+    """The column half of fc2mat (find_cluster.py:767-858) -- the DEFINITION the device stage (so_apc_rows, csrc/apc.hip) is pinned to.
+    cx, cy: id codes of the rows with x <= y in file order (codes 0 .. n_codes - 1 in the byte order of the ids; codes may be unused),
+    Z: their float64 weights, taxon_of_code[c]: an int32 code of `id.split('|')[0]`.  Genes are numbered by first appearance in cx0, cy0,
+    cx1, cy1, ...; entry 2r = (X_r, Y_r, f32(z_r)), entry 2r + 1 = (Y_r, X_r, f32(z_r)), entry 2R + g = (g, g, f32(-20.0 * n_taxa_used)),
+    n_taxa_used = the distinct taxon codes of the numbered genes (a taxon carried by unused codes alone does not count); f32 rounds once,
+    to nearest even (overflow: an infinity; denormals kept; a NaN stays a NaN).
+    -> (gene_code int64[n_genes], row int32, col int32, score float32, n_genes, n_taxa_used)"""
+    cx, cy = np.asarray(cx, dtype=np.int64), np.asarray(cy, dtype=np.int64)
+    Z = np.asarray(Z, dtype=np.float64)
+    tax = np.asarray(taxon_of_code, dtype=np.int32)
+    nrow = len(cx)
+    seq = np.empty(2 * nrow, dtype=np.int64)
+    seq[0::2], seq[1::2] = cx, cy
+    vals, first = np.unique(seq, return_index=True)
+    gene_code = vals[np.argsort(first, kind='stable')]
+    n = len(gene_code)
+    number_of_code = np.zeros(int(n_codes), dtype=np.int64)
+    number_of_code[gene_code] = np.arange(n)
+    X, Y = number_of_code[cx], number_of_code[cy]
+    n_taxa_used = len(np.unique(tax[gene_code]))
+    m = 2 * nrow
+    row = np.empty(m + n, dtype=np.int32)
+    col = np.empty(m + n, dtype=np.int32)
+    score = np.empty(m + n, dtype=np.float32)
+    row[0:m:2], row[1:m:2], col[0:m:2], col[1:m:2] = X, Y, Y, X
+    with np.errstate(over='ignore'):
+        score[0:m:2] = score[1:m:2] = Z.astype(np.float32)
+    row[m:] = col[m:] = np.arange(n)
+    score[m:] = np.float32(n_taxa_used * -20.)
+    return gene_code, row, col, score, n, n_taxa_used
+
+
+def _apc_input(lines):
+    """the rows of `-a apc` as far as the tokeniser takes them: ('columns', ids by code, cx, cy, z) for plain input, ('rows', ids by
+    number, X, Y, Z) from the literal loop for anything the fast path does not take (a weight only Python can judge, a row of another
+    shape, a tiny input, a kept row without a weight)"""
     data = _text_bytes(lines)
     cols = None
     if data is not None:
@@ -785,16 +827,12 @@ def apc_entries(lines):
             cols = _edge_columns_native(data)
         lines = data.decode('utf-8').splitlines(True)
     if cols is not None:
-        ids, cx, cy, z, _ = cols
-        seq = np.empty(2 * len(cx), dtype=np.int64)
-        seq[0::2], seq[1::2] = cx, cy
-        vals, first = np.unique(seq, return_index=True)
-        order = np.argsort(first, kind='stable')
-        number_of_code = np.zeros(len(ids), dtype=np.int64)
-        number_of_code[vals[order]] = np.arange(len(vals))
-        names, X, Y, Z = [ids[c] for c in vals[order].tolist()], number_of_code[cx], number_of_code[cy], z
-    else:
-        names, X, Y, Z = _apc_rows_python(lines)
+        return ('columns',) + tuple(cols[:4])
+    return ('rows',) + _apc_rows_python(lines)
+
+
+def _apc_entries_of_rows(names, X, Y, Z):
+    """the entry list of rows the literal loop numbered: -> (ids by number, row int32, col int32, score float32, number of genes)"""
     n = len(names)
     pref = len(set(g.split('|')[0] for g in names)) * -20.
     row = np.empty(2 * len(X) + n, dtype=np.int32)
@@ -806,6 +844,21 @@ def apc_entries(lines):
     row[m:] = col[m:] = np.arange(n)
     score[m:] = np.float32(pref)
     return names, row, col, score, n
+
+
+def apc_entries(lines):
+    """The entry list fc2mat (find_cluster.py:767-858) writes for `-a apc`: genes numbered by first appearance over the rows with
+    x <= y (x before y); per kept row (X, Y, w) then (Y, X, w); after all rows one preference entry (g, g, -20 * number of distinct
+    `id.split('|')[0]`) per gene.  `lines`: an open file, bytes or an iterable of lines.  Plain input goes through libsohit's
+    tokeniser, the taxon codes and apc_entry_columns; anything the tokeniser does not take (a weight only Python can judge, a row of
+    another shape, a tiny input) through the literal loop.
+    -> (ids by number, row int32, col int32, score float32, number of genes)"""
+    inp = _apc_input(lines)
+    if inp[0] == 'rows':
+        return _apc_entries_of_rows(*inp[1:])
+    ids, cx, cy, z = inp[1:]
+    gene_code, row, col, score, n, _ = apc_entry_columns(cx, cy, z, len(ids), _taxon_codes(ids)[0])
+    return [ids[c] for c in gene_code.tolist()], row, col, score, n
 
 
 def device_apc(row, col, score, n_genes, damp, rounds=100, device=0):
@@ -836,16 +889,111 @@ def device_apc(row, col, score, n_genes, damp, rounds=100, device=0):
     return labels, r, a
 
 
-def apc(lines, damp=0.5, loop=device_apc):
+def device_apc_rows(cx, cy, z, n_codes, taxon_of_code, damp, rounds=100, device=0, want_entries=False, info=None):
+    """`-a apc` from id-coded rows to exemplar labels in one device call (libsohit so_apc_rows, csrc/apc.hip): apc_entry_columns and the
+    loop of device_apc without the entry list ever existing on the host.  cx <= cy: id codes in 0 .. n_codes - 1 of the rows in file
+    order, z: their float64 weights, taxon_of_code: an int32 taxon code per id code.  -> (gene_code int64[n_genes], labels
+    int64[n_genes]); with `want_entries` also (row int32, col int32, score float32, r float32, a float32) in entry order -- R and A stay
+    on the device otherwise.  `info`: a dict that receives n_genes, n_entries, n_taxa_used, rounds and waits (host waits of the call).
+    A code or a taxon code out of range and a row with cx > cy are refused (RuntimeError).  No CPU path: raises when the HIP library or
+    a device is missing."""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    res = _lib.SoApcRowsResult()
+    xi = np.ascontiguousarray(cx, dtype=np.int64)
+    yi = np.ascontiguousarray(cy, dtype=np.int64)
+    zv = np.ascontiguousarray(z, dtype=np.float64)
+    tx = np.ascontiguousarray(taxon_of_code, dtype=np.int64)
+    if not (len(xi) == len(yi) == len(zv)):
+        raise ValueError('device_apc_rows: cx, cy and z differ in length')
+    if len(tx) != int(n_codes) and int(n_codes) >= 0:
+        raise ValueError('device_apc_rows: taxon_of_code does not hold one taxon per code')
+    for v in (xi, yi, tx):
+        if len(v) and (int(v.min()) < -2 ** 31 or int(v.max()) >= 2 ** 31):
+            raise RuntimeError('so_apc_rows: a code does not fit 32 bits')
+    xi, yi, tx = xi.astype(np.int32), yi.astype(np.int32), tx.astype(np.int32)
+    nr = len(xi)
+    n_taxa = int(tx.max()) + 1 if len(tx) else 0
+    rc = L.so_apc_rows(device, int(n_codes), nr, xi.ctypes.data if nr else None, yi.ctypes.data if nr else None, zv.ctypes.data if nr else None,
+                       tx.ctypes.data if len(tx) else None, n_taxa, float(damp), int(rounds), 1 if want_entries else 0, C.byref(res))
+    if rc != 0:
+        raise RuntimeError(L.so_apc_last_error().decode())
+    try:
+        d, n = int(res.n_genes), int(res.n_entries)
+        if isinstance(info, dict):
+            info.update({k: int(getattr(res, k)) for k in ('n_genes', 'n_entries', 'n_taxa_used', 'rounds', 'waits')})
+        col = lambda p, k: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].copy()
+        out = (col(res.gene_code, d).astype(np.int64), col(res.labels, d))
+        if want_entries:
+            out += (col(res.row, n), col(res.col, n), col(res.score, n), col(res.r, n), col(res.a, n))
+    finally:
+        L.so_apc_rows_free(C.byref(res))
+    return out
+
+
+def _device_loop(row, col, score, n_genes, damp):
+    """the command's loop: (device_apc is looked up per call)"""
+    return device_apc(row, col, score, n_genes, damp)
+
+
+def _device_rows(cx, cy, z, n_codes, taxon_of_code, damp):
+    """the command's device stage: (device_apc_rows is looked up per call)"""
+    return device_apc_rows(cx, cy, z, n_codes, taxon_of_code, damp)
+
+
+def _exemplar_groups(names, labels):
+    """the read-out of `-a apc`: the connected components of the graph after `add_edge(g, exemplar of g)` for the genes in number order
+    (host code: the member order inside a group is Python's set order)"""
+    n = len(names)
+    g = _Graph.from_pairs((np.arange(n, dtype=np.int64), np.asarray(labels, dtype=np.int64)))
+    return [[names[e] for e in comp] for comp in g.components()]
+
+
+def apc_columns(names, cx, cy, Z, damp=0.5, device_stage=False, loop=device_apc, rows=device_apc_rows):
+    """apc behind its tokeniser: rows that are columns already -> groups.  names: the ids by code (code order = their byte order); cx, cy:
+    the codes of the rows with x <= y in file order; Z: their float64 weights.  With `device_stage` the rows go to the labels in one
+    device call, `rows`: (cx, cy, Z, number of codes, taxon_of_code, damp) -> (gene_code, labels, ...) (device_apc_rows; the tests plug
+    in a numpy restatement); otherwise through apc_entry_columns and `loop` (see apc).  Both end in the same read-out on the host."""
+    if len(cx) == 0:
+        return []
+    tax, _ = _taxon_codes(names)
+    if device_stage:
+        res = rows(cx, cy, Z, len(names), tax, damp)
+        gene_code, labels = np.asarray(res[0], dtype=np.int64), res[1]
+    else:
+        gene_code, row, col, score, n, _ = apc_entry_columns(cx, cy, Z, len(names), tax)
+        labels = loop(row, col, score, n, damp)[0]
+    return _exemplar_groups([names[c] for c in gene_code.tolist()], labels)
+
+
+def apc_from_tables(names, tables, damp=0.5, device_stage=False, loop=device_apc, rows=device_apc_rows):
+    """find_orth's RelationTables -> the groups of `-a apc` (lists of ids, str) without the relation text: what apc() returns for the lines
+    find_orth.lines_from_tables() writes -- the counterpart of groups_from_tables.  names: the ids by code as find_orth numbers them
+    (np.unique: byte order); rows = the IP, OT and CO sections in output order, kept where a <= b; a weight is the table's value (repr
+    round-trips: the number the tokeniser would read back).  `device_stage`, `loop`, `rows`: see apc_columns."""
+    a = np.concatenate([np.asarray(getattr(tables, k + '_a'), dtype=np.int64) for k in ('ip', 'ot', 'co')])
+    b = np.concatenate([np.asarray(getattr(tables, k + '_b'), dtype=np.int64) for k in ('ip', 'ot', 'co')])
+    v = np.concatenate([np.asarray(getattr(tables, k + '_v'), dtype=np.float64) for k in ('ip', 'ot', 'co')])
+    use = a <= b
+    ids = [t.decode('utf-8') if isinstance(t, bytes) else str(t) for t in (names.tolist() if hasattr(names, 'tolist') else names)]
+    return apc_columns(ids, a[use], b[use], v[use], damp, device_stage, loop, rows)
+
+
+def apc(lines, damp=0.5, loop=device_apc, device_stage=False, rows=device_apc_rows):
     """`-a apc` (fc2mat, apclust_blk, main 1705-1723): relation rows -> groups (lists of gene ids) in the reference's output order: the
     connected components of the graph after `add_edge(g, exemplar of g)` for the genes in number order.  `loop`: the affinity-propagation
-    loop over the entry list (the device implementation; the tests pass the literal numpy oracle to check this host bookkeeping on CPU)."""
-    names, row, col, score, n = apc_entries(lines)
+    loop over the entry list (the device implementation; the tests pass the literal numpy oracle to check this host bookkeeping on CPU).
+    `device_stage`: the rows go from their id codes to the labels in one device call (`rows`, see apc_columns) -- but for input that
+    only the literal loop can judge (a weight Python alone parses, a row of another shape, fewer than SOHIT_TSV_MIN lines, a kept row
+    without a weight), which keeps the host entry list and `loop`."""
+    inp = _apc_input(lines)
+    if inp[0] == 'columns':
+        return apc_columns(*inp[1:], damp=damp, device_stage=device_stage, loop=loop, rows=rows)
+    names, row, col, score, n = _apc_entries_of_rows(*inp[1:])
     if n == 0:
         return []
-    labels = np.asarray(loop(row, col, score, n, damp)[0], dtype=np.int64)
-    g = _Graph.from_pairs((np.arange(n, dtype=np.int64), labels))
-    return [[names[e] for e in comp] for comp in g.components()]
+    return _exemplar_groups(names, loop(row, col, score, n, damp)[0])
 
 
 def parse(argv):
@@ -868,7 +1016,8 @@ def main(argv=None):
         raise SystemExit()
     named = any((t == '-a' and i + 2 < len(argv)) or (t[:2] == '-a' and len(t) > 2) for i, t in enumerate(argv[1:]))   # (the default is 'apc': only a named algorithm runs)
     if alg == 'apc' and named and bch > 0:
-        run, warm_up = (lambda f: apc(f, dmp)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
+        gpu = str(args['-G']).upper()[:1] == 'A'
+        run, warm_up = (lambda f: apc(f, dmp, _device_loop, gpu, _device_rows)), (lambda: device_apc([0], [0], [0.], 1, dmp, rounds=1))
     elif alg == 'mcl':
         gpu = {'T': True, 'M': 'matrix', 'A': 'all'}.get(str(args['-G']).upper()[:1], False)
         run = lambda f: cnc(f, ifl, device_stage=gpu)

@@ -4,8 +4,9 @@ The reference pipeline writes the 16-column .sc file and bin/find_orth.py parses
 search produced (fixed-width so_hit structs, `Hits.array()`; on several GPUs the records gathered over RCCL) are handed
 to the columnar find_orth stage directly; the .sc file is still written when asked for (it is the drop-in artefact), but
 nothing reads it.  `orthology_from_search()` is what `bin/find_hit.py ... && bin/find_orth.py -i x.sc` computes.
-`groups_from_search()` goes one stage further, to what `bin/find_cluster.py -i x.orth -a mcl` prints: the relation tables the device
-computed are clustered as columns (find_cluster.groups_from_tables), so no relation text lies between the stages either."""
+`groups_from_search()` goes one stage further, to what `bin/find_cluster.py -i x.orth -a mcl` (or `-a apc`) prints: the relation tables
+the device computed are clustered as columns (find_cluster.groups_from_tables, apc_from_tables), so no relation text lies between the
+stages either."""
 import os
 import time
 
@@ -74,14 +75,18 @@ def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relatio
 
 
 def groups_from_search(fasta_path, inflation=1.5, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage='all', orth_path=None, sc_path=None,
-                       **search_kw):
+                       algorithm='mcl', damp=0.5, **search_kw):
     """one process from a FASTA file to ortholog groups: self-search on the GPU, the relation tables on the device from the records in
     HBM (find_orth.device_relation_tables_from_records), the groups from those tables (find_cluster.groups_from_tables) -- what
     `bin/find_hit.py ... && bin/find_orth.py -i x.sc > x.orth && bin/find_cluster.py -i x.orth -a mcl -I <inflation>` prints, one
-    group per line.  `device_stage`: find_cluster's (False | True | 'matrix' | 'all').  The .sc and the .orth file are written only when
-    `sc_path` / `orth_path` name them; nothing reads them.
+    group per line.  `device_stage`: find_cluster's (False | True | 'matrix' | 'all').  `algorithm='apc'`: the groups of
+    `bin/find_cluster.py -i x.orth -a apc -d <damp>` instead (find_cluster.apc_from_tables; any true `device_stage` = its one device call
+    from the rows to the exemplar labels); any other name raises ValueError before anything is loaded.  The .sc and the .orth file are
+    written only when `sc_path` / `orth_path` name them; nothing reads them.
     -> (groups as lists of ids, dict of stage wall times in seconds: load, search, [write_sc,] orth_relations, [write_orth,] cluster,
     and the counts rows, relations, groups)"""
+    if algorithm not in ('mcl', 'apc'):
+        raise ValueError("groups_from_search: unknown algorithm %r ('mcl' and 'apc' are provided)" % (algorithm,))
     import numpy as np
     from . import find_cluster, find_orth, fsearch
     t = {}
@@ -114,7 +119,10 @@ def groups_from_search(fasta_path, inflation=1.5, coverage=.5, identity=0., norm
             f.write(b''.join(l + b'\n' for l in find_orth.lines_from_tables(names, tables)))
         t['write_orth'] = time.time() - t0
         t0 = time.time()
-    groups = find_cluster.groups_from_tables(names, tables, inflation, device_stage)
+    if algorithm == 'apc':
+        groups = find_cluster.apc_from_tables(names, tables, damp, device_stage=bool(device_stage))
+    else:
+        groups = find_cluster.groups_from_tables(names, tables, inflation, device_stage)
     t['cluster'] = time.time() - t0
     t['relations'] = len(tables.ip_a) + len(tables.ot_a) + len(tables.co_a)
     t['groups'] = len(groups)
