@@ -489,6 +489,36 @@ int so_orth_relations_records(int device, const so_hit *d_hits, int64_t n, const
                               int norm, so_orth_rel *out);
 void so_orth_rel_free(so_orth_rel *result);
 
+/* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
+ * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
+ * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as
+ * swiftortho_amd/nr.py `expand_records()` restates it on records, byte for byte.
+ * Input: n so_hit records in DEVICE memory (d_hits: the pointer so_search_device hands out, or any 16-byte aligned device buffer of
+ * records), in the order the search returns them (ascending qidx; a run = consecutive records of one qidx), and two member tables (host
+ * arrays, borrowed): qmem[qoff[c] .. qoff[c + 1]) = the ordinals, in the full file, of the members of collapsed query c, in file order
+ * (qoff: n_q + 1 offsets); soff / smem the same for the subjects.
+ * Output: n_out records in device memory the library owns until so_nr_expand_free(): for the run of collapsed query c with members m_0 ..
+ * m_{k-1}, rows j = 0 .. t-1, n_j members of row j's subject, S = sum n_j, P_j = sum_{i<j} n_i, the record of (member a, row j, subject
+ * member b) stands at base_c + a * S + P_j + b (base_c: the expanded records of all earlier runs) and equals row j with qidx = m_a and
+ * sidx = subject member b; every other field is unchanged.  All totals are 64-bit.  n_runs: runs of the input; waits: host waits of
+ * the call (the totals, the end).  flags & 1: count only -- n_out and n_runs are filled, d_out stays NULL.  n = 0 launches nothing.
+ * Ordering: that of so_orth_*_records -- the call first waits for ALL work queued on the device, works on a stream of its own and has
+ * synchronised it when it returns.  The records are only read.
+ * Refused with a message (so_nr_last_error) and nothing left allocated: before a device is touched negative counts, n >= 2^31, a member
+ * table that does not rise from 0, a table whose members are not each named exactly once, records that are not 16-byte aligned, no HIP
+ * device; found on the device before d_out is allocated a qidx outside 0 .. n_q - 1 or a sidx outside 0 .. n_s - 1, and n_out >= 2^31
+ * (what the orthology stage refuses too).  No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON). */
+typedef struct so_nr_expand_result {
+    int64_t n_in, n_out, n_runs;
+    int32_t waits;
+    int32_t reserved;
+    so_hit *d_out;     /* n_out records, device memory */
+} so_nr_expand_result;
+int so_nr_expand(int device, const so_hit *d_hits, int64_t n, const int64_t *qoff, const int32_t *qmem, int64_t n_q, const int64_t *soff,
+                 const int32_t *smem, int64_t n_s, int32_t flags, so_nr_expand_result *out);
+void so_nr_expand_free(so_nr_expand_result *result);
+const char *so_nr_last_error(void);
+
 /* Host-side tokeniser of tab-separated text for the stages behind the search (csrc/tsv.hip; no device, no so_ctx).  Replaces: the
  * per-line `split('\t')` + `float()` loops of bin/find_orth.py (blastparse, 58-125) and bin/find_cluster.py (1425-1467) as the
  * numpy tokeniser of swiftortho_amd/find_orth.py restates them.

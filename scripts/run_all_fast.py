@@ -12,7 +12,10 @@ What is NOT the reference here: for `-A mcl` -- its default -- the reference wra
 `bin/find_cluster.py -a mcl` (the reference's own Python implementation of the algorithm, SURVEY.md 8f-2, Markov loop on the GPU) on the
 same .xyz instead: the two implement the same algorithm with different pruning schemes, so the .clsr of `-A mcl` is not pinned against
 the reference wrapper's.  `-A apc` is handed to find_cluster as `-a apc` (affinity propagation, loop on the GPU; ids without '|', so
-every gene counts as a taxon of its own in the preference, as in the reference wrapper); `-A sap` is refused by find_cluster."""
+every gene counts as a taxon of its own in the preference, as in the reference wrapper); `-A sap` is refused by find_cluster.
+Addition: `-G T` (default `F`: the commands above) takes the .sc and the .opc file from ONE process, with the hit records expanded and
+turned into relations on the GPU (swiftortho_amd.pipeline.orthology_from_search(collapse=True)): same file names, same bytes; one GPU.
+The clustering step is the same either way."""
 import os
 import subprocess
 import sys
@@ -24,7 +27,7 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000'}
+        '-I': '1.5', '-v': '1000', '-G': 'F'}
 
 
 def main(argv):
@@ -34,14 +37,26 @@ def main(argv):
         raise SystemExit()
     fas, name = a['-i'], a['-i'].split(os.sep)[-1]
     t = time()
-    sc = nr.search_collapsed(fas, a['-s'], a['-a'], a['-v'])
-    print('all to all homologous searching time:', time() - t)
-    t = time()
     opc = '%s_results/%s.opc' % (fas, name)
-    with open(opc, 'wb') as o:
-        subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_orth.py'), '-i', sc, '-c', a['-c'], '-y', a['-y'], '-n', a['-n'], '-t', 'y'],
-                       stdout=o, check=True)
-    print('orthomcl algorithm time:', time() - t)
+    if a['-G'].upper()[:1] == 'T':
+        # the same two files from one process: duplicates collapsed, searched once, multiplied back and turned into relations on the GPU
+        # (pipeline.orthology_from_search(collapse=True)); the .sc is written for the record, nothing reads it
+        from swiftortho_amd import pipeline
+        os.makedirs(fas + '_results', exist_ok=True)
+        lines, _ = pipeline.orthology_from_search(fas, sc_path='%s_results/%s.sc' % (fas, name), coverage=float(a['-c']), identity=float(a['-y']), norm=a['-n'],
+                                                  device_stage='relations', collapse=True, **nr.collapsed_search_kw(a['-s'], a['-v']))
+        with open(opc, 'wb') as o:
+            if lines:
+                o.write(b'\n'.join(lines) + b'\n')
+        print('all to all homologous searching and orthomcl algorithm time:', time() - t)
+    else:
+        sc = nr.search_collapsed(fas, a['-s'], a['-a'], a['-v'])
+        print('all to all homologous searching time:', time() - t)
+        t = time()
+        with open(opc, 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_orth.py'), '-i', sc, '-c', a['-c'], '-y', a['-y'], '-n', a['-n'], '-t', 'y'],
+                           stdout=o, check=True)
+        print('orthomcl algorithm time:', time() - t)
     t = time()
     # gene ids -> numbers by first appearance (run_all_fast.py:143-160)
     xyz, grp, clsr = ('%s_results/%s.%s' % (fas, name, e) for e in ('xyz', 'grp', 'clsr'))

@@ -54,7 +54,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
-           "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free"]
+           "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -97,6 +97,10 @@ class SoOrthCand(C.Structure):
                [("ot_a", C.POINTER(C.c_int64)), ("ot_b", C.POINTER(C.c_int64)), ("ot_s", C.POINTER(C.c_double)),
                 ("ip_a", C.POINTER(C.c_int64)), ("ip_b", C.POINTER(C.c_int64)), ("ip_s", C.POINTER(C.c_double)),
                 ("co_key", C.POINTER(C.c_int64)), ("co_best", C.POINTER(C.c_double))]
+
+
+class SoNrExpandResult(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("n_runs", C.c_int64), ("waits", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p)]
 
 
 _lib = None
@@ -227,6 +231,9 @@ def load():
     L.so_orth_relations_cols.argtypes = L.so_orth_candidates_cols.argtypes[:-1] + [C.POINTER(SoOrthRel)]
     L.so_orth_relations_records.argtypes = L.so_orth_candidates_records.argtypes[:-1] + [C.POINTER(SoOrthRel)]
     L.so_orth_rel_free.argtypes = [C.POINTER(SoOrthRel)]
+    L.so_nr_expand.argtypes = [C.c_int, vp, i64, vp, vp, i64, vp, vp, i64, C.c_int32, C.POINTER(SoNrExpandResult)]
+    L.so_nr_expand_free.argtypes = [C.POINTER(SoNrExpandResult)]
+    L.so_nr_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

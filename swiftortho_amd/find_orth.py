@@ -576,7 +576,7 @@ def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep, 
     rec = C.sizeof(_lib.SoHit)
     keep_alive = dev
     if hasattr(dev, 'device_pointer'):
-        d_ptr, n, device = dev.device_pointer(), len(dev), dev.s.device
+        d_ptr, n, device = dev.device_pointer(), len(dev), dev.device if hasattr(dev, 'device') else dev.s.device   # (nr.ExpandedHits | DeviceHits)
     else:
         import torch
         if not (isinstance(dev, torch.Tensor) and dev.is_cuda and dev.dtype == torch.uint8):

@@ -6,31 +6,94 @@ to the columnar find_orth stage directly; the .sc file is still written when ask
 nothing reads it.  `orthology_from_search()` is what `bin/find_hit.py ... && bin/find_orth.py -i x.sc` computes.
 `groups_from_search()` goes one stage further, to what `bin/find_cluster.py -i x.orth -a mcl` (or `-a apc`) prints: the relation tables
 the device computed are clustered as columns (find_cluster.groups_from_tables, apc_from_tables), so no relation text lies between the
-stages either."""
+stages either.
+`collapse=True` on either function is the reference's recommended route (scripts/run_all_fast.py: nr_flt -> find_hit -> nr2full -> ...)
+in the same process: identical sequences are searched once (nr.collapse_tables), the records of the collapsed search are multiplied back
+in HBM (nr.device_expand, so_nr_expand) in nr2full's order, and the device stages of find_orth read the expanded records where they lie."""
 import os
 import time
 
 
-def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage=False, **search_kw):
+def _collapse(data, t):
+    """collapse=True, the host half: -> (CollapseTables, the bytes to search, the ids of the full file)"""
+    from . import nr
+    t0 = time.time()
+    tables = nr.collapse_tables(data)
+    t['collapse'] = time.time() - t0
+    return tables, tables.fasta, tables.ids
+
+
+def _check_collapsed(s, tables):
+    if s.num_queries != len(tables.off) - 1 or s.num_refs != len(tables.off) - 1:
+        raise ValueError('collapse=True: the search reads %d records in the collapsed file, the member table holds %d (a record without residues?)'
+                         % (s.num_queries, len(tables.off) - 1))
+
+
+def _search_records(s, tables, sc_path, t, t0):
+    """search_device, the .sc file when asked for, and with `tables` (collapse=True) the expansion on the device
+    -> (the records the relation stage reads, the object to close after it or None, t0)"""
+    import numpy as np
+    from . import fsearch, nr
+    dev = s.search_device()
+    t['search'] = time.time() - t0
+    t0 = time.time()
+    if sc_path:
+        raw = dev.tensor().cpu().numpy() if len(dev) else np.zeros(0, dtype=np.uint8)
+        arr, n = fsearch.hits_from_bytes(s, raw)
+        if tables is None:
+            s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(sc_path), b'w'))
+        else:
+            # the cold path: the collapsed rows as text, multiplied out by the text nr2full(); nothing reads the file
+            import tempfile
+            fd, tmp = tempfile.mkstemp(suffix='.sc', dir=os.path.dirname(os.path.abspath(sc_path)))
+            os.close(fd)
+            try:
+                s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(tmp), b'w'))
+                with open(tmp, 'r') as f, open(sc_path, 'w') as o:
+                    for l in nr.nr2full(f):
+                        o.write(l + '\n')
+            finally:
+                os.remove(tmp)
+        t['write_sc'] = time.time() - t0
+        t0 = time.time()
+    if tables is None:
+        return dev, None, t0
+    exp = nr.device_expand(dev, tables)
+    t['expand'] = time.time() - t0
+    t['rows_collapsed'] = len(dev)
+    return exp, exp, time.time()
+
+
+def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage=False, collapse=False, **search_kw):
     """self-search of one proteome on the GPU, then IP / OT / CO relations from the hit RECORDS.
     device_stage=True: the records stay in HBM (search_device) and the candidate stage of find_orth runs on them there
     (find_orth.relations_from_device); they are downloaded only when `sc_path` asks for the file.
     device_stage='relations': the relation tables are computed on the device as well (find_orth.device_relation_tables_from_records)
     and the host only writes the text.
+    collapse=True (needs a true device_stage): exact duplicates are searched once and multiplied back on the device -- the lines are those
+    of find_orth on the .sc file nr.search_collapsed() writes, byte for byte, and `sc_path` receives that file's bytes (through the text
+    nr2full(), the cold path).  The timing dict then also holds 'collapse', 'expand', 'rows_collapsed'; 'rows' counts the expanded records.
+    Files nr.collapse_tables() refuses (an empty, repeated or ';;;'-holding id) raise its ValueError: the script chain serves them.
     -> (relation lines as bytes, dict of stage wall times in seconds; with device_stage also 'orth_candidates', or 'orth_relations')"""
     from . import find_orth, fsearch
+    if collapse and not device_stage:
+        raise ValueError("orthology_from_search: collapse=True expands the records on the device: device_stage must be True or 'relations'")
     t = {}
     t0 = time.time()
     data = open(fasta_path, 'rb').read()
-    ids = find_orth.fasta_ids(data)
+    tables = None
+    if collapse:
+        tables, data, ids = _collapse(data, t)
+    else:
+        ids = find_orth.fasta_ids(data)
     s = fsearch.Searcher(device=device, **search_kw)
     try:
         s.load_ref_bytes(data)
         s.load_queries_bytes(data)
-        t['load'] = time.time() - t0
+        t['load'] = time.time() - t0 - t.get('collapse', 0.)
         t0 = time.time()
         if device_stage:
-            return _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=device_stage == 'relations')
+            return _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=device_stage == 'relations', tables=tables)
         hits = s.search()
         t['search'] = time.time() - t0
         t0 = time.time()
@@ -48,69 +111,68 @@ def orthology_from_search(fasta_path, sc_path=None, coverage=.5, identity=0., no
     return lines, t
 
 
-def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=False):
+def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relations=False, tables=None):
     """orthology_from_search() from the search on, with the records left on the device (the caller closes the searcher)"""
-    import numpy as np
-    from . import find_orth, fsearch
-    dev = s.search_device()
-    t['search'] = time.time() - t0
-    t0 = time.time()
-    if sc_path:
-        raw = dev.tensor().cpu().numpy() if len(dev) else np.zeros(0, dtype=np.uint8)
-        arr, n = fsearch.hits_from_bytes(s, raw)
-        s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(sc_path), b'w'))
-        t['write_sc'] = time.time() - t0
-        t0 = time.time()
-    if relations:
-        names, tables = find_orth.device_relation_tables_from_records(dev, ids, ids, coverage, identity, norm, sep)
-        t['orth_relations'] = time.time() - t0
-        lines = find_orth.lines_from_tables(names, tables)
-    else:
-        names, tax, taxa, cand = find_orth._device_records(dev, ids, ids, coverage, identity, norm, sep)
-        t['orth_candidates'] = time.time() - t0
-        lines = find_orth.relations_from_candidates(names, tax, taxa, cand)
-    t['find_orth'] = time.time() - t0
-    t['rows'] = len(dev)
+    from . import find_orth
+    if tables is not None:
+        _check_collapsed(s, tables)
+    dev, owned, t0 = _search_records(s, tables, sc_path, t, t0)
+    try:
+        if relations:
+            names, rel = find_orth.device_relation_tables_from_records(dev, ids, ids, coverage, identity, norm, sep)
+            t['orth_relations'] = time.time() - t0
+            lines = find_orth.lines_from_tables(names, rel)
+        else:
+            names, tax, taxa, cand = find_orth._device_records(dev, ids, ids, coverage, identity, norm, sep)
+            t['orth_candidates'] = time.time() - t0
+            lines = find_orth.relations_from_candidates(names, tax, taxa, cand)
+        t['find_orth'] = time.time() - t0
+        t['rows'] = len(dev)
+    finally:
+        if owned is not None:
+            owned.close()
     return lines, t
 
 
 def groups_from_search(fasta_path, inflation=1.5, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage='all', orth_path=None, sc_path=None,
-                       algorithm='mcl', damp=0.5, **search_kw):
+                       algorithm='mcl', damp=0.5, collapse=False, **search_kw):
     """one process from a FASTA file to ortholog groups: self-search on the GPU, the relation tables on the device from the records in
     HBM (find_orth.device_relation_tables_from_records), the groups from those tables (find_cluster.groups_from_tables) -- what
     `bin/find_hit.py ... && bin/find_orth.py -i x.sc > x.orth && bin/find_cluster.py -i x.orth -a mcl -I <inflation>` prints, one
     group per line.  `device_stage`: find_cluster's (False | True | 'matrix' | 'all').  `algorithm='apc'`: the groups of
     `bin/find_cluster.py -i x.orth -a apc -d <damp>` instead (find_cluster.apc_from_tables; any true `device_stage` = its one device call
     from the rows to the exemplar labels); any other name raises ValueError before anything is loaded.  The .sc and the .orth file are
-    written only when `sc_path` / `orth_path` name them; nothing reads them.
+    written only when `sc_path` / `orth_path` name them; nothing reads them.  collapse=True: exact duplicates are searched once and the
+    records multiplied back on the device, as in orthology_from_search (the dict then also holds collapse, expand, rows_collapsed).
     -> (groups as lists of ids, dict of stage wall times in seconds: load, search, [write_sc,] orth_relations, [write_orth,] cluster,
     and the counts rows, relations, groups)"""
     if algorithm not in ('mcl', 'apc'):
         raise ValueError("groups_from_search: unknown algorithm %r ('mcl' and 'apc' are provided)" % (algorithm,))
-    import numpy as np
     from . import find_cluster, find_orth, fsearch
     t = {}
     t0 = time.time()
     data = open(fasta_path, 'rb').read()
-    ids = find_orth.fasta_ids(data)
+    members = None
+    if collapse:
+        members, data, ids = _collapse(data, t)
+    else:
+        ids = find_orth.fasta_ids(data)
     s = fsearch.Searcher(device=device, **search_kw)
     try:
         s.load_ref_bytes(data)
         s.load_queries_bytes(data)
-        t['load'] = time.time() - t0
+        t['load'] = time.time() - t0 - t.get('collapse', 0.)
         t0 = time.time()
-        dev = s.search_device()
-        t['search'] = time.time() - t0
-        t0 = time.time()
-        if sc_path:
-            raw = dev.tensor().cpu().numpy() if len(dev) else np.zeros(0, dtype=np.uint8)
-            arr, n = fsearch.hits_from_bytes(s, raw)
-            s._chk(s.L.so_write_sc(s.h, arr, n, os.fsencode(sc_path), b'w'))
-            t['write_sc'] = time.time() - t0
-            t0 = time.time()
-        names, tables = find_orth.device_relation_tables_from_records(dev, ids, ids, coverage, identity, norm, sep)
-        t['orth_relations'] = time.time() - t0
-        t['rows'] = len(dev)
+        if members is not None:
+            _check_collapsed(s, members)
+        dev, owned, t0 = _search_records(s, members, sc_path, t, t0)
+        try:
+            names, tables = find_orth.device_relation_tables_from_records(dev, ids, ids, coverage, identity, norm, sep)
+            t['orth_relations'] = time.time() - t0
+            t['rows'] = len(dev)
+        finally:
+            if owned is not None:
+                owned.close()
     finally:
         s.close()
     t0 = time.time()
