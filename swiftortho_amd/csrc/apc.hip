@@ -33,6 +33,7 @@
 // from id-coded rows" below.  so_apc (layout prepared on the host) and so_apc_rows (on the device) feed one function, apc_queue_loop, which
 // queues the four kernels above.  Only gene codes and labels are downloaded; the host waits three times (number of genes, list lengths, end).
 #include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 #include "../../include/sohit.h"
 
@@ -299,57 +300,29 @@ void split_by_length(const std::vector<u32>& ptr, std::vector<u32>& shorts, std:
     }
 }
 
-template <class T>
-void upload(DevBuf<T>& d, const std::vector<T>& h) {
-    d.ensure(h.size() + 2);
-    if (!h.empty()) HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-}
-
 // ---- the layout from id-coded rows, on the device (so_apc_rows) ----------------------------------------------------------------------
 // Rows come as id CODES (cx <= cy).  Genes are numbered by first appearance in cx0, cy0, cx1, ... as cnc.hip's plan numbers them
-// (atomicMin of the position per code, flag the positions that are a code's first, scan: the scan value at a code's first position is its
-// number); the taxa of the first positions are flagged and counted for the preference.  The entry list is never written: entry e is
+// (number_by_first_appearance, k_util.hip); the taxa of the first positions are flagged and counted for the preference.  The entry
+// list is never written: entry e is
 // (X_r, Y_r) for e = 2r, (Y_r, X_r) for e = 2r + 1 and (g, g) for e = 2 * rows + g, and every kernel below derives it from e.  A row of
 // the layout holds one entry per occurrence of its gene in the rows and its preference entry, and so does its column: ONE array of
 // pointers serves as rptr and cptr, one pair of lists as the short / long rows and columns.  A stable radix sort of (row of e, e) gives
 // the entries in row order, a second one of (column of e, e) the columns' entries in entry order.  Integer atomics only.
-inline dim3 rows_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-#define ROWS_TID ((size_t)blockIdx.x * 256u + threadIdx.x)
-#define ROWS_NONE 0xFFFFFFFFu
 
-__global__ __launch_bounds__(256) void k_apcr_first(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, u32* __restrict__ first) {
-    const size_t i = ROWS_TID;
+// after the numbering (flag[p]: position p is its code's first): the taxon of such a code is in use; cnt[g] = the occurrences of gene g
+__global__ __launch_bounds__(256) void k_apcr_count(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ flag,
+                                                    const int* __restrict__ taxon_of_code, const int* __restrict__ X, const int* __restrict__ Y,
+                                                    u32* __restrict__ taxflag, u32* __restrict__ cnt) {
+    const size_t i = tid256();
     if (i >= nr) return;
-    atomicMin(&first[cx[i]], (u32)(2 * i));
-    atomicMin(&first[cy[i]], (u32)(2 * i + 1));
-}
-// flag[p] = position p is its code's first; the taxon of such a code is in use
-__global__ __launch_bounds__(256) void k_apcr_firstflag(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
-                                                        const int* __restrict__ taxon_of_code, u32* __restrict__ flag, u32* __restrict__ taxflag) {
-    const size_t p = ROWS_TID;
-    if (p >= 2 * (size_t)nr) return;
-    const int code = (p & 1) ? cy[p >> 1] : cx[p >> 1];
-    const u32 f = first[code] == (u32)p ? 1u : 0u;
-    flag[p] = f;
-    if (f) atomicOr(&taxflag[taxon_of_code[code]], 1u);
-}
-// a code's number = the scan value at its first position; cnt[g] = the occurrences of gene g in the rows
-__global__ __launch_bounds__(256) void k_apcr_number(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
-                                                     const u32* __restrict__ flag, const u32* __restrict__ rank, int* __restrict__ X, int* __restrict__ Y,
-                                                     int* __restrict__ gene_code, u32* __restrict__ cnt) {
-    const size_t i = ROWS_TID;
-    if (i >= nr) return;
-    const int a = cx[i], b = cy[i];
-    const u32 x = rank[first[a]], y = rank[first[b]];
-    X[i] = (int)x, Y[i] = (int)y;
-    if (flag[2 * i]) gene_code[rank[2 * i]] = a;
-    if (flag[2 * i + 1]) gene_code[rank[2 * i + 1]] = b;
-    atomicAdd(&cnt[x], 1u);
-    atomicAdd(&cnt[y], 1u);
+    if (flag[2 * i]) atomicOr(&taxflag[taxon_of_code[cx[i]]], 1u);
+    if (flag[2 * i + 1]) atomicOr(&taxflag[taxon_of_code[cy[i]]], 1u);
+    atomicAdd(&cnt[X[i]], 1u);
+    atomicAdd(&cnt[Y[i]], 1u);
 }
 // len[g] = cnt[g] + 1 (the preference entry), len[D] = 0 for the scan that ends the pointers; which list gene g goes to
 __global__ __launch_bounds__(256) void k_apcr_len(const u32* __restrict__ cnt, u32 D, u32* __restrict__ len, u32* __restrict__ sflag, u32* __restrict__ lflag) {
-    const size_t g = ROWS_TID;
+    const size_t g = tid256();
     if (g > D) return;
     if (g == D) {
         len[g] = 0;
@@ -360,7 +333,7 @@ __global__ __launch_bounds__(256) void k_apcr_len(const u32* __restrict__ cnt, u
 }
 __global__ __launch_bounds__(256) void k_apcr_lists(const u32* __restrict__ sflag, const u32* __restrict__ spos, const u32* __restrict__ lflag,
                                                     const u32* __restrict__ lpos, u32 D, u32* __restrict__ shorts, u32* __restrict__ longs) {
-    const size_t g = ROWS_TID;
+    const size_t g = tid256();
     if (g >= D) return;
     if (sflag[g]) shorts[spos[g]] = (u32)g;
     if (lflag[g]) longs[lpos[g]] = (u32)g;
@@ -376,7 +349,7 @@ __device__ __forceinline__ void apcr_entry(u32 e, u32 nr2, const int* __restrict
 }
 template <bool BYCOL>
 __global__ __launch_bounds__(256) void k_apcr_keys(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, u64* __restrict__ key, u32* __restrict__ val) {
-    const size_t e = ROWS_TID;
+    const size_t e = tid256();
     if (e >= N) return;
     int row, col;
     apcr_entry((u32)e, nr2, X, Y, row, col);
@@ -386,7 +359,7 @@ __global__ __launch_bounds__(256) void k_apcr_keys(const int* __restrict__ X, co
 __global__ __launch_bounds__(256) void k_apcr_place(const int* __restrict__ X, const int* __restrict__ Y, const double* __restrict__ z, u32 nr2, u32 N,
                                                     const u32* __restrict__ rorder, float pref, u32* __restrict__ place, int* __restrict__ kcol,
                                                     float* __restrict__ s) {
-    const size_t p = ROWS_TID;
+    const size_t p = tid256();
     if (p >= N) return;
     const u32 e = rorder[p];
     int row, col;
@@ -395,7 +368,7 @@ __global__ __launch_bounds__(256) void k_apcr_place(const int* __restrict__ X, c
 }
 __global__ __launch_bounds__(256) void k_apcr_cols(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, const u32* __restrict__ corder,
                                                    const u32* __restrict__ place, u32* __restrict__ cpos, int* __restrict__ crow) {
-    const size_t q = ROWS_TID;
+    const size_t q = tid256();
     if (q >= N) return;
     const u32 e = corder[q];
     int row, col;
@@ -406,19 +379,12 @@ __global__ __launch_bounds__(256) void k_apcr_cols(const int* __restrict__ X, co
 __global__ __launch_bounds__(256) void k_apcr_entries(const int* __restrict__ X, const int* __restrict__ Y, u32 nr2, u32 N, const u32* __restrict__ place,
                                                       const float* __restrict__ s, const float* __restrict__ R, const float* __restrict__ A, int* __restrict__ orow,
                                                       int* __restrict__ ocol, float* __restrict__ os, float* __restrict__ o_r, float* __restrict__ o_a) {
-    const size_t e = ROWS_TID;
+    const size_t e = tid256();
     if (e >= N) return;
     int row, col;
     apcr_entry((u32)e, nr2, X, Y, row, col);
     const u32 p = place[e];
     orow[e] = row, ocol[e] = col, os[e] = s[p], o_r[e] = R[p], o_a[e] = A[p];
-}
-
-template <class T>
-T* rows_alloc(size_t n) {
-    T* p = (T*)malloc((n ? n : 1) * sizeof(T));
-    if (!p) throw SoError("so_apc_rows: out of host memory");
-    return p;
 }
 
 thread_local std::string g_apc_err;
@@ -447,13 +413,7 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         const size_t D = (size_t)n_genes, N = (size_t)n_entries;
         for (size_t e = 0; e < N; ++e)
             if (row[e] < 0 || row[e] >= n_genes || col[e] < 0 || col[e] >= n_genes) throw SoError("so_apc: entry " + std::to_string(e) + " names a gene outside 0 .. n_genes - 1");
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_apc: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_apc: device index out of range");
-        HIP_CHECK(hipSetDevice(device));
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
+        check_device("so_apc", device);
 
         // rows: the entries in row order; columns: positions (in row order) and rows of each column's entries, in entry order
         std::vector<u32> rptr, rorder, cptr, corder;
@@ -468,17 +428,14 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         split_by_length(rptr, rshort, rlong);
         split_by_length(cptr, cshort, clong);
 
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipStreamCreate(&st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{st};
+        DeviceCall call(device);
+        const hipStream_t st = call.st;
         DevBuf<u32> d_rptr, d_cptr, d_cpos, d_rshort, d_rlong, d_cshort, d_clong;
         DevBuf<int> d_kcol, d_crow;
         DevBuf<float> d_s;
-        upload(d_rptr, rptr), upload(d_cptr, cptr), upload(d_cpos, cpos), upload(d_kcol, kcol), upload(d_crow, crow), upload(d_s, sc);
-        upload(d_rshort, rshort), upload(d_rlong, rlong), upload(d_cshort, cshort), upload(d_clong, clong);
+        auto up = [&](auto& d, const auto& h) { upload(d, h.data(), h.size(), st); };
+        up(d_rptr, rptr), up(d_cptr, cptr), up(d_cpos, cpos), up(d_kcol, kcol), up(d_crow, crow), up(d_s, sc);
+        up(d_rshort, rshort), up(d_rlong, rlong), up(d_cshort, cshort), up(d_clong, clong);
         const ApcLayout lay{d_rptr.p, d_cptr.p, d_cpos.p, d_rshort.p, d_rlong.p, d_cshort.p, d_clong.p, d_kcol.p, d_crow.p, d_s.p,
                             (u32)rshort.size(), (u32)rlong.size(), (u32)cshort.size(), (u32)clong.size()};
         ApcLoop lp;
@@ -493,18 +450,13 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
             HIP_CHECK(hipMemcpy(ha.data(), lp.A.p, N * sizeof(float), hipMemcpyDeviceToHost));
         }
         out->n_genes = n_genes, out->n_entries = n_entries, out->rounds = rounds;
-        out->labels = (int64_t*)malloc((D ? D : 1) * sizeof(int64_t));
-        out->r = (float*)malloc((N ? N : 1) * sizeof(float));
-        out->a = (float*)malloc((N ? N : 1) * sizeof(float));
-        if (!out->labels || !out->r || !out->a) {
-            so_apc_free(out);
-            throw SoError("so_apc: out of host memory");
-        }
+        out->labels = host_array<int64_t>("so_apc", D), out->r = host_array<float>("so_apc", N), out->a = host_array<float>("so_apc", N);
         for (size_t i = 0; i < D; ++i) out->labels[i] = lab[i];
         for (size_t e = 0; e < N; ++e) out->r[e] = hr[place[e]], out->a[e] = ha[place[e]];   // back to entry order
         g_apc_err.clear();
         return 0;
     } catch (const std::exception& e) {
+        if (out) so_apc_free(out);
         g_apc_err = e.what();
         return 1;
     }
@@ -534,39 +486,23 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
                 throw SoError("so_apc_rows: row " + std::to_string(i) + " names a code outside 0 .. n_codes - 1");
             if (cx[i] > cy[i]) throw SoError("so_apc_rows: row " + std::to_string(i) + " has cx > cy (fc2mat drops such rows before anything is numbered)");
         }
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_apc_rows: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_apc_rows: device index out of range");
+        const char* const who = "so_apc_rows";
+        check_device(who, device);
         out->n_codes = n_codes, out->n_rows = n_rows, out->rounds = rounds;
         const bool want_entries = (flags & 1) != 0;
         if (!N1) {   // no row: no gene, no entry, nothing to launch
-            out->gene_code = rows_alloc<int32_t>(0), out->labels = rows_alloc<int64_t>(0);
+            out->gene_code = host_array<int32_t>(who, 0), out->labels = host_array<int64_t>(who, 0);
             if (want_entries)
-                out->row = rows_alloc<int32_t>(0), out->col = rows_alloc<int32_t>(0), out->score = rows_alloc<float>(0), out->r = rows_alloc<float>(0),
-                out->a = rows_alloc<float>(0);
+                out->row = host_array<int32_t>(who, 0), out->col = host_array<int32_t>(who, 0), out->score = host_array<float>(who, 0), out->r = host_array<float>(who, 0),
+                out->a = host_array<float>(who, 0);
             g_apc_err.clear();
             return 0;
         }
 
-        HIP_CHECK(hipSetDevice(device));
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipStreamCreate(&st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{st};
+        DeviceCall call(device);
+        const hipStream_t st = call.st;
         const u32 nr = (u32)N1, nr2 = 2 * nr;
         const size_t N2 = 2 * N1, T = (size_t)n_taxa, Dmax = std::min(C, N2);
-        int waits = 0;
-        auto read2 = [&](const u32* a, u32& va, const u32* b, u32& vb) {   // one host wait for two device words
-            HIP_CHECK(hipMemcpyAsync(&va, a, sizeof(u32), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipMemcpyAsync(&vb, b, sizeof(u32), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++waits;
-        };
 
         // genes numbered by first appearance, the taxa in use, the occurrences of every gene
         DevBuf<int> d_cx, d_cy, d_tax, d_x, d_y, d_gene;
@@ -580,17 +516,14 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         HIP_CHECK(hipMemcpyAsync(d_cy.p, cy, N1 * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_z.p, z, N1 * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_tax.p, taxon_of_code, C * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemsetAsync(d_first.p, 0xFF, C * sizeof(u32), st));   // ROWS_NONE (positions stay below 2^32 - 1)
         HIP_CHECK(hipMemsetAsync(d_taxflag.p, 0, T * sizeof(u32), st));
         HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (Dmax + 2) * sizeof(u32), st));
-        hipLaunchKernelGGL(k_apcr_first, rows_grid(N1), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p);
-        hipLaunchKernelGGL(k_apcr_firstflag, rows_grid(N2), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_tax.p, d_flag.p, d_taxflag.p);
-        const u32* d_ngenes = scan_u32(d_flag.p, d_rank.p, N2, false, d_tmp_a.p, st);
+        const u32* d_ngenes = number_by_first_appearance(d_cx.p, d_cy.p, nr, (u32)C, d_first.p, d_flag.p, d_rank.p, d_tmp_a.p, d_x.p, d_y.p, d_gene.p, st);
+        hipLaunchKernelGGL(k_apcr_count, grid256(N1), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_flag.p, d_tax.p, d_x.p, d_y.p, d_taxflag.p, d_cnt.p);
         const u32* d_ntaxa = scan_u32(d_taxflag.p, d_taxpos.p, T, false, d_tmp_b.p, st);
-        hipLaunchKernelGGL(k_apcr_number, rows_grid(N1), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_flag.p, d_rank.p, d_x.p, d_y.p, d_gene.p, d_cnt.p);
         HIP_CHECK(hipGetLastError());
         u32 n = 0, ntax = 0;
-        read2(d_ngenes, n, d_ntaxa, ntax);
+        call.read(d_ngenes, n, d_ntaxa, ntax);
         if (n < 1 || n > Dmax || ntax < 1 || ntax > T || ntax > n)
             throw SoError("so_apc_rows: internal error: " + std::to_string(n) + " genes of " + std::to_string(ntax) + " taxa in " + std::to_string(nr) + " rows");
         if (n > (1u << 24)) throw SoError("so_apc_rows" APC_TOO_MANY_GENES);
@@ -602,11 +535,11 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         DevBuf<u32> d_len, d_ptr, d_sflag, d_lflag, d_spos, d_lpos, d_short, d_long;
         d_len.ensure(D + 3), d_ptr.ensure(D + 3), d_sflag.ensure(D + 2), d_lflag.ensure(D + 2), d_spos.ensure(D + 2), d_lpos.ensure(D + 2), d_short.ensure(D + 2),
             d_long.ensure(D + 2);
-        hipLaunchKernelGGL(k_apcr_len, rows_grid(D + 1), dim3(256), 0, st, d_cnt.p, n, d_len.p, d_sflag.p, d_lflag.p);
+        hipLaunchKernelGGL(k_apcr_len, grid256(D + 1), dim3(256), 0, st, d_cnt.p, n, d_len.p, d_sflag.p, d_lflag.p);
         scan_u32(d_len.p, d_ptr.p, D + 1, false, d_tmp_a.p, st);
         const u32* d_nshort = scan_u32(d_sflag.p, d_spos.p, D, false, d_tmp_b.p, st);
         const u32* d_nlong = scan_u32(d_lflag.p, d_lpos.p, D, false, d_tmp_c.p, st);
-        hipLaunchKernelGGL(k_apcr_lists, rows_grid(D), dim3(256), 0, st, d_sflag.p, d_spos.p, d_lflag.p, d_lpos.p, n, d_short.p, d_long.p);
+        hipLaunchKernelGGL(k_apcr_lists, grid256(D), dim3(256), 0, st, d_sflag.p, d_spos.p, d_lflag.p, d_lpos.p, n, d_short.p, d_long.p);
 
         // the entries in row order, the columns' entries in entry order
         const int bits = ceil_log2((u64)D);
@@ -617,15 +550,15 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         DevBuf<u8> d_sort_tmp;
         d_key.ensure(N + 2), d_skey.ensure(N + 2), d_val.ensure(N + 2), d_order.ensure(N + 2), d_place.ensure(N + 2), d_cpos.ensure(N + 2), d_kcol.ensure(N + 2);
         d_crow.ensure(N + 2), d_s.ensure(N + 2), d_sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(N, bits) + 256);
-        hipLaunchKernelGGL(k_apcr_keys<false>, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
+        hipLaunchKernelGGL(k_apcr_keys<false>, grid256(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
         sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_val.p, d_order.p, N, bits, st);   // stable: entry order inside a row
-        hipLaunchKernelGGL(k_apcr_place, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, d_z.p, nr2, ne, d_order.p, pref, d_place.p, d_kcol.p, d_s.p);
-        hipLaunchKernelGGL(k_apcr_keys<true>, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
+        hipLaunchKernelGGL(k_apcr_place, grid256(N), dim3(256), 0, st, d_x.p, d_y.p, d_z.p, nr2, ne, d_order.p, pref, d_place.p, d_kcol.p, d_s.p);
+        hipLaunchKernelGGL(k_apcr_keys<true>, grid256(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_key.p, d_val.p);
         sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_val.p, d_order.p, N, bits, st);   // stable: entry order inside a column
-        hipLaunchKernelGGL(k_apcr_cols, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_order.p, d_place.p, d_cpos.p, d_crow.p);
+        hipLaunchKernelGGL(k_apcr_cols, grid256(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_order.p, d_place.p, d_cpos.p, d_crow.p);
         HIP_CHECK(hipGetLastError());
         u32 nshort = 0, nlong = 0;
-        read2(d_nshort, nshort, d_nlong, nlong);
+        call.read(d_nshort, nshort, d_nlong, nlong);
         if ((size_t)nshort + nlong != D) throw SoError("so_apc_rows: internal error: " + std::to_string(nshort) + " short and " + std::to_string(nlong) + " long rows of " + std::to_string(n));
 
         const ApcLayout lay{d_ptr.p, d_ptr.p, d_cpos.p, d_short.p, d_long.p, d_short.p, d_long.p, d_kcol.p, d_crow.p, d_s.p, nshort, nlong, nshort, nlong};
@@ -633,16 +566,16 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         apc_queue_loop(lay, D, N, lp, damp, rounds, st);
 
         out->n_genes = n, out->n_entries = (int64_t)N, out->n_taxa_used = ntax;
-        out->gene_code = rows_alloc<int32_t>(D), out->labels = rows_alloc<int64_t>(D);
+        out->gene_code = host_array<int32_t>(who, D), out->labels = host_array<int64_t>(who, D);
         std::vector<int> lab(D);
         HIP_CHECK(hipMemcpyAsync(out->gene_code, d_gene.p, D * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(lab.data(), lp.lab.p, D * sizeof(int), hipMemcpyDeviceToHost, st));
         DevBuf<int> d_orow, d_ocol;
         DevBuf<float> d_os, d_or, d_oa;
         if (want_entries) {
-            out->row = rows_alloc<int32_t>(N), out->col = rows_alloc<int32_t>(N), out->score = rows_alloc<float>(N), out->r = rows_alloc<float>(N), out->a = rows_alloc<float>(N);
+            out->row = host_array<int32_t>(who, N), out->col = host_array<int32_t>(who, N), out->score = host_array<float>(who, N), out->r = host_array<float>(who, N), out->a = host_array<float>(who, N);
             d_orow.ensure(N + 2), d_ocol.ensure(N + 2), d_os.ensure(N + 2), d_or.ensure(N + 2), d_oa.ensure(N + 2);
-            hipLaunchKernelGGL(k_apcr_entries, rows_grid(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_place.p, d_s.p, lp.R.p, lp.A.p, d_orow.p, d_ocol.p, d_os.p, d_or.p,
+            hipLaunchKernelGGL(k_apcr_entries, grid256(N), dim3(256), 0, st, d_x.p, d_y.p, nr2, ne, d_place.p, d_s.p, lp.R.p, lp.A.p, d_orow.p, d_ocol.p, d_os.p, d_or.p,
                                d_oa.p);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpyAsync(out->row, d_orow.p, N * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -652,9 +585,9 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
             HIP_CHECK(hipMemcpyAsync(out->a, d_oa.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
         }
         HIP_CHECK(hipStreamSynchronize(st));
-        ++waits;
+        ++call.waits;
         for (size_t i = 0; i < D; ++i) out->labels[i] = lab[i];
-        out->waits = waits;
+        out->waits = call.waits;
         g_apc_err.clear();
         return 0;
     } catch (const std::exception& e) {

@@ -40,6 +40,7 @@
 // so_cnc_plan (the k_plan_* kernels further down) wraps the same stage into the whole plan cnc needs in front of its batches: from
 // id codes to gene numbers, through the component stage where the arrays lie, to the kept rows in `sort -n` order with their cuts.
 #include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 #include "../../include/sohit.h"
 
@@ -51,8 +52,7 @@
 
 namespace {
 
-#define CNC_JUMP 32          // label steps one lane follows per sweep
-#define CNC_NONE 0xFFFFFFFFu   // no row yet (row indices stay below 2^31)
+#define CNC_JUMP 32   // label steps one lane follows per sweep
 
 // doubles (no NaN) -> u64 that order the same way; -0.0 and +0.0 share one image
 __device__ __forceinline__ u64 cnc_image(double z) {
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_cnc_grp(const u32* __restrict__ comp1, 
     int r = -1;
     if (c != 0) {
         const u32 f = first[lab2[c]];
-        if (f != CNC_NONE) r = (int)rank[f];
+        if (f != NONE32) r = (int)rank[f];
     }
     grp[g] = r;
 }
@@ -175,16 +175,14 @@ __global__ __launch_bounds__(256) void k_cnc_keep(const int* __restrict__ x, con
     keep[i] = (a == b && a != 0) ? 1 : 0;
 }
 
-inline dim3 cnc_grid(u32 n) { return dim3((n + 255u) / 256u); }
-
 // hook + jump until a sweep moves no label; -> sweeps run, the confirming one included
 template <int LEVEL>
 int cnc_sweeps(const int* x, const int* y, u32 nr, const u8* tie, const u32* comp1, u32* lab, u32 nodes, u32* changed, hipStream_t st, const std::string& who) {
     const u64 cap = (u64)nodes + 2;
     for (u64 s = 1; s <= cap; ++s) {
         HIP_CHECK(hipMemsetAsync(changed, 0, sizeof(u32), st));
-        hipLaunchKernelGGL(k_cnc_hook<LEVEL>, cnc_grid(nr), dim3(256), 0, st, x, y, nr, tie, comp1, lab, changed);
-        hipLaunchKernelGGL(k_cnc_jump, cnc_grid(nodes), dim3(256), 0, st, lab, nodes, changed);
+        hipLaunchKernelGGL(k_cnc_hook<LEVEL>, grid256(nr), dim3(256), 0, st, x, y, nr, tie, comp1, lab, changed);
+        hipLaunchKernelGGL(k_cnc_jump, grid256(nodes), dim3(256), 0, st, lab, nodes, changed);
         u32 moved = 0;
         HIP_CHECK(hipMemcpyAsync(&moved, changed, sizeof(u32), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
@@ -212,15 +210,15 @@ bool cnc_component_stage(const int* d_x, const int* d_y, const double* d_z, u32 
     const size_t D = n, N = nr;
     c.best.ensure(D + 2), c.tie.ensure(N + 2), c.lab.ensure(D + 2), c.changed.ensure(4);
     HIP_CHECK(hipMemsetAsync(c.best.p, 0, D * sizeof(unsigned long long), st));   // below every weight's image
-    hipLaunchKernelGGL(k_cnc_best, cnc_grid(nr), dim3(256), 0, st, d_x, d_y, d_z, nr, c.best.p);
-    hipLaunchKernelGGL(k_cnc_tie, cnc_grid(nr), dim3(256), 0, st, d_x, d_y, d_z, nr, c.best.p, c.tie.p);
-    hipLaunchKernelGGL(k_cnc_iota, cnc_grid(n), dim3(256), 0, st, c.lab.p, n);
+    hipLaunchKernelGGL(k_cnc_best, grid256(nr), dim3(256), 0, st, d_x, d_y, d_z, nr, c.best.p);
+    hipLaunchKernelGGL(k_cnc_tie, grid256(nr), dim3(256), 0, st, d_x, d_y, d_z, nr, c.best.p, c.tie.p);
+    hipLaunchKernelGGL(k_cnc_iota, grid256(n), dim3(256), 0, st, c.lab.p, n);
     c.sweeps1 = cnc_sweeps<1>(d_x, d_y, nr, c.tie.p, nullptr, c.lab.p, n, c.changed.p, st, who);
 
     c.root.ensure(D + 2), c.below.ensure(D + 2), c.comp1.ensure(D + 2), c.tmp.ensure(scan_u32_temp_elems(std::max(D, N)) + 8);
-    hipLaunchKernelGGL(k_cnc_roots, cnc_grid(n), dim3(256), 0, st, c.lab.p, n, c.root.p);
+    hipLaunchKernelGGL(k_cnc_roots, grid256(n), dim3(256), 0, st, c.lab.p, n, c.root.p);
     const u32* d_roots = scan_u32(c.root.p, c.below.p, D, false, c.tmp.p, st);
-    hipLaunchKernelGGL(k_cnc_number, cnc_grid(n), dim3(256), 0, st, c.lab.p, c.below.p, d_roots, n, c.comp1.p);
+    hipLaunchKernelGGL(k_cnc_number, grid256(n), dim3(256), 0, st, c.lab.p, c.below.p, d_roots, n, c.comp1.p);
     u32 roots = 0;
     HIP_CHECK(hipMemcpyAsync(&roots, d_roots, sizeof(u32), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -232,57 +230,30 @@ bool cnc_component_stage(const int* d_x, const int* d_y, const double* d_z, u32 
     }
 
     c.lab2.ensure((size_t)roots + 2), c.first.ensure((size_t)roots + 2), c.flag.ensure(N + 2), c.rank.ensure(N + 2), c.grp.ensure(D + 2);
-    hipLaunchKernelGGL(k_cnc_iota, cnc_grid(roots), dim3(256), 0, st, c.lab2.p, roots);
+    hipLaunchKernelGGL(k_cnc_iota, grid256(roots), dim3(256), 0, st, c.lab2.p, roots);
     c.sweeps2 = cnc_sweeps<2>(d_x, d_y, nr, nullptr, c.comp1.p, c.lab2.p, roots, c.changed.p, st, who);
     c.waits += c.sweeps2;
-    HIP_CHECK(hipMemsetAsync(c.first.p, 0xFF, (size_t)roots * sizeof(u32), st));   // CNC_NONE
-    hipLaunchKernelGGL(k_cnc_first, cnc_grid(nr), dim3(256), 0, st, d_x, d_y, nr, c.comp1.p, c.lab2.p, c.first.p);
-    hipLaunchKernelGGL(k_cnc_firstflag, cnc_grid(nr), dim3(256), 0, st, d_x, d_y, nr, c.comp1.p, c.lab2.p, c.first.p, c.flag.p);
+    HIP_CHECK(hipMemsetAsync(c.first.p, 0xFF, (size_t)roots * sizeof(u32), st));   // NONE32
+    hipLaunchKernelGGL(k_cnc_first, grid256(nr), dim3(256), 0, st, d_x, d_y, nr, c.comp1.p, c.lab2.p, c.first.p);
+    hipLaunchKernelGGL(k_cnc_firstflag, grid256(nr), dim3(256), 0, st, d_x, d_y, nr, c.comp1.p, c.lab2.p, c.first.p, c.flag.p);
     c.d_ngrp = scan_u32(c.flag.p, c.rank.p, N, false, c.tmp.p, st);
-    hipLaunchKernelGGL(k_cnc_grp, cnc_grid(n), dim3(256), 0, st, c.comp1.p, c.lab2.p, c.first.p, c.rank.p, n, c.grp.p);
+    hipLaunchKernelGGL(k_cnc_grp, grid256(n), dim3(256), 0, st, c.comp1.p, c.lab2.p, c.first.p, c.rank.p, n, c.grp.p);
     return true;
 }
 
 // ---- the row plan (so_cnc_plan): what cnc does between the id codes and the batches -------------------------------------------------
 // Rows come as id CODES (cx <= cy, code order = the ids' byte order).  Genes are numbered by first appearance in cx0, cy0, cx1, ...
-// (atomicMin of the position per code, flag the positions that are a code's first, scan: the scan value at a code's first position is
-// its number); the component stage runs on those numbers; the kept rows are flagged, scanned and compacted into (key, row) pairs; a
-// stable radix sort puts them into (grp as a signed number, cx, cy) order -- grp + 1 is the unsigned image: the pool -1 becomes 0, group 0
-// is never kept -- and rows with an equal triple stay in file order; the positions where grp changes (`cut`) and where the whole triple
-// repeats (`tied`) are a neighbour comparison, a scan and a compaction each.  Integer atomics only.
-inline dim3 plan_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-#define PLAN_TID ((size_t)blockIdx.x * 256u + threadIdx.x)
+// (number_by_first_appearance, k_util.hip); the component stage runs on those numbers; the kept rows are flagged, scanned and compacted
+// into (key, row) pairs; a stable radix sort puts them into (grp as a signed number, cx, cy) order -- grp + 1 is the unsigned image: the
+// pool -1 becomes 0, group 0 is never kept -- and rows with an equal triple stay in file order; the positions where grp changes (`cut`)
+// and where the whole triple repeats (`tied`) are a neighbour comparison, a scan and a compaction each.  Integer atomics only.
 
-__global__ __launch_bounds__(256) void k_plan_first(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, u32* __restrict__ first) {
-    const size_t i = PLAN_TID;
-    if (i >= nr) return;
-    atomicMin(&first[cx[i]], (u32)(2 * i));
-    atomicMin(&first[cy[i]], (u32)(2 * i + 1));
-}
-__global__ __launch_bounds__(256) void k_plan_firstflag(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
-                                                        u32* __restrict__ flag) {
-    const size_t p = PLAN_TID;
-    if (p >= 2 * (size_t)nr) return;
-    const int code = (p & 1) ? cy[p >> 1] : cx[p >> 1];
-    flag[p] = first[code] == (u32)p ? 1u : 0u;
-}
-// a code's number = the scan value at its first position
-__global__ __launch_bounds__(256) void k_plan_number(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
-                                                     const u32* __restrict__ flag, const u32* __restrict__ rank, int* __restrict__ X, int* __restrict__ Y,
-                                                     int* __restrict__ gene_code) {
-    const size_t i = PLAN_TID;
-    if (i >= nr) return;
-    const int a = cx[i], b = cy[i];
-    X[i] = (int)rank[first[a]], Y[i] = (int)rank[first[b]];
-    if (flag[2 * i]) gene_code[rank[2 * i]] = a;
-    if (flag[2 * i + 1]) gene_code[rank[2 * i + 1]] = b;
-}
 // kept row i -> slot pos[i]: its row index and its key.  ONE: grp + 1, cx, cy in one word (cb bits per code);  else cx << 32 | cy
 template <bool ONE>
 __global__ __launch_bounds__(256) void k_plan_keys(const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ X, const int* __restrict__ grp,
                                                    u32 nr, const u32* __restrict__ flag, const u32* __restrict__ pos, int cb, u64* __restrict__ key,
                                                    u32* __restrict__ row) {
-    const size_t i = PLAN_TID;
+    const size_t i = tid256();
     if (i >= nr || !flag[i]) return;
     const u32 p = pos[i];
     row[p] = (u32)i;
@@ -292,13 +263,13 @@ __global__ __launch_bounds__(256) void k_plan_keys(const int* __restrict__ cx, c
 // the second pass's key of the rows in (cx, cy) order
 __global__ __launch_bounds__(256) void k_plan_grpkey(const int* __restrict__ X, const int* __restrict__ grp, const u32* __restrict__ row, u32 nk,
                                                      u64* __restrict__ key) {
-    const size_t p = PLAN_TID;
+    const size_t p = tid256();
     if (p < nk) key[p] = (u64)(u32)(grp[X[row[p]]] + 1);
 }
 // position p >= 1 of the sorted rows against p - 1 (position 0 carries no flag)
 __global__ __launch_bounds__(256) void k_plan_edges(const int* __restrict__ cx, const int* __restrict__ cy, const int* __restrict__ X, const int* __restrict__ grp,
                                                     const u32* __restrict__ order, u32 nk, u32* __restrict__ cutflag, u32* __restrict__ tiedflag) {
-    const size_t p = PLAN_TID;
+    const size_t p = tid256();
     if (p >= nk) return;
     u32 c = 0, t = 0;
     if (p) {
@@ -311,17 +282,10 @@ __global__ __launch_bounds__(256) void k_plan_edges(const int* __restrict__ cx, 
 }
 __global__ __launch_bounds__(256) void k_plan_compact(const u32* __restrict__ cutflag, const u32* __restrict__ cutpos, const u32* __restrict__ tiedflag,
                                                       const u32* __restrict__ tiedpos, u32 nk, int* __restrict__ cut, int* __restrict__ tied) {
-    const size_t p = PLAN_TID;
+    const size_t p = tid256();
     if (p >= nk) return;
     if (cutflag[p]) cut[cutpos[p]] = (int)p;
     if (tiedflag[p]) tied[tiedpos[p]] = (int)p;
-}
-
-template <class T>
-T* plan_alloc(size_t n) {
-    T* p = (T*)malloc((n ? n : 1) * sizeof(T));
-    if (!p) throw SoError("so_cnc_plan: out of host memory");
-    return p;
 }
 
 thread_local std::string g_cnc_err;
@@ -356,14 +320,9 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
             for (size_t g = 0; g < seen.size(); ++g)
                 if (!seen[g]) throw SoError("so_cnc_groups: gene " + std::to_string(g) + " occurs in no row (genes are numbered by first appearance)");
         }
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_cnc_groups: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_cnc_groups: device index out of range");
+        check_device("so_cnc_groups", device);
 
-        out->comp1 = (int64_t*)malloc((D ? D : 1) * sizeof(int64_t));
-        out->grp = (int64_t*)malloc((D ? D : 1) * sizeof(int64_t));
-        out->keep = (uint8_t*)malloc(N ? N : 1);
-        if (!out->comp1 || !out->grp || !out->keep) throw SoError("so_cnc_groups: out of host memory");
+        out->comp1 = host_array<int64_t>("so_cnc_groups", D), out->grp = host_array<int64_t>("so_cnc_groups", D), out->keep = host_array<uint8_t>("so_cnc_groups", N);
         out->n_genes = n_genes, out->n_rows = n_rows;
         // no gene or no row: nothing to launch (a grid of 0 blocks is an invalid configuration).  Without a row no gene is linked:
         // group_numbers() leaves every comp1 at 0 and every grp at -1
@@ -380,16 +339,8 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
             return 0;
         }
 
-        HIP_CHECK(hipSetDevice(device));
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipStreamCreate(&st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{st};
+        DeviceCall call(device);
+        const hipStream_t st = call.st;
         const u32 n = (u32)D, nr = (u32)N;
         DevBuf<int> d_x, d_y;
         DevBuf<double> d_z;
@@ -407,7 +358,7 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
             return 0;
         }
         d_keep.ensure(N + 2);
-        hipLaunchKernelGGL(k_cnc_keep<u8>, cnc_grid(nr), dim3(256), 0, st, d_x.p, d_y.p, nr, c.grp.p, d_keep.p);
+        hipLaunchKernelGGL(k_cnc_keep<u8>, grid256(nr), dim3(256), 0, st, d_x.p, d_y.p, nr, c.grp.p, d_keep.p);
         HIP_CHECK(hipGetLastError());
         u32 ngrp = 0;
         std::vector<u32> hc(D);
@@ -449,36 +400,20 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
             if (cx[i] > cy[i]) throw SoError("so_cnc_plan: row " + std::to_string(i) + " has cx > cy (cnc drops such rows before anything is numbered)");
             if (z[i] != z[i]) throw SoError("so_cnc_plan: row " + std::to_string(i) + " has a NaN weight (numpy's answer to it has no integer order; not served)");
         }
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_cnc_plan: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_cnc_plan: device index out of range");
+        check_device("so_cnc_plan", device);
         out->n_codes = n_codes, out->n_rows = n_rows;
+        auto alloc = [](size_t n) { return host_array<int32_t>("so_cnc_plan", n); };
         if (!N) {   // no row: no gene, nothing kept, nothing to launch
-            out->gene_code = plan_alloc<int32_t>(0), out->x = plan_alloc<int32_t>(0), out->y = plan_alloc<int32_t>(0), out->comp1 = plan_alloc<int32_t>(0);
-            out->grp = plan_alloc<int32_t>(0), out->order = plan_alloc<int32_t>(0), out->cut = plan_alloc<int32_t>(0), out->tied = plan_alloc<int32_t>(0);
+            out->gene_code = alloc(0), out->x = alloc(0), out->y = alloc(0), out->comp1 = alloc(0);
+            out->grp = alloc(0), out->order = alloc(0), out->cut = alloc(0), out->tied = alloc(0);
             g_cnc_err.clear();
             return 0;
         }
 
-        HIP_CHECK(hipSetDevice(device));
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipStreamCreate(&st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{st};
+        DeviceCall call(device);
+        const hipStream_t st = call.st;
         const u32 nr = (u32)N;
         const size_t C = (size_t)n_codes, N2 = 2 * N;
-        int waits = 0;
-        auto read2 = [&](const u32* a, u32& va, const u32* b, u32& vb) {   // one host wait for up to two device words
-            if (a) HIP_CHECK(hipMemcpyAsync(&va, a, sizeof(u32), hipMemcpyDeviceToHost, st));
-            if (b) HIP_CHECK(hipMemcpyAsync(&vb, b, sizeof(u32), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++waits;
-        };
 
         // genes numbered by first appearance
         DevBuf<int> d_cx, d_cy, d_x, d_y, d_gene;
@@ -490,20 +425,14 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         HIP_CHECK(hipMemcpyAsync(d_cx.p, cx, N * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_cy.p, cy, N * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_z.p, z, N * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemsetAsync(d_first.p, 0xFF, C * sizeof(u32), st));   // CNC_NONE (positions stay below 2^32 - 1)
-        hipLaunchKernelGGL(k_plan_first, plan_grid(N), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p);
-        hipLaunchKernelGGL(k_plan_firstflag, plan_grid(N2), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_flag.p);
-        const u32* d_ngenes = scan_u32(d_flag.p, d_rank.p, N2, false, d_tmp_a.p, st);
-        hipLaunchKernelGGL(k_plan_number, plan_grid(N), dim3(256), 0, st, d_cx.p, d_cy.p, nr, d_first.p, d_flag.p, d_rank.p, d_x.p, d_y.p, d_gene.p);
-        u32 n = 0, none = 0;
-        read2(d_ngenes, n, nullptr, none);
+        const u32 n = call.read(number_by_first_appearance(d_cx.p, d_cy.p, nr, (u32)C, d_first.p, d_flag.p, d_rank.p, d_tmp_a.p, d_x.p, d_y.p, d_gene.p, st));
         if (n < 1 || n > C || n > N2) throw SoError("so_cnc_plan: internal error: " + std::to_string(n) + " genes in " + std::to_string(nr) + " rows");
         const size_t D = n;
 
         // the component stage, on the rows where they are
         CncDev c;
         const bool level2 = cnc_component_stage(d_x.p, d_y.p, d_z.p, n, nr, c, st, "so_cnc_plan");
-        waits += c.waits;
+        call.waits += c.waits;
         if (!level2) {   // one level-1 component: comp1 0 and grp -1 for every gene
             c.grp.ensure(D + 2);
             HIP_CHECK(hipMemsetAsync(c.comp1.p, 0, D * sizeof(u32), st));
@@ -513,15 +442,15 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         // kept rows: flag, scan, compact
         DevBuf<u32> d_keep, d_pos;
         d_keep.ensure(N + 2), d_pos.ensure(N + 2);
-        hipLaunchKernelGGL(k_cnc_keep<u32>, cnc_grid(nr), dim3(256), 0, st, d_x.p, d_y.p, nr, c.grp.p, d_keep.p);
+        hipLaunchKernelGGL(k_cnc_keep<u32>, grid256(nr), dim3(256), 0, st, d_x.p, d_y.p, nr, c.grp.p, d_keep.p);
         const u32* d_nkeep = scan_u32(d_keep.p, d_pos.p, N, false, d_tmp_a.p, st);
         u32 nk = 0, ngrp = 0;
-        read2(d_nkeep, nk, level2 ? c.d_ngrp : nullptr, ngrp);
+        call.read(d_nkeep, nk, level2 ? c.d_ngrp : nullptr, ngrp);
         if (nk > nr || ngrp > n) throw SoError("so_cnc_plan: internal error: " + std::to_string(nk) + " rows kept, " + std::to_string(ngrp) + " groups");
         HIP_CHECK(hipGetLastError());
 
-        out->gene_code = plan_alloc<int32_t>(D), out->x = plan_alloc<int32_t>(N), out->y = plan_alloc<int32_t>(N), out->comp1 = plan_alloc<int32_t>(D);
-        out->grp = plan_alloc<int32_t>(D), out->order = plan_alloc<int32_t>(nk);
+        out->gene_code = alloc(D), out->x = alloc(N), out->y = alloc(N), out->comp1 = alloc(D);
+        out->grp = alloc(D), out->order = alloc(nk);
         HIP_CHECK(hipMemcpyAsync(out->gene_code, d_gene.p, D * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(out->x, d_x.p, N * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(out->y, d_y.p, N * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -541,37 +470,37 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
             passes = one ? 1 : 2;
             d_key.ensure(K + 2), d_skey.ensure(K + 2), d_row.ensure(K + 2), d_order.ensure(K + 2);
             if (one) {
-                hipLaunchKernelGGL(k_plan_keys<true>, plan_grid(N), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, nr, d_keep.p, d_pos.p, cb, d_key.p, d_row.p);
+                hipLaunchKernelGGL(k_plan_keys<true>, grid256(N), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, nr, d_keep.p, d_pos.p, cb, d_key.p, d_row.p);
                 d_sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(K, gb + 2 * cb) + 256);
                 sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_row.p, d_order.p, K, gb + 2 * cb, st);   // stable: file order inside a triple
             } else {
-                hipLaunchKernelGGL(k_plan_keys<false>, plan_grid(N), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, nr, d_keep.p, d_pos.p, cb, d_key.p, d_row.p);
+                hipLaunchKernelGGL(k_plan_keys<false>, grid256(N), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, nr, d_keep.p, d_pos.p, cb, d_key.p, d_row.p);
                 d_sort_tmp.ensure(std::max(sort_pairs_u64_u32_temp_bytes(K, 32 + cb), sort_pairs_u64_u32_temp_bytes(K, gb)) + 256);
                 sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_row.p, d_order.p, K, 32 + cb, st);          // (cx, cy), stable
-                hipLaunchKernelGGL(k_plan_grpkey, plan_grid(K), dim3(256), 0, st, d_x.p, c.grp.p, d_order.p, nk, d_key.p);
+                hipLaunchKernelGGL(k_plan_grpkey, grid256(K), dim3(256), 0, st, d_x.p, c.grp.p, d_order.p, nk, d_key.p);
                 sort_pairs_u64_u32(d_sort_tmp.p, d_sort_tmp.cap, d_key.p, d_skey.p, d_order.p, d_row.p, K, gb, st);                // then grp + 1, stable
                 std::swap(d_order.p, d_row.p), std::swap(d_order.cap, d_row.cap);
             }
             HIP_CHECK(hipMemcpyAsync(out->order, d_order.p, K * sizeof(u32), hipMemcpyDeviceToHost, st));
             // cut and tied: neighbour comparison, scan, compact
             d_cutflag.ensure(K + 2), d_tiedflag.ensure(K + 2), d_cutpos.ensure(K + 2), d_tiedpos.ensure(K + 2), d_cut.ensure(K + 2), d_tied.ensure(K + 2);
-            hipLaunchKernelGGL(k_plan_edges, plan_grid(K), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, d_order.p, nk, d_cutflag.p, d_tiedflag.p);
+            hipLaunchKernelGGL(k_plan_edges, grid256(K), dim3(256), 0, st, d_cx.p, d_cy.p, d_x.p, c.grp.p, d_order.p, nk, d_cutflag.p, d_tiedflag.p);
             const u32* d_ncut = scan_u32(d_cutflag.p, d_cutpos.p, K, false, d_tmp_a.p, st);
             const u32* d_ntied = scan_u32(d_tiedflag.p, d_tiedpos.p, K, false, d_tmp_b.p, st);
-            hipLaunchKernelGGL(k_plan_compact, plan_grid(K), dim3(256), 0, st, d_cutflag.p, d_cutpos.p, d_tiedflag.p, d_tiedpos.p, nk, d_cut.p, d_tied.p);
+            hipLaunchKernelGGL(k_plan_compact, grid256(K), dim3(256), 0, st, d_cutflag.p, d_cutpos.p, d_tiedflag.p, d_tiedpos.p, nk, d_cut.p, d_tied.p);
             HIP_CHECK(hipGetLastError());
-            read2(d_ncut, ncut, d_ntied, ntied);   // (the arrays queued above arrive with this wait)
+            call.read(d_ncut, ncut, d_ntied, ntied);   // (the arrays queued above arrive with this wait)
             if (ncut >= nk || ntied >= nk || ncut > ngrp) throw SoError("so_cnc_plan: internal error: " + std::to_string(ncut) + " cuts and " + std::to_string(ntied) + " ties among " + std::to_string(nk) + " rows");
         }
-        out->cut = plan_alloc<int32_t>(ncut), out->tied = plan_alloc<int32_t>(ntied);
+        out->cut = alloc(ncut), out->tied = alloc(ntied);
         if (ncut) HIP_CHECK(hipMemcpyAsync(out->cut, d_cut.p, (size_t)ncut * sizeof(int), hipMemcpyDeviceToHost, st));
         if (ntied) HIP_CHECK(hipMemcpyAsync(out->tied, d_tied.p, (size_t)ntied * sizeof(int), hipMemcpyDeviceToHost, st));
         if (ncut || ntied || !nk) {
             HIP_CHECK(hipStreamSynchronize(st));
-            ++waits;
+            ++call.waits;
         }
         out->n_genes = n, out->n_comp1 = c.roots, out->n_grp = ngrp, out->n_keep = nk, out->n_cut = ncut, out->n_tied = ntied;
-        out->sweeps1 = c.sweeps1, out->sweeps2 = c.sweeps2, out->sort_passes = passes, out->waits = waits;
+        out->sweeps1 = c.sweeps1, out->sweeps2 = c.sweeps2, out->sort_passes = passes, out->waits = call.waits;
         g_cnc_err.clear();
         return 0;
     } catch (const std::exception& e) {

@@ -307,6 +307,46 @@ const u32* scan_u32(const u32* in, u32* out, size_t n, bool inclusive, u32* temp
     return temp + nb;
 }
 
+// ---- genes numbered by first appearance (the cluster stages: cnc.hip's plan, apc.hip's layout, mcl.hip's assembly) ------------------
+// Rows come as codes (cx[i], cy[i]); position 2 i is cx[i], 2 i + 1 is cy[i].  atomicMin of the position per code, flag the positions
+// that are a code's first, scan: the scan value at a code's first position is its number.  Integer atomics only: the result is fixed by
+// the input alone.
+__global__ __launch_bounds__(256) void k_first_pos(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, u32* __restrict__ first) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= nr) return;
+    atomicMin(&first[cx[i]], (u32)(2 * i));
+    atomicMin(&first[cy[i]], (u32)(2 * i + 1));
+}
+__global__ __launch_bounds__(256) void k_first_flag(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
+                                                    u32* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= 2 * (size_t)nr) return;
+    const int code = (p & 1) ? cy[p >> 1] : cx[p >> 1];
+    flag[p] = first[code] == (u32)p ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_first_number(const int* __restrict__ cx, const int* __restrict__ cy, u32 nr, const u32* __restrict__ first,
+                                                      const u32* __restrict__ flag, const u32* __restrict__ rank, int* __restrict__ X, int* __restrict__ Y,
+                                                      int* __restrict__ gene_code) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= nr) return;
+    const int a = cx[i], b = cy[i];
+    X[i] = (int)rank[first[a]], Y[i] = (int)rank[first[b]];
+    if (flag[2 * i]) gene_code[rank[2 * i]] = a;
+    if (flag[2 * i + 1]) gene_code[rank[2 * i + 1]] = b;
+}
+
+const u32* number_by_first_appearance(const int* cx, const int* cy, u32 nr, u32 n_codes, u32* first, u32* flag, u32* rank, u32* scan_tmp, int* X, int* Y,
+                                      int* gene_code, hipStream_t st) {
+    const size_t N = nr, N2 = 2 * N;
+    const dim3 rows((unsigned)((N + 255) / 256)), positions((unsigned)((N2 + 255) / 256));
+    HIP_CHECK(hipMemsetAsync(first, 0xFF, (size_t)n_codes * sizeof(u32), st));   // above every position (they stay below 2^32 - 1)
+    hipLaunchKernelGGL(k_first_pos, rows, dim3(256), 0, st, cx, cy, nr, first);
+    hipLaunchKernelGGL(k_first_flag, positions, dim3(256), 0, st, cx, cy, nr, first, flag);
+    const u32* d_ngenes = scan_u32(flag, rank, N2, false, scan_tmp, st);
+    hipLaunchKernelGGL(k_first_number, rows, dim3(256), 0, st, cx, cy, nr, first, flag, rank, X, Y, gene_code);
+    return d_ngenes;
+}
+
 // ---- tiny helpers ------------------------------------------------------------------------------
 __global__ void k_fill_u32(u32* p, size_t n, u32 v) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -10,6 +10,12 @@ size_t effscan_temp_elems(size_t n);
 const u32* effscan(const u8* mark, const u32* scnt, size_t n, u32* hoff, u32* cidx, u32* temp, hipStream_t st);
 const u32* scan_u32(const u32* in, u32* out, size_t n, bool inclusive, u32* temp, hipStream_t st);  // returns device ptr to total
 void fill_u32(u32* p, size_t n, u32 v, hipStream_t st);
+// genes numbered by first appearance in cx0, cy0, cx1, ...; everything queued on st, no host wait.
+// first: n_codes words, flag/rank: 2*nr words, scan_tmp: scan_u32_temp_elems(2*nr), gene_code: min(n_codes, 2*nr) words.
+// -> device word holding the number of genes; X[i], Y[i] = numbers of row i; gene_code[g] = code of gene g;
+//    first/flag/rank stay valid for the caller (flag[p]: position p is its code's first)
+const u32* number_by_first_appearance(const int* cx, const int* cy, u32 nr, u32 n_codes, u32* first, u32* flag, u32* rank,
+                                      u32* scan_tmp, int* X, int* Y, int* gene_code, hipStream_t st);
 
 // k_sort.hip
 size_t sort_keys_u64_temp_bytes(size_t n, int bits);

@@ -23,6 +23,7 @@
 // so_mcl_rows runs the same rounds on a matrix it assembles on the device from a batch's rows, and reads the result out there
 // (k_rows_*, k_ro_* below); so_mcl_readout is that read-out alone.
 #include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 #include "../../include/sohit.h"
 
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(64) void k_mcl_diff(const u32* __restrict__ rp, con
 }
 
 struct Mcl {
-    hipStream_t st = nullptr;
+    const hipStream_t st;   // the call's stream (declare the Mcl after its DeviceCall)
     DevBuf<u64> ck, ck2;
     DevBuf<u32> cp, cp2, flags, P, ccnt, scratch, small, rows;
     std::vector<u32> tier_rows;
@@ -312,6 +313,10 @@ struct Mcl {
     std::vector<u32> hP;
     std::vector<u64> hoff;
     size_t budget = (size_t)1 << 28;   // u32 words (1 GiB) of scratch per range of rows (SOHIT_MCL_SCRATCH: tests)
+
+    explicit Mcl(const DeviceCall& call) : st(call.st) {
+        if (call.tn.mcl_scratch >= 0) budget = (size_t)call.tn.mcl_scratch;
+    }
 
     void normalize(Csr& x) {
         if (!x.nnz) return;
@@ -481,7 +486,7 @@ void copy_csr(const Csr& a, Csr& b, hipStream_t st) {
 
 // ---- a batch's matrix from its rows, and the read-out, on the device (so_mcl_rows, so_mcl_readout) ------------------------------
 // find_cluster.py `block_matrix_arrays` and `surviving_pair_columns` are the definitions, bit for bit.  Assembly: genes numbered by
-// first appearance in x0, y0, x1, y1, ... (atomicMin of the position per label, flag the positions that are a first appearance, scan);
+// first appearance in x0, y0, x1, y1, ... (number_by_first_appearance, k_util.hip: it leaves the two gene numbers of every row);
 // weights rounded to float32 once; per ordered pair (X, Y) the LAST line wins (stable radix sort of X << 32 | Y with the line index as
 // payload: the winner is the last of its run); the diagonal = the largest positive weight of ANY line at the gene (atomicMax on the bit
 // patterns: positive floats, denormals and +inf included, order like their patterns); zeros of either sign are not stored; a second
@@ -489,7 +494,6 @@ void copy_csr(const Csr& a, Csr& b, hipStream_t st) {
 // (a, b) and (b, a) were rows (refused: numpy emits the coordinate twice).  Read-out: flag the non-zero entries, scan, compact their
 // coordinates; then flag the first M RAW values above the threshold, scan, compact.  Every comparison of values is one of bit
 // patterns, so nothing hangs on the kernels' denormal mode.  All stores are vector stores, all atomics integer min / max.
-#define ROWS_NONE 0xFFFFFFFFu
 
 // float64 -> float32, round to nearest even, in integer arithmetic (numpy's astype on the host: overflow -> +-inf, results below the
 // normal range are denormals, below half the smallest of them zero)
@@ -521,36 +525,12 @@ __host__ __device__ inline u32 f32_image(u32 b) {
     return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
-inline dim3 rows_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-#define ROWS_TID ((size_t)blockIdx.x * 256u + threadIdx.x)
-
-__global__ __launch_bounds__(256) void k_rows_first(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, u32* __restrict__ first) {
-    const size_t i = ROWS_TID;
+// (gx, gy: the gene numbers of the rows' two ends)
+__global__ __launch_bounds__(256) void k_rows_keys(const int* __restrict__ gx, const int* __restrict__ gy, const double* __restrict__ z, u32 nr,
+                                                   u64* __restrict__ key, u32* __restrict__ line, u32* __restrict__ zbits, u32* __restrict__ diag /*zeroed*/) {
+    const size_t i = tid256();
     if (i >= nr) return;
-    atomicMin(&first[gx[i]], (u32)(2 * i));
-    atomicMin(&first[gy[i]], (u32)(2 * i + 1));
-}
-__global__ __launch_bounds__(256) void k_rows_firstflag(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, const u32* __restrict__ first,
-                                                        u32* __restrict__ flag) {
-    const size_t p = ROWS_TID;
-    if (p >= 2 * (size_t)nr) return;
-    const u32 label = (p & 1) ? gy[p >> 1] : gx[p >> 1];
-    flag[p] = first[label] == (u32)p ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_rows_number(const u32* __restrict__ gx, const u32* __restrict__ gy, u32 nr, const u32* __restrict__ flag,
-                                                     const u32* __restrict__ rank, u32* __restrict__ num /*by label*/, u32* __restrict__ gene /*by number*/) {
-    const size_t p = ROWS_TID;
-    if (p >= 2 * (size_t)nr || !flag[p]) return;
-    const u32 label = (p & 1) ? gy[p >> 1] : gx[p >> 1];
-    num[label] = rank[p];
-    gene[rank[p]] = label;
-}
-__global__ __launch_bounds__(256) void k_rows_keys(const u32* __restrict__ gx, const u32* __restrict__ gy, const double* __restrict__ z, u32 nr,
-                                                   const u32* __restrict__ num, u64* __restrict__ key, u32* __restrict__ line, u32* __restrict__ zbits,
-                                                   u32* __restrict__ diag /*zeroed*/) {
-    const size_t i = ROWS_TID;
-    if (i >= nr) return;
-    const u32 X = num[gx[i]], Y = num[gy[i]];
+    const u32 X = (u32)gx[i], Y = (u32)gy[i];
     const u32 zb = f64_to_f32_bits((u64)__double_as_longlong(z[i]));
     key[i] = ((u64)X << 32) | Y, line[i] = (u32)i, zbits[i] = zb;
     if (zb - 1u < 0x7F800000u) atomicMax(&diag[X], zb), atomicMax(&diag[Y], zb);   // 0 < weight <= +inf
@@ -558,19 +538,19 @@ __global__ __launch_bounds__(256) void k_rows_keys(const u32* __restrict__ gx, c
 // the sorted lines that are the last of their pair and whose weight is not a zero
 __global__ __launch_bounds__(256) void k_rows_winflag(const u64* __restrict__ skey, const u32* __restrict__ sline, const u32* __restrict__ zbits, u32 nr,
                                                       u32* __restrict__ flag) {
-    const size_t k = ROWS_TID;
+    const size_t k = tid256();
     if (k >= nr) return;
     const bool win = k + 1 == nr || skey[k + 1] != skey[k];
     flag[k] = (win && (zbits[sline[k]] & 0x7FFFFFFFu)) ? 1u : 0u;
 }
 __global__ __launch_bounds__(256) void k_rows_diagflag(const u32* __restrict__ diag, u32 D, u32* __restrict__ flag) {
-    const size_t g = ROWS_TID;
+    const size_t g = tid256();
     if (g < D) flag[g] = diag[g] ? 1u : 0u;
 }
 __global__ __launch_bounds__(256) void k_rows_emit_pairs(const u64* __restrict__ skey, const u32* __restrict__ sline, const u32* __restrict__ zbits, u32 nr,
                                                          const u32* __restrict__ flag, const u32* __restrict__ off, u64* __restrict__ ekey,
                                                          u32* __restrict__ eval) {
-    const size_t k = ROWS_TID;
+    const size_t k = tid256();
     if (k >= nr || !flag[k]) return;
     const size_t o = 2 * (size_t)off[k];
     const u64 xy = skey[k];
@@ -580,20 +560,20 @@ __global__ __launch_bounds__(256) void k_rows_emit_pairs(const u64* __restrict__
 }
 __global__ __launch_bounds__(256) void k_rows_emit_diag(const u32* __restrict__ diag, u32 D, const u32* __restrict__ flag, const u32* __restrict__ off,
                                                         size_t base, u64* __restrict__ ekey, u32* __restrict__ eval) {
-    const size_t g = ROWS_TID;
+    const size_t g = tid256();
     if (g >= D || !flag[g]) return;
     ekey[base + off[g]] = ((u64)g << 32) | g, eval[base + off[g]] = diag[g];
 }
 __global__ __launch_bounds__(256) void k_rows_split(const u64* __restrict__ skey, const u32* __restrict__ sval, u32 nnz, u32* __restrict__ idx,
                                                     u32* __restrict__ val /*float32 patterns*/, u32* __restrict__ dup /*zeroed*/) {
-    const size_t k = ROWS_TID;
+    const size_t k = tid256();
     if (k >= nnz) return;
     idx[k] = (u32)skey[k], val[k] = sval[k];
     if (k + 1 < nnz && skey[k + 1] == skey[k]) *dup = 1u;
 }
 // rp[r] = entries in front of row r, r = 0 .. n (keys are row << 32 | column, ascending)
 __global__ __launch_bounds__(256) void k_rows_rowptr(const u64* __restrict__ skey, u32 nnz, u32 n, u32* __restrict__ rp) {
-    const size_t r = ROWS_TID;
+    const size_t r = tid256();
     if (r > n) return;
     const u64 want = (u64)r << 32;
     u32 lo = 0, hi = nnz;
@@ -606,12 +586,12 @@ __global__ __launch_bounds__(256) void k_rows_rowptr(const u64* __restrict__ ske
 }
 
 __global__ __launch_bounds__(256) void k_ro_nzflag(const u32* __restrict__ val /*float32 patterns*/, u32 nnz, u32* __restrict__ flag) {
-    const size_t k = ROWS_TID;
+    const size_t k = tid256();
     if (k < nnz) flag[k] = (val[k] & 0x7FFFFFFFu) ? 1u : 0u;   // (a NaN is not zero, -0.0 is)
 }
 __global__ __launch_bounds__(256) void k_ro_coords(const u32* __restrict__ rp, u32 n, const u32* __restrict__ idx, u32 nnz, const u32* __restrict__ flag,
                                                    const u32* __restrict__ pos, u32* __restrict__ cr, u32* __restrict__ cc) {
-    const size_t k = ROWS_TID;
+    const size_t k = tid256();
     if (k >= nnz || !flag[k]) return;
     u32 lo = 0, hi = n - 1;   // the row r with rp[r] <= k < rp[r + 1]
     while (lo < hi) {
@@ -623,27 +603,21 @@ __global__ __launch_bounds__(256) void k_ro_coords(const u32* __restrict__ rp, u
 }
 // the k-th coordinate is kept when the k-th RAW value exceeds the threshold
 __global__ __launch_bounds__(256) void k_ro_keepflag(const u32* __restrict__ val, u32 m, u32 prune_image, u32* __restrict__ flag) {
-    const size_t j = ROWS_TID;
+    const size_t j = tid256();
     if (j >= m) return;
     const u32 b = val[j];
     flag[j] = ((b & 0x7FFFFFFFu) <= 0x7F800000u && f32_image(b) > prune_image) ? 1u : 0u;   // (a NaN exceeds nothing)
 }
 __global__ __launch_bounds__(256) void k_ro_compact(const u32* __restrict__ cr, const u32* __restrict__ cc, u32 m, const u32* __restrict__ flag,
                                                     const u32* __restrict__ pos, u32* __restrict__ pr, u32* __restrict__ pc) {
-    const size_t j = ROWS_TID;
+    const size_t j = tid256();
     if (j >= m || !flag[j]) return;
     pr[pos[j]] = cr[j], pc[pos[j]] = cc[j];
 }
 
-u32 read_u32(const u32* d, hipStream_t st) {
-    u32 v = 0;
-    HIP_CHECK(hipMemcpyAsync(&v, d, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return v;
-}
-
 // the read-out of a device-resident matrix -> the surviving pairs on the host
-void read_out(const Csr& x, double prune, hipStream_t st, std::vector<u32>& pr, std::vector<u32>& pc) {
+void read_out(const Csr& x, double prune, DeviceCall& call, std::vector<u32>& pr, std::vector<u32>& pc) {
+    const hipStream_t st = call.st;
     pr.clear(), pc.clear();
     const float prunef = (float)prune;
     u32 pb;
@@ -652,16 +626,16 @@ void read_out(const Csr& x, double prune, hipStream_t st, std::vector<u32>& pr, 
     const u32 nnz = x.nnz;
     DevBuf<u32> flag, pos, cr, cc, dr, dc, tmp;
     flag.ensure((size_t)nnz + 2), pos.ensure((size_t)nnz + 2), tmp.ensure(scan_u32_temp_elems(nnz) + 8);
-    hipLaunchKernelGGL(k_ro_nzflag, rows_grid(nnz), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), nnz, flag.p);
-    const u32 m = read_u32(scan_u32(flag.p, pos.p, nnz, false, tmp.p, st), st);
+    hipLaunchKernelGGL(k_ro_nzflag, grid256(nnz), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), nnz, flag.p);
+    const u32 m = call.read(scan_u32(flag.p, pos.p, nnz, false, tmp.p, st));
     if (!m) return;
     cr.ensure((size_t)m + 2), cc.ensure((size_t)m + 2);
-    hipLaunchKernelGGL(k_ro_coords, rows_grid(nnz), dim3(256), 0, st, x.rp.p, x.n, x.idx.p, nnz, flag.p, pos.p, cr.p, cc.p);
-    hipLaunchKernelGGL(k_ro_keepflag, rows_grid(m), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), m, f32_image(pb), flag.p);
-    const u32 np = read_u32(scan_u32(flag.p, pos.p, m, false, tmp.p, st), st);
+    hipLaunchKernelGGL(k_ro_coords, grid256(nnz), dim3(256), 0, st, x.rp.p, x.n, x.idx.p, nnz, flag.p, pos.p, cr.p, cc.p);
+    hipLaunchKernelGGL(k_ro_keepflag, grid256(m), dim3(256), 0, st, reinterpret_cast<const u32*>(x.val.p), m, f32_image(pb), flag.p);
+    const u32 np = call.read(scan_u32(flag.p, pos.p, m, false, tmp.p, st));
     if (!np) return;
     dr.ensure((size_t)np + 2), dc.ensure((size_t)np + 2);
-    hipLaunchKernelGGL(k_ro_compact, rows_grid(m), dim3(256), 0, st, cr.p, cc.p, m, flag.p, pos.p, dr.p, dc.p);
+    hipLaunchKernelGGL(k_ro_compact, grid256(m), dim3(256), 0, st, cr.p, cc.p, m, flag.p, pos.p, dr.p, dc.p);
     pr.resize(np), pc.resize(np);
     HIP_CHECK(hipMemcpyAsync(pr.data(), dr.p, (size_t)np * sizeof(u32), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(pc.data(), dc.p, (size_t)np * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -669,39 +643,36 @@ void read_out(const Csr& x, double prune, hipStream_t st, std::vector<u32>& pr, 
 }
 
 // a batch's rows (labels below n_labels, checked; nr > 0) -> its matrix in x (n = genes + 1) and the label of every matrix row
-void assemble(const std::vector<u32>& hx, const std::vector<u32>& hy, const double* z, u32 n_labels, Mcl& m, Csr& x, std::vector<u32>& gene) {
-    hipStream_t st = m.st;
+void assemble(const std::vector<int>& hx, const std::vector<int>& hy, const double* z, u32 n_labels, DeviceCall& call, Mcl& m, Csr& x, std::vector<u32>& gene) {
+    const hipStream_t st = call.st;
     const u32 nr = (u32)hx.size();
     const size_t N = nr, N2 = 2 * N;
-    DevBuf<u32> gx, gy, first, flag, rank, num, dgene, line, sline, zbits, diag, off, eval, sval, dup;
+    DevBuf<int> lx, ly, gx, gy, dgene;
+    DevBuf<u32> first, flag, rank, line, sline, zbits, diag, off, eval, sval, dup;
     DevBuf<double> dz;
     DevBuf<u64> key, skey, ekey, sekey;
-    gx.ensure(N + 2), gy.ensure(N + 2), dz.ensure(N + 2), first.ensure((size_t)n_labels + 2), num.ensure((size_t)n_labels + 2);
-    flag.ensure(N2 + 2), rank.ensure(N2 + 2), m.scan_tmp.ensure(scan_u32_temp_elems(N2) + 8);
-    HIP_CHECK(hipMemcpyAsync(gx.p, hx.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(gy.p, hy.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
+    lx.ensure(N + 2), ly.ensure(N + 2), dz.ensure(N + 2), gx.ensure(N + 2), gy.ensure(N + 2), first.ensure((size_t)n_labels + 2);
+    flag.ensure(N2 + 2), rank.ensure(N2 + 2), m.scan_tmp.ensure(scan_u32_temp_elems(N2) + 8), dgene.ensure(std::min<size_t>(n_labels, N2) + 2);
+    HIP_CHECK(hipMemcpyAsync(lx.p, hx.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(ly.p, hy.data(), N * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(dz.p, z, N * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(first.p, 0xFF, (size_t)n_labels * sizeof(u32), st));   // ROWS_NONE
-    hipLaunchKernelGGL(k_rows_first, rows_grid(N), dim3(256), 0, st, gx.p, gy.p, nr, first.p);
-    hipLaunchKernelGGL(k_rows_firstflag, rows_grid(N2), dim3(256), 0, st, gx.p, gy.p, nr, first.p, flag.p);
-    const u32 D = read_u32(scan_u32(flag.p, rank.p, N2, false, m.scan_tmp.p, st), st);
+    const u32 D = call.read(number_by_first_appearance(lx.p, ly.p, nr, n_labels, first.p, flag.p, rank.p, m.scan_tmp.p, gx.p, gy.p, dgene.p, st));
     if (D < 1 || D > n_labels || D > N2) throw SoError("so_mcl_rows: internal error: " + std::to_string(D) + " genes in " + std::to_string(nr) + " rows");
-    dgene.ensure((size_t)D + 2), diag.ensure((size_t)D + 2);
+    diag.ensure((size_t)D + 2);
     key.ensure(N + 2), skey.ensure(N + 2), line.ensure(N + 2), sline.ensure(N + 2), zbits.ensure(N + 2), off.ensure(std::max<size_t>(N, D) + 2);
-    hipLaunchKernelGGL(k_rows_number, rows_grid(N2), dim3(256), 0, st, gx.p, gy.p, nr, flag.p, rank.p, num.p, dgene.p);
     HIP_CHECK(hipMemsetAsync(diag.p, 0, ((size_t)D + 1) * sizeof(u32), st));
-    hipLaunchKernelGGL(k_rows_keys, rows_grid(N), dim3(256), 0, st, gx.p, gy.p, dz.p, nr, num.p, key.p, line.p, zbits.p, diag.p);
+    hipLaunchKernelGGL(k_rows_keys, grid256(N), dim3(256), 0, st, gx.p, gy.p, dz.p, nr, key.p, line.p, zbits.p, diag.p);
     const int gbits = ceil_log2((u64)D + 1);
     m.sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(N, 32 + gbits) + 256);
     sort_pairs_u64_u32(m.sort_tmp.p, m.sort_tmp.cap, key.p, skey.p, line.p, sline.p, N, 32 + gbits, st);   // stable: lines ascend inside a pair
-    hipLaunchKernelGGL(k_rows_winflag, rows_grid(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p);
-    const u32 K = read_u32(scan_u32(flag.p, off.p, N, false, m.scan_tmp.p, st), st);
+    hipLaunchKernelGGL(k_rows_winflag, grid256(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p);
+    const u32 K = call.read(scan_u32(flag.p, off.p, N, false, m.scan_tmp.p, st));
     if ((size_t)2 * K + D > 0x7FFFFFF0ull) throw SoError("so_mcl_rows: matrix too large for 32-bit positions");
     ekey.ensure((size_t)2 * K + D + 2), eval.ensure((size_t)2 * K + D + 2);
-    if (K) hipLaunchKernelGGL(k_rows_emit_pairs, rows_grid(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p, off.p, ekey.p, eval.p);
-    hipLaunchKernelGGL(k_rows_diagflag, rows_grid(D), dim3(256), 0, st, diag.p, D, flag.p);   // (D <= 2 nr: the flags fit)
-    const u32 Kd = read_u32(scan_u32(flag.p, off.p, D, false, m.scan_tmp.p, st), st);
-    if (Kd) hipLaunchKernelGGL(k_rows_emit_diag, rows_grid(D), dim3(256), 0, st, diag.p, D, flag.p, off.p, (size_t)2 * K, ekey.p, eval.p);
+    if (K) hipLaunchKernelGGL(k_rows_emit_pairs, grid256(N), dim3(256), 0, st, skey.p, sline.p, zbits.p, nr, flag.p, off.p, ekey.p, eval.p);
+    hipLaunchKernelGGL(k_rows_diagflag, grid256(D), dim3(256), 0, st, diag.p, D, flag.p);   // (D <= 2 nr: the flags fit)
+    const u32 Kd = call.read(scan_u32(flag.p, off.p, D, false, m.scan_tmp.p, st));
+    if (Kd) hipLaunchKernelGGL(k_rows_emit_diag, grid256(D), dim3(256), 0, st, diag.p, D, flag.p, off.p, (size_t)2 * K, ekey.p, eval.p);
     const u32 nnz = 2 * K + Kd;
     x.n = D + 1, x.nnz = nnz;
     x.rp.ensure((size_t)x.n + 2), x.idx.ensure((size_t)nnz + 2), x.val.ensure((size_t)nnz + 2);
@@ -710,26 +681,17 @@ void assemble(const std::vector<u32>& hx, const std::vector<u32>& hy, const doub
     if (nnz) {
         m.sort_tmp.ensure(sort_pairs_u64_u32_temp_bytes(nnz, 32 + gbits) + 256);
         sort_pairs_u64_u32(m.sort_tmp.p, m.sort_tmp.cap, ekey.p, sekey.p, eval.p, sval.p, nnz, 32 + gbits, st);
-        hipLaunchKernelGGL(k_rows_split, rows_grid(nnz), dim3(256), 0, st, sekey.p, sval.p, nnz, x.idx.p, reinterpret_cast<u32*>(x.val.p), dup.p);
+        hipLaunchKernelGGL(k_rows_split, grid256(nnz), dim3(256), 0, st, sekey.p, sval.p, nnz, x.idx.p, reinterpret_cast<u32*>(x.val.p), dup.p);
     }
-    hipLaunchKernelGGL(k_rows_rowptr, rows_grid((size_t)x.n + 1), dim3(256), 0, st, sekey.p, nnz, x.n, x.rp.p);
+    hipLaunchKernelGGL(k_rows_rowptr, grid256((size_t)x.n + 1), dim3(256), 0, st, sekey.p, nnz, x.n, x.rp.p);
     gene.resize(D);
     HIP_CHECK(hipMemcpyAsync(gene.data(), dgene.p, (size_t)D * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (read_u32(dup.p, st)) throw SoError("so_mcl_rows: some pair occurs as (a, b) and as (b, a) (the reference stores its coordinate twice; not served)");
+    if (call.read(dup.p)) throw SoError("so_mcl_rows: some pair occurs as (a, b) and as (b, a) (the reference stores its coordinate twice; not served)");
     HIP_CHECK(hipGetLastError());
 }
 
-// what every call without a context begins with: the device, or the refusal
-void need_device(int device, const char* who) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError(std::string(who) + ": no HIP device available (libsohit has no CPU fallback)");
-    if (device < 0 || device >= nd) throw SoError(std::string(who) + ": device index out of range");
-    HIP_CHECK(hipSetDevice(device));
-}
-
 int64_t* widen(const std::vector<u32>& v) {
-    int64_t* p = (int64_t*)malloc(std::max<size_t>(1, v.size()) * sizeof(int64_t));
-    if (!p) throw SoError("so_mcl_rows: out of host memory");
+    int64_t* p = host_array<int64_t>("so_mcl_rows", v.size());
     for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
     return p;
 }
@@ -778,23 +740,12 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
         if (!out) throw SoError("so_mcl: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n < 0 || n > 0x7FFFFFF0ll || !indptr) throw SoError("so_mcl: bad matrix");
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_mcl: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_mcl: device index out of range");
-        HIP_CHECK(hipSetDevice(device));
+        check_device("so_mcl", device);
         const int64_t nnz0 = indptr[n];
         if (nnz0 < 0 || nnz0 > 0x7FFFFFF0ll) throw SoError("so_mcl: matrix too large for 32-bit positions");
         if (check_every < 1) check_every = 1;
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
-        Mcl m;
-        if (tn.mcl_scratch >= 0) m.budget = (size_t)tn.mcl_scratch;
-        HIP_CHECK(hipStreamCreate(&m.st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{m.st};
+        DeviceCall call(device);
+        Mcl m(call);
         Csr x, old, c;
         x.n = (u32)n, x.nnz = (u32)nnz0;
         x.rp.ensure((size_t)n + 2), x.idx.ensure((size_t)nnz0 + 2), x.val.ensure((size_t)nnz0 + 2);
@@ -812,13 +763,7 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
         HIP_CHECK(hipStreamSynchronize(m.st));
         HIP_CHECK(hipGetLastError());
         out->n = n, out->nnz = px->nnz, out->rounds = rounds, out->converged = conv;
-        out->indptr = (int64_t*)malloc(((size_t)n + 1) * sizeof(int64_t));
-        out->indices = (int32_t*)malloc(std::max<size_t>(1, px->nnz) * sizeof(int32_t));
-        out->data = (float*)malloc(std::max<size_t>(1, px->nnz) * sizeof(float));
-        if (!out->indptr || !out->indices || !out->data) {
-            so_mcl_free(out);
-            throw SoError("so_mcl: out of host memory");
-        }
+        out->indptr = host_array<int64_t>("so_mcl", (size_t)n + 1), out->indices = host_array<int32_t>("so_mcl", px->nnz), out->data = host_array<float>("so_mcl", px->nnz);
         std::vector<u32> rp((size_t)n + 1);
         HIP_CHECK(hipMemcpy(rp.data(), px->rp.p, ((size_t)n + 1) * sizeof(u32), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i <= n; ++i) out->indptr[i] = rp[(size_t)i];
@@ -829,6 +774,7 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
         g_mcl_err.clear();
         return 0;
     } catch (const std::exception& e) {
+        if (out) so_mcl_free(out);
         g_mcl_err = e.what();
         return 1;
     }
@@ -848,34 +794,26 @@ int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx,
         if (n_labels < 0 || n_rows < 0 || (n_rows > 0 && (!gx || !gy || !z))) throw SoError("so_mcl_rows: bad arguments");
         if (n_labels >= (1ll << 31) || n_rows >= (1ll << 31)) throw SoError("so_mcl_rows: 2^31 labels or rows and more are not served (32-bit numbers and positions)");
         const size_t N = (size_t)n_rows;
-        std::vector<u32> hx(N), hy(N);
+        std::vector<int> hx(N), hy(N);
         for (size_t i = 0; i < N; ++i) {
             if (gx[i] < 0 || gx[i] >= n_labels || gy[i] < 0 || gy[i] >= n_labels)
                 throw SoError("so_mcl_rows: row " + std::to_string(i) + " names a gene outside 0 .. n_labels - 1");
             if (z[i] != z[i]) throw SoError("so_mcl_rows: row " + std::to_string(i) + " has a NaN weight (not served: the caller keeps the host path)");
             if (gx[i] == gy[i])
                 throw SoError("so_mcl_rows: row " + std::to_string(i) + " is a self pair (the reference overwrites the diagonal in line order; not served)");
-            hx[i] = (u32)gx[i], hy[i] = (u32)gy[i];
+            hx[i] = (int)gx[i], hy[i] = (int)gy[i];
         }
-        need_device(device, "so_mcl_rows");
+        check_device("so_mcl_rows", device);
         const bool want_matrix = flags & 1;
         std::vector<u32> gene, pr, pc, hrp, hidx;
         std::vector<float> hval;
         int rounds = 0, conv = 0;
         if (N) {   // (no row: no gene, a 1 x 1 matrix without entries, no round, no pair -- and no launch)
             if (check_every < 1) check_every = 1;
-            Tune tn;   // no context: the switches are read per call
-            tn.read();
-            const PoisonScope poison((int)tn.poison);
-            Mcl m;
-            if (tn.mcl_scratch >= 0) m.budget = (size_t)tn.mcl_scratch;
-            HIP_CHECK(hipStreamCreate(&m.st));
-            struct Guard {
-                hipStream_t s;
-                ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-            } guard{m.st};
+            DeviceCall call(device);
+            Mcl m(call);
             Csr x, old, c;
-            assemble(hx, hy, z, (u32)n_labels, m, x, gene);
+            assemble(hx, hy, z, (u32)n_labels, call, m, x, gene);
             if (want_matrix) {
                 hrp.resize((size_t)x.n + 1), hidx.resize(x.nnz), hval.resize(x.nnz);
                 HIP_CHECK(hipMemcpyAsync(hrp.data(), x.rp.p, hrp.size() * sizeof(u32), hipMemcpyDeviceToHost, m.st));
@@ -886,7 +824,7 @@ int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx,
                 HIP_CHECK(hipStreamSynchronize(m.st));
             }
             const Csr* px = run_rounds(m, x, old, c, inflation, max_rounds, check_every, prune, rtol, atol, rounds, conv);
-            read_out(*px, prune, m.st, pr, pc);
+            read_out(*px, prune, call, pr, pc);
             HIP_CHECK(hipStreamSynchronize(m.st));
             HIP_CHECK(hipGetLastError());
         } else if (want_matrix) {
@@ -895,9 +833,7 @@ int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx,
         out->gene = widen(gene), out->pair_r = widen(pr), out->pair_c = widen(pc);
         if (want_matrix) {
             out->indptr = widen(hrp);
-            out->indices = (int32_t*)malloc(std::max<size_t>(1, hidx.size()) * sizeof(int32_t));
-            out->data = (float*)malloc(std::max<size_t>(1, hval.size()) * sizeof(float));
-            if (!out->indices || !out->data) throw SoError("so_mcl_rows: out of host memory");
+            out->indices = host_array<int32_t>("so_mcl_rows", hidx.size()), out->data = host_array<float>("so_mcl_rows", hval.size());
             if (!hidx.empty()) memcpy(out->indices, hidx.data(), hidx.size() * sizeof(u32)), memcpy(out->data, hval.data(), hval.size() * sizeof(float));
             out->nnz = (int64_t)hidx.size();
         }
@@ -921,18 +857,11 @@ int so_mcl_readout(int device, int64_t n, const int64_t* indptr, const int32_t* 
         const int64_t nnz = indptr[n];
         if (nnz > 0x7FFFFFF0ll) throw SoError("so_mcl_readout: matrix too large for 32-bit positions");
         if (nnz > 0 && (!indices || !data)) throw SoError("so_mcl_readout: bad matrix");
-        need_device(device, "so_mcl_readout");
+        check_device("so_mcl_readout", device);
         std::vector<u32> pr, pc;
         if (n && nnz) {
-            Tune tn;
-            tn.read();
-            const PoisonScope poison((int)tn.poison);
-            hipStream_t st = nullptr;
-            HIP_CHECK(hipStreamCreate(&st));
-            struct Guard {
-                hipStream_t s;
-                ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-            } guard{st};
+            DeviceCall call(device);
+            const hipStream_t st = call.st;
             Csr x;
             x.n = (u32)n, x.nnz = (u32)nnz;
             x.rp.ensure((size_t)n + 2), x.idx.ensure((size_t)nnz + 2), x.val.ensure((size_t)nnz + 2);
@@ -941,7 +870,7 @@ int so_mcl_readout(int device, int64_t n, const int64_t* indptr, const int32_t* 
             HIP_CHECK(hipMemcpyAsync(x.rp.p, rp.data(), rp.size() * sizeof(u32), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(x.idx.p, indices, (size_t)nnz * sizeof(u32), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(x.val.p, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
-            read_out(x, prune, st, pr, pc);
+            read_out(x, prune, call, pr, pc);
             HIP_CHECK(hipStreamSynchronize(st));
             HIP_CHECK(hipGetLastError());
         }

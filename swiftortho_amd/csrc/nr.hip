@@ -18,8 +18,10 @@
 //                 bases, a = rel / S, the row in N, b; builds the record in LDS; the workgroup then writes its piece as consecutive
 //                 16-byte stores.  (With a thread per SOURCE row the single row between two collapsed records of 700 members each
 //                 would be 490 000 records, 39 MB, written by one thread.)
-// Host waits: one for the totals (n_out, n_runs, the error words: they size the buffer and are the count-only answer), one for the end.
+// Host waits (after the member tables are up): one for the totals (n_out, n_runs, the error words: they size the buffer and are the
+// count-only answer), one for the end.
 #include "common.h"
+#include "device_call.h"
 #include "../../include/sohit.h"
 
 #include <cstring>
@@ -185,12 +187,6 @@ void nr_check_table(const char* side, const int64_t* off, const int32_t* mem, in
     }
 }
 
-template <class T>
-void nr_upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t st) {
-    d.ensure(n + 2);
-    if (n) HIP_CHECK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-}
-
 thread_local std::string g_nr_err;
 
 }  // namespace
@@ -217,28 +213,17 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
         nr_check_table("subject", soff, smem, n_s);
         if (n > 0 && !d_hits) throw SoError("so_nr_expand: the record pointer is NULL");
         if ((uintptr_t)d_hits & 15u) throw SoError("so_nr_expand: the records are not 16-byte aligned");
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError("so_nr_expand: no HIP device available (libsohit has no CPU fallback)");
-        if (device < 0 || device >= nd) throw SoError("so_nr_expand: device index out of range");
+        check_device("so_nr_expand", device);
         out->n_in = n;
         if (n == 0) {   // nothing to launch (a grid of 0 blocks is an invalid configuration)
             g_nr_err.clear();
             return 0;
         }
 
-        HIP_CHECK(hipSetDevice(device));
         // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
         // (the ordering rule of so_orth_*_records)
-        HIP_CHECK(hipDeviceSynchronize());
-        Tune tn;   // no context: the switches are read per call
-        tn.read();
-        const PoisonScope poison((int)tn.poison);
-        hipStream_t st = nullptr;
-        HIP_CHECK(hipStreamCreate(&st));
-        struct Guard {
-            hipStream_t s;
-            ~Guard() { (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s); }
-        } guard{st};
+        DeviceCall call(device, true);
+        const hipStream_t st = call.st;
 
         const size_t R = (size_t)n, nb = (R + NR_THREADS - 1) / NR_THREADS;
         const size_t stride = R + 2, bstride = nb + 2;
@@ -248,8 +233,8 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
         DevBuf<int> d_qmem, d_smem;
         DevBuf<u64> v, bs, rbase, rN;
         DevBuf<u32> rrow, err;
-        nr_upload(d_qoff, n_q ? qoff : &zero, (size_t)n_q + 1, st), nr_upload(d_soff, n_s ? soff : &zero, (size_t)n_s + 1, st);
-        nr_upload(d_qmem, qmem, (size_t)mq, st), nr_upload(d_smem, smem, (size_t)ms, st);
+        upload(d_qoff, n_q ? qoff : &zero, (size_t)n_q + 1, st), upload(d_soff, n_s ? soff : &zero, (size_t)n_s + 1, st);
+        upload(d_qmem, qmem, (size_t)mq, st), upload(d_smem, smem, (size_t)ms, st);
         v.ensure(3 * stride), bs.ensure(3 * bstride), rbase.ensure(R + 2), rN.ensure(R + 2), rrow.ensure(R + 2), err.ensure(4);
         u64 *W = v.p, *N = v.p + stride, *Rn = v.p + 2 * stride;
         const uint4* hits16 = reinterpret_cast<const uint4*>(d_hits);
@@ -287,7 +272,7 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
             }
             HIP_CHECK(e);
         }
-        if (tn.poison >= 0) HIP_CHECK(hipMemsetAsync(d_out, (int)tn.poison & 0xFF, bytes, st));
+        if (call.tn.poison >= 0) HIP_CHECK(hipMemsetAsync(d_out, (int)call.tn.poison & 0xFF, bytes, st));
         hipLaunchKernelGGL(k_nr_emit, dim3((unsigned)((n_out + NR_PIECE - 1) / NR_PIECE)), dim3(NR_THREADS), 0, st, hits16, N, rbase.p, rN.p, rrow.p, (u32)n_runs, d_qoff.p,
                            d_qmem.p, d_soff.p, d_smem.p, n_out, reinterpret_cast<uint4*>(d_out));
         HIP_CHECK(hipGetLastError());

@@ -30,6 +30,7 @@
 // All three append their candidates to the three lists, one reservation per wave and list.  Then per list: library radix sort of
 // (key, score), k_orth_twice / k_orth_distinct flag the key groups, scan, k_orth_twice_emit / k_orth_distinct_emit write the tables.
 #include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 #include "../../include/sohit.h"
 
@@ -309,17 +310,9 @@ __global__ __launch_bounds__(256) void k_orth_distinct_emit(const u64* __restric
     okey[pos[i]] = (i64)k, obest[pos[i]] = acc;
 }
 
-// (a synchronous copy: the host array may go away before the stream is waited for)
-template <class T>
-void upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t) {
-    d.ensure(n + 2);
-    if (n) HIP_CHECK(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
-}
-
 template <class T>
 T* host_copy(const T* d, size_t n, hipStream_t st) {
-    T* h = (T*)malloc((n ? n : 1) * sizeof(T));
-    if (!h) throw SoError("so_orth_candidates: out of host memory");
+    T* h = host_array<T>("so_orth_candidates", n);
     if (n) {
         const hipError_t e = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) {
@@ -329,8 +322,6 @@ T* host_copy(const T* d, size_t n, hipStream_t st) {
     }
     return h;
 }
-
-inline dim3 grid256(size_t n) { return dim3((u32)((n + 255) / 256)); }
 
 thread_local std::string g_orth_err;
 
@@ -878,13 +869,6 @@ void orth_finish(OrthDev& D, hipStream_t st, const char* who, so_orth_rel* out) 
 }
 
 
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() {
-        if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
-    }
-};
-
 // what every entry point checks before anything touches the device
 void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, void* out, size_t out_bytes) {
     if (!out) throw SoError(std::string(who) + ": result pointer is NULL");
@@ -894,9 +878,7 @@ void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* 
     if (n_names > 3037000499ll) throw SoError(std::string(who) + ": n_names * n_names reaches 2^63 (pair keys a * n_names + b are 63-bit)");
     for (i64 i = 0; i < n_names; ++i)
         if (tax[i] < 0 || tax[i] >= n_taxa) throw SoError(std::string(who) + ": name " + std::to_string(i) + " has a taxon outside 0 .. n_taxa - 1");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw SoError(std::string(who) + ": no HIP device available (libsohit has no CPU fallback)");
-    if (device < 0 || device >= nd) throw SoError(std::string(who) + ": device index out of range");
+    check_device(who, device);
 }
 
 // an output of no rows still hands out arrays that its free function can release
@@ -929,27 +911,22 @@ int orth_from_cols(const char* who, int device, int64_t n, const int32_t* q, con
         orth_check(who, device, n, n_names, tax, n_taxa, norm, out, sizeof *out);
         if (n > 0 && (!q || !s || !idy || !aln || !qst || !qed || !score || !qlen)) throw SoError(std::string(who) + ": a column is NULL");
         if (n > 0) {
-            HIP_CHECK(hipSetDevice(device));
-            Tune tn;   // no context: the switches are read per call
-            tn.read();
-            const PoisonScope poison((int)tn.poison);
-            StreamGuard g;
-            HIP_CHECK(hipStreamCreate(&g.s));
+            DeviceCall call(device);
             OrthDev D;
             {
                 DevBuf<int> dq, ds;
                 DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
                 DevBuf<u32> d_err;
                 const size_t N = (size_t)n;
-                upload(dq, q, N, g.s), upload(ds, s, N, g.s), upload(d_idy, idy, N, g.s), upload(d_aln, aln, N, g.s), upload(d_qst, qst, N, g.s), upload(d_qed, qed, N, g.s);
-                upload(d_score, score, N, g.s), upload(d_qlen, qlen, N, g.s);
+                upload(dq, q, N, call.st), upload(ds, s, N, call.st), upload(d_idy, idy, N, call.st), upload(d_aln, aln, N, call.st), upload(d_qst, qst, N, call.st), upload(d_qed, qed, N, call.st);
+                upload(d_score, score, N, call.st), upload(d_qlen, qlen, N, call.st);
                 d_err.ensure(4);
-                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
+                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
                 const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-                orth_run(n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, &D);
-                HIP_CHECK(hipStreamSynchronize(g.s));   // (the columns go away here)
+                orth_run(n, c, call.st, n_names, tax, n_taxa, coverage, identity, norm, call.tn, d_err.p, who, &D);
+                HIP_CHECK(hipStreamSynchronize(call.st));   // (the columns go away here)
             }
-            orth_finish(D, g.s, who, out);
+            orth_finish(D, call.st, who, out);
         }
         orth_fill_empty(out);
         g_orth_err.clear();
@@ -969,32 +946,26 @@ int orth_from_records(const char* who, int device, const so_hit* d_hits, int64_t
         if (n_q < 0 || n_s < 0 || (n_q > 0 && !qmap) || (n_s > 0 && !smap)) throw SoError(std::string(who) + ": bad arguments");
         if (n > 0 && !d_hits) throw SoError(std::string(who) + ": the record pointer is NULL");
         if (n > 0) {
-            HIP_CHECK(hipSetDevice(device));
             // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
             // (so_search_device has synchronised its stream when it returns; a torch tensor's producer is on torch's stream)
-            HIP_CHECK(hipDeviceSynchronize());
-            Tune tn;
-            tn.read();
-            const PoisonScope poison((int)tn.poison);
-            StreamGuard g;
-            HIP_CHECK(hipStreamCreate(&g.s));
+            DeviceCall call(device, true);
             OrthDev D;
             {
                 DevBuf<int> dq, ds, d_qmap, d_smap;
                 DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
                 DevBuf<u32> d_err;
                 const size_t N = (size_t)n;
-                upload(d_qmap, qmap, (size_t)n_q, g.s), upload(d_smap, smap, (size_t)n_s, g.s);
+                upload(d_qmap, qmap, (size_t)n_q, call.st), upload(d_smap, smap, (size_t)n_s, call.st);
                 dq.ensure(N + 2), ds.ensure(N + 2), d_idy.ensure(N + 2), d_aln.ensure(N + 2), d_qst.ensure(N + 2), d_qed.ensure(N + 2), d_score.ensure(N + 2), d_qlen.ensure(N + 2);
                 d_err.ensure(4);
-                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), g.s));
-                hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, g.s, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
+                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
+                hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, call.st, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
                                    d_qed.p, d_score.p, d_qlen.p, d_err.p);
                 const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-                orth_run(n, c, g.s, n_names, tax, n_taxa, coverage, identity, norm, tn, d_err.p, who, &D);
-                HIP_CHECK(hipStreamSynchronize(g.s));
+                orth_run(n, c, call.st, n_names, tax, n_taxa, coverage, identity, norm, call.tn, d_err.p, who, &D);
+                HIP_CHECK(hipStreamSynchronize(call.st));
             }
-            orth_finish(D, g.s, who, out);
+            orth_finish(D, call.st, who, out);
         }
         orth_fill_empty(out);
         g_orth_err.clear();

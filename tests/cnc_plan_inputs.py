@@ -6,7 +6,7 @@ codes.  Genes are written as sortable tuples; a gene's code is its rank among th
 the ids is to real rows), optionally spread out so that codes stay unused; a row's ends are put smaller code first.
 
 Every input is at the smallest shape where its kernel can go wrong.  The sizes are the code's own (read out of swiftortho_amd/csrc):
-the k_plan_* / k_cnc_* kernels run 256 lanes a workgroup over the rows, over the 2 x rows positions of cx0, cy0, cx1, ... and over the
+the numbering (k_util.hip) / k_plan_* / k_cnc_* kernels run 256 lanes a workgroup over the rows, over the 2 x rows positions of cx0, cy0, cx1, ... and over the
 kept rows; scan_u32 (k_util.hip: SCAN_TILE = 256 * 4 * 8, SCAN_SMALL_TILES = 4) takes 8192 values per workgroup and changes from one launch
 to three above 4 x 8192 values -- it scans the positions, the rows and the kept rows.  The family graph of about 19 000 rows is the only
 large input.
@@ -23,7 +23,7 @@ import numpy as np
 
 import cnc_inputs as ci
 
-LANES = 256                 # lanes per workgroup of the k_plan_* / k_cnc_* kernels
+LANES = 256                 # lanes per workgroup of the numbering / k_plan_* / k_cnc_* kernels
 SCAN_TILE = 8192            # values per workgroup of scan_u32
 SCAN_ONE_LAUNCH = 4 * 8192  # scan_u32: up to here one launch, above it three
 KEPT = (LANES - 1, LANES, LANES + 1, 1023, 1024, 1025, 4095, 4096, 4097, SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1,

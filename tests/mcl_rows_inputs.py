@@ -14,7 +14,7 @@ import numpy as np
 
 import cnc_inputs as ci
 
-LANES = 256                 # lanes per workgroup of the k_rows_* / k_ro_* kernels
+LANES = 256                 # lanes per workgroup of the numbering / k_rows_* / k_ro_* kernels
 SCAN_TILE = 8192            # values per workgroup of scan_u32
 SCAN_ONE_LAUNCH = 4 * 8192  # scan_u32: up to here one launch, above it three
 

@@ -99,6 +99,28 @@ def test_ordered_column_bits(name):
     assert bits == (0x3E800001 if "tiny_first" in name else 0x3E800000)
 
 
+def test_taxa_of_genes_first_seen_in_the_second_column():
+    """129 rows (2 x 129 = 258 positions: one workgroup and two positions of the next) in which every gene but the one at position 0
+    -- cx of row 0, which no input can move -- first appears in the cy column, and taxa 1 and 2 are carried by those genes alone: the
+    taxa in use come from the shared numbering's flags at the ODD positions, read by so_apc_rows' own kernel"""
+    from swiftortho_amd import find_cluster as fc
+    nrow = 129
+    cy = np.random.RandomState(7).permutation(np.arange(1, nrow + 1)).astype(np.int32)   # code order is not gene order
+    cx = np.zeros(nrow, dtype=np.int32)
+    z = np.linspace(0.25, 3.0, nrow)
+    tax = np.array([0] + [1 + c % 2 for c in range(1, nrow + 1)] + [3], dtype=np.int32)   # code nrow + 1 is unused: taxon 3 does not count
+    gene_code, row, col, score, n, n_used = fc.apc_entry_columns(cx, cy, z, len(tax), tax)
+    seq = np.stack([cx, cy], axis=1).ravel()
+    first = np.array([np.flatnonzero(seq == c)[0] for c in gene_code])
+    assert n == nrow + 1 and n_used == 3 and (first[1:] % 2 == 1).all() and first[0] == 0 and first.max() == 2 * nrow - 1 > 256
+    assert set(tax[gene_code[first % 2 == 1]]) == {1, 2} and tax[gene_code[0]] == 0
+    info = {}
+    got = fc.device_apc_rows(cx, cy, z, len(tax), tax, 0.5, rounds=1, want_entries=True, info=info)
+    assert np.array_equal(got[0], gene_code) and np.array_equal(got[2], row) and np.array_equal(got[3], col)
+    assert np.array_equal(got[4].view(np.uint32), score.view(np.uint32))
+    assert info["n_genes"] == n and info["n_entries"] == len(row) and info["n_taxa_used"] == n_used and info["waits"] == 3, info
+
+
 def test_no_row():
     from swiftortho_amd import find_cluster as fc
     for want_entries in (False, True):
