@@ -489,6 +489,43 @@ int so_orth_relations_records(int device, const so_hit *d_hits, int64_t n, const
                               int norm, so_orth_rel *out);
 void so_orth_rel_free(so_orth_rel *result);
 
+/* Reciprocal best hits and the core-gene table on the device (csrc/rbh.hip).  Replaces: scripts/get_rbh.py -- per run of one query id the
+ * best hit per subject taxon (get_rbh, 33-48) and "a pair is printed at every second proposal of its key" (51-65) -- and the two passes
+ * of scripts/rbh2phy.py over the hit file (78-161): the forward best hits of the reference taxon's genes and the flags of those a best
+ * hit back confirms -- as swiftortho_amd/rbh.py `reciprocal_best_hits()` and `core_table()` restate them, id for id and in their order.
+ * Input: n hit rows in file order -- name codes q / s in 0 .. n_names - 1 and the float64 score column (host arrays, borrowed), or
+ * so_hit records in DEVICE memory with the host maps query ordinal -> code (qmap, n_q) and subject ordinal -> code (smap, n_s), whose
+ * score is `bit`.  Name codes ascend in the ids' string order.  tax[n_names]: taxon code of every name, in 0 .. n_taxa - 1.
+ * ref_taxon: the reference taxon of the core table, or -1: the pairs only.  flags: reserved, 0.
+ * A run = consecutive rows of one query code.  Per run and subject taxon other than the query's, the winner is the FIRST row holding the
+ * largest score (+0 and -0 are equal); winners are listed by the first row of their (run, taxon) group.
+ * Output (allocated by the library, released with so_rbh_free()): rbh_a / rbh_b: every winner proposes (smaller code, larger code); the
+ * pair is listed at each even-numbered proposal of its key, in stream order.  core_gene[n_core]: the genes of ref_taxon that have a
+ * winner, by their first one; core_fwd[n_core * n_taxa]: per gene and taxon the subject of the gene's LAST winner in that taxon, or -1;
+ * core_rec[n_core * n_taxa]: 1 where a run of core_fwd's gene has its winner in ref_taxon at this gene.  n_runs runs, n_winners
+ * winners; n_runs_long / n_rows_long: what the sorted tier took (the rest: one wave per run); waits: host waits of the call.
+ * n = 0 is served and launches nothing.
+ * Ordering of the records call: that of so_orth_*_records -- it first waits for ALL work queued on the device, works on a stream of its
+ * own and has synchronised it when it returns.  The records are only read.
+ * Refused with a message (so_rbh_last_error) and nothing left allocated: n >= 2^31, n_core * n_taxa >= 2^31, a name code, map index,
+ * taxon or ref_taxon out of range, flags != 0, a NaN score (Python's `<` and sort disagree on it: the caller decides), no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON, SOHIT_RBH_TIER). */
+typedef struct so_rbh_result {
+    int64_t n_rbh, n_core, n_taxa, n_runs, n_winners, n_runs_long, n_rows_long;
+    int32_t waits;
+    int32_t reserved;
+    int32_t *rbh_a, *rbh_b;   /* n_rbh */
+    int32_t *core_gene;       /* n_core */
+    int32_t *core_fwd;        /* n_core * n_taxa */
+    uint8_t *core_rec;        /* n_core * n_taxa */
+} so_rbh_result;
+int so_rbh_cols(int device, int64_t n, const int32_t *q, const int32_t *s, const double *score, int64_t n_names, const int32_t *tax,
+                int64_t n_taxa, int32_t ref_taxon, int32_t flags, so_rbh_result *out);
+int so_rbh_records(int device, const so_hit *d_hits, int64_t n, const int32_t *qmap, int64_t n_q, const int32_t *smap, int64_t n_s,
+                   int64_t n_names, const int32_t *tax, int64_t n_taxa, int32_t ref_taxon, int32_t flags, so_rbh_result *out);
+void so_rbh_free(so_rbh_result *result);
+const char *so_rbh_last_error(void);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

@@ -54,7 +54,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
-           "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error"]
+           "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
+           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -101,6 +102,12 @@ class SoOrthCand(C.Structure):
 
 class SoNrExpandResult(C.Structure):
     _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("n_runs", C.c_int64), ("waits", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p)]
+
+
+class SoRbhResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_rbh", "n_core", "n_taxa", "n_runs", "n_winners", "n_runs_long", "n_rows_long")] + \
+               [("waits", C.c_int32), ("reserved", C.c_int32), ("rbh_a", C.POINTER(C.c_int32)), ("rbh_b", C.POINTER(C.c_int32)),
+                ("core_gene", C.POINTER(C.c_int32)), ("core_fwd", C.POINTER(C.c_int32)), ("core_rec", C.POINTER(C.c_uint8))]
 
 
 _lib = None
@@ -234,6 +241,10 @@ def load():
     L.so_nr_expand.argtypes = [C.c_int, vp, i64, vp, vp, i64, vp, vp, i64, C.c_int32, C.POINTER(SoNrExpandResult)]
     L.so_nr_expand_free.argtypes = [C.POINTER(SoNrExpandResult)]
     L.so_nr_last_error.restype = cp
+    L.so_rbh_cols.argtypes = [C.c_int, i64, vp, vp, vp, i64, vp, i64, C.c_int32, C.c_int32, C.POINTER(SoRbhResult)]
+    L.so_rbh_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, C.c_int32, C.c_int32, C.POINTER(SoRbhResult)]
+    L.so_rbh_free.argtypes = [C.POINTER(SoRbhResult)]
+    L.so_rbh_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

@@ -56,6 +56,8 @@
     X(I, mcl_scratch, "SOHIT_MCL_SCRATCH", -1, "tests: u32 words of expansion / convergence scratch per range of rows (-1: 2^28)")                             \
     /* ---- find_orth candidates (so_orth_candidates_*: read per call) ---- */                                                                                  \
     X(T, orth_tier, "SOHIT_ORTH_TIER", 0, "tests: every run of query rows through one tier of k_orth_run wherever that tier can take it (0 = auto: by run length)") \
+    /* ---- reciprocal best hits (so_rbh_*: read per call) ---- */                                                                                              \
+    X(T, rbh_tier, "SOHIT_RBH_TIER", 0, "tests: wave = runs of up to 64 rows through k_rbh_run_wave (what auto does), long or sort = every run through the sorted tier (0 = auto: by run length)") \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
@@ -76,6 +78,9 @@ static inline int orth_tier_of(const char* v) {
         default: return ORTH_TIER_AUTO;
     }
 }
+
+// ---- reciprocal best hits (rbh.hip): SOHIT_RBH_TIER is read with orth_tier_of -- w[ave] = 1; l[ong], s[ort] (2, 3) = the sorted tier ----
+#define RBH_WAVE_ROWS 64      // longest run k_rbh_run_wave holds, a row per lane; longer runs go through the (run, taxon) sort
 
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;

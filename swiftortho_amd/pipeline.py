@@ -134,6 +134,48 @@ def _device_stage(s, ids, sc_path, coverage, identity, norm, sep, t, t0, relatio
     return lines, t
 
 
+def core_genes_from_search(fasta_path, reference='', device=0, collapse=False, sep='|', sc_path=None, **search_kw):
+    """one process from a FASTA file to the reciprocal best hits between its taxa and the core-gene families of `reference` (default:
+    the taxon with most genes): self-search on the GPU, then ONE device call on the records where they lie (rbh.device_core_table_from_records,
+    so_rbh_records) -- what `bin/find_hit.py ... && scripts/get_rbh.py x.sc` prints and the groups `scripts/rbh2phy.py -i x.sc -f x.fsa
+    [-r reference]` writes, with no .sc text in between (`sc_path` still receives the file when named; nothing reads it).
+    collapse=True: exact duplicates are searched once and the records multiplied back on the device, as in orthology_from_search.
+    -> (pairs as a list of (id, id) bytes in print order, groups as lists of ids (bytes), dict of stage wall times in seconds: load, search,
+    [write_sc,] rbh, and the counts rows, pairs, groups, core_genes)"""
+    from . import find_orth, fsearch, rbh
+    t = {}
+    t0 = time.time()
+    full = open(fasta_path, 'rb').read()
+    data, tables = full, None
+    if collapse:
+        tables, data, ids = _collapse(full, t)
+    else:
+        ids = find_orth.fasta_ids(full)
+    s = fsearch.Searcher(device=device, **search_kw)
+    try:
+        s.load_ref_bytes(data)
+        s.load_queries_bytes(data)
+        t['load'] = time.time() - t0 - t.get('collapse', 0.)
+        t0 = time.time()
+        if tables is not None:
+            _check_collapsed(s, tables)
+        dev, owned, t0 = _search_records(s, tables, sc_path, t, t0)
+        try:
+            names, table = rbh.device_core_table_from_records(dev, ids, ids, full, reference, sep)
+            t['rbh'] = time.time() - t0
+            t['rows'] = len(dev)
+        finally:
+            if owned is not None:
+                owned.close()
+    finally:
+        s.close()
+    nm = names.tolist()
+    pairs = [(nm[a], nm[b]) for a, b in zip(table.pairs[0].tolist(), table.pairs[1].tolist())]
+    groups = rbh.core_groups(names, table)
+    t['pairs'], t['groups'], t['core_genes'] = len(pairs), len(groups), len(table.genes)
+    return pairs, groups, t
+
+
 def groups_from_search(fasta_path, inflation=1.5, coverage=.5, identity=0., norm='no', sep='|', device=0, device_stage='all', orth_path=None, sc_path=None,
                        algorithm='mcl', damp=0.5, collapse=False, **search_kw):
     """one process from a FASTA file to ortholog groups: self-search on the GPU, the relation tables on the device from the records in
