@@ -137,6 +137,14 @@ def _preload_torch_hip_runtime():
             pass
 
 
+def result_array(p, n, dtype=None):
+    """an own numpy copy of the n elements at p, a typed pointer of a result struct (never NULL, n = 0 included); dtype: the type the
+    caller wants them in (None: as the library holds them).  numpy is imported here: this module loads without it (the cold find_hit)"""
+    import numpy as np
+    a = np.ctypeslib.as_array(p, shape=(max(int(n), 1),))[:int(n)]
+    return a.astype(a.dtype if dtype is None else dtype, copy=True)
+
+
 def load():
     """Load libsohit.so (never builds, never falls back)."""
     global _lib

@@ -389,6 +389,9 @@ __global__ __launch_bounds__(256) void k_apcr_entries(const int* __restrict__ X,
 
 thread_local std::string g_apc_err;
 
+auto slots(so_apc_result* r) { return result_slots(&r->labels, &r->r, &r->a); }
+auto slots(so_apc_rows_result* r) { return result_slots(&r->gene_code, &r->labels, &r->row, &r->col, &r->score, &r->r, &r->a); }
+
 }  // namespace
 
 extern "C" {
@@ -396,14 +399,12 @@ extern "C" {
 const char* so_apc_last_error(void) { return g_apc_err.c_str(); }
 
 void so_apc_free(so_apc_result* r) {
-    if (!r) return;
-    free(r->labels), free(r->r), free(r->a);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, const int32_t* col, const float* score, double damp, int32_t rounds,
            so_apc_result* out) {
-    try {
+    return guarded_call(g_apc_err, out, so_apc_free, [&] {
         if (!out) throw SoError("so_apc: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n_genes < 0 || n_entries < 0 || rounds < 0 || (n_entries > 0 && (!row || !col || !score))) throw SoError("so_apc: bad arguments");
@@ -453,24 +454,16 @@ int so_apc(int device, int64_t n_genes, int64_t n_entries, const int32_t* row, c
         out->labels = host_array<int64_t>("so_apc", D), out->r = host_array<float>("so_apc", N), out->a = host_array<float>("so_apc", N);
         for (size_t i = 0; i < D; ++i) out->labels[i] = lab[i];
         for (size_t e = 0; e < N; ++e) out->r[e] = hr[place[e]], out->a[e] = ha[place[e]];   // back to entry order
-        g_apc_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_apc_free(out);
-        g_apc_err = e.what();
-        return 1;
-    }
+    });
 }
 
 void so_apc_rows_free(so_apc_rows_result* r) {
-    if (!r) return;
-    free(r->gene_code), free(r->labels), free(r->row), free(r->col), free(r->score), free(r->r), free(r->a);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, const int32_t* cy, const double* z, const int32_t* taxon_of_code,
                 int64_t n_taxa, double damp, int32_t rounds, int32_t flags, so_apc_rows_result* out) {
-    try {
+    return guarded_call(g_apc_err, out, so_apc_rows_free, [&] {
         if (!out) throw SoError("so_apc_rows: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n_codes < 0 || n_rows < 0 || n_taxa < 0 || rounds < 0 || (n_rows > 0 && (!cx || !cy || !z)) || (n_codes > 0 && !taxon_of_code))
@@ -495,8 +488,7 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
             if (want_entries)
                 out->row = host_array<int32_t>(who, 0), out->col = host_array<int32_t>(who, 0), out->score = host_array<float>(who, 0), out->r = host_array<float>(who, 0),
                 out->a = host_array<float>(who, 0);
-            g_apc_err.clear();
-            return 0;
+            return;
         }
 
         DeviceCall call(device);
@@ -584,17 +576,10 @@ int so_apc_rows(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
             HIP_CHECK(hipMemcpyAsync(out->r, d_or.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(out->a, d_oa.p, N * sizeof(float), hipMemcpyDeviceToHost, st));
         }
-        HIP_CHECK(hipStreamSynchronize(st));
-        ++call.waits;
+        call.wait();
         for (size_t i = 0; i < D; ++i) out->labels[i] = lab[i];
         out->waits = call.waits;
-        g_apc_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_apc_rows_free(out);
-        g_apc_err = e.what();
-        return 1;
-    }
+    });
 }
 
 }  // extern "C"

@@ -290,6 +290,9 @@ __global__ __launch_bounds__(256) void k_plan_compact(const u32* __restrict__ cu
 
 thread_local std::string g_cnc_err;
 
+auto slots(so_cnc_result* r) { return result_slots(&r->comp1, &r->grp, &r->keep); }
+auto slots(so_cnc_plan_result* r) { return result_slots(&r->gene_code, &r->x, &r->y, &r->comp1, &r->grp, &r->order, &r->cut, &r->tied); }
+
 }  // namespace
 
 extern "C" {
@@ -297,13 +300,11 @@ extern "C" {
 const char* so_cnc_last_error(void) { return g_cnc_err.c_str(); }
 
 void so_cnc_free(so_cnc_result* r) {
-    if (!r) return;
-    free(r->comp1), free(r->grp), free(r->keep);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x, const int32_t* y, const double* z, so_cnc_result* out) {
-    try {
+    return guarded_call(g_cnc_err, out, so_cnc_free, [&] {
         if (!out) throw SoError("so_cnc_groups: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n_genes < 0 || n_rows < 0 || (n_rows > 0 && (!x || !y || !z))) throw SoError("so_cnc_groups: bad arguments");
@@ -335,8 +336,7 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
         if (!D || !N) {
             one_pool();
             out->n_comp1 = D ? 1 : 0;
-            g_cnc_err.clear();
-            return 0;
+            return;
         }
 
         DeviceCall call(device);
@@ -354,8 +354,7 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
         out->sweeps1 = c.sweeps1, out->sweeps2 = c.sweeps2, out->n_comp1 = c.roots;
         if (!level2) {
             one_pool();
-            g_cnc_err.clear();
-            return 0;
+            return;
         }
         d_keep.ensure(N + 2);
         hipLaunchKernelGGL(k_cnc_keep<u8>, grid256(nr), dim3(256), 0, st, d_x.p, d_y.p, nr, c.grp.p, d_keep.p);
@@ -372,23 +371,15 @@ int so_cnc_groups(int device, int64_t n_genes, int64_t n_rows, const int32_t* x,
         for (size_t g = 0; g < D; ++g) out->comp1[g] = hc[g], out->grp[g] = hg[g];
         for (size_t i = 0; i < N; ++i) nk += out->keep[i];
         out->n_grp = ngrp, out->n_keep = nk;
-        g_cnc_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_cnc_free(out);
-        g_cnc_err = e.what();
-        return 1;
-    }
+    });
 }
 
 void so_cnc_plan_free(so_cnc_plan_result* r) {
-    if (!r) return;
-    free(r->gene_code), free(r->x), free(r->y), free(r->comp1), free(r->grp), free(r->order), free(r->cut), free(r->tied);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, const int32_t* cy, const double* z, int32_t flags, so_cnc_plan_result* out) {
-    try {
+    return guarded_call(g_cnc_err, out, so_cnc_plan_free, [&] {
         if (!out) throw SoError("so_cnc_plan: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n_codes < 0 || n_rows < 0 || (n_rows > 0 && (!cx || !cy || !z))) throw SoError("so_cnc_plan: bad arguments");
@@ -406,8 +397,7 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         if (!N) {   // no row: no gene, nothing kept, nothing to launch
             out->gene_code = alloc(0), out->x = alloc(0), out->y = alloc(0), out->comp1 = alloc(0);
             out->grp = alloc(0), out->order = alloc(0), out->cut = alloc(0), out->tied = alloc(0);
-            g_cnc_err.clear();
-            return 0;
+            return;
         }
 
         DeviceCall call(device);
@@ -496,18 +486,11 @@ int so_cnc_plan(int device, int64_t n_codes, int64_t n_rows, const int32_t* cx, 
         if (ncut) HIP_CHECK(hipMemcpyAsync(out->cut, d_cut.p, (size_t)ncut * sizeof(int), hipMemcpyDeviceToHost, st));
         if (ntied) HIP_CHECK(hipMemcpyAsync(out->tied, d_tied.p, (size_t)ntied * sizeof(int), hipMemcpyDeviceToHost, st));
         if (ncut || ntied || !nk) {
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++call.waits;
+            call.wait();
         }
         out->n_genes = n, out->n_comp1 = c.roots, out->n_grp = ngrp, out->n_keep = nk, out->n_cut = ncut, out->n_tied = ntied;
         out->sweeps1 = c.sweeps1, out->sweeps2 = c.sweeps2, out->sort_passes = passes, out->waits = call.waits;
-        g_cnc_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_cnc_plan_free(out);
-        g_cnc_err = e.what();
-        return 1;
-    }
+    });
 }
 
 }  // extern "C"

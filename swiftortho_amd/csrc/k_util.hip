@@ -347,6 +347,33 @@ const u32* number_by_first_appearance(const int* cx, const int* cy, u32 nr, u32 
     return d_ngenes;
 }
 
+// ---- runs of equal consecutive keys (the hit-table stages: orth.hip, rbh.hip) -------------------------------------------------------
+// head flags, their inclusive scan (rid[i] = run of element i, from 1), then the first element of every run.
+template <class K>
+__global__ __launch_bounds__(256) void k_run_heads(const K* __restrict__ key, u32 n, u32* __restrict__ head) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_run_starts(u32 n, const u32* __restrict__ head, const u32* __restrict__ rid, const u32* __restrict__ nruns,
+                                                    u32* __restrict__ start) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (head[i]) start[rid[i] - 1u] = i;
+    if (i == 0) start[*nruns] = n;
+}
+
+template <class K>
+const u32* key_runs(const K* key, u32 n, u32* head, u32* rid, u32* scan_tmp, hipStream_t st) {
+    hipLaunchKernelGGL(k_run_heads<K>, dim3((n + 255u) / 256u), dim3(256), 0, st, key, n, head);
+    return scan_u32(head, rid, n, true, scan_tmp, st);
+}
+template const u32* key_runs<int>(const int*, u32, u32*, u32*, u32*, hipStream_t);
+template const u32* key_runs<u64>(const u64*, u32, u32*, u32*, u32*, hipStream_t);
+
+void run_starts(const u32* head, const u32* rid, u32 n, const u32* d_nruns, u32* start, hipStream_t st) {
+    hipLaunchKernelGGL(k_run_starts, dim3((n + 255u) / 256u), dim3(256), 0, st, n, head, rid, d_nruns, start);
+}
+
 // ---- tiny helpers ------------------------------------------------------------------------------
 __global__ void k_fill_u32(u32* p, size_t n, u32 v) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

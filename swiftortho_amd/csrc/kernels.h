@@ -16,6 +16,15 @@ void fill_u32(u32* p, size_t n, u32 v, hipStream_t st);
 //    first/flag/rank stay valid for the caller (flag[p]: position p is its code's first)
 const u32* number_by_first_appearance(const int* cx, const int* cy, u32 nr, u32 n_codes, u32* first, u32* flag, u32* rank,
                                       u32* scan_tmp, int* X, int* Y, int* gene_code, hipStream_t st);
+// runs of equal consecutive keys among n > 0 elements (K: int or u64); everything queued on st, no host wait.
+// key_runs: head[i] = 1 where a run starts, rid = inclusive scan of head (scan_tmp: scan_u32_temp_elems(n))
+//    -> device word holding the number of runs.  It lies in scan_tmp: valid until scan_tmp is scanned with again.  (Every caller queues
+//    its run_starts, or reads the word, before the next scan on that scratch; so does cnc.hip with CncDev::d_ngrp.)
+// run_starts: start[r] = first element of run r, start[*d_nruns] = n (start: runs + 1 words); head / rid as key_runs left them, or from a
+//    heads kernel of the caller's own
+template <class K>
+const u32* key_runs(const K* key, u32 n, u32* head, u32* rid, u32* scan_tmp, hipStream_t st);
+void run_starts(const u32* head, const u32* rid, u32 n, const u32* d_nruns, u32* start, hipStream_t st);
 
 // k_sort.hip
 size_t sort_keys_u64_temp_bytes(size_t n, int bits);

@@ -722,6 +722,9 @@ Csr* run_rounds(Mcl& m, Csr& x, Csr& old, Csr& c, double inflation, int max_roun
 
 thread_local std::string g_mcl_err;
 
+auto slots(so_mcl_result* r) { return result_slots(&r->indptr, &r->indices, &r->data); }
+auto slots(so_mcl_rows_result* r) { return result_slots(&r->gene, &r->pair_r, &r->pair_c, &r->indptr, &r->indices, &r->data); }
+
 }  // namespace
 
 extern "C" {
@@ -729,14 +732,12 @@ extern "C" {
 const char* so_mcl_last_error(void) { return g_mcl_err.c_str(); }
 
 void so_mcl_free(so_mcl_result* r) {
-    if (!r) return;
-    free(r->indptr), free(r->indices), free(r->data);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices, const float* data, double inflation, int32_t max_rounds,
            int32_t check_every, double prune, double rtol, double atol, so_mcl_result* out) {
-    try {
+    return guarded_call(g_mcl_err, out, so_mcl_free, [&] {
         if (!out) throw SoError("so_mcl: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n < 0 || n > 0x7FFFFFF0ll || !indptr) throw SoError("so_mcl: bad matrix");
@@ -771,24 +772,16 @@ int so_mcl(int device, int64_t n, const int64_t* indptr, const int32_t* indices,
             HIP_CHECK(hipMemcpy(out->indices, px->idx.p, (size_t)px->nnz * sizeof(u32), hipMemcpyDeviceToHost));
             HIP_CHECK(hipMemcpy(out->data, px->val.p, (size_t)px->nnz * sizeof(float), hipMemcpyDeviceToHost));
         }
-        g_mcl_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_mcl_free(out);
-        g_mcl_err = e.what();
-        return 1;
-    }
+    });
 }
 
 void so_mcl_rows_free(so_mcl_rows_result* r) {
-    if (!r) return;
-    free(r->gene), free(r->pair_r), free(r->pair_c), free(r->indptr), free(r->indices), free(r->data);
-    memset(r, 0, sizeof *r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx, const int64_t* gy, const double* z, double inflation,
                 int32_t max_rounds, int32_t check_every, double prune, double rtol, double atol, int32_t flags, so_mcl_rows_result* out) {
-    try {
+    return guarded_call(g_mcl_err, out, so_mcl_rows_free, [&] {
         if (!out) throw SoError("so_mcl_rows: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n_labels < 0 || n_rows < 0 || (n_rows > 0 && (!gx || !gy || !z))) throw SoError("so_mcl_rows: bad arguments");
@@ -838,17 +831,11 @@ int so_mcl_rows(int device, int64_t n_labels, int64_t n_rows, const int64_t* gx,
             out->nnz = (int64_t)hidx.size();
         }
         out->n_genes = (int64_t)gene.size(), out->n_pairs = (int64_t)pr.size(), out->rounds = rounds, out->converged = conv;
-        g_mcl_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_mcl_rows_free(out);
-        g_mcl_err = e.what();
-        return 1;
-    }
+    });
 }
 
 int so_mcl_readout(int device, int64_t n, const int64_t* indptr, const int32_t* indices, const float* data, double prune, so_mcl_rows_result* out) {
-    try {
+    return guarded_call(g_mcl_err, out, so_mcl_rows_free, [&] {
         if (!out) throw SoError("so_mcl_readout: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n < 0 || n > 0x7FFFFFF0ll || !indptr || indptr[0] != 0) throw SoError("so_mcl_readout: bad matrix");
@@ -876,13 +863,7 @@ int so_mcl_readout(int device, int64_t n, const int64_t* indptr, const int32_t* 
         }
         out->pair_r = widen(pr), out->pair_c = widen(pc);
         out->n_pairs = (int64_t)pr.size();
-        g_mcl_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) so_mcl_rows_free(out);
-        g_mcl_err = e.what();
-        return 1;
-    }
+    });
 }
 
 }  // extern "C"

@@ -203,8 +203,12 @@ void so_nr_expand_free(so_nr_expand_result* r) {
 
 int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qoff, const int32_t* qmem, int64_t n_q, const int64_t* soff, const int32_t* smem,
                  int64_t n_s, int32_t flags, so_nr_expand_result* out) {
-    void* d_out = nullptr;
-    try {
+    void* d_out = nullptr;   // the output until the result owns it: released with the result when the call is refused
+    auto drop = [&](so_nr_expand_result* r) {
+        if (d_out) (void)hipFree(d_out);
+        memset(r, 0, sizeof *r);
+    };
+    return guarded_call(g_nr_err, out, drop, [&] {
         if (!out) throw SoError("so_nr_expand: result pointer is NULL");
         memset(out, 0, sizeof *out);
         if (n < 0 || n_q < 0 || n_s < 0) throw SoError("so_nr_expand: a negative count");
@@ -215,10 +219,7 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
         if ((uintptr_t)d_hits & 15u) throw SoError("so_nr_expand: the records are not 16-byte aligned");
         check_device("so_nr_expand", device);
         out->n_in = n;
-        if (n == 0) {   // nothing to launch (a grid of 0 blocks is an invalid configuration)
-            g_nr_err.clear();
-            return 0;
-        }
+        if (n == 0) return;   // nothing to launch (a grid of 0 blocks is an invalid configuration)
 
         // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
         // (the ordering rule of so_orth_*_records)
@@ -257,10 +258,7 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
         if (n_runs < 1 || n_runs > R) throw SoError("so_nr_expand: internal error: " + std::to_string(n_runs) + " runs among " + std::to_string(R) + " records");
         if (n_out >= (1ull << 31)) throw SoError("so_nr_expand: the records expand to " + std::to_string(n_out) + " or more; 2^31 and more are not served (the orthology stage refuses them too)");
         out->n_out = (int64_t)n_out, out->n_runs = (int64_t)n_runs;
-        if ((flags & 1) || n_out == 0) {
-            g_nr_err.clear();
-            return 0;
-        }
+        if ((flags & 1) || n_out == 0) return;
 
         const size_t bytes = (size_t)n_out * sizeof(so_hit);
         {
@@ -279,14 +277,7 @@ int so_nr_expand(int device, const so_hit* d_hits, int64_t n, const int64_t* qof
         HIP_CHECK(hipStreamSynchronize(st));   // wait 2: the end
         out->waits = 2;
         out->d_out = (so_hit*)d_out;
-        g_nr_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (d_out) (void)hipFree(d_out);
-        if (out) memset(out, 0, sizeof *out);
-        g_nr_err = e.what();
-        return 1;
-    }
+    });
 }
 
 }  // extern "C"

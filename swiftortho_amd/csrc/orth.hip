@@ -21,18 +21,17 @@
 // code, as numpy's maximum lets it win; its payload is not kept.  (Where +0 and -0 tie numpy keeps the one it met first; here +0 wins.
 // Bit scores are integers, and their quotients are zero only as +0.)
 //
-// Kernels.  k_orth_unpack (records -> columns), k_orth_rows (keep flags) -> scan -> k_orth_compact (kept rows, scores, first row per
-// code) -> k_orth_bsr -> k_orth_heads -> scan -> k_orth_starts (run bounds).  The host reads the run bounds and sorts the runs into three
-// lists by length (tune.h: ORTH_WAVE_ROWS, ORTH_LDS_ROWS, ORTH_LDS_TAXA; SOHIT_ORTH_TIER forces one tier wherever it can take the run):
+// Kernels.  k_orth_unpack (records -> columns; hit_codes, hit_table.h), k_orth_rows (keep flags) -> scan -> k_orth_compact (kept rows,
+// scores, first row per code) -> k_orth_bsr -> key_runs -> run_starts (k_util.hip: k_run_heads -> scan -> k_run_starts, the run bounds).
+// Every host wait goes through the call's DeviceCall (device_call.h: read, fetch + wait).  The host reads the run bounds and sorts the
+// runs into three lists by length (tune.h: ORTH_WAVE_ROWS, ORTH_LDS_ROWS, ORTH_LDS_TAXA; SOHIT_ORTH_TIER forces one tier wherever it can take the run):
 //   k_orth_run_wave     a run of up to 64 rows, a row per lane of one wave: dedupe and maxima with shuffles over the run's lanes;
 //   k_orth_run_table    one run per workgroup: an open-addressing table subject -> best score and a table taxon -> maximum, in LDS
 //                       (<false>) or, for longer runs and more taxa, in global scratch whose extents the host planned (<true>).
 // All three append their candidates to the three lists, one reservation per wave and list.  Then per list: library radix sort of
 // (key, score), k_orth_twice / k_orth_distinct flag the key groups, scan, k_orth_twice_emit / k_orth_distinct_emit write the tables.
 #include "common.h"
-#include "device_call.h"
-#include "kernels.h"
-#include "../../include/sohit.h"
+#include "hit_table.h"
 
 #include <cmath>
 #include <cstring>
@@ -103,11 +102,8 @@ __global__ __launch_bounds__(256) void k_orth_unpack(const so_hit* __restrict__ 
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const so_hit r = h[i];
-    int qc = 0, sc = 0;
-    if (r.qidx < 0 || r.qidx >= nq) atomicOr(err, 1u);
-    else qc = qmap[r.qidx];
-    if (r.sidx < 0 || r.sidx >= ns) atomicOr(err, 2u);
-    else sc = smap[r.sidx];
+    int qc, sc;
+    hit_codes(r, qmap, nq, smap, ns, qc, sc, err);
     q[i] = qc, s[i] = sc;
     // numpy rounds to 6 decimals as rint(x * 1e6) / 1e6; then the two decimals the text row would carry
     const double r6 = __ddiv_rn(rint(__dmul_rn(r.identity, 1e6)), 1e6);
@@ -141,19 +137,6 @@ __global__ __launch_bounds__(256) void k_orth_compact(u32 n, const u32* __restri
 __global__ __launch_bounds__(256) void k_orth_bsr(u32 nk, const int* __restrict__ kq, const double* __restrict__ bit, const u32* __restrict__ first, double* __restrict__ sco) {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i < nk) sco[i] = __ddiv_rn(bit[i], bit[first[kq[i]]]);
-}
-
-__global__ __launch_bounds__(256) void k_orth_heads(u32 nk, const int* __restrict__ kq, u32* __restrict__ head) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i < nk) head[i] = (i == 0 || kq[i] != kq[i - 1]) ? 1u : 0u;
-}
-
-// rstart[r] = first row of run r; rstart[number of runs] = nk.  rid: inclusive scan of head
-__global__ __launch_bounds__(256) void k_orth_starts(u32 nk, const u32* __restrict__ head, const u32* __restrict__ rid, const u32* __restrict__ nruns, u32* __restrict__ rstart) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= nk) return;
-    if (head[i]) rstart[rid[i] - 1u] = i;
-    if (i == 0) rstart[*nruns] = nk;
 }
 
 // ---- runs ----------------------------------------------------------------------------------------------------------------------------
@@ -310,19 +293,6 @@ __global__ __launch_bounds__(256) void k_orth_distinct_emit(const u64* __restric
     okey[pos[i]] = (i64)k, obest[pos[i]] = acc;
 }
 
-template <class T>
-T* host_copy(const T* d, size_t n, hipStream_t st) {
-    T* h = host_array<T>("so_orth_candidates", n);
-    if (n) {
-        const hipError_t e = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            free(h);
-            HIP_CHECK(e);
-        }
-    }
-    return h;
-}
-
 thread_local std::string g_orth_err;
 
 struct OrthCols {   // device columns of n rows
@@ -360,8 +330,10 @@ struct OrthDev {
     u32 T = 1;
 };
 
-void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm, const Tune& tn,
-              u32* d_err, const char* who, OrthDev* out) {
+void orth_run(DeviceCall& call, i64 n, const OrthCols& c, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm, u32* d_err,
+              const char* who, OrthDev* out) {
+    hipStream_t st = call.st;
+    const Tune& tn = call.tn;
     const u64 M = (u64)(n_names > 0 ? n_names : 1);
     const u32 T = (u32)(n_taxa > 0 ? n_taxa : 1);
     const u32 N = (u32)n;
@@ -375,12 +347,8 @@ void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32
     hipLaunchKernelGGL(k_orth_rows, grid256(N), dim3(256), 0, st, N, c.q, c.s, c.idy, c.qst, c.qed, c.qlen, n_names, coverage, identity, keep.p, d_err);
     const u32* d_nk = scan_u32(keep.p, pos.p, N, false, tmp_a.p, st);
     u32 nk = 0, err = 0;
-    HIP_CHECK(hipMemcpyAsync(&nk, d_nk, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&err, d_err, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (err & 1u) throw SoError(std::string(who) + ": a record's qidx lies outside the query map");
-    if (err & 2u) throw SoError(std::string(who) + ": a record's sidx lies outside the subject map");
-    if (err & 4u) throw SoError(std::string(who) + ": a name code lies outside 0 .. n_names - 1");
+    call.read(d_nk, nk, d_err, err);
+    hit_table_errors(who, err);
     out->n_rows = nk;
     if (!nk) return;   // every row filtered: all tables empty
 
@@ -397,15 +365,12 @@ void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32
         sco = ksco.p;
     }
     head.ensure(nk + 2), rid.ensure(nk + 2), rstart.ensure(nk + 3), tmp_b.ensure(scan_u32_temp_elems(nk) + 2);
-    hipLaunchKernelGGL(k_orth_heads, grid256(nk), dim3(256), 0, st, nk, kq.p, head.p);
-    const u32* d_nruns = scan_u32(head.p, rid.p, nk, true, tmp_b.p, st);
-    hipLaunchKernelGGL(k_orth_starts, grid256(nk), dim3(256), 0, st, nk, head.p, rid.p, d_nruns, rstart.p);
-    u32 nruns = 0;
-    HIP_CHECK(hipMemcpyAsync(&nruns, d_nruns, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    const u32* d_nruns = key_runs(kq.p, nk, head.p, rid.p, tmp_b.p, st);
+    run_starts(head.p, rid.p, nk, d_nruns, rstart.p, st);
+    const u32 nruns = call.read(d_nruns);
     std::vector<u32> rs((size_t)nruns + 1);
-    HIP_CHECK(hipMemcpyAsync(rs.data(), rstart.p, rs.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    call.fetch(rs.data(), rstart.p, rs.size());
+    call.wait();
     out->n_runs = nruns;
 
     // the runs by tier; the scratch tier's tables laid out one behind the other
@@ -453,9 +418,9 @@ void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32
         hipLaunchKernelGGL(k_orth_run_table<true>, dim3((u32)l_scr.size()), dim3(256), 0, st, d_ls.p, (u32)l_scr.size(), d_plan.p, ghk.p, ghv.p, gtm.p, rstart.p, kq.p, ks.p,
                            sco, d_tax.p, T, M, L);
     u32 hc[4] = {0, 0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost, st));
+    call.fetch(hc, cnt.p, 4);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st));
+    call.wait();
     out->n_groups = hc[3];
     if (hc[1] >= (1u << 31)) throw SoError(std::string(who) + ": 2^31 in-paralog candidates and more are not supported");
     if (hc[0] > nk || hc[2] > nk || hc[1] > 2ull * nk) throw SoError(std::string(who) + ": internal error: a candidate list overflowed");
@@ -467,10 +432,8 @@ void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32
     p_ip.run(true, ip_k.p, ip_v.p, hc[1], bits, st);
     p_co.run(false, co_k.p, co_v.p, hc[2], bits, st);
     u32 tot[3] = {0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(tot + 0, p_ot.total, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(tot + 1, p_ip.total, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(tot + 2, p_co.total, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    call.fetch(tot + 0, p_ot.total), call.fetch(tot + 1, p_ip.total), call.fetch(tot + 2, p_co.total);
+    call.wait();
     DevBuf<i64>&o_ota = out->ot_a, &o_otb = out->ot_b, &o_ipa = out->ip_a, &o_ipb = out->ip_b, &o_cok = out->co_key;
     DevBuf<double>&o_ots = out->ot_s, &o_ips = out->ip_s, &o_cob = out->co_best;
     o_ota.ensure(tot[0] + 2), o_otb.ensure(tot[0] + 2), o_ots.ensure(tot[0] + 2), o_ipa.ensure(tot[1] + 2), o_ipb.ensure(tot[1] + 2), o_ips.ensure(tot[1] + 2);
@@ -483,13 +446,14 @@ void orth_run(i64 n, const OrthCols& c, hipStream_t st, i64 n_names, const int32
 }
 
 // so_orth_candidates_*: the tables come to the host
-void orth_finish(OrthDev& D, hipStream_t st, const char*, so_orth_cand* out) {
+void orth_finish(OrthDev& D, DeviceCall& call, const char* who, so_orth_cand* out) {
+    hipStream_t st = call.st;
     out->n_rows = D.n_rows, out->n_runs = D.n_runs, out->n_groups = D.n_groups;
     out->n_ot = D.n_ot, out->n_ip = D.n_ip, out->n_co = D.n_co;
-    out->ot_a = host_copy(D.ot_a.p, D.n_ot, st), out->ot_b = host_copy(D.ot_b.p, D.n_ot, st), out->ot_s = host_copy(D.ot_s.p, D.n_ot, st);
-    out->ip_a = host_copy(D.ip_a.p, D.n_ip, st), out->ip_b = host_copy(D.ip_b.p, D.n_ip, st), out->ip_s = host_copy(D.ip_s.p, D.n_ip, st);
-    out->co_key = host_copy(D.co_key.p, D.n_co, st), out->co_best = host_copy(D.co_best.p, D.n_co, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    out->ot_a = host_copy(who, D.ot_a.p, D.n_ot, st), out->ot_b = host_copy(who, D.ot_b.p, D.n_ot, st), out->ot_s = host_copy(who, D.ot_s.p, D.n_ot, st);
+    out->ip_a = host_copy(who, D.ip_a.p, D.n_ip, st), out->ip_b = host_copy(who, D.ip_b.p, D.n_ip, st), out->ip_s = host_copy(who, D.ip_s.p, D.n_ip, st);
+    out->co_key = host_copy(who, D.co_key.p, D.n_co, st), out->co_best = host_copy(who, D.co_best.p, D.n_co, st);
+    call.wait();
 }
 
 // ---- relations -----------------------------------------------------------------------------------------------------------------------
@@ -503,8 +467,8 @@ void orth_finish(OrthDev& D, hipStream_t st, const char*, so_orth_cand* out) {
 // of the co-ortholog products) decides no position.
 //   k_rel_has_ot -> k_rel_fwd_flag / scan / k_rel_fwd_emit (forward in-paralog pairs, keyed by the taxon of a) -> sort -> segments ->
 //   k_rel_ip_avg -> k_rel_ip_flag / scan / k_rel_ip_emit;  k_rel_co_count / scan / k_rel_co_probe / scan / k_rel_co_emit;
-//   per section (OT, CO): k_rel_blk_heads / scan / k_rel_starts, [sort by pair, k_rel_occ], scan, k_rel_keep_emit, sort by group,
-//   segments, k_rel_group_norm.
+//   per section (OT, CO): k_rel_blk_heads / scan / run_starts, [sort by pair, k_rel_occ], scan, k_rel_keep_emit, sort by group,
+//   segments, k_rel_group_norm.  (sort, segments: SortedGroups, device_call.h -- stable radix sort, then key_runs / run_starts.)
 __device__ __forceinline__ u32 lower_i64(const i64* __restrict__ a, u32 n, i64 x) {   // first position with a[p] >= x
     u32 lo = 0, hi = n;
     while (lo < hi) {
@@ -547,18 +511,6 @@ __global__ __launch_bounds__(256) void k_rel_fwd_emit(const i64* __restrict__ ip
     if (i >= n || !flag[i]) return;
     const u32 p = pos[i];
     fidx[p] = i, fkey[p] = (u64)tax[ip_a[i]];
-}
-
-// segments of a sorted key list: head flags, and (after their inclusive scan) the segment starts; start[nseg] = n
-__global__ __launch_bounds__(256) void k_rel_heads(const u64* __restrict__ key, u32 n, u32* __restrict__ head) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_rel_starts(u32 n, const u32* __restrict__ head, const u32* __restrict__ rid, u32 nseg, u32* __restrict__ start) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    if (head[i]) start[rid[i] - 1u] = i;
-    if (i == 0) start[nseg] = n;
 }
 
 // one wave per taxon that has forward pairs: the sum over all its pairs and over those with an ortholog on either side, each one chain in
@@ -720,42 +672,6 @@ __global__ __launch_bounds__(256) void k_rel_group_norm(const u32* __restrict__ 
     }
 }
 
-// scan + its total on the host (the stage sizes its next buffers by it)
-struct RelScan {
-    DevBuf<u32> tmp;
-    u32 run(const u32* in, u32* out, u32 n, bool inclusive, hipStream_t st) {
-        tmp.ensure(scan_u32_temp_elems(n) + 2);
-        const u32* d = scan_u32(in, out, n, inclusive, tmp.p, st);
-        u32 tot = 0;
-        HIP_CHECK(hipMemcpyAsync(&tot, d, sizeof(u32), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(st));
-        return tot;
-    }
-};
-
-// (key, row) pairs -> sorted by key, rows of one key in their order, and the bounds of the key groups
-struct RelGroups {
-    DevBuf<u64> skey;
-    DevBuf<u32> sidx, head, rid, start;
-    DevBuf<u8> sort_tmp;
-    RelScan sc;
-    u32 nseg = 0;
-    void sort(const u64* key, const u32* idx, u32 n, int bits, hipStream_t st) {
-        skey.ensure(n + 2), sidx.ensure(n + 2);
-        const size_t tb = sort_pairs_u64_u32_temp_bytes(n, bits);
-        sort_tmp.ensure(tb + 16);
-        sort_pairs_u64_u32(sort_tmp.p, tb, key, skey.p, idx, sidx.p, n, bits, st);
-    }
-    void segments(u32 n, hipStream_t st) {
-        head.ensure(n + 2), rid.ensure(n + 2);
-        hipLaunchKernelGGL(k_rel_heads, grid256(n), dim3(256), 0, st, skey.p, n, head.p);
-        nseg = sc.run(head.p, rid.p, n, true, st);
-        start.ensure((size_t)nseg + 3);
-        hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, st, n, head.p, rid.p, nseg, start.p);
-    }
-};
-
 struct RelSection {   // one output section on the device
     DevBuf<i64> a, b;
     DevBuf<double> v;
@@ -764,42 +680,53 @@ struct RelSection {   // one output section on the device
 
 // the repeat rule and the normalisation of one section (n > 0 rows pa, pb, ps); distinct: no pair occurs twice (the ortholog table: one row
 // per key that was proposed twice), so every row stays
-void rel_section(const i64* pa, const i64* pb, const double* ps, u32 n, bool distinct, const OrthDev& D, hipStream_t st, RelSection* out) {
-    DevBuf<u32> head, bid, bstart, keep, pos, idx, gidx;
+void rel_section(DeviceCall& call, const i64* pa, const i64* pb, const double* ps, u32 n, bool distinct, const OrthDev& D, RelSection* out) {
+    hipStream_t st = call.st;
+    DevBuf<u32> head, bid, bstart, keep, pos, idx, gidx, tmp;
     DevBuf<u64> key, gkey;
     DevBuf<double> ks;
-    RelScan sc;
-    head.ensure(n + 2), bid.ensure(n + 2), keep.ensure(n + 2), pos.ensure(n + 2);
+    head.ensure(n + 2), bid.ensure(n + 2), keep.ensure(n + 2), pos.ensure(n + 2), tmp.ensure(scan_u32_temp_elems(n) + 2);
     hipLaunchKernelGGL(k_rel_blk_heads, grid256(n), dim3(256), 0, st, pa, D.tax.p, n, head.p);
-    const u32 nblk = sc.run(head.p, bid.p, n, true, st);
+    const u32* d_nblk = scan_u32(head.p, bid.p, n, true, tmp.p, st);
+    HIP_CHECK(hipGetLastError());
+    const u32 nblk = call.read(d_nblk);
     if (distinct) fill_u32(keep.p, n, 1u, st);
     else {
         bstart.ensure((size_t)nblk + 3), key.ensure(n + 2), idx.ensure(n + 2);
-        hipLaunchKernelGGL(k_rel_starts, grid256(n), dim3(256), 0, st, n, head.p, bid.p, nblk, bstart.p);
+        run_starts(head.p, bid.p, n, d_nblk, bstart.p, st);   // (d_nblk lies in tmp, which is scanned with again only below)
         hipLaunchKernelGGL(k_rel_pair_keys, grid256(n), dim3(256), 0, st, pa, pb, n, D.M, key.p, idx.p);
-        RelGroups g;
-        g.sort(key.p, idx.p, n, ceil_log2(D.M * D.M), st);
+        SortedGroups g;
+        g.sort(call, key.p, idx.p, n, ceil_log2(D.M * D.M));
         hipLaunchKernelGGL(k_rel_occ, grid256(n), dim3(256), 0, st, g.skey.p, g.sidx.p, n, bid.p, bstart.p, pa, pb, D.M, keep.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(st));   // (g's buffers go away here)
+        call.wait();   // (g's buffers go away here)
     }
-    const u32 nk = sc.run(keep.p, pos.p, n, false, st);
+    const u32* d_nk = scan_u32(keep.p, pos.p, n, false, tmp.p, st);
+    HIP_CHECK(hipGetLastError());
+    const u32 nk = call.read(d_nk);
     out->n = nk;
     out->a.ensure(nk + 2), out->b.ensure(nk + 2), out->v.ensure(nk + 2), ks.ensure(nk + 2), gkey.ensure(nk + 2), gidx.ensure(nk + 2);
     hipLaunchKernelGGL(k_rel_keep_emit, grid256(n), dim3(256), 0, st, n, keep.p, pos.p, pa, pb, ps, bid.p, D.tax.p, D.T, out->a.p, out->b.p, ks.p, gkey.p, gidx.p);
-    RelGroups g;
-    g.sort(gkey.p, gidx.p, nk, ceil_log2((u64)nblk * D.T), st);
-    g.segments(nk, st);
+    SortedGroups g;
+    g.sort(call, gkey.p, gidx.p, nk, ceil_log2((u64)nblk * D.T));
+    g.segments(call, nk);
     hipLaunchKernelGGL(k_rel_group_norm, dim3((g.nseg + 3u) / 4u), dim3(256), 0, st, g.start.p, g.nseg, g.sidx.p, ks.p, out->v.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st));
+    call.wait();
 }
 
 // so_orth_relations_*: the relation tables are computed where the candidate tables are; only they come to the host
-void orth_finish(OrthDev& D, hipStream_t st, const char* who, so_orth_rel* out) {
+void orth_finish(OrthDev& D, DeviceCall& call, const char* who, so_orth_rel* out) {
+    hipStream_t st = call.st;
     out->n_rows = D.n_rows, out->n_runs = D.n_runs, out->n_groups = D.n_groups;
     RelSection ip, ot, co;
-    RelScan sc;
+    DevBuf<u32> tmp;   // scan scratch, grown before every scan; each total is read before the next scan
+    auto scan_total = [&](const u32* in, u32* pos, u32 n) {
+        tmp.ensure(scan_u32_temp_elems(n) + 2);
+        const u32* d = scan_u32(in, pos, n, false, tmp.p, st);
+        HIP_CHECK(hipGetLastError());
+        return call.read(d);
+    };
     DevBuf<i64> c_a, c_b;   // the co-ortholog rows before the repeat rule
     DevBuf<double> c_s;
     u32 n_c = 0;
@@ -813,20 +740,20 @@ void orth_finish(OrthDev& D, hipStream_t st, const char* who, so_orth_rel* out) 
         HIP_CHECK(hipMemsetAsync(has.p, 0, (size_t)D.M * sizeof(u32), st));
         if (D.n_ot) hipLaunchKernelGGL(k_rel_has_ot, grid256(D.n_ot), dim3(256), 0, st, D.ot_a.p, D.ot_b.p, D.n_ot, has.p);
         hipLaunchKernelGGL(k_rel_fwd_flag, grid256(n), dim3(256), 0, st, D.ip_a.p, D.ip_b.p, n, flag.p);
-        const u32 nf = sc.run(flag.p, pos.p, n, false, st);
+        const u32 nf = scan_total(flag.p, pos.p, n);
         if (nf) {
             fidx.ensure(nf + 2), fkey.ensure(nf + 2), flag2.ensure(nf + 2), pos2.ensure(nf + 2), avg.ensure((size_t)D.T + 2);
             hipLaunchKernelGGL(k_rel_fwd_emit, grid256(n), dim3(256), 0, st, D.ip_a.p, n, flag.p, pos.p, D.tax.p, fidx.p, fkey.p);
-            RelGroups g;
-            g.sort(fkey.p, fidx.p, nf, ceil_log2(D.T), st);
-            g.segments(nf, st);
+            SortedGroups g;
+            g.sort(call, fkey.p, fidx.p, nf, ceil_log2(D.T));
+            g.segments(call, nf);
             hipLaunchKernelGGL(k_rel_ip_avg, dim3((g.nseg + 3u) / 4u), dim3(256), 0, st, g.start.p, g.nseg, g.skey.p, g.sidx.p, D.ip_a.p, D.ip_b.p, D.ip_s.p, has.p, avg.p);
             hipLaunchKernelGGL(k_rel_ip_flag, grid256(nf), dim3(256), 0, st, fidx.p, nf, D.ip_a.p, D.tax.p, avg.p, flag2.p);
-            ip.n = sc.run(flag2.p, pos2.p, nf, false, st);
+            ip.n = scan_total(flag2.p, pos2.p, nf);
             ip.a.ensure(ip.n + 2), ip.b.ensure(ip.n + 2), ip.v.ensure(ip.n + 2);
             hipLaunchKernelGGL(k_rel_ip_emit, grid256(nf), dim3(256), 0, st, fidx.p, nf, flag2.p, pos2.p, D.ip_a.p, D.ip_b.p, D.ip_s.p, D.tax.p, avg.p, ip.a.p, ip.b.p, ip.v.p);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(st));
+            call.wait();
         }
     }
     if (D.n_ip && D.n_co && D.n_ot) {
@@ -840,141 +767,112 @@ void orth_finish(OrthDev& D, hipStream_t st, const char* who, so_orth_rel* out) 
         hipLaunchKernelGGL(k_rel_co_count, grid256(n), dim3(256), 0, st, D.ot_a.p, D.ot_b.p, n, D.ip_a.p, D.n_ip, lo_q.p, nq.p, lo_s.p, ns.p, cnt.p, total.p, err.p);
         unsigned long long tot = 0;
         u32 e = 0;
-        HIP_CHECK(hipMemcpyAsync(&tot, total.p, sizeof tot, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(&e, err.p, sizeof e, hipMemcpyDeviceToHost, st));
+        call.fetch(&tot, total.p), call.fetch(&e, err.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(st));
+        call.wait();
         if (e || tot >= (1ull << 31)) throw SoError(std::string(who) + ": 2^31 co-ortholog products and more are not supported (32-bit product numbers)");
         if (tot) {
             const u32 P = (u32)tot;
-            if (sc.run(cnt.p, base.p, n, false, st) != P) throw SoError(std::string(who) + ": internal error: the co-ortholog products do not add up");
+            if (scan_total(cnt.p, base.p, n) != P) throw SoError(std::string(who) + ": internal error: the co-ortholog products do not add up");
             hit.ensure((size_t)P + 2), hpos.ensure((size_t)P + 2), cpos.ensure((size_t)P + 2);
             hipLaunchKernelGGL(k_rel_co_probe, grid256(P), dim3(256), 0, st, P, base.p, n, lo_q.p, nq.p, lo_s.p, ns.p, D.ot_a.p, D.ot_b.p, D.ip_b.p, D.co_key.p, D.n_co, D.M,
                                hit.p, cpos.p);
-            n_c = sc.run(hit.p, hpos.p, P, false, st);
+            n_c = scan_total(hit.p, hpos.p, P);
             c_a.ensure(n_c + 2), c_b.ensure(n_c + 2), c_s.ensure(n_c + 2);
             hipLaunchKernelGGL(k_rel_co_emit, grid256(P), dim3(256), 0, st, P, hit.p, hpos.p, cpos.p, D.co_key.p, D.co_best.p, D.M, c_a.p, c_b.p, c_s.p);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(st));
+            call.wait();
         }
     }
     // ---- the repeat rule and the normalisation
-    if (D.n_ot) rel_section(D.ot_a.p, D.ot_b.p, D.ot_s.p, D.n_ot, true, D, st, &ot);
-    if (n_c) rel_section(c_a.p, c_b.p, c_s.p, n_c, false, D, st, &co);
+    if (D.n_ot) rel_section(call, D.ot_a.p, D.ot_b.p, D.ot_s.p, D.n_ot, true, D, &ot);
+    if (n_c) rel_section(call, c_a.p, c_b.p, c_s.p, n_c, false, D, &co);
     out->n_ip = ip.n, out->n_ot = ot.n, out->n_co = co.n;
-    out->ip_a = host_copy(ip.a.p, ip.n, st), out->ip_b = host_copy(ip.b.p, ip.n, st), out->ip_v = host_copy(ip.v.p, ip.n, st);
-    out->ot_a = host_copy(ot.a.p, ot.n, st), out->ot_b = host_copy(ot.b.p, ot.n, st), out->ot_v = host_copy(ot.v.p, ot.n, st);
-    out->co_a = host_copy(co.a.p, co.n, st), out->co_b = host_copy(co.b.p, co.n, st), out->co_v = host_copy(co.v.p, co.n, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+    out->ip_a = host_copy(who, ip.a.p, ip.n, st), out->ip_b = host_copy(who, ip.b.p, ip.n, st), out->ip_v = host_copy(who, ip.v.p, ip.n, st);
+    out->ot_a = host_copy(who, ot.a.p, ot.n, st), out->ot_b = host_copy(who, ot.b.p, ot.n, st), out->ot_v = host_copy(who, ot.v.p, ot.n, st);
+    out->co_a = host_copy(who, co.a.p, co.n, st), out->co_b = host_copy(who, co.b.p, co.n, st), out->co_v = host_copy(who, co.v.p, co.n, st);
+    call.wait();
 }
 
-
 // what every entry point checks before anything touches the device
-void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, void* out, size_t out_bytes) {
+template <class Out>
+void orth_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int norm, Out* out) {
     if (!out) throw SoError(std::string(who) + ": result pointer is NULL");
-    memset(out, 0, out_bytes);
-    if (n < 0 || n_names < 0 || n_taxa < 0 || (n_names > 0 && !tax) || norm < 0 || norm > 2) throw SoError(std::string(who) + ": bad arguments");
-    if (n >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 rows and more are not supported (32-bit row numbers)");
-    if (n_names > 3037000499ll) throw SoError(std::string(who) + ": n_names * n_names reaches 2^63 (pair keys a * n_names + b are 63-bit)");
-    for (i64 i = 0; i < n_names; ++i)
-        if (tax[i] < 0 || tax[i] >= n_taxa) throw SoError(std::string(who) + ": name " + std::to_string(i) + " has a taxon outside 0 .. n_taxa - 1");
+    memset(out, 0, sizeof *out);
+    if (norm < 0 || norm > 2) throw SoError(std::string(who) + ": bad arguments");
+    hit_table_check(who, n, n_names, tax, n_taxa, [&] {
+        if (n_names > 3037000499ll) throw SoError(std::string(who) + ": n_names * n_names reaches 2^63 (pair keys a * n_names + b are 63-bit)");
+    });
     check_device(who, device);
 }
 
-// an output of no rows still hands out arrays that its free function can release
-void orth_fill_empty(so_orth_cand* out) {
-    void** slots[8] = {(void**)&out->ot_a, (void**)&out->ot_b, (void**)&out->ot_s, (void**)&out->ip_a, (void**)&out->ip_b, (void**)&out->ip_s, (void**)&out->co_key,
-                       (void**)&out->co_best};
-    for (void** p : slots)
-        if (!*p) *p = calloc(1, 8);
-}
-void orth_fill_empty(so_orth_rel* out) {
-    void** slots[9] = {(void**)&out->ip_a, (void**)&out->ip_b, (void**)&out->ip_v, (void**)&out->ot_a, (void**)&out->ot_b, (void**)&out->ot_v, (void**)&out->co_a,
-                       (void**)&out->co_b, (void**)&out->co_v};
-    for (void** p : slots)
-        if (!*p) *p = calloc(1, 8);
-}
-void orth_release(so_orth_cand* r) {
-    free(r->ot_a), free(r->ot_b), free(r->ot_s), free(r->ip_a), free(r->ip_b), free(r->ip_s), free(r->co_key), free(r->co_best);
-    memset(r, 0, sizeof *r);
-}
-void orth_release(so_orth_rel* r) {
-    free(r->ip_a), free(r->ip_b), free(r->ip_v), free(r->ot_a), free(r->ot_b), free(r->ot_v), free(r->co_a), free(r->co_b), free(r->co_v);
-    memset(r, 0, sizeof *r);
+auto slots(so_orth_cand* r) { return result_slots(&r->ot_a, &r->ot_b, &r->ot_s, &r->ip_a, &r->ip_b, &r->ip_s, &r->co_key, &r->co_best); }
+auto slots(so_orth_rel* r) { return result_slots(&r->ip_a, &r->ip_b, &r->ip_v, &r->ot_a, &r->ot_b, &r->ot_v, &r->co_a, &r->co_b, &r->co_v); }
+template <class Out>
+void orth_release(Out* r) {
+    release_slots(r, slots(r));
 }
 
-// the two entry families: the candidate tables from host columns / device records, then orth_finish for the kind of result asked for
+struct OrthColBufs {   // the device columns of a call, and the maps they were unpacked through
+    DevBuf<int> q, s, qmap, smap;
+    DevBuf<double> idy, aln, qst, qed, score, qlen;
+    DevBuf<u32> err;
+};
+
+// What the two entry families (host columns / device records) end with: columns(call, b) brings the n rows to the device -- records must
+// be complete before this call's own stream reads them, so everything queued on the device so far is waited for (so_search_device has
+// synchronised its stream when it returns; a torch tensor's producer is on torch's stream) -- then the candidate tables, then
+// orth_finish for the kind of result asked for
+template <class Out, class Columns>
+void orth_tail(const char* who, int device, bool records, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, double coverage, double identity, int norm, Out* out,
+               Columns columns) {
+    if (n > 0) {
+        DeviceCall call(device, records);
+        OrthDev D;
+        {
+            OrthColBufs b;
+            b.err.ensure(4);
+            HIP_CHECK(hipMemsetAsync(b.err.p, 0, sizeof(u32), call.st));
+            columns(call, b);
+            const OrthCols c{b.q.p, b.s.p, b.idy.p, b.aln.p, b.qst.p, b.qed.p, b.score.p, b.qlen.p};
+            orth_run(call, n, c, n_names, tax, n_taxa, coverage, identity, norm, b.err.p, who, &D);
+            call.wait();   // (the columns go away here)
+        }
+        orth_finish(D, call, who, out);
+    }
+    fill_empty_slots(slots(out));
+}
+
 template <class Out>
 int orth_from_cols(const char* who, int device, int64_t n, const int32_t* q, const int32_t* s, const double* idy, const double* aln, const double* qst, const double* qed,
                    const double* score, const double* qlen, int64_t n_names, const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, Out* out) {
-    try {
-        orth_check(who, device, n, n_names, tax, n_taxa, norm, out, sizeof *out);
+    return guarded_call(g_orth_err, out, orth_release<Out>, [&] {
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
         if (n > 0 && (!q || !s || !idy || !aln || !qst || !qed || !score || !qlen)) throw SoError(std::string(who) + ": a column is NULL");
-        if (n > 0) {
-            DeviceCall call(device);
-            OrthDev D;
-            {
-                DevBuf<int> dq, ds;
-                DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
-                DevBuf<u32> d_err;
-                const size_t N = (size_t)n;
-                upload(dq, q, N, call.st), upload(ds, s, N, call.st), upload(d_idy, idy, N, call.st), upload(d_aln, aln, N, call.st), upload(d_qst, qst, N, call.st), upload(d_qed, qed, N, call.st);
-                upload(d_score, score, N, call.st), upload(d_qlen, qlen, N, call.st);
-                d_err.ensure(4);
-                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
-                const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-                orth_run(n, c, call.st, n_names, tax, n_taxa, coverage, identity, norm, call.tn, d_err.p, who, &D);
-                HIP_CHECK(hipStreamSynchronize(call.st));   // (the columns go away here)
-            }
-            orth_finish(D, call.st, who, out);
-        }
-        orth_fill_empty(out);
-        g_orth_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) orth_release(out);
-        g_orth_err = e.what();
-        return 1;
-    }
+        orth_tail(who, device, false, n, n_names, tax, n_taxa, coverage, identity, norm, out, [&](DeviceCall& call, OrthColBufs& b) {
+            const size_t N = (size_t)n;
+            const hipStream_t st = call.st;
+            upload(b.q, q, N, st), upload(b.s, s, N, st), upload(b.idy, idy, N, st), upload(b.aln, aln, N, st), upload(b.qst, qst, N, st), upload(b.qed, qed, N, st);
+            upload(b.score, score, N, st), upload(b.qlen, qlen, N, st);
+        });
+    });
 }
 
 template <class Out>
 int orth_from_records(const char* who, int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names,
                       const int32_t* tax, int64_t n_taxa, double coverage, double identity, int norm, Out* out) {
-    try {
-        orth_check(who, device, n, n_names, tax, n_taxa, norm, out, sizeof *out);
+    return guarded_call(g_orth_err, out, orth_release<Out>, [&] {
+        orth_check(who, device, n, n_names, tax, n_taxa, norm, out);
         if (n_q < 0 || n_s < 0 || (n_q > 0 && !qmap) || (n_s > 0 && !smap)) throw SoError(std::string(who) + ": bad arguments");
         if (n > 0 && !d_hits) throw SoError(std::string(who) + ": the record pointer is NULL");
-        if (n > 0) {
-            // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
-            // (so_search_device has synchronised its stream when it returns; a torch tensor's producer is on torch's stream)
-            DeviceCall call(device, true);
-            OrthDev D;
-            {
-                DevBuf<int> dq, ds, d_qmap, d_smap;
-                DevBuf<double> d_idy, d_aln, d_qst, d_qed, d_score, d_qlen;
-                DevBuf<u32> d_err;
-                const size_t N = (size_t)n;
-                upload(d_qmap, qmap, (size_t)n_q, call.st), upload(d_smap, smap, (size_t)n_s, call.st);
-                dq.ensure(N + 2), ds.ensure(N + 2), d_idy.ensure(N + 2), d_aln.ensure(N + 2), d_qst.ensure(N + 2), d_qed.ensure(N + 2), d_score.ensure(N + 2), d_qlen.ensure(N + 2);
-                d_err.ensure(4);
-                HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
-                hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, call.st, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p,
-                                   d_qed.p, d_score.p, d_qlen.p, d_err.p);
-                const OrthCols c{dq.p, ds.p, d_idy.p, d_aln.p, d_qst.p, d_qed.p, d_score.p, d_qlen.p};
-                orth_run(n, c, call.st, n_names, tax, n_taxa, coverage, identity, norm, call.tn, d_err.p, who, &D);
-                HIP_CHECK(hipStreamSynchronize(call.st));
-            }
-            orth_finish(D, call.st, who, out);
-        }
-        orth_fill_empty(out);
-        g_orth_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) orth_release(out);
-        g_orth_err = e.what();
-        return 1;
-    }
+        orth_tail(who, device, true, n, n_names, tax, n_taxa, coverage, identity, norm, out, [&](DeviceCall& call, OrthColBufs& b) {
+            const size_t N = (size_t)n;
+            upload(b.qmap, qmap, (size_t)n_q, call.st), upload(b.smap, smap, (size_t)n_s, call.st);
+            b.q.ensure(N + 2), b.s.ensure(N + 2), b.idy.ensure(N + 2), b.aln.ensure(N + 2), b.qst.ensure(N + 2), b.qed.ensure(N + 2), b.score.ensure(N + 2), b.qlen.ensure(N + 2);
+            hipLaunchKernelGGL(k_orth_unpack, grid256(N), dim3(256), 0, call.st, d_hits, (u32)N, b.qmap.p, (i64)n_q, b.smap.p, (i64)n_s, b.q.p, b.s.p, b.idy.p, b.aln.p, b.qst.p,
+                               b.qed.p, b.score.p, b.qlen.p, b.err.p);
+        });
+    });
 }
 
 }  // namespace

@@ -14,19 +14,19 @@
 // Nothing in the output depends on scheduling: positions come from flag -> scan -> compact, the sorts are stable, and the three atomics
 // are integer minima / maxima of stream positions (first winner per gene, last winner per cell) -- exact whatever the order.
 //
-// Kernels.  k_rbh_unpack (records -> columns), k_rbh_check, k_rbh_heads -> scan -> k_rbh_starts (run bounds).  The host reads the run
-// bounds and lists the runs the wave tier cannot hold (tune.h RBH_WAVE_ROWS; SOHIT_RBH_TIER=long sends every run there):
+// Kernels.  k_rbh_unpack (records -> columns; hit_codes, hit_table.h), k_rbh_check, key_runs -> run_starts (k_util.hip: k_run_heads ->
+// scan -> k_run_starts, the run bounds).  Every host wait goes through the call's DeviceCall (device_call.h) and is counted.  The host
+// reads the run bounds and lists the runs the wave tier cannot hold (tune.h RBH_WAVE_ROWS; SOHIT_RBH_TIER=long sends every run there):
 //   k_rbh_run_wave   a run of up to 64 rows per wave, a row per lane: every lane walks the run's lanes with shuffles and keeps the first
 //                    maximum of its own subject taxon; the first lane of a taxon stands for the group;
-//   k_rbh_long_keys -> stable radix sort of (long run, taxon) with the row as payload -> segments -> k_rbh_seg_max: one wave per
-//                    (run, taxon) segment, rows ascending inside it, first maximum by a strided walk and a butterfly.
+//   k_rbh_long_keys -> SortedGroups (device_call.h: stable radix sort of (long run, taxon) with the row as payload, segments) ->
+//                    k_rbh_seg_max: one wave per (run, taxon) segment, rows ascending inside it, first maximum by a strided walk and
+//                    a butterfly.
 // Both write flag[first row of the group] = 1 and wrow[first row] = winner row; scan, k_rbh_winners compacts (q, s) of the winners.
-// Pairs: k_rbh_pair_keys -> stable sort -> segments -> k_rbh_even (occurrence = index - segment start) -> scan -> k_rbh_pair_emit.
+// Pairs: k_rbh_pair_keys -> SortedGroups -> k_rbh_even (occurrence = index - segment start) -> scan -> k_rbh_pair_emit.
 // Core: k_rbh_first (atomicMin) -> k_rbh_gene_flag -> scan -> k_rbh_gene_emit -> k_rbh_last (atomicMax) -> k_rbh_fwd -> k_rbh_rec.
 #include "common.h"
-#include "device_call.h"
-#include "kernels.h"
-#include "../../include/sohit.h"
+#include "hit_table.h"
 
 #include <cstring>
 #include <string>
@@ -42,12 +42,8 @@ __global__ __launch_bounds__(256) void k_rbh_unpack(const so_hit* __restrict__ h
                                                     int* __restrict__ q, int* __restrict__ s, double* __restrict__ score, u32* __restrict__ err) {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const i64 qi = h[i].qidx, si = h[i].sidx;
-    int qc = 0, sc = 0;
-    if (qi < 0 || qi >= nq) atomicOr(err, 1u);
-    else qc = qmap[qi];
-    if (si < 0 || si >= ns) atomicOr(err, 2u);
-    else sc = smap[si];
+    int qc, sc;
+    hit_codes(h[i], qmap, nq, smap, ns, qc, sc, err);
     q[i] = qc, s[i] = sc, score[i] = (double)h[i].bit;
 }
 
@@ -58,19 +54,6 @@ __global__ __launch_bounds__(256) void k_rbh_check(u32 n, const int* __restrict_
     if (i >= n) return;
     if (q[i] < 0 || q[i] >= n_names || s[i] < 0 || s[i] >= n_names) atomicOr(err, 4u);
     if (score[i] != score[i]) atomicOr(err, 16u);
-}
-
-template <class K>   // head[i] = 1 where a run of equal keys starts
-__global__ __launch_bounds__(256) void k_rbh_heads(u32 n, const K* __restrict__ key, u32* __restrict__ head) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
-}
-// start[r] = first element of segment r; start[number of segments] = n.  rid: inclusive scan of head
-__global__ __launch_bounds__(256) void k_rbh_starts(u32 n, const u32* __restrict__ head, const u32* __restrict__ rid, const u32* __restrict__ nseg, u32* __restrict__ start) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    if (head[i]) start[rid[i] - 1u] = i;
-    if (i == 0) start[*nseg] = n;
 }
 
 // ---- winners -------------------------------------------------------------------------------------------------------------------------
@@ -213,39 +196,6 @@ __global__ __launch_bounds__(256) void k_rbh_rec(u32 nw, const int* __restrict__
 
 thread_local std::string g_rbh_err;
 
-template <class T>
-T* rbh_host_copy(const T* d, size_t n, hipStream_t st) {
-    T* h = host_array<T>("so_rbh", n);
-    if (n) {
-        const hipError_t e = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            free(h);
-            HIP_CHECK(e);
-        }
-    }
-    return h;
-}
-
-// sorted (key, position) list and the bounds of its key groups
-struct RbhGroups {
-    DevBuf<u64> skey;
-    DevBuf<u32> sidx, head, rid, start, tmp;
-    DevBuf<u8> sort_tmp;
-    u32 nseg = 0;
-    void run(DeviceCall& call, const u64* key, const u32* idx, u32 n, int bits) {
-        skey.ensure(n + 2), sidx.ensure(n + 2), head.ensure(n + 2), rid.ensure(n + 2), tmp.ensure(scan_u32_temp_elems(n) + 2);
-        const size_t tb = sort_pairs_u64_u32_temp_bytes(n, bits);
-        sort_tmp.ensure(tb + 16);
-        sort_pairs_u64_u32(sort_tmp.p, tb, key, skey.p, idx, sidx.p, n, bits, call.st);
-        hipLaunchKernelGGL(k_rbh_heads<u64>, grid256(n), dim3(256), 0, call.st, n, skey.p, head.p);
-        const u32* d_nseg = scan_u32(head.p, rid.p, n, true, tmp.p, call.st);
-        HIP_CHECK(hipGetLastError());
-        nseg = call.read(d_nseg);
-        start.ensure((size_t)nseg + 3);
-        hipLaunchKernelGGL(k_rbh_starts, grid256(n), dim3(256), 0, call.st, n, head.p, rid.p, d_nseg, start.p);
-    }
-};
-
 // the stage on device columns of n > 0 rows; d_err: what the unpack kernel may have set already
 void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* score, i64 n_names, const int32_t* tax, i64 n_taxa, int R, u32* d_err, const char* who,
              so_rbh_result* out) {
@@ -257,23 +207,19 @@ void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* 
     upload(d_tax, tax, (size_t)n_names, st);
     head.ensure(n + 2), rid.ensure(n + 2), rstart.ensure((size_t)n + 3), tmp.ensure(scan_u32_temp_elems(n) + 2);
     hipLaunchKernelGGL(k_rbh_check, grid256(n), dim3(256), 0, st, n, q, s, score, n_names, d_err);
-    hipLaunchKernelGGL(k_rbh_heads<int>, grid256(n), dim3(256), 0, st, n, q, head.p);
-    const u32* d_nruns = scan_u32(head.p, rid.p, n, true, tmp.p, st);
-    hipLaunchKernelGGL(k_rbh_starts, grid256(n), dim3(256), 0, st, n, head.p, rid.p, d_nruns, rstart.p);
+    const u32* d_nruns = key_runs(q, n, head.p, rid.p, tmp.p, st);
+    run_starts(head.p, rid.p, n, d_nruns, rstart.p, st);
     HIP_CHECK(hipGetLastError());
     u32 nruns = 0, err = 0;
     call.read(d_nruns, nruns, d_err, err);
-    if (err & 1u) throw SoError(std::string(who) + ": a record's qidx lies outside the query map");
-    if (err & 2u) throw SoError(std::string(who) + ": a record's sidx lies outside the subject map");
-    if (err & 4u) throw SoError(std::string(who) + ": a name code lies outside 0 .. n_names - 1");
+    hit_table_errors(who, err);
     if (err & 16u) throw SoError(std::string(who) + ": a NaN score (the order of such rows is not defined here)");
     out->n_runs = nruns;
 
     // the runs the wave tier cannot hold, their rows laid out one run behind the other
     std::vector<u32> rs((size_t)nruns + 1), lrun, loff;
-    HIP_CHECK(hipMemcpyAsync(rs.data(), rstart.p, rs.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    ++call.waits;
+    call.fetch(rs.data(), rstart.p, rs.size());
+    call.wait();
     const bool all_long = call.tn.rbh_tier >= 2;   // (forcing the wave tier changes nothing: it already takes every run it can hold)
     u64 nlong = 0;
     for (u32 r = 0; r < nruns; ++r) {
@@ -287,13 +233,14 @@ void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* 
     hipLaunchKernelGGL(k_rbh_run_wave, dim3((nruns + 3u) / 4u), dim3(256), 0, st, rstart.p, nruns, all_long ? 1 : 0, q, s, score, d_tax.p, flag.p, wrow.p);
     DevBuf<u32> d_lrun, d_loff, lval;
     DevBuf<u64> lkey;
-    RbhGroups lg;
+    SortedGroups lg;
     if (!lrun.empty()) {
         const u32 NL = (u32)nlong;   // <= n < 2^31
         upload(d_lrun, lrun.data(), lrun.size(), st), upload(d_loff, loff.data(), loff.size(), st);
         lkey.ensure((size_t)NL + 2), lval.ensure((size_t)NL + 2);
         hipLaunchKernelGGL(k_rbh_long_keys, dim3((u32)lrun.size()), dim3(256), 0, st, d_lrun.p, d_loff.p, rstart.p, s, d_tax.p, T, lkey.p, lval.p);
-        lg.run(call, lkey.p, lval.p, NL, ceil_log2((u64)lrun.size() * T));
+        lg.sort(call, lkey.p, lval.p, NL, ceil_log2((u64)lrun.size() * T));
+        lg.segments(call, NL);
         hipLaunchKernelGGL(k_rbh_seg_max, dim3((lg.nseg + 3u) / 4u), dim3(256), 0, st, lg.start.p, lg.nseg, lg.skey.p, lg.sidx.p, d_lrun.p, rstart.p, q, score, d_tax.p, T,
                            flag.p, wrow.p);
     }
@@ -310,10 +257,11 @@ void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* 
         DevBuf<u64> key;
         DevBuf<u32> idx, even, epos, etmp;
         DevBuf<int> oa, ob;
-        RbhGroups g;
+        SortedGroups g;
         key.ensure(nw + 2), idx.ensure(nw + 2), even.ensure(nw + 2), epos.ensure(nw + 2), etmp.ensure(scan_u32_temp_elems(nw) + 2);
         hipLaunchKernelGGL(k_rbh_pair_keys, grid256(nw), dim3(256), 0, st, nw, wq.p, ws.p, M, key.p, idx.p);
-        g.run(call, key.p, idx.p, nw, ceil_log2(M * M));
+        g.sort(call, key.p, idx.p, nw, ceil_log2(M * M));
+        g.segments(call, nw);
         hipLaunchKernelGGL(k_rbh_even, grid256(nw), dim3(256), 0, st, nw, g.sidx.p, g.rid.p, g.start.p, even.p);
         const u32* d_ne = scan_u32(even.p, epos.p, nw, false, etmp.p, st);
         HIP_CHECK(hipGetLastError());
@@ -321,9 +269,8 @@ void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* 
         oa.ensure(ne + 2), ob.ensure(ne + 2);
         hipLaunchKernelGGL(k_rbh_pair_emit, grid256(nw), dim3(256), 0, st, nw, even.p, epos.p, wq.p, ws.p, oa.p, ob.p);
         HIP_CHECK(hipGetLastError());
-        out->rbh_a = rbh_host_copy(oa.p, ne, st), out->rbh_b = rbh_host_copy(ob.p, ne, st);
-        HIP_CHECK(hipStreamSynchronize(st));   // (the buffers of this block go away here)
-        ++call.waits;
+        out->rbh_a = host_copy(who, oa.p, ne, st), out->rbh_b = host_copy(who, ob.p, ne, st);
+        call.wait();   // (the buffers of this block go away here)
         out->n_rbh = ne;
     }
     if (R < 0) return;
@@ -352,37 +299,46 @@ void rbh_run(DeviceCall& call, u32 n, const int* q, const int* s, const double* 
     hipLaunchKernelGGL(k_rbh_fwd, grid256(cells), dim3(256), 0, st, cells, last.p, ws.p, fwd.p);
     hipLaunchKernelGGL(k_rbh_rec, grid256(nw), dim3(256), 0, st, nw, wq.p, ws.p, d_tax.p, R, T, first.p, fwd.p, rec.p);
     HIP_CHECK(hipGetLastError());
-    out->core_gene = rbh_host_copy(gene.p, nc, st), out->core_fwd = rbh_host_copy(fwd.p, cells, st), out->core_rec = rbh_host_copy(rec.p, cells, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    ++call.waits;
+    out->core_gene = host_copy(who, gene.p, nc, st), out->core_fwd = host_copy(who, fwd.p, cells, st), out->core_rec = host_copy(who, rec.p, cells, st);
+    call.wait();
     out->n_core = nc;
 }
 
-void rbh_release(so_rbh_result* r) {
-    free(r->rbh_a), free(r->rbh_b), free(r->core_gene), free(r->core_fwd), free(r->core_rec);
-    memset(r, 0, sizeof *r);
-}
-
-// an output of no rows still hands out arrays that so_rbh_free can release
-void rbh_fill_empty(so_rbh_result* out) {
-    void** slots[5] = {(void**)&out->rbh_a, (void**)&out->rbh_b, (void**)&out->core_gene, (void**)&out->core_fwd, (void**)&out->core_rec};
-    for (void** p : slots)
-        if (!*p) *p = calloc(1, 8);
-}
+auto slots(so_rbh_result* r) { return result_slots(&r->rbh_a, &r->rbh_b, &r->core_gene, &r->core_fwd, &r->core_rec); }
 
 // what both entry points check before anything touches the device
 void rbh_check(const char* who, int device, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int ref_taxon, int flags, so_rbh_result* out) {
     if (!out) throw SoError(std::string(who) + ": result pointer is NULL");
     memset(out, 0, sizeof *out);
-    if (n < 0 || n_names < 0 || n_taxa < 0 || (n_names > 0 && !tax)) throw SoError(std::string(who) + ": bad arguments");
-    if (flags != 0) throw SoError(std::string(who) + ": flags is reserved and must be 0");
-    if (n >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 rows and more are not supported (32-bit row numbers)");
-    if (n_names >= (1ll << 31) || n_taxa >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 names or taxa and more are not supported (32-bit codes)");
-    if (ref_taxon < -1 || ref_taxon >= n_taxa) throw SoError(std::string(who) + ": ref_taxon lies outside -1 .. n_taxa - 1");
-    for (i64 i = 0; i < n_names; ++i)
-        if (tax[i] < 0 || tax[i] >= n_taxa) throw SoError(std::string(who) + ": name " + std::to_string(i) + " has a taxon outside 0 .. n_taxa - 1");
+    hit_table_check(who, n, n_names, tax, n_taxa, [&] {
+        if (flags != 0) throw SoError(std::string(who) + ": flags is reserved and must be 0");
+        if (n_names >= (1ll << 31) || n_taxa >= (1ll << 31)) throw SoError(std::string(who) + ": 2^31 names or taxa and more are not supported (32-bit codes)");
+        if (ref_taxon < -1 || ref_taxon >= n_taxa) throw SoError(std::string(who) + ": ref_taxon lies outside -1 .. n_taxa - 1");
+    });
     out->n_taxa = n_taxa;
     check_device(who, device);
+}
+
+struct RbhCols {   // the device columns of a call, and the maps they were unpacked through
+    DevBuf<int> q, s, qmap, smap;
+    DevBuf<double> score;
+    DevBuf<u32> err;
+};
+
+// what both entry points end with: columns(call, c) brings the n rows to the device, by upload or from the records -- those must be
+// complete before this call's own stream reads them: everything queued on the device so far is waited for
+template <class Columns>
+void rbh_tail(const char* who, int device, bool records, i64 n, i64 n_names, const int32_t* tax, i64 n_taxa, int ref_taxon, so_rbh_result* out, Columns columns) {
+    if (n > 0) {
+        DeviceCall call(device, records);
+        RbhCols c;
+        c.err.ensure(4);
+        HIP_CHECK(hipMemsetAsync(c.err.p, 0, sizeof(u32), call.st));
+        columns(call, c);
+        rbh_run(call, (u32)n, c.q.p, c.s.p, c.score.p, n_names, tax, n_taxa, ref_taxon, c.err.p, who, out);
+        out->waits = call.waits;
+    }
+    fill_empty_slots(slots(out));
 }
 
 }  // namespace
@@ -392,68 +348,36 @@ extern "C" {
 const char* so_rbh_last_error(void) { return g_rbh_err.c_str(); }
 
 void so_rbh_free(so_rbh_result* r) {
-    if (r) rbh_release(r);
+    if (r) release_slots(r, slots(r));
 }
 
 int so_rbh_cols(int device, int64_t n, const int32_t* q, const int32_t* s, const double* score, int64_t n_names, const int32_t* tax, int64_t n_taxa, int32_t ref_taxon,
                 int32_t flags, so_rbh_result* out) {
     const char* who = "so_rbh_cols";
-    try {
+    return guarded_call(g_rbh_err, out, so_rbh_free, [&] {
         rbh_check(who, device, n, n_names, tax, n_taxa, ref_taxon, flags, out);
         if (n > 0 && (!q || !s || !score)) throw SoError(std::string(who) + ": a column is NULL");
-        if (n > 0) {
-            DeviceCall call(device);
-            DevBuf<int> dq, ds;
-            DevBuf<double> d_score;
-            DevBuf<u32> d_err;
+        rbh_tail(who, device, false, n, n_names, tax, n_taxa, ref_taxon, out, [&](DeviceCall& call, RbhCols& c) {
             const size_t N = (size_t)n;
-            upload(dq, q, N, call.st), upload(ds, s, N, call.st), upload(d_score, score, N, call.st);
-            d_err.ensure(4);
-            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
-            rbh_run(call, (u32)N, dq.p, ds.p, d_score.p, n_names, tax, n_taxa, ref_taxon, d_err.p, who, out);
-            HIP_CHECK(hipStreamSynchronize(call.st));
-            out->waits = call.waits;
-        }
-        rbh_fill_empty(out);
-        g_rbh_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) rbh_release(out);
-        g_rbh_err = e.what();
-        return 1;
-    }
+            upload(c.q, q, N, call.st), upload(c.s, s, N, call.st), upload(c.score, score, N, call.st);
+        });
+    });
 }
 
 int so_rbh_records(int device, const so_hit* d_hits, int64_t n, const int32_t* qmap, int64_t n_q, const int32_t* smap, int64_t n_s, int64_t n_names, const int32_t* tax,
                    int64_t n_taxa, int32_t ref_taxon, int32_t flags, so_rbh_result* out) {
     const char* who = "so_rbh_records";
-    try {
+    return guarded_call(g_rbh_err, out, so_rbh_free, [&] {
         rbh_check(who, device, n, n_names, tax, n_taxa, ref_taxon, flags, out);
         if (n_q < 0 || n_s < 0 || (n_q > 0 && !qmap) || (n_s > 0 && !smap)) throw SoError(std::string(who) + ": bad arguments");
         if (n > 0 && !d_hits) throw SoError(std::string(who) + ": the record pointer is NULL");
-        if (n > 0) {
-            // the records must be complete before this call's own stream reads them: wait for everything queued on the device so far
-            DeviceCall call(device, true);
-            DevBuf<int> dq, ds, d_qmap, d_smap;
-            DevBuf<double> d_score;
-            DevBuf<u32> d_err;
+        rbh_tail(who, device, true, n, n_names, tax, n_taxa, ref_taxon, out, [&](DeviceCall& call, RbhCols& c) {
             const size_t N = (size_t)n;
-            upload(d_qmap, qmap, (size_t)n_q, call.st), upload(d_smap, smap, (size_t)n_s, call.st);
-            dq.ensure(N + 2), ds.ensure(N + 2), d_score.ensure(N + 2), d_err.ensure(4);
-            HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(u32), call.st));
-            hipLaunchKernelGGL(k_rbh_unpack, grid256(N), dim3(256), 0, call.st, d_hits, (u32)N, d_qmap.p, (i64)n_q, d_smap.p, (i64)n_s, dq.p, ds.p, d_score.p, d_err.p);
-            rbh_run(call, (u32)N, dq.p, ds.p, d_score.p, n_names, tax, n_taxa, ref_taxon, d_err.p, who, out);
-            HIP_CHECK(hipStreamSynchronize(call.st));
-            out->waits = call.waits;
-        }
-        rbh_fill_empty(out);
-        g_rbh_err.clear();
-        return 0;
-    } catch (const std::exception& e) {
-        if (out) rbh_release(out);
-        g_rbh_err = e.what();
-        return 1;
-    }
+            upload(c.qmap, qmap, (size_t)n_q, call.st), upload(c.smap, smap, (size_t)n_s, call.st);
+            c.q.ensure(N + 2), c.s.ensure(N + 2), c.score.ensure(N + 2);
+            hipLaunchKernelGGL(k_rbh_unpack, grid256(N), dim3(256), 0, call.st, d_hits, (u32)N, c.qmap.p, (i64)n_q, c.smap.p, (i64)n_s, c.q.p, c.s.p, c.score.p, c.err.p);
+        });
+    });
 }
 
 }  // extern "C"

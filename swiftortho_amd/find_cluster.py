@@ -250,9 +250,9 @@ def device_mcl(indptr, indices, data, inflation, device=0, rounds=100, check=5, 
         n, nnz = int(res.n), int(res.nnz)
         if isinstance(info, dict):
             info.update(rounds=int(res.rounds), converged=int(res.converged))
-        out_ip = np.ctypeslib.as_array(res.indptr, shape=(n + 1,)).copy()
-        out_ix = np.ctypeslib.as_array(res.indices, shape=(max(nnz, 1),))[:nnz].copy()
-        out_dv = np.ctypeslib.as_array(res.data, shape=(max(nnz, 1),))[:nnz].copy()
+        out_ip = _lib.result_array(res.indptr, n + 1)
+        out_ix = _lib.result_array(res.indices, nnz)
+        out_dv = _lib.result_array(res.data, nnz)
     finally:
         L.so_mcl_free(C.byref(res))
     return out_ip, out_ix, out_dv
@@ -284,13 +284,10 @@ def device_mcl_rows(gx, gy, z, n_labels, inflation, device=0, rounds=100, check=
         d, npair, nnz = int(res.n_genes), int(res.n_pairs), int(res.nnz)
         if isinstance(info, dict):
             info.update(rounds=int(res.rounds), converged=int(res.converged))
-        out = (np.ctypeslib.as_array(res.gene, shape=(max(d, 1),))[:d].copy(),
-               np.ctypeslib.as_array(res.pair_r, shape=(max(npair, 1),))[:npair].copy(),
-               np.ctypeslib.as_array(res.pair_c, shape=(max(npair, 1),))[:npair].copy())
+        arr = _lib.result_array
+        out = (arr(res.gene, d), arr(res.pair_r, npair), arr(res.pair_c, npair))
         if want_matrix:
-            out += (np.ctypeslib.as_array(res.indptr, shape=(d + 2,)).copy(),
-                    np.ctypeslib.as_array(res.indices, shape=(max(nnz, 1),))[:nnz].copy(),
-                    np.ctypeslib.as_array(res.data, shape=(max(nnz, 1),))[:nnz].copy())
+            out += (arr(res.indptr, d + 2), arr(res.indices, nnz), arr(res.data, nnz))
     finally:
         L.so_mcl_rows_free(C.byref(res))
     return out
@@ -312,8 +309,8 @@ def device_readout(indptr, indices, data, prune=1e-5, device=0):
         raise RuntimeError(L.so_mcl_last_error().decode())
     try:
         npair = int(res.n_pairs)
-        r = np.ctypeslib.as_array(res.pair_r, shape=(max(npair, 1),))[:npair].copy()
-        c = np.ctypeslib.as_array(res.pair_c, shape=(max(npair, 1),))[:npair].copy()
+        r = _lib.result_array(res.pair_r, npair)
+        c = _lib.result_array(res.pair_c, npair)
     finally:
         L.so_mcl_rows_free(C.byref(res))
     return r, c
@@ -560,9 +557,9 @@ def device_group_numbers(X, Y, Z, n, device=0, info=None):
         d = int(res.n_genes)
         if isinstance(info, dict):
             info.update(n_comp1=int(res.n_comp1), n_grp=int(res.n_grp), n_keep=int(res.n_keep), sweeps1=int(res.sweeps1), sweeps2=int(res.sweeps2))
-        comp1 = np.ctypeslib.as_array(res.comp1, shape=(max(d, 1),))[:d].copy()
-        grp = np.ctypeslib.as_array(res.grp, shape=(max(d, 1),))[:d].copy()
-        keep = np.ctypeslib.as_array(res.keep, shape=(max(nr, 1),))[:nr].astype(bool)
+        comp1 = _lib.result_array(res.comp1, d)
+        grp = _lib.result_array(res.grp, d)
+        keep = _lib.result_array(res.keep, nr, bool)
     finally:
         L.so_cnc_free(C.byref(res))
     return comp1, grp, keep
@@ -652,7 +649,7 @@ def device_row_plan(cx, cy, Z, n_codes, device=0, info=None, two_pass=False):
     try:
         if isinstance(info, dict):
             info.update({k: int(getattr(res, k)) for k in ('n_genes', 'n_comp1', 'n_grp', 'n_keep', 'sweeps1', 'sweeps2', 'sort_passes', 'waits')})
-        col = lambda p, n: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(np.int64)
+        col = lambda p, n: _lib.result_array(p, n, np.int64)
         d, k = int(res.n_genes), int(res.n_keep)
         plan = RowPlan(col(res.gene_code, d), col(res.x, nr), col(res.y, nr), col(res.comp1, d), col(res.grp, d), col(res.order, k),
                        col(res.cut, int(res.n_cut)), col(res.tied, int(res.n_tied)))
@@ -881,9 +878,9 @@ def device_apc(row, col, score, n_genes, damp, rounds=100, device=0):
         raise RuntimeError(L.so_apc_last_error().decode())
     try:
         d = int(res.n_genes)
-        labels = np.ctypeslib.as_array(res.labels, shape=(max(d, 1),))[:d].copy()
-        r = np.ctypeslib.as_array(res.r, shape=(max(n, 1),))[:n].copy()
-        a = np.ctypeslib.as_array(res.a, shape=(max(n, 1),))[:n].copy()
+        labels = _lib.result_array(res.labels, d)
+        r = _lib.result_array(res.r, n)
+        a = _lib.result_array(res.a, n)
     finally:
         L.so_apc_free(C.byref(res))
     return labels, r, a
@@ -923,7 +920,7 @@ def device_apc_rows(cx, cy, z, n_codes, taxon_of_code, damp, rounds=100, device=
         d, n = int(res.n_genes), int(res.n_entries)
         if isinstance(info, dict):
             info.update({k: int(getattr(res, k)) for k in ('n_genes', 'n_entries', 'n_taxa_used', 'rounds', 'waits')})
-        col = lambda p, k: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].copy()
+        col = _lib.result_array
         out = (col(res.gene_code, d).astype(np.int64), col(res.labels, d))
         if want_entries:
             out += (col(res.row, n), col(res.col, n), col(res.score, n), col(res.r, n), col(res.a, n))

@@ -521,9 +521,7 @@ def _orth_call(fn, tail_of, names, tax, taxa, coverage, identity, norm, stage='c
     if rc != 0:
         raise RuntimeError(L.so_orth_last_error().decode())
     try:
-        def arr(p, n, dt):
-            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
-        i, f = np.int64, np.float64
+        arr, i, f = _lib.result_array, np.int64, np.float64
         if rel:
             return RelationTables(arr(out.ip_a, out.n_ip, i), arr(out.ip_b, out.n_ip, i), arr(out.ip_v, out.n_ip, f),
                                   arr(out.ot_a, out.n_ot, i), arr(out.ot_b, out.n_ot, i), arr(out.ot_v, out.n_ot, f),
@@ -546,15 +544,21 @@ def device_relation_tables(cols, coverage=.5, identity=0., norm='no', sep='|', d
     return _device_cols(cols, coverage, identity, norm, sep, device, 'relations')
 
 
-def _device_cols(cols, coverage, identity, norm, sep, device, stage):
-    import ctypes as C
+def code_columns32(cols, who):
+    """-> (rows, q, s as contiguous int32) of host columns, or the refusal in `who`'s name: the library takes 32-bit rows and codes"""
     n = len(cols.q)
     if n >= 1 << 31:
-        raise RuntimeError('so_orth_candidates: 2^31 rows and more are not supported')
+        raise RuntimeError('%s: 2^31 rows and more are not supported' % who)
     q32 = np.ascontiguousarray(cols.q, dtype=np.int32)
     s32 = np.ascontiguousarray(cols.s, dtype=np.int32)
     if n and not (np.array_equal(q32, cols.q) and np.array_equal(s32, cols.s)):
-        raise RuntimeError('so_orth_candidates: a name code does not fit 32 bits')
+        raise RuntimeError('%s: a name code does not fit 32 bits' % who)
+    return n, q32, s32
+
+
+def _device_cols(cols, coverage, identity, norm, sep, device, stage):
+    import ctypes as C
+    n, q32, s32 = code_columns32(cols, 'so_orth_candidates')
     dbl = [np.ascontiguousarray(getattr(cols, k), dtype=np.float64) for k in ('idy', 'aln', 'qst', 'qed', 'score', 'qlen')]
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     head = [int(device), n, ptr(q32), ptr(s32)] + [ptr(a) for a in dbl]
@@ -569,24 +573,28 @@ def _record_maps(query_ids, subject_ids):
     return names, np.ascontiguousarray(qmap, dtype=np.int32), np.ascontiguousarray(smap, dtype=np.int32)
 
 
-def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep, stage='candidates'):
-    """-> (names, tax, taxa, Candidates | RelationTables) of the records `dev` holds"""
+def records_on_device(dev, who):
+    """records that are on the device -- a fsearch.DeviceHits, a nr.ExpandedHits or a CUDA uint8 torch tensor of so_hit records -- ->
+    (device pointer, records, device index, what must stay alive while the library reads them); `who` names the caller in a refusal"""
     import ctypes as C
     from . import _lib
     rec = C.sizeof(_lib.SoHit)
-    keep_alive = dev
     if hasattr(dev, 'device_pointer'):
-        d_ptr, n, device = dev.device_pointer(), len(dev), dev.device if hasattr(dev, 'device') else dev.s.device   # (nr.ExpandedHits | DeviceHits)
-    else:
-        import torch
-        if not (isinstance(dev, torch.Tensor) and dev.is_cuda and dev.dtype == torch.uint8):
-            raise TypeError('device_candidates_from_records: a DeviceHits or a CUDA uint8 tensor of so_hit records is needed')
-        if dev.numel() % rec:
-            raise ValueError('device_candidates_from_records: the tensor does not hold whole so_hit records')
-        keep_alive = dev = dev.contiguous()
-        # the records were written on torch's stream; the library works on a stream of its own
-        torch.cuda.current_stream(dev.device).synchronize()
-        d_ptr, n, device = dev.data_ptr(), dev.numel() // rec, dev.device.index or 0
+        return dev.device_pointer(), len(dev), dev.device if hasattr(dev, 'device') else dev.s.device, dev   # (nr.ExpandedHits | DeviceHits)
+    import torch
+    if not (isinstance(dev, torch.Tensor) and dev.is_cuda and dev.dtype == torch.uint8):
+        raise TypeError('%s: a DeviceHits or a CUDA uint8 tensor of so_hit records is needed' % who)
+    if dev.numel() % rec:
+        raise ValueError('%s: the tensor does not hold whole so_hit records' % who)
+    dev = dev.contiguous()
+    torch.cuda.current_stream(dev.device).synchronize()   # the records were written on torch's stream; the library works on a stream of its own
+    return dev.data_ptr(), dev.numel() // rec, dev.device.index or 0, dev
+
+
+def _device_records(dev, query_ids, subject_ids, coverage, identity, norm, sep, stage='candidates'):
+    """-> (names, tax, taxa, Candidates | RelationTables) of the records `dev` holds"""
+    import ctypes as C
+    d_ptr, n, device, keep_alive = records_on_device(dev, 'device_candidates_from_records')
     names, qmap, smap = _record_maps(query_ids, subject_ids)
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     head = [int(device), C.c_void_p(d_ptr), n, ptr(qmap), len(qmap), ptr(smap), len(smap)]

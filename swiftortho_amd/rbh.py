@@ -247,8 +247,7 @@ def _rbh_call(fn, head, n_names, tax, n_taxa, ref_taxon):
     if rc != 0:
         raise RuntimeError(L.so_rbh_last_error().decode())
     try:
-        def arr(p, n, dt):
-            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+        arr = _lib.result_array
         nc, nt = int(out.n_core), int(n_taxa)
         stats = {k: int(getattr(out, k)) for k in ('n_runs', 'n_winners', 'n_runs_long', 'n_rows_long', 'waits')}
         return (arr(out.rbh_a, out.n_rbh, np.int64), arr(out.rbh_b, out.n_rbh, np.int64), arr(out.core_gene, nc, np.int64),
@@ -259,13 +258,7 @@ def _rbh_call(fn, head, n_names, tax, n_taxa, ref_taxon):
 
 def _cols_head(cols, device):
     import ctypes as C
-    n = len(cols.q)
-    if n >= 1 << 31:
-        raise RuntimeError('so_rbh_cols: 2^31 rows and more are not supported')
-    q32 = np.ascontiguousarray(cols.q, dtype=np.int32)
-    s32 = np.ascontiguousarray(cols.s, dtype=np.int32)
-    if n and not (np.array_equal(q32, cols.q) and np.array_equal(s32, cols.s)):
-        raise RuntimeError('so_rbh_cols: a name code does not fit 32 bits')
+    n, q32, s32 = find_orth.code_columns32(cols, 'so_rbh_cols')
     sco = np.ascontiguousarray(cols.score, dtype=np.float64)
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     return [int(device), n, ptr(q32), ptr(s32), ptr(sco)], (q32, s32, sco)
@@ -274,19 +267,7 @@ def _cols_head(cols, device):
 def _records_head(dev, query_ids, subject_ids):
     """-> (names, head arguments of so_rbh_records, what must stay alive during the call)"""
     import ctypes as C
-    from . import _lib
-    rec = C.sizeof(_lib.SoHit)
-    if hasattr(dev, 'device_pointer'):
-        d_ptr, n, device = dev.device_pointer(), len(dev), dev.device if hasattr(dev, 'device') else dev.s.device   # (nr.ExpandedHits | DeviceHits)
-    else:
-        import torch
-        if not (isinstance(dev, torch.Tensor) and dev.is_cuda and dev.dtype == torch.uint8):
-            raise TypeError('rbh: a DeviceHits or a CUDA uint8 tensor of so_hit records is needed')
-        if dev.numel() % rec:
-            raise ValueError('rbh: the tensor does not hold whole so_hit records')
-        dev = dev.contiguous()
-        torch.cuda.current_stream(dev.device).synchronize()   # the records were written on torch's stream; the library works on its own
-        d_ptr, n, device = dev.data_ptr(), dev.numel() // rec, dev.device.index or 0
+    d_ptr, n, device, dev = find_orth.records_on_device(dev, 'rbh')
     names, qmap, smap = find_orth._record_maps(query_ids, subject_ids)
     ptr = lambda a: C.c_void_p(a.ctypes.data)
     return names, [int(device), C.c_void_p(d_ptr), n, ptr(qmap), len(qmap), ptr(smap), len(smap)], (dev, qmap, smap)

@@ -305,3 +305,19 @@ def records_from_columns(cols, n_dup=6, seed=0):
     rec["bit"] = cols.score.astype(np.int32)
     rec["evalue"] = 1e-30
     return rec, query_ids, subject_ids
+
+
+KEPT_EDGES = (256, 8192, 32768)   # kept-row positions at a workgroup, a scan tile and the single-launch scan's limit (csrc/k_util.hip)
+
+
+def kept_edges(seed=0):
+    """generate(seed) with a row that every FLAG_SETS filter drops (coverage 1 / 400) directly before and directly after the kept rows
+    number KEPT_EDGES (from 0): the compaction offsets and the run heads of the kept rows change exactly on those edges.  The dropped
+    rows ask the other way round with a score above every other, so a row kept by mistake changes runs, maxima and the bsr divisor."""
+    c = generate(seed)
+    kept = np.flatnonzero(~(((1. + np.abs(c.qed - c.qst)) / c.qlen < .5) | (c.idy < 0.)))
+    at = np.array([r + d for k in KEPT_EDGES for r in [kept[k]] for d in (0, 1)])   # np.insert: before these rows of the table as it is
+    src = np.repeat(kept[list(KEPT_EDGES)], 2)
+    ins = lambda a, v: np.insert(a, at, v)
+    return fo.HitColumns(c.names, ins(c.q, c.s[src]), ins(c.s, c.q[src]), ins(c.idy, 90.), ins(c.aln, 100.), ins(c.qst, 1.), ins(c.qed, 1.), ins(c.score, 300.),
+                         ins(c.qlen, 400.))

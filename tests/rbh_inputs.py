@@ -6,6 +6,7 @@ REAL scripts and stores what they print (tests/golden/rbh_<name>.json), so every
 
 What each input holds is said at its builder.  Everything is deterministic (seeded)."""
 import collections
+import functools
 
 import numpy as np
 
@@ -235,3 +236,47 @@ def random_columns(seed, n_runs=400, n_taxa=6, genes=7, long_every=37):
     lens = [int(rng.integers(65, 200)) if k % long_every == long_every - 1 else int(rng.integers(1, 20)) for k in range(n_runs)]
     text = "".join(random_runs(seed + 1000, lens, n_taxa=n_taxa, genes=genes))
     return text.encode(), fasta_of(text)
+
+
+# ---- run shapes at the edges of the run kernels and of the scan under them (csrc/k_util.hip: 256 rows a workgroup, SCAN_TILE = 8192 values
+# a tile, up to SCAN_SMALL_TILES = 4 tiles in one launch) ---------------------------------------------------------------------------------
+RUN_SIZES = (1, 256, 257, 8192, 8193, 32768, 32769)
+RUN_SHAPES = ("each", "one", "cut")
+RUN_CUTS = (255, 256, 257, 8191, 8192, 8193, 32767, 32768)   # rows a head stands on in shape "cut", where n reaches them
+_FILL = 97                                                  # filler genes per taxon
+
+
+def run_shape_starts(n, shape):
+    """first row of every run: "each" -- every row its own query; "one" -- all rows one query; "cut" -- heads on row 0 and on RUN_CUTS"""
+    if shape == "each":
+        return np.arange(n, dtype=np.int64)
+    if shape == "one":
+        return np.zeros(1, dtype=np.int64)
+    return np.array([0] + [c for c in RUN_CUTS if c < n], dtype=np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def run_shape_case(n, shape):
+    """(columns, fasta, run starts, numpy pairs, {-r value: numpy table}) of n rows in runs of the given shape: computed once, shared,
+    left unchanged.  Run r asks as ta|q<r> (r even) or tb|q<r> (r odd); runs 2k and 2k + 1 are partners: each holds the other's query
+    in its middle row with the largest score of the run, so they are a reciprocal best hit and ta|q<2k> a core gene.  Every other row
+    holds a filler gene of ta, tb or tc with a score of 1 .. 50 that repeats inside a long run (ties: the first row wins).  A run without
+    a partner (the last of an odd number, and the only run of shape "one") still has a winner per foreign taxon -- a core gene when it
+    asks as ta -- but no pair: one run proposes every key once."""
+    from swiftortho_amd import find_orth, rbh
+    starts = run_shape_starts(n, shape)
+    nruns = len(starts)
+    rid = np.searchsorted(starts, np.arange(n), side="right") - 1
+    j = np.arange(n) - starts[rid]
+    length = np.diff(np.concatenate([starts, [n]]))[rid]
+    partner = rid ^ 1
+    at_partner = (j == length // 2) & (partner < nruns)
+    ids = [("t%s|q%05d" % ("ab"[r & 1], r)).encode() for r in range(nruns)] + [("t%s|f%03d" % (t, g)).encode() for t in "abc" for g in range(_FILL)]
+    names, code = np.unique(np.array(ids), return_inverse=True)
+    filler = nruns + (rid * 7 + j * 3) % (3 * _FILL)
+    s = code[np.where(at_partner, partner, filler)].astype(np.int64)
+    score = np.where(at_partner, 1000., 1. + (rid * 13 + j * 31) % 50).astype(np.float64)
+    one, hundred = np.ones(n), np.full(n, 100.)
+    cols = find_orth.HitColumns(names, code[rid].astype(np.int64), s, hundred, hundred, one, hundred, score, hundred)
+    fasta = dummy_fasta([i.decode() for i in ids])
+    return cols, fasta, starts, rbh.reciprocal_best_hits(cols), {r: rbh.core_table(cols, fasta, r) for r in ("ta", "tb")}

@@ -78,6 +78,24 @@ def test_clique_inputs(fo, monkeypatch, k, flags, poison):
     assert len(got.co_a) == 3 * k * (k - 1) + 2
 
 
+@functools.lru_cache(maxsize=None)
+def kept_edges_case(flags):
+    from swiftortho_amd import find_orth
+    cols = oi.kept_edges()
+    return cols, find_orth.candidates(cols, *oi.FLAG_SETS[flags]), ri.numpy_tables(cols, *oi.FLAG_SETS[flags])
+
+
+@pytest.mark.parametrize("flags", ("no", "bsr"))
+def test_kept_row_edges(fo, monkeypatch, flags):
+    """more than 32768 kept rows with a dropped row directly before and after kept rows 256, 8192 and 32768 (tests/orth_inputs.py
+    kept_edges; tests/test_orth_relations.py asserts that it holds them): the compaction offsets and the run heads of the kept rows on a
+    workgroup's, a scan tile's and the single-launch scan's edge -- candidates and relation tables against the numpy stage, poisoned"""
+    monkeypatch.setenv("SOHIT_POISON", "165")
+    cols, want_cand, want = kept_edges_case(flags)
+    assert oi.same_candidates(fo.device_candidates(cols, *oi.FLAG_SETS[flags]), want_cand) == ""
+    assert ri.same_tables(fo.device_relation_tables(cols, *oi.FLAG_SETS[flags]), want) == ""
+
+
 def _edge_cases():
     both = dict(oi.edge_inputs())
     both.update(ri.edge_inputs())

@@ -107,6 +107,20 @@ def test_random_tables(rbh, monkeypatch, tier, seed):
     assert 0 < stats["n_runs_long"] <= stats["n_runs"] and stats["n_winners"] > 0 and stats["waits"] > 0
 
 
+@pytest.mark.parametrize("shape", ri.RUN_SHAPES)
+@pytest.mark.parametrize("n", ri.RUN_SIZES)
+def test_run_shapes(rbh, monkeypatch, n, shape):
+    """run heads, scans and run starts at their edges (a workgroup of 256 rows, a scan tile of 8192 values, the single-launch scan's
+    32768): every row a run, one run of all rows (the sorted tier), heads exactly on 255 .. 257, 8191 .. 8193, 32767 and 32768 --
+    pairs, tables and the run count against the numpy definitions, device memory poisoned"""
+    monkeypatch.setenv("SOHIT_POISON", "165")
+    cols, fasta, starts, pairs, tables = ri.run_shape_case(n, shape)
+    stats = check_against_numpy(rbh, cols, fasta, pairs, tables)
+    assert stats["n_runs"] == len(starts)
+    if shape == "one" and n > ri.WAVE_ROWS:
+        assert stats["n_runs_long"] == 1 and stats["n_rows_long"] == n
+
+
 def _upload(rec):
     import torch
     return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).cuda()

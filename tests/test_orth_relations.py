@@ -63,6 +63,22 @@ def test_clique_tables_equal_plain_python(k, flags):
     assert (tables.n_rows, tables.n_runs, tables.n_groups) == (cand.n_rows, cand.n_runs, cand.n_groups)
 
 
+@pytest.mark.parametrize("flags", ("no", "bsr"))
+def test_kept_edges_input_holds_what_it_promises(flags):
+    """oi.kept_edges(): more than 32768 rows survive the filter, a dropped row stands directly before and after kept rows 256, 8192 and
+    32768, and every section of the numpy answer is there"""
+    cols = oi.kept_edges()
+    coverage, identity, _ = oi.FLAG_SETS[flags]
+    keep = ~(((1. + np.abs(cols.qed - cols.qst)) / cols.qlen < coverage) | (cols.idy < identity))
+    kept = np.flatnonzero(keep)
+    assert len(kept) > 32768
+    for k in (256, 8192, 32768):
+        assert not keep[kept[k] - 1] and not keep[kept[k] + 1]
+    t = ri.numpy_tables(cols, *oi.FLAG_SETS[flags])
+    assert t.n_rows == len(kept) and len(t.ot_a) > 0 and len(t.ip_a) > 0 and len(t.co_a) > 0
+    assert ri.same_tables(t, ri.numpy_tables(generated(0), *oi.FLAG_SETS[flags])) == ""      # the dropped rows change nothing
+
+
 @pytest.mark.parametrize("k", CPU_KS)
 def test_clique_guarantees(k):
     cols, cand, tables, ref = clique_stage(k, "no")

@@ -56,6 +56,26 @@ def test_designed_inputs_hold_what_they_promise(rbh):
     assert {1, 2, 63, 64, 65, 300} <= set(per_run) and len(taxa) == 301
 
 
+@pytest.mark.parametrize("shape", ri.RUN_SHAPES)
+@pytest.mark.parametrize("n", ri.RUN_SIZES)
+def test_run_shapes_hold_what_they_promise(n, shape):
+    """the heads stand on the rows the shape names, and the numpy answer is not trivially empty: a core gene for every shape above one
+    row, and a pair wherever the table has two runs -- "one" has none by definition: a single run proposes every pair key once, and a
+    pair is a key proposed twice (asserted as such)"""
+    cols, fasta, starts, pairs, tables = ri.run_shape_case(n, shape)
+    q = np.asarray(cols.q)
+    heads = np.flatnonzero(np.concatenate([[True], q[1:] != q[:-1]]))
+    assert len(q) == n and heads.tolist() == starts.tolist()
+    want = {"each": list(range(n)), "one": [0], "cut": [0] + [c for c in ri.RUN_CUTS if c < n]}[shape]
+    assert heads.tolist() == want
+    if shape == "cut":
+        assert set(heads.tolist()) >= {c for c in (255, 256, 257, 8191, 8192, 8193, 32767, 32768) if c < n}
+    if n > 1:
+        assert len(tables["ta"].genes) >= 1 and bool((tables["ta"].fwd >= 0).any())
+        assert (len(heads) == 1) == (shape == "one")
+        assert len(pairs[0]) == (0 if shape == "one" else len(heads) // 2) and (shape == "one" or len(pairs[0]) >= 1)
+
+
 @pytest.mark.parametrize("name", ri.golden_names())
 def test_pairs_numpy(rbh, name):
     cols = _cols(name)
