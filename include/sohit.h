@@ -100,6 +100,13 @@ typedef struct so_counters {
      * priced against the HBM roofline, not one pass of it (params.profile) */
     int64_t bgroup_launches;           /* launches of the bucket grouping kernel (k_bkt_group)                                    */
     double bgroup_ms;                  /* their summed duration                                                                   */
+    /* sparse passes whose leftover hits (the ones k_ungapq does not extend itself) are sorted per query on chip -- a wave's registers, a
+     * workgroup's LDS for long lists -- and chained from the list of their group heads (SOHIT_UQ_CHAINS); such groups count into `groups`
+     * only.  Appended like the fields above: so_abi_version stays 3, a caller built against the shorter struct must not pass it here. */
+    int64_t uq_chain_queries;          /* queries with leftover hits that took this flow                                          */
+    int64_t uq_chain_groups;           /* their groups                                                                            */
+    int64_t uq_chain_overcap;          /* ... of them, queries above the largest LDS tier (sorted in place in the key array)      */
+    int64_t uq_left_max;               /* most leftover hits of one query in one pass                                             */
 } so_counters;
 
 /* Lifetime.  Replaces: spawning `fsearch-c` with its flags (find_hit.py:119-123). */
@@ -200,6 +207,8 @@ int so_write_sc_cigar(so_ctx *ctx, const so_hit *hits, int64_t n_hits, const uin
 int so_set_profile(so_ctx *ctx, int on);
 /* NC actually in use: -M, or the reference's `bins` default when -M < 1 (fsearch.py:2228-2231) */
 int64_t so_bucket_count(const so_ctx *ctx);
+/* Leftover hits per query the chain flow's wave tier (0) and workgroup tier (1) sort in LDS. */
+int64_t so_uq_chain_tier(int tier);
 /* Host-only helper of the row formatter (tests): for v[0..n) writes "<%f of v>\t<f2s(v)>\n" lines (f2s: fsearch.py:43-61) into out;
  * returns the bytes written or -1 when cap is too small (allow 1400 per value). */
 int64_t so_fmt_rows(const double *v, int64_t n, char *out, int64_t cap);

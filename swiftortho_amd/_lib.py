@@ -37,7 +37,8 @@ class SoCounters(C.Structure):
                 ("total_ms", C.c_double), ("count_launches", C.c_int64), ("count_ms", C.c_double),
                 ("hits_bucketed", C.c_int64), ("align_wide", C.c_int64), ("cells_wide", C.c_int64), ("seed_passes", C.c_int64),
                 ("ungap_steps", C.c_int64), ("groups_single", C.c_int64), ("groups_chain", C.c_int64),
-                ("bgroup_launches", C.c_int64), ("bgroup_ms", C.c_double)]
+                ("bgroup_launches", C.c_int64), ("bgroup_ms", C.c_double),
+                ("uq_chain_queries", C.c_int64), ("uq_chain_groups", C.c_int64), ("uq_chain_overcap", C.c_int64), ("uq_left_max", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -48,7 +49,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_load_queries", "so_load_queries_mem", "so_num_queries", "so_num_refs", "so_query_len", "so_search_loaded",
            "so_search", "so_free_hits", "so_search_loaded_aln", "so_free_aln", "so_write_sc", "so_format_hit", "so_get_counters", "so_reset_counters", "so_timing_report",
            "so_chunk_threshold", "so_chunk_entries", "so_chunk_download", "so_masked_query", "so_query_candidates", "so_query_phase2", "so_align_pairs", "so_align_pairs_aln", "so_set_profile",
-           "so_bucket_count", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
+           "so_bucket_count", "so_uq_chain_tier", "so_ref_len", "so_search_device", "so_device_hits_copy", "so_query_work", "so_mcl", "so_mcl_free",
            "so_mcl_last_error", "so_tsv_lines", "so_tsv_scan", "so_tsv_codes", "so_format_pairs", "so_py_repr", "so_fmt_rows",
            "so_search_loaded_cigar", "so_free_cigar", "so_format_cigar", "so_write_sc_cigar", "so_align_pairs_cigar",
            "so_apc", "so_apc_free", "so_apc_last_error", "so_cnc_groups", "so_cnc_free", "so_cnc_last_error",
@@ -197,6 +198,8 @@ def load():
     L.so_set_profile.argtypes = [vp, C.c_int]
     L.so_bucket_count.restype = i64
     L.so_bucket_count.argtypes = [vp]
+    L.so_uq_chain_tier.restype = i64
+    L.so_uq_chain_tier.argtypes = [C.c_int]
     L.so_reset_counters.argtypes = [vp]
     L.so_timing_report.restype = i64
     L.so_timing_report.argtypes = [vp, cp, i64]

@@ -550,6 +550,7 @@ int so_set_profile(so_ctx* c, int on) {
 }
 
 int64_t so_bucket_count(const so_ctx* c) { return c ? c->nc : -1; }
+int64_t so_uq_chain_tier(int tier) { return (tier == 0 || tier == 1) ? (int64_t)uqchain_tier(tier) : -1; }
 
 int so_get_counters(const so_ctx* c, so_counters* out) {
     if (!c || !out) return 1;

@@ -480,9 +480,10 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     const size_t pcap = (size_t)shard_cap * UG_SHARDS + 2 + ungap1_list_slack(c->ncu);   // (+ the unused slots of k_ungap1's reserved pieces)
     b.p_qs.ensure(pcap), b.p_sd.ensure(pcap), b.p_ft.ensure(pcap);
     b.shard.ensure(2 * UG_SHARDS + 8);
-    b.stepshard.ensure(UG_SHARDS + 4);   // group counts, then (Tune::count_steps) b62 lookups, singleton groups, chained groups
+    b.stepshard.ensure(UG_SHARDS + 8);   // group counts, then (Tune::count_steps) b62 lookups, singleton groups, chained groups, -, then the sparse chain flow's four (launch_uqsort)
     b.bflag.ensure(8);
     double t1 = wall();
+    bool uq_chains = false;   // set by group_sorted: the pass took the sparse chain flow (its records carry their first-touch keys)
     bool bbest = false;   // set by group_bucketed: pass records were flushed per bucket, k_bkt_best reduces them
     BktLayout bL;
     u32 bnb = 0;
@@ -490,7 +491,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     unsigned long long* const ugstat = c->tune.count_steps ? b.stepshard.p + UG_SHARDS : nullptr;   // the counting instances of the extension kernels
     auto reset_pass_lists = [&] {
         HIP_CHECK(hipMemsetAsync(b.shard.p, 0, (2 * UG_SHARDS + 8) * sizeof(u32), c->st));
-        HIP_CHECK(hipMemsetAsync(b.stepshard.p, 0, (UG_SHARDS + 4) * sizeof(unsigned long long), c->st));
+        HIP_CHECK(hipMemsetAsync(b.stepshard.p, 0, (UG_SHARDS + 8) * sizeof(unsigned long long), c->st));
         HIP_CHECK(hipMemsetAsync(b.bflag.p, 0, 8 * sizeof(u32), c->st));
     };
 
@@ -640,6 +641,10 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     // of them -- are found and extended by k_ungapq, a wave per query, without a key being written for them; the rest are written as
     // k_lookup's keys into an array of all-ones (= dropped) and take the sort + k_ungap below.
     const bool uq = tune().ungapq && tune().segsort && AS == 1 && compact && !ft_walk && UG_SHARDS == 1 && pmaxq <= ungapq_qcap() && nseg >= 256;
+    // ... and (SOHIT_UQ_CHAINS) what k_ungapq leaves over is sorted per query in LDS and chained by k_ungap2 from the list of group heads: no
+    // library sort, no walk over all H slots, and every pass record leaves with its first-touch key
+    uq_chains = uq && tune().uq_chains != 0;
+    const int ftp = uq_chains ? (ft_bits_entry | (bsp << 8)) : 0;
     if (uq || nseg >= 256) {
         b.qseg.ensure((size_t)b.nq + 4);
         launch_query_segments(b.hoff.p, b.dev.d_off.p, qa, qb, AS, H, b.qseg.p, c->st);
@@ -655,7 +660,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         ProfTimer pt(c, &c->cnt.lookup_ms, &c->cnt.lookup_launches);
         launch_ungapq(c->ncu, b.qseg.p + qa, nseg, qa, b.blk_first.p, b.cs_hoff.p, b.cs_beg.p, b.cs_kbase.p, K, dk32, kl, klr, btab, b.dev.d_scls.p, b.dev.d_off.p,
                       c->ref.d_ug_store.p + U1_UG_PAD, c->ref.d_off.p + ch.seq_lo, c->d_b62c.p, b.bflag.p + 1, b.shard.p, b.p_qs.p, b.p_sd.p, b.p_ft.p, b.stepshard.p,
-                      b.keys.p, b.keys2.p, b.flags.p, ugstat, c->st);
+                      b.keys.p, uq_chains ? nullptr : b.keys2.p, b.flags.p, ugstat, c->st, ftp);
         pt.stop();
         if (c->profile) c->cnt.lookup_bytes += (i64)8 * (i64)H;
     } else {
@@ -671,6 +676,44 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     }
     t1 = wall();
     sc.lap("seed.compact_lookup");
+    if (uq_chains) {
+        if (!b.dev.ug_valid) {
+            const size_t nres = b.h_off[b.nq];
+            b.dev.d_ug_store.ensure(nres + 2 * (size_t)U1_UG_PAD);
+            launch_make_ug(b.dev.d_scls.p, b.dev.d_off.p, b.nq, nres, 1u, b.dev.d_ug_store.p + U1_UG_PAD, c->st);
+            b.dev.ug_valid = true;
+        }
+        b.keys2.ensure((size_t)H + 8);   // as 32-bit words: the hits' words (H + 8: the chain kernel reads four ahead), then the heads' diagonal ids (H)
+        b.mlist.ensure(uqchain_mlist_cap(H, c->ncu, nseg));
+        u32* words = reinterpret_cast<u32*>(b.keys2.p);
+        u32* garr = words + (size_t)H + 8;
+        unsigned long long* ustat = b.stepshard.p + UG_SHARDS + 4;
+        if (!launch_uqsort(c->ncu, b.qseg.p + qa, b.flags.p, nseg, H, b.keys.p, kl, tune().uq_chains, words, garr, b.mlist.p, b.mlist.cap, b.bflag.p + 3, b.bflag.p + 4,
+                           b.blk_first.p, ustat, c->st))
+            throw SoError("chain list too small for this pass");
+        sc.lap("group.sort_keys");
+        BktLayout Lq{};
+        Lq.bd = kl.bd, Lq.bp = kl.bp, Lq.sh_q = kl.sh_q, Lq.sh_qpos = kl.sh_qpos, Lq.nqp = nseg, Lq.qa = qa, Lq.R = 1;
+        launch_ungap2(c->ncu, b.mlist.p, b.bflag.p + 3, words, b.flags.p, Lq, kl, klr, btab, U1_WAIT, b.dev.d_ug_store.p + U1_UG_PAD, b.dev.d_off.p,
+                      c->ref.d_ug_store.p + U1_UG_PAD, c->ref.d_off.p + ch.seq_lo, c->d_b62c.p, b.bflag.p + 2, b.shard.p, b.p_qs.p, b.p_sd.p, b.p_ft.p, b.stepshard.p, ugstat,
+                      c->st, garr, ftp, ustat, c->cfg.mink);
+        if (tune().debug) {   // leftover hits per query: what the tier limits of k_uqchain.hip are chosen from
+            HIP_CHECK(hipStreamSynchronize(c->st));
+            std::vector<u32> s0(nseg), s1(nseg);
+            HIP_CHECK(hipMemcpy(s0.data(), b.qseg.p + qa, (size_t)nseg * sizeof(u32), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(s1.data(), b.flags.p, (size_t)nseg * sizeof(u32), hipMemcpyDeviceToHost));
+            unsigned long long hist[34] = {0};
+            for (u32 q = 0; q < nseg; ++q) {
+                const u32 n = s1[q] - s0[q];
+                hist[n ? ceil_log2((u64)n) + 1 : 0]++;
+            }
+            fprintf(stderr, "[sohit] chain flow: leftover hits per query (count of queries): 0: %llu", hist[0]);
+            for (int k = 1; k < 34; ++k)
+                if (hist[k]) fprintf(stderr, ", <=%llu: %llu", 1ull << (k - 1), hist[k]);
+            fprintf(stderr, "\n");
+        }
+        return;
+    }
     // Hits are generated in (query, qpos, as) order (position-major seed ordinals) and the radix sorts are
     // stable, so only the (subject, diagonal) bits need sorting, inside each query's segment: 2 radix passes
     // fewer than a device-wide sort of the (query, subject, diagonal) bits.  One block sorts one segment, so
@@ -706,14 +749,16 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         launch_shard_scan(b.shard.p, shard_off, c->st);
         u32 NP;
         {
-            static_assert((UG_SHARDS + 4) * sizeof(unsigned long long) + sizeof(u32) <= 1024, "h_small too small");
+            static_assert((UG_SHARDS + 8) * sizeof(unsigned long long) + sizeof(u32) <= 1024, "h_small too small");
             unsigned long long* gc = (unsigned long long*)small_host(c);
-            u32* np = (u32*)(gc + UG_SHARDS + 4);
-            HIP_CHECK(hipMemcpyAsync(gc, b.stepshard.p, (UG_SHARDS + 4) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
+            u32* np = (u32*)(gc + UG_SHARDS + 8);
+            HIP_CHECK(hipMemcpyAsync(gc, b.stepshard.p, (UG_SHARDS + 8) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
             HIP_CHECK(hipMemcpyAsync(np, shard_off + UG_SHARDS, sizeof(u32), hipMemcpyDeviceToHost, c->st));
             HIP_CHECK(hipStreamSynchronize(c->st));
             for (int k = 0; k < UG_SHARDS; ++k) c->cnt.groups += (i64)gc[k];
             c->cnt.ungap_steps += (i64)gc[UG_SHARDS], c->cnt.groups_single += (i64)gc[UG_SHARDS + 1], c->cnt.groups_chain += (i64)gc[UG_SHARDS + 2];
+            c->cnt.uq_chain_queries += (i64)gc[UG_SHARDS + 4], c->cnt.uq_chain_groups += (i64)gc[UG_SHARDS + 5], c->cnt.uq_chain_overcap += (i64)gc[UG_SHARDS + 6];
+            c->cnt.uq_left_max = std::max<i64>(c->cnt.uq_left_max, (i64)gc[UG_SHARDS + 7]);
             NP = *np;
         }
         sc.lap("group.ungap");
@@ -754,7 +799,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
             break;
         }
         // first-touch keys of the passing groups (k_ungap left the head hit's key / position in the third array)
-        if (NP) launch_first_touch(ft_walk, b.keys2.p, H, klr, ft_bits_entry, bsp, c->ref.d_off.p + ch.seq_lo, const_cast<u64*>(q_ft), NP, c->st);
+        if (NP && !uq_chains) launch_first_touch(ft_walk, b.keys2.p, H, klr, ft_bits_entry, bsp, c->ref.d_off.p + ch.seq_lo, const_cast<u64*>(q_ft), NP, c->st);
         if (NP == 0) break;
         // Sparse pass (tens of records per query): best diagonal per subject and the candidate order by one wave per query, in LDS -- no
         // sort of the records (k_q_best, k_group.hip).  A query with more records than the LDS instance holds sends the pass down the

@@ -269,14 +269,20 @@ __global__ __launch_bounds__(64 * U1_WAVES, WGS) __attribute__((amdgpu_num_sgpr(
 struct U2Entry {   // 32 bytes
     u32 sa, w, pos, b, qb, e1, pad0, pad1;
 };
-template <bool BANDS, int TSH, bool COUNT>
+// QSEG (sparse passes, behind k_ungapq and k_uqsort, k_uqchain.hip): the words are a query's leftover hits in (diagonal id, query position)
+// order, query position | bit 30 on the first hit of a group; a list entry is (position, query of the pass), the group's diagonal id
+// stands in garr at the head's position and `bext` holds the END of every query's words.  ftp: see u1_record_g.  Such groups count into
+// group_count and ustat[1] only.  klen (the seed pattern's length): a segment whose right end reaches the query's last window covers every
+// seed still to come -- the group is complete without a look at them (a query against itself: some 290 covered seeds, four per visit).
+template <bool BANDS, int TSH, bool COUNT, bool QSEG>
 __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restrict__ mlist, const u32* __restrict__ mlist_cnt, const u32* __restrict__ words,
                                                             const u32* __restrict__ bext, BktLayout L, int sh_qpos, int diag_off, int rbs, int rsh_subj, int rsh_diag,
                                                             int rdoff, const uint2* __restrict__ btab, u32 wait_n, const u8* __restrict__ q_ug, const u32* __restrict__ qoff,
                                                             const u8* __restrict__ r_ug, const u32* __restrict__ roff, const signed char* __restrict__ b62g,
                                                             u32* __restrict__ work_ctr, u32* __restrict__ shard_cnt, u64* __restrict__ p_qs, u64* __restrict__ p_sd,
                                                             u64* __restrict__ p_ft, unsigned long long* __restrict__ group_count,
-                                                            unsigned long long* __restrict__ stat /*COUNT: [0] += b62 lookups, [2] += groups*/) {
+                                                            unsigned long long* __restrict__ stat /*COUNT: [0] += b62 lookups, [2] += groups*/,
+                                                            const u32* __restrict__ garr, int ftp, unsigned long long* __restrict__ ustat, int klen) {
     constexpr u32 TBYTES = (u32)U1_ROWS << (8 + TSH);
     constexpr u32 WBYTES = U2_RING * 32 + U1_PCAP * 16;
     __shared__ __align__(16) unsigned char u2_smem[TBYTES + 17 * 16 + U1_WAVES * WBYTES];
@@ -292,7 +298,7 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
     __syncthreads();
     unsigned char* wbase = u2_smem + TBYTES + 17 * 16 + (u32)w * WBYTES;
     U2Entry* ring = reinterpret_cast<U2Entry*>(wbase);
-    uint4* s_pass = reinterpret_cast<uint4*>(wbase + U2_RING * 32);   // (head word, score, bucket, -)
+    uint4* s_pass = reinterpret_cast<uint4*>(wbase + U2_RING * 32);   // (head word, score, bucket, QSEG: diagonal id)
     const unsigned long long lt = (1ull << lane) - 1ull;
     const u32 lanebase = (u32)(size_t)(__attribute__((address_space(3))) unsigned char*)u2_smem + ((u32)(lane & 31) << (TSH == 4 ? 2 : 1));
     const u32 WM = 0x7FFFFFFFu;
@@ -308,8 +314,12 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
         const u32 at = u1_reserve(npb, lane, ch_pos, ch_end, &shard_cnt[0], U1_CHUNK);
         if ((u32)lane < npb) {
             const uint4 e = s_pass[lane];
-            const u32 r = e.z / L.nqp, gq = L.qa + (e.z - r * L.nqp);
-            u1_record<BANDS>(e.x, (u64)e.y << 32, r, gq, L, diag_off, rbs, rsh_subj, rsh_diag, rdoff, sh_qpos, btab, p_qs, p_sd, p_ft, at);
+            if (QSEG) {
+                u1_record_g<BANDS>(e.w, e.x & pmask, (u64)e.y << 32, L.qa + e.z, L.bd, diag_off, rbs, rsh_subj, rsh_diag, rdoff, sh_qpos, btab, ftp, roff, p_qs, p_sd, p_ft, at);
+            } else {
+                const u32 r = e.z / L.nqp, gq = L.qa + (e.z - r * L.nqp);
+                u1_record<BANDS>(e.x, (u64)e.y << 32, r, gq, L, diag_off, rbs, rsh_subj, rsh_diag, rdoff, sh_qpos, btab, p_qs, p_sd, p_ft, at);
+            }
         }
         npb = 0;
     };
@@ -318,7 +328,8 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
     bool walking = false;      // between segments, looking for the group's next seed behind `lo`
     i64 qR = 0, qL = 0, sR = 0, sL = 0;   // byte offsets of the next windows in q_ug / r_ug
     i64 sa0 = 0, qa0 = 0;      // byte of the head hit in r_ug; byte of the query's position 0 in q_ug
-    u32 hw = 0, hb = 0, he1 = 0;   // the group's head word, bucket, end of the bucket's words
+    u32 hw = 0, hb = 0, he1 = 0, hG = 0;   // the group's head word, bucket, end of the bucket's words; QSEG: its diagonal id
+    int hlast = 0;             // QSEG: position of the query's last seed window
     u32 h = 0;                 // position of the current seed's hit
     uint4 nx = make_uint4(0, 0, 0, 0);   // the four words behind it
     int scores = 0, lo = -1, Qst = 0, eb = 0;
@@ -360,9 +371,9 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
                 const unsigned long long vb = __ballot(valid);
                 if (valid) {
                     const u32 pos = (u32)e, b = (u32)(e >> 32);
-                    const u32 wv = words[pos] & WM;
-                    const u32 r = b / L.nqp, gq = L.qa + (b - r * L.nqp);
-                    const u32 G = (r << gb) | (wv >> L.bp);
+                    const u32 wv = words[pos] & (QSEG ? pmask : WM);
+                    const u32 r = QSEG ? 0u : b / L.nqp, gq = L.qa + (b - r * L.nqp);
+                    const u32 G = QSEG ? garr[pos] : (r << gb) | (wv >> L.bp);
                     u32 gsubj;
                     int dlt;
                     if (BANDS) {
@@ -375,7 +386,7 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
                     }
                     U2Entry en;
                     en.sa = roff[gsubj] + (u32)((int)(wv & pmask) + dlt);
-                    en.w = wv, en.pos = pos, en.b = b, en.qb = qoff[gq], en.e1 = bext[b + 1], en.pad0 = en.pad1 = 0;
+                    en.w = wv, en.pos = pos, en.b = b, en.qb = qoff[gq], en.e1 = bext[QSEG ? b : b + 1], en.pad0 = QSEG ? G : 0u, en.pad1 = QSEG ? qoff[gq + 1] - en.qb : 0u;
                     ring[(rback + (u32)__popcll(vb & lt)) & (U2_RING - 1)] = en;
                 }
                 rback += (u32)__popcll(vb);
@@ -388,7 +399,8 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
                 if (rk < avail) {
                     const U2Entry en = ring[(rfront + rk) & (U2_RING - 1)];
                     sa0 = (i64)en.sa, qa0 = (i64)en.qb;
-                    hw = en.w, hb = en.b, he1 = en.e1, h = en.pos;
+                    hw = en.w, hb = en.b, he1 = en.e1, h = en.pos, hG = QSEG ? en.pad0 : 0u;
+                    if (QSEG) hlast = (int)en.pad1 - klen;
                     nx = u1_load16(reinterpret_cast<const u8*>(words + h + 1));   // (the array is readable 8 words past its end)
                     scores = 0, lo = -1;
                     start_segment((int)(hw & pmask));
@@ -422,6 +434,7 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
                 const int am = tr.gsel + (tr.sv1.x == M.x ? 0 : (tr.sv2.x == M.x ? 1 : 2));
                 lo = M.x > 0 ? Qst + am : Qst;
                 working = false, walking = true;
+                if (QSEG && lo >= hlast) walking = false, fin = true;   // no seed behind lo
             }
         }
         if (walking && !working) {
@@ -434,7 +447,7 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
             for (int i = 0; i < 4; ++i) {
                 if (!found && !ended) {
                     const u32 c = nxd[i] & WM;
-                    if (h + 1u + (u32)i >= he1 || (nxd[i] >> 31) != 0 || (c >> L.bp) != (hw >> L.bp)) ended = true;
+                    if (h + 1u + (u32)i >= he1 || (nxd[i] >> 31) != 0 || (QSEG ? (c >> 30) != 0 : (c >> L.bp) != (hw >> L.bp))) ended = true;
                     else {
                         adv = (u32)i + 1u;
                         qp = (int)(c & pmask);
@@ -462,7 +475,7 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
                 if (!pb) break;
                 const u32 room = U1_PCAP - npb, rk = (u32)__popcll(pb & lt);
                 if (todo && rk < room) {
-                    s_pass[npb + rk] = make_uint4(hw, (u32)scores, hb, 0u);
+                    s_pass[npb + rk] = make_uint4(hw, (u32)scores, hb, hG);
                     todo = false;
                 }
                 npb += min((u32)__popcll(pb), room);
@@ -481,8 +494,12 @@ __global__ __launch_bounds__(64 * U1_WAVES, 1) void k_ungap2(const u64* __restri
         unsigned long long nst = ct.n;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nst += __shfl_xor(nst, o);
-        if (lane == 0) atomicAdd(&stat[0], nst), atomicAdd(&stat[2], (unsigned long long)ngroups);
+        if (lane == 0) {
+            atomicAdd(&stat[0], nst);
+            if (!QSEG) atomicAdd(&stat[2], (unsigned long long)ngroups);
+        }
     }
+    if (QSEG && lane == 0 && ngroups) atomicAdd(&ustat[1], (unsigned long long)ngroups);
 }
 
 u32 ungap1_qcap() { return U1_QCAP; }
@@ -539,13 +556,20 @@ void launch_ungap1(u32 ncu, u32 pmaxq, const u32* words, const u32* bext, u32 nb
 
 void launch_ungap2(u32 ncu, const u64* mlist, const u32* mlist_cnt, const u32* words, const u32* bext, const BktLayout& L, const KeyLayout& kl, const KeyLayout& klr,
                    const void* btab, u32 wait_n, const u8* q_ug, const u32* qoff, const u8* r_ug, const u32* roff, const signed char* b62g, u32* work_ctr, u32* shard_cnt,
-                   u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, unsigned long long* stat, hipStream_t st) {
-#define U2_GO(B, CT) hipLaunchKernelGGL((k_ungap2<B, 3, CT>), dim3(ncu), dim3(64 * U1_WAVES), 0, st, mlist, mlist_cnt, words, bext, L, kl.sh_qpos, (int)kl.diag_off, klr.bs, klr.sh_subj, \
-                                    klr.sh_diag, (int)klr.diag_off, (const uint2*)btab, wait_n, q_ug, qoff, r_ug, roff, b62g, work_ctr, shard_cnt, p_qs, p_sd, p_ft, group_count, stat)
+                   u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, unsigned long long* stat, hipStream_t st, const u32* garr, int ftp,
+                   unsigned long long* ustat, int klen) {
+#define U2_GO(B, CT, QS) hipLaunchKernelGGL((k_ungap2<B, 3, CT, QS>), dim3(ncu), dim3(64 * U1_WAVES), 0, st, mlist, mlist_cnt, words, bext, L, kl.sh_qpos, (int)kl.diag_off, klr.bs, klr.sh_subj, \
+                                    klr.sh_diag, (int)klr.diag_off, (const uint2*)btab, wait_n, q_ug, qoff, r_ug, roff, b62g, work_ctr, shard_cnt, p_qs, p_sd, p_ft, group_count, stat, garr, ftp, ustat, klen)
+#define U2_GOQ(B, CT)            \
+    do {                         \
+        if (garr) U2_GO(B, CT, true); \
+        else U2_GO(B, CT, false);     \
+    } while (0)
     if (stat) {
-        if (btab) U2_GO(true, true);
-        else U2_GO(false, true);
-    } else if (btab) U2_GO(true, false);
-    else U2_GO(false, false);
+        if (btab) U2_GOQ(true, true);
+        else U2_GOQ(false, true);
+    } else if (btab) U2_GOQ(true, false);
+    else U2_GOQ(false, false);
+#undef U2_GOQ
 #undef U2_GO
 }

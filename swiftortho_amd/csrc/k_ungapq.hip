@@ -75,7 +75,7 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
     int rsh_subj, int rsh_diag, int rdoff, const uint2* __restrict__ btab, u32 wait_n, u32 csteps /*steps of 64 ordinals kept in registers, <= UQ_CSTEPS*/, const u8* __restrict__ q_scls, const u32* __restrict__ qoff,
     const u8* __restrict__ r_ug, const u32* __restrict__ roff, const signed char* __restrict__ b62g, u32* __restrict__ work_ctr, u32* __restrict__ shard_cnt,
     u64* __restrict__ p_qs, u64* __restrict__ p_sd, u64* __restrict__ p_ft, unsigned long long* __restrict__ group_count, u64* __restrict__ keys,
-    u64* __restrict__ keys_sorted, u32* __restrict__ seg_end, unsigned long long* __restrict__ stat /*COUNT: [0] += b62 lookups, [1] += groups*/) {
+    u64* __restrict__ keys_sorted, u32* __restrict__ seg_end, unsigned long long* __restrict__ stat /*COUNT: [0] += b62 lookups, [1] += groups*/, int ftp) {
     constexpr int TSH = 3;
     constexpr u32 TBYTES = (u32)U1_ROWS << (8 + TSH);
     __shared__ __align__(16) unsigned char uq_smem[TBYTES + UQ_WAVES * UQ_WAVE_BYTES];
@@ -233,20 +233,8 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
             const u32 at = u1_reserve(npb, lane, ch_pos, ch_end, &shard_cnt[0], U1_CHUNK);
             if ((u32)lane < npb) {
                 const u64 e = s_pass[lane];
-                const u32 G = (u32)e, qp = (u32)s_passq[lane];
-                u32 gsubj;
-                int dlt;
-                if (BANDS) {
-                    const uint2 be = btab[G >> bd];
-                    gsubj = be.x;
-                    dlt = (int)(be.y - G);
-                } else {
-                    gsubj = G >> bd;
-                    dlt = diag_off - (int)(G & dmask);
-                }
-                p_qs[at] = ((u64)gq << rbs) | gsubj;
-                p_sd[at] = (e & 0xFFFFFFFF00000000ull) | (u64)(u32)dlt;
-                p_ft[at] = ((u64)gsubj << rsh_subj) | ((u64)(u32)(rdoff - dlt) << rsh_diag) | ((u64)qp << sh_qpos);
+                u1_record_g<BANDS>((u32)e, (u32)s_passq[lane], e & 0xFFFFFFFF00000000ull, gq, bd, diag_off, rbs, rsh_subj, rsh_diag, rdoff, sh_qpos, btab, ftp, roff, p_qs, p_sd,
+                                   p_ft, at);
             }
             npb = 0;
         };
@@ -391,7 +379,8 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
         }
         // the sorted path's view of this query: keys [h0, h0 + ns) to sort, dropped keys behind them in the sort's OUTPUT array
         if (lane == 0) seg_end[qrel] = h0 + ns;
-        for (u32 i = h0 + ns + (u32)lane; i < h1; i += 64) keys_sorted[i] = ~0ull;
+        if (keys_sorted)
+            for (u32 i = h0 + ns + (u32)lane; i < h1; i += 64) keys_sorted[i] = ~0ull;
     }
     for (u32 i = ch_pos + (u32)lane; i < ch_end; i += 64) p_qs[i] = UG_REC_NONE, p_ft[i] = 0;   // unused slots of the wave's last piece: skipped downstream
     if (lane == 0 && ngroups) atomicAdd(&group_count[0], (unsigned long long)ngroups);
@@ -405,12 +394,12 @@ __global__ __launch_bounds__(64 * UQ_WAVES, 1) __attribute__((amdgpu_num_sgpr(96
 
 u32 ungapq_qcap() { return UQ_QCAP; }
 
-// qk: nqp + 1 words of scratch.  Afterwards a query's keys to sort are keys[qseg[q] .. seg_end[q]); keys_sorted (the sort's output array) holds
-// dropped keys (all-ones) behind them up to qseg[q + 1].
+// qk: nqp + 1 words of scratch.  Afterwards a query's keys to sort are keys[qseg[q] .. seg_end[q]); keys_sorted (the sort's output array; null
+// when the leftover hits go to launch_uqsort, which reads seg_end) holds dropped keys (all-ones) behind them up to qseg[q + 1].
 void launch_ungapq(u32 ncu, const u32* qseg, u32 nqp, u32 qa, u32* qk, const u32* cs_hoff, const u32* cs_base, const u64* cs_kbase, u32 K, const u32* dk32,
                    const KeyLayout& kl, const KeyLayout& klr, const void* btab, const u8* q_scls, const u32* qoff, const u8* r_ug, const u32* roff, const signed char* b62g,
                    u32* work_ctr, u32* shard_cnt, u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, u64* keys, u64* keys_sorted, u32* seg_end,
-                   unsigned long long* stat, hipStream_t st) {
+                   unsigned long long* stat, hipStream_t st, int ftp) {
     if (!nqp) return;
     hipLaunchKernelGGL(k_uq_first, dim3((nqp + 1 + 255) / 256), dim3(256), 0, st, qseg, nqp, cs_hoff, K, qk);
     static_assert(((size_t)U1_ROWS << 11) + (size_t)UQ_WAVES * UQ_WAVE_BYTES <= 160 * 1024, "LDS of a CU");
@@ -420,7 +409,7 @@ void launch_ungapq(u32 ncu, const u32* qseg, u32 nqp, u32 qa, u32* qk, const u32
 #define UQ_GO(B, CT)                                                                                                                                              \
     hipLaunchKernelGGL((k_ungapq<B, CT>), g, bl, 0, st, qseg, nqp, qa, qk, cs_hoff, cs_base, cs_kbase, dk32, kl.bp, kl.bd, kl.sh_q, kl.sh_qpos, kl.sh_diag, (int)kl.diag_off, klr.bs,  \
                        klr.sh_subj, klr.sh_diag, (int)klr.diag_off, (const uint2*)btab, U1_WAIT, csteps, q_scls, qoff, r_ug, roff, b62g, work_ctr, shard_cnt, p_qs, p_sd, p_ft,      \
-                       group_count, keys, keys_sorted, seg_end, stat)
+                       group_count, keys, keys_sorted, seg_end, stat, ftp)
     if (stat) {
         if (btab) UQ_GO(true, true);
         else UQ_GO(false, true);

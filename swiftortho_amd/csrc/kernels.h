@@ -150,11 +150,21 @@ void launch_ungap1(u32 ncu, u32 pmaxq, const u32* words, const u32* bext, u32 nb
 u32 ungapq_qcap();
 void launch_ungapq(u32 ncu, const u32* qseg, u32 nqp, u32 qa, u32* qk, const u32* cs_hoff, const u32* cs_base, const u64* cs_kbase, u32 K, const u32* dk32,
                    const KeyLayout& kl, const KeyLayout& klr, const void* btab, const u8* q_scls, const u32* qoff, const u8* r_ug, const u32* roff, const signed char* b62g,
-                   u32* work_ctr, u32* shard_cnt, u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, u64* keys, u64* keys_sorted, u32* seg_end,
-                   unsigned long long* stat, hipStream_t st);
+                   u32* work_ctr, u32* shard_cnt, u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, u64* keys,
+                   u64* keys_sorted /*null: no dropped keys written behind a query's leftover keys*/, u32* seg_end, unsigned long long* stat, hipStream_t st,
+                   int ftp = 0 /*see launch_ungap2*/);
 void launch_ungap2(u32 ncu, const u64* mlist, const u32* mlist_cnt, const u32* words, const u32* bext, const BktLayout& L, const KeyLayout& kl, const KeyLayout& klr,
                    const void* btab, u32 wait_n, const u8* q_ug, const u32* qoff, const u8* r_ug, const u32* roff, const signed char* b62g, u32* work_ctr /*zeroed*/,
                    u32* shard_cnt, u64* p_qs, u64* p_sd, u64* p_ft, unsigned long long* group_count, unsigned long long* stat /*nullable: [0], [2] += chained groups*/,
+                   hipStream_t st,
+                   // sparse passes (launch_uqsort's words, diagonal ids and chain list; bext = the end of every query's words): ftp != 0: first-touch
+                   // keys written here (ft_bits_entry | bsp << 8); the groups count into ustat[1], not into stat[2]; klen: the seed pattern's length
+                   const u32* garr = nullptr, int ftp = 0, unsigned long long* ustat = nullptr, int klen = 0);
+// k_uqchain.hip: the hits launch_ungapq leaves over (keys[qseg[q] .. seg_end[q])) sorted per query in LDS -> words (H + 8), garr (H), chain list
+u32 uqchain_tier(int tier);   // keys per query the wave tier (0) and the workgroup tier (1) sort in LDS
+size_t uqchain_mlist_cap(u32 H, u32 ncu, u32 nqp);   // entries of the chain list: the heads + a piece per wave that the pass's grids launch
+bool launch_uqsort(u32 ncu, const u32* qseg, const u32* seg_end, u32 nqp, u32 H, u64* keys, const KeyLayout& kl, long long cap_max, u32* words, u32* garr, u64* mlist,
+                   size_t mlist_cap /*false and no launch when below uqchain_mlist_cap*/, u32* mlist_cnt, u32* ctr /*four zeroed words*/, u32* big /*nqp words*/, unsigned long long* ustat /*[0] queries, [2] above the LDS tiers, [3] max*/,
                    hipStream_t st);
 void launch_first_touch(bool walk, const u64* keys, u32 H, const KeyLayout& kl, int ft_bits_entry, int bsp, const u32* roff, u64* p_ft, u32 n,
                         hipStream_t st);

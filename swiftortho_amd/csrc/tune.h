@@ -15,6 +15,7 @@
     X(B, count_steps, "SOHIT_UG_COUNT", 0, "counting instances of the extension kernels: so_counters.ungap_steps, groups_single, groups_chain")                \
     X(B, ungapq, "SOHIT_UNGAPQ", 1, "sparse passes of queries up to 512 residues: hits alone on their diagonal by k_ungapq, a wave per query (0: every hit through the sorted keys)")     \
     X(I, uq_cache, "SOHIT_UQ_CACHE", -1, "... its hit ordinals per query whose index entries stay in registers between the two walks, in steps of 64 (-1: the compiled 1024; 0: every entry read twice; tests move the boundary)") \
+    X(I, uq_chains, "SOHIT_UQ_CHAINS", -1, "... what it leaves over sorted per query (k_uqsort_wave: a wave's registers, k_uqsort_wg: a workgroup's LDS) and chained by k_ungap2 from the list of group heads (0: library segmented sort + k_ungap + k_first_touch; N > 0: the largest tier holds N keys -- tests reach the in-place instance with small inputs)") \
     X(B, ug_w32, "SOHIT_UG_W32", 1, "bucketed passes hand k_ungap the buckets' 32-bit words (0: 64-bit keys; no k_ungap1 then)")                               \
     /* ---- seed stage: which path a pass takes ---- */                                                                                                         \
     X(B, bucket, "SOHIT_BUCKET", 1, "bucketed diagonal binning (0: every pass on the sorted path)")                                                            \

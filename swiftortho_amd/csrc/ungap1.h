@@ -141,25 +141,41 @@ __device__ __forceinline__ u32 u1_step(const uint4& qr4, const uint4& ql4, const
     return msk;
 }
 
-// pass record of a group with head word fw in bucket (range r, batch query gq): p_qs = (q << bs) | subject, p_sd = (score << 32) |
-// (sst - qst), p_ft = the head hit's key in the record layout (k_rec_scatter turns it into the first-touch key)
+// pass record of the group on banded diagonal id G whose head hit sits at query position qpos, of batch query gq: p_qs = (q << bs) |
+// subject, p_sd = (score << 32) | (sst - qst), p_ft = the head hit's key in the record layout (k_first_touch / k_rec_scatter turn it into
+// the first-touch key) -- or, with ftp = ft_bits_entry | bsp << 8 non-zero, that first-touch key itself (one alphabet x one pattern: what
+// k_first_touch makes of the head's key, ft_key_of_head)
 template <bool BANDS>
-__device__ __forceinline__ void u1_record(u32 fw, u64 score_hi, u32 r, u32 gq, const BktLayout& L, int diag_off, int rbs, int rsh_subj, int rsh_diag, int rdoff,
-                                          int sh_qpos, const uint2* __restrict__ btab, u64* __restrict__ p_qs, u64* __restrict__ p_sd, u64* __restrict__ p_ft, u32 at) {
-    const u32 G = (r << (L.wb + L.bd)) | (fw >> L.bp);
+__device__ __forceinline__ void u1_record_g(u32 G, u32 qpos, u64 score_hi, u32 gq, int bd, int diag_off, int rbs, int rsh_subj, int rsh_diag, int rdoff, int sh_qpos,
+                                            const uint2* __restrict__ btab, int ftp, const u32* __restrict__ roff, u64* __restrict__ p_qs, u64* __restrict__ p_sd,
+                                            u64* __restrict__ p_ft, u32 at) {
     u32 gsubj;
     int dlt;
     if (BANDS) {
-        const uint2 be = btab[G >> L.bd];
+        const uint2 be = btab[G >> bd];
         gsubj = be.x;
         dlt = (int)(be.y - G);
     } else {
-        gsubj = G >> L.bd;
-        dlt = diag_off - (int)(G & ((1u << L.bd) - 1u));
+        gsubj = G >> bd;
+        dlt = diag_off - (int)(G & ((1u << bd) - 1u));
     }
     p_qs[at] = ((u64)gq << rbs) | gsubj;
     p_sd[at] = score_hi | (u64)(u32)dlt;
-    p_ft[at] = ((u64)gsubj << rsh_subj) | ((u64)(u32)(rdoff - dlt) << rsh_diag) | ((u64)(fw & ((1u << L.bp) - 1u)) << sh_qpos);
+    if (ftp) {
+        const int ft_bits_entry = ftp & 255, bsp = ftp >> 8;
+        const int sst = (int)qpos + dlt, sl = (int)(roff[gsubj + 1] - roff[gsubj]);
+        u32 j = gsubj, pos = (u32)sst;
+        if (sst == sl) j = gsubj + 1, pos = 0;   // offset-0 entry of the next chunk sequence
+        const u64 jmax = (1ull << (rbs + 1)) - 1ull, pmax = (1ull << bsp) - 1ull;
+        p_ft[at] = ((u64)qpos << ft_bits_entry) | ((jmax - j) << bsp) | (pmax - pos);
+    } else p_ft[at] = ((u64)gsubj << rsh_subj) | ((u64)(u32)(rdoff - dlt) << rsh_diag) | ((u64)qpos << sh_qpos);
+}
+// ... of a group with head word fw in bucket (range r, batch query gq) of a bucketed pass
+template <bool BANDS>
+__device__ __forceinline__ void u1_record(u32 fw, u64 score_hi, u32 r, u32 gq, const BktLayout& L, int diag_off, int rbs, int rsh_subj, int rsh_diag, int rdoff,
+                                          int sh_qpos, const uint2* __restrict__ btab, u64* __restrict__ p_qs, u64* __restrict__ p_sd, u64* __restrict__ p_ft, u32 at) {
+    u1_record_g<BANDS>((r << (L.wb + L.bd)) | (fw >> L.bp), fw & ((1u << L.bp) - 1u), score_hi, gq, L.bd, diag_off, rbs, rsh_subj, rsh_diag, rdoff, sh_qpos, btab, 0, nullptr,
+                       p_qs, p_sd, p_ft, at);
 }
 
 // Slots of the pass list come from the wave's reserved piece; a new piece of U1_CHUNK slots costs ONE atomic.  (One atomic per flush of
