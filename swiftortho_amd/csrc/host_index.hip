@@ -120,8 +120,9 @@ void build_index(so_ctx* c) {
             dlap("alloc pairs / plan");
             launch_index_windows_sparse(c->ref.d_words.p, c->ref.d_pseq.p, c->ref.d_off.p, ch->p_lo, ch->p_hi, c->ref.Ppad, (u32)ch->seq_lo, c->cfg, c->ref.lut,
                                         (u32)c->step, c->ix_bkt.p, c->ix_ent.p, c->st);
-            // 2. group by bucket id (ascending): the slot layout of the reference's CSR.  Hand-written: two counting passes, k_ixsort.hip; the
-            //    first one's scan leaves the number of entries; members of a bucket land in no particular order (order_chunk)
+            // 2. group by bucket id (ascending): the slot layout of the reference's CSR.  Hand-written: counting passes, k_ixsort.hip (one count,
+            //    two hops into <= 8192 bins, the bins by id); the count's scan leaves the number of entries; members of a bucket land in no
+            //    particular order (order_chunk); the pair arrays ix_bkt / ix_ent are overwritten
             E = d2h_u32(c, ixsort_count(c->ix_bkt.p, nslots, (u32)NC, c->ix_plan.p, c->d_scan_tmp.p, c->st));
             dlap("windows + level-1 count");
         }

@@ -47,7 +47,7 @@ void sort_pairs_u64_u64(void* temp, size_t temp_bytes, const u64* kin, u64* kout
                         hipStream_t st);
 
 // k_ixsort.hip: (bucket id, entry) pairs grouped by ascending bucket id, members of a bucket in no particular order.  plan:
-// ixsort_plan_elems(NC) u32, scan_tmp: scan_u32_temp_elems of that, (tk, tv): E pairs of scratch; (kin, vin) are scratch too when NC > 2^27
+// ixsort_plan_elems(NC) u32 (both plans), scan_tmp: scan_u32_temp_elems of that, (tk, tv): E pairs of scratch; (kin, vin) are overwritten (the second hop's output)
 size_t ixsort_plan_elems(u32 NC);
 void ixsort_pairs(u32* kin, u64* vin, u32 E, u32 NC, u32* plan, u32* scan_tmp, u32* tk, u64* tv, u32* kout, u64* vout, hipStream_t st);
 // the same in two steps over n SLOTS of which some hold no pair (key ~0): the count and its scan leave the number of pairs in the returned device word

@@ -62,6 +62,8 @@
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
+    X(I, ixs_k, "SOHIT_IXS_K", -1, "pair grouping, second hop: slices per workgroup, a power of two up to 64 (-1: the compiled 16)")                            \
+    X(I, ixs_cap, "SOHIT_IXS_CAP", -1, "pair grouping, bins: most pairs of a bin ordered in the LDS, up to 4096 (-1: 4096; 0: every bin by the counters per id; tests move the boundary)") \
     /* ---- traces ---- */                                                                                                                                      \
     X(P, debug, "SOHIT_DEBUG", 0, "per-pass lines on stderr")                                                                                                  \
     X(P, debug_index, "SOHIT_DEBUG_INDEX", 0, "wall laps of the index build on stderr")
