@@ -535,6 +535,37 @@ int so_rbh_records(int device, const so_hit *d_hits, int64_t n, const int32_t *q
 void so_rbh_free(so_rbh_result *result);
 const char *so_rbh_last_error(void);
 
+/* The pan-genome statistics of ortholog groups on the device (csrc/pan.hip).  Replaces: scripts/pan_genome.py -- the family-by-taxon count
+ * table and the type of every family (108-157, the singleton rows 161-188) and the rarefaction pan_feature() over 20 seeded genome orders
+ * (274-375, the branch taken without numexpr: 327-335) -- as swiftortho_amd/pan.py `count_matrix()`, `row_types()` and `rarefaction()`
+ * restate them, count for count.  All of it is integer work; the host rounds the reference's float thresholds once.
+ * Input (host arrays, borrowed): m kept members as pairs (row[k], taxon[k]), a pair listed twice counting twice; n_rows rows, of which the
+ * first n_file_rows are lines of the groups file (the rest: one row per ungrouped gene); n_taxa taxa.  spec_max / core_min: with thr =
+ * the taxa present in a row, a file row is Specific (type 0) when thr <= spec_max, Share (1) when thr < core_min, else Core (2); the
+ * rows behind the file rows are Specific.  size genome orders perm[size * n_taxa], each a permutation of 0 .. n_taxa - 1; S[n_taxa] and
+ * C[n_taxa]: the thresholds of step i = 1 .. n_taxa - 1 (entry 0 is not read).  want_counts: 0 = no count matrix.  flags: reserved, 0.
+ * Curves: per order p, ys = presence (count > 0) of genome perm[p][0] per row; at step i, with yn the presence of genome perm[p][i]:
+ * spec = rows with ys <= S[i] and yn, then ys += yn, core = rows with ys >= C[i], panz = rows with ys > 0.
+ * Output (allocated by the library, released with so_pan_free()): counts[n_rows * n_taxa] (want_counts), type[n_rows], n_core / n_share /
+ * n_spec: the types of the FILE rows counted; core / spec / panz [p * (n_taxa - 1) + i - 1]; tier: 1 = counters in the LDS, 2 = in global
+ * memory, 0 = no curve launched; waits: host waits of the call.  n_rows = 0 is served and launches nothing (the curves are zeros).
+ * Refused with a message (so_pan_last_error) and nothing left allocated: a row or taxon out of range, a perm row that is not a permutation,
+ * n_rows, m or n_taxa >= 2^31, n_rows * n_taxa >= 2^31 when the matrix is wanted, size * n_taxa >= 2^31, flags != 0, no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON, SOHIT_PAN_TIER). */
+typedef struct so_pan_result {
+    int64_t n_rows, n_taxa, size, n_core, n_share, n_spec;
+    int32_t waits;
+    int32_t tier;
+    int32_t *counts;              /* n_rows * n_taxa, or empty */
+    uint8_t *type;                /* n_rows */
+    int64_t *core, *spec, *panz;  /* size * (n_taxa - 1) */
+} so_pan_result;
+int so_pan_genome(int device, int64_t m, const int32_t *row, const int32_t *taxon, int64_t n_rows, int64_t n_file_rows, int64_t n_taxa,
+                  int32_t spec_max, int32_t core_min, int64_t size, const int32_t *perm, const int32_t *S, const int32_t *C,
+                  int32_t want_counts, int32_t flags, so_pan_result *out);
+void so_pan_free(so_pan_result *result);
+const char *so_pan_last_error(void);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Counterpart of the search + orthology + clustering steps of SwiftOrtho's scripts/run_all_fast.py (95-193): duplicate
 collapse, all-vs-all search on the GPU, expansion, find_orth, clustering.  Same flags for those steps (-i -s -a -v -c -y -n -A -I),
-same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the pan-genome / species-tree / operon steps of the reference (external
-tools: trimal, fasttree) are outside SURVEY.md section 8 and are not run.
+same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the species-tree / operon steps of the reference (external tools: trimal,
+fasttree) are outside SURVEY.md section 8 and are not run.  The pan-genome step (204-214) runs on request: `-P T` (default `F`: the
+files and the output above, nothing more) runs scripts/pan_genome.py on the .clsr file after the clustering step and leaves
+<name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
 (<name>.xyz, three columns), THAT file is clustered, and the numbers are mapped back into <name>.clsr (the .grp file in between is
@@ -27,7 +29,7 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F'}
 
 
 def main(argv):
@@ -77,6 +79,12 @@ def main(argv):
             o.write('\t'.join(n2id[k] for k in line[:-1].split('\t')) + '\n')
     os.remove(grp)
     print('use %s to group protein family time:' % a['-A'], time() - t)
+    if a['-P'].upper()[:1] == 'T':
+        # statistics of the pan-genome (run_all_fast.py:204-214): the report into <name>.pan, the curves into <name>.clsr_xy.txt
+        t = time()
+        with open('%s_results/%s.pan' % (fas, name), 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'pan_genome.py'), '-i', fas, '-g', clsr, '-G', a['-G']], stdout=o, check=True)
+        print('pan-genome analysis time:', time() - t)
     return 0
 
 

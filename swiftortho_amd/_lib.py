@@ -56,7 +56,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
-           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error"]
+           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -109,6 +109,12 @@ class SoRbhResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_rbh", "n_core", "n_taxa", "n_runs", "n_winners", "n_runs_long", "n_rows_long")] + \
                [("waits", C.c_int32), ("reserved", C.c_int32), ("rbh_a", C.POINTER(C.c_int32)), ("rbh_b", C.POINTER(C.c_int32)),
                 ("core_gene", C.POINTER(C.c_int32)), ("core_fwd", C.POINTER(C.c_int32)), ("core_rec", C.POINTER(C.c_uint8))]
+
+
+class SoPanResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_rows", "n_taxa", "size", "n_core", "n_share", "n_spec")] + \
+               [("waits", C.c_int32), ("tier", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("type", C.POINTER(C.c_uint8)),
+                ("core", C.POINTER(C.c_int64)), ("spec", C.POINTER(C.c_int64)), ("panz", C.POINTER(C.c_int64))]
 
 
 _lib = None
@@ -256,6 +262,9 @@ def load():
     L.so_rbh_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, C.c_int32, C.c_int32, C.POINTER(SoRbhResult)]
     L.so_rbh_free.argtypes = [C.POINTER(SoRbhResult)]
     L.so_rbh_last_error.restype = cp
+    L.so_pan_genome.argtypes = [C.c_int, i64, vp, vp, i64, i64, i64, C.c_int32, C.c_int32, i64, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(SoPanResult)]
+    L.so_pan_free.argtypes = [C.POINTER(SoPanResult)]
+    L.so_pan_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

@@ -59,6 +59,8 @@
     X(T, orth_tier, "SOHIT_ORTH_TIER", 0, "tests: every run of query rows through one tier of k_orth_run wherever that tier can take it (0 = auto: by run length)") \
     /* ---- reciprocal best hits (so_rbh_*: read per call) ---- */                                                                                              \
     X(T, rbh_tier, "SOHIT_RBH_TIER", 0, "tests: wave = runs of up to 64 rows through k_rbh_run_wave (what auto does), long or sort = every run through the sorted tier (0 = auto: by run length)") \
+    /* ---- pan-genome statistics (so_pan_genome: read per call) ---- */                                                                                        \
+    X(T, pan_tier, "SOHIT_PAN_TIER", 0, "tests: lds = what auto does where the taxa fit the LDS of k_pan_curve, global = words, orders and counters in global memory (0 = auto: by the number of taxa)") \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
@@ -78,12 +80,17 @@ static inline int orth_tier_of(const char* v) {
         case 'w': case '1': return ORTH_TIER_WAVE;
         case 'l': case '2': return ORTH_TIER_LDS;
         case 's': case '3': return ORTH_TIER_SCRATCH;
+        case 'g': return ORTH_TIER_SCRATCH;   // g[lobal]: SOHIT_PAN_TIER's name for the tier without LDS tables
         default: return ORTH_TIER_AUTO;
     }
 }
 
 // ---- reciprocal best hits (rbh.hip): SOHIT_RBH_TIER is read with orth_tier_of -- w[ave] = 1; l[ong], s[ort] (2, 3) = the sorted tier ----
 #define RBH_WAVE_ROWS 64      // longest run k_rbh_run_wave holds, a row per lane; longer runs go through the (run, taxon) sort
+
+// ---- pan-genome statistics (pan.hip): SOHIT_PAN_TIER is read with orth_tier_of -- l[ds] = 2; g[lobal] (3) = the tier without LDS tables ----
+#define PAN_LDS_BYTES 65536u  // most LDS k_pan_curve asks for: 80 bytes per taxon (a tile's words, four orders, thresholds, 12 counters per step)
+#define PAN_TILE_RANGES 256u  // ranges the row tiles are cut into: a workgroup walks one range for four orders and flushes its counters once
 
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;

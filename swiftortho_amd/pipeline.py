@@ -231,3 +231,27 @@ def groups_from_search(fasta_path, inflation=1.5, coverage=.5, identity=0., norm
     t['relations'] = len(tables.ip_a) + len(tables.ot_a) + len(tables.co_a)
     t['groups'] = len(groups)
     return groups, t
+
+
+def pan_genome_from_search(fasta_path, ts=.05, tc=.95, taxa=None, pan_device=True, **groups_from_search_kw):
+    """one process from a FASTA file to the pan-genome statistics of its ortholog groups: groups_from_search(fasta_path,
+    **groups_from_search_kw), then the pan-genome stage (swiftortho_amd.pan) on those groups -- what `scripts/pan_genome.py -i x.fsa -g
+    x.clsr -l ts -u tc` computes on the groups file of the same search, with no groups text in between.  `taxa`: the column order
+    (None: the taxa of the header lines by first appearance; the script has Python's set order).  pan_device: the count of taxa per
+    family, the types and the rarefaction in one device call (pan.device_pan_genome), else by the numpy definitions.
+    -> (taxa, type per row (uint8: 0 Specific, 1 Share, 2 Core; the file rows first, then one row per ungrouped gene), (core, share,
+    specific) counted over the group rows, (core, spec, panz) int64[20, taxa - 1], the dict of groups_from_search with pan_host (ids and
+    taxa coded on the host) and pan (the stage) added, in seconds)"""
+    from . import pan
+    groups, t = groups_from_search(fasta_path, **groups_from_search_kw)
+    t0 = time.time()
+    with open(fasta_path, 'r') as f:
+        text = f.read()
+    if taxa is None:
+        taxa = pan.taxa_of_fasta(text)
+    table = pan.member_table_of(groups, pan.fasta_ids(text), taxa)
+    t['pan_host'] = time.time() - t0
+    t0 = time.time()
+    res = pan.pan_genome(table, len(taxa), ts, tc, device_stage=pan_device, want_counts=False, device=groups_from_search_kw.get('device', 0))
+    t['pan'] = time.time() - t0
+    return list(taxa), res.types, res.totals, (res.core, res.spec, res.panz), t
