@@ -566,6 +566,40 @@ int so_pan_genome(int device, int64_t m, const int32_t *row, const int32_t *taxo
 void so_pan_free(so_pan_result *result);
 const char *so_pan_last_error(void);
 
+/* The operon pairs of the operon-clustering step on the device (csrc/operon.hip).  Replaces: the pair loop of scripts/operon_cluster.py
+ * `operon_clust()` (136-168) -- for every operon the operons listed under the families of its genes, and per such pair the size of the
+ * intersection of the two family sets -- as swiftortho_amd/operon.py `candidate_pairs()` restates it, count for count.  All of it is
+ * integer work: the score and the text stay on the host.
+ * Input (host arrays, borrowed): n_ops operons; fam[start[i] .. start[i + 1]) = the distinct indexed families (1 .. n_fam - 1; family 0 is
+ * never indexed) of operon i in order of first token; length[i] = tokens of operon i (>= 1); has0[i] != 0: operon i holds a gene of
+ * family 0; n_fam: families of the groups file.  flags bit 0: all candidates (below); every other bit must be 0.
+ * A pair (i, j), i == j included, is a CANDIDATE when the two slices share a family; nshr = the families they share, + 1 when both have
+ * has0; rank = the position in i's slice of the first family that j holds too.  A candidate PASSES when nshr > 2 and
+ * 2 * nshr > min(length[i], length[j]).
+ * Output (allocated by the library, released with so_operon_free()):
+ *   flags = 0: the n_pairs passing pairs as i[], j[], nshr[], ordered by (i, j); cand_start is empty;
+ *   flags = 1: all n_candidates candidates as i[], j[], nshr[], ordered by (i, rank, j) -- per operon the order in which j first occurs in
+ *     the concatenation of the (ascending) operon lists of i's families -- and cand_start[n_ops + 1], the bounds of every operon's rows.
+ *   n_pairs (passing) and n_candidates are filled in both modes; n_expansions = the sum over the entries of the size of their family's
+ *   operon list (64-bit); batches: the consecutive ranges of operons the expansion was cut into (SOHIT_OPERON_EXPAND expansions each;
+ *   an operon above that is a batch of its own); waits: host waits of the call (a constant per batch, whatever n_ops).  n_ops = 0, and
+ *   operons without any indexed family, are served and launch nothing.
+ * Refused with a message (so_operon_last_error) before any device work and with nothing left allocated: a null array or negative counts,
+ * a start that does not rise from 0, a family outside 1 .. n_fam - 1, a family repeated inside one operon's slice, length[i] < 1, n_ops,
+ * n_fam or the number of entries >= 2^31, an operon that alone expands to 2^32 - 16 pairs or more, unknown flag bits, no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON, SOHIT_OPERON_EXPAND). */
+typedef struct so_operon_result {
+    int64_t n_ops, n_pairs, n_candidates, n_expansions;
+    int32_t batches;
+    int32_t waits;
+    int32_t *i, *j, *nshr;        /* n_pairs (flags = 0) or n_candidates (flags = 1) */
+    int64_t *cand_start;          /* n_ops + 1 (flags = 1), or empty */
+} so_operon_result;
+int so_operon_pairs(int device, int64_t n_ops, const int64_t *start, const int32_t *fam, const int32_t *length, const uint8_t *has0,
+                    int64_t n_fam, int32_t flags, so_operon_result *out);
+void so_operon_free(so_operon_result *result);
+const char *so_operon_last_error(void);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Counterpart of the search + orthology + clustering steps of SwiftOrtho's scripts/run_all_fast.py (95-193): duplicate
 collapse, all-vs-all search on the GPU, expansion, find_orth, clustering.  Same flags for those steps (-i -s -a -v -c -y -n -A -I),
-same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the species-tree / operon steps of the reference (external tools: trimal,
-fasttree) are outside SURVEY.md section 8 and are not run.  The pan-genome step (204-214) runs on request: `-P T` (default `F`: the
-files and the output above, nothing more) runs scripts/pan_genome.py on the .clsr file after the clustering step and leaves
+same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the species-tree step of the reference (external tools: trimal, fasttree) is
+outside SURVEY.md section 8 and is not run.  The operon step (241-255) runs when `-p foo.operon` names a file: scripts/operon_cluster.py
+on the .clsr file and the operon file writes <operon name>.xyz (with `-G T`: the shared-family counts on the GPU), and
+`bin/find_cluster.py -i` that file with the wrapper's -A, -I and -G writes <operon name>.clsr.  This wrapper keeps its intermediates --
+the reference removes every .xyz at its end --, so both files stay.  Without -p nothing of this happens.
+The pan-genome step (204-214) runs on request: `-P T` (default `F`: the files and the output above, nothing more) runs scripts/pan_genome.py on the .clsr file after the clustering step and leaves
 <name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
@@ -35,7 +38,7 @@ ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '
 def main(argv):
     a = parse_flags(argv, ARGS)
     if a['-i'] == '':
-        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5]' % argv[0])
+        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon]' % argv[0])
         raise SystemExit()
     fas, name = a['-i'], a['-i'].split(os.sep)[-1]
     t = time()
@@ -85,6 +88,16 @@ def main(argv):
         with open('%s_results/%s.pan' % (fas, name), 'wb') as o:
             subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'pan_genome.py'), '-i', fas, '-g', clsr, '-G', a['-G']], stdout=o, check=True)
         print('pan-genome analysis time:', time() - t)
+    if os.path.isfile(a['-p']):
+        # operon clustering (run_all_fast.py:241-255): scored operon pairs from the gene families, then the same clustering as above
+        t = time()
+        oname = a['-p'].split(os.sep)[-1]
+        oxyz, oclsr = ('%s_results/%s.%s' % (fas, oname, e) for e in ('xyz', 'clsr'))
+        with open(oxyz, 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'operon_cluster.py'), '-g', clsr, '-p', a['-p'], '-G', a['-G']], stdout=o, check=True)
+        with open(oclsr, 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_cluster.py'), '-i', oxyz, '-a', a['-A'], '-I', a['-I'], '-G', a['-G']], stdout=o, check=True)
+        print('operon clustering time:', time() - t)
     return 0
 
 

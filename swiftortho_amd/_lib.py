@@ -56,7 +56,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
-           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error"]
+           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error",
+           "so_operon_pairs", "so_operon_free", "so_operon_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -115,6 +116,12 @@ class SoPanResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_rows", "n_taxa", "size", "n_core", "n_share", "n_spec")] + \
                [("waits", C.c_int32), ("tier", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("type", C.POINTER(C.c_uint8)),
                 ("core", C.POINTER(C.c_int64)), ("spec", C.POINTER(C.c_int64)), ("panz", C.POINTER(C.c_int64))]
+
+
+class SoOperonResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_ops", "n_pairs", "n_candidates", "n_expansions")] + \
+               [("batches", C.c_int32), ("waits", C.c_int32), ("i", C.POINTER(C.c_int32)), ("j", C.POINTER(C.c_int32)),
+                ("nshr", C.POINTER(C.c_int32)), ("cand_start", C.POINTER(C.c_int64))]
 
 
 _lib = None
@@ -265,6 +272,9 @@ def load():
     L.so_pan_genome.argtypes = [C.c_int, i64, vp, vp, i64, i64, i64, C.c_int32, C.c_int32, i64, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(SoPanResult)]
     L.so_pan_free.argtypes = [C.POINTER(SoPanResult)]
     L.so_pan_last_error.restype = cp
+    L.so_operon_pairs.argtypes = [C.c_int, i64, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(SoOperonResult)]
+    L.so_operon_free.argtypes = [C.POINTER(SoOperonResult)]
+    L.so_operon_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

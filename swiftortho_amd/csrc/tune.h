@@ -61,6 +61,8 @@
     X(T, rbh_tier, "SOHIT_RBH_TIER", 0, "tests: wave = runs of up to 64 rows through k_rbh_run_wave (what auto does), long or sort = every run through the sorted tier (0 = auto: by run length)") \
     /* ---- pan-genome statistics (so_pan_genome: read per call) ---- */                                                                                        \
     X(T, pan_tier, "SOHIT_PAN_TIER", 0, "tests: lds = what auto does where the taxa fit the LDS of k_pan_curve, global = words, orders and counters in global memory (0 = auto: by the number of taxa)") \
+    /* ---- operon pairs (so_operon_pairs: read per call) ---- */                                                                                               \
+    X(I, operon_expand, "SOHIT_OPERON_EXPAND", -1, "tests: expansions per batch (-1: 2^28)")                                                                   \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
@@ -91,6 +93,10 @@ static inline int orth_tier_of(const char* v) {
 // ---- pan-genome statistics (pan.hip): SOHIT_PAN_TIER is read with orth_tier_of -- l[ds] = 2; g[lobal] (3) = the tier without LDS tables ----
 #define PAN_LDS_BYTES 65536u  // most LDS k_pan_curve asks for: 80 bytes per taxon (a tile's words, four orders, thresholds, 12 counters per step)
 #define PAN_TILE_RANGES 256u  // ranges the row tiles are cut into: a workgroup walks one range for four orders and flushes its counters once
+
+// ---- operon pairs (operon.hip): expansions of one batch.  A memory bound, not a tuned value: the sort helpers take 12 bytes per element
+// (u64 key, u32 payload) for input and output each, so 2^28 expansions are about 6 GB of keys, payloads and sort scratch ----
+#define OPERON_EXPAND_DEFAULT (1ull << 28)
 
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;
