@@ -19,40 +19,62 @@ __all__ = ["AA", "HT", "SEED", "to_fasta", "ChainModel", "shape_set", "tier_set"
 DSH = 20   # group key = subject << DSH | (diagonal + 2^(DSH - 1))
 
 
-def windows(oracle, seq, masked=False):
-    """(buckets, positions) of the seed windows of one protein (uint8 ASCII array); masked: as a QUERY"""
+def windows(oracle, seq, masked=False, ssd=SEED):
+    """(buckets, positions) of the seed windows of one protein (uint8 ASCII array); masked: as a QUERY (None: no SEG mask, -F F)"""
     b = seq.tobytes()
     if masked:
         b = oracle.seg(b)
-    w = oracle.spseeds(b, SEED, oracle.AA9, HT, 1)
+    w = oracle.spseeds(b, ssd, oracle.AA9, HT, 1)
     return np.array([x[0] for x in w], dtype=np.int64), np.array([x[1] for x in w], dtype=np.int64)
 
 
 class ChainModel:
-    """groups of every query of `qrys` against the subjects `refs` (qrys None: all-vs-all)"""
+    """groups of every query of `qrys` against the subjects `refs` (qrys None: all-vs-all).  ssd: the seed pattern (one); flt: the queries
+    pass the SEG mask (-F T); chk: sequences per chunk (None: one chunk) -- the offset-0 entry of a chunk's FIRST sequence is the one the
+    library drops (`drop`; the oracle counts it, a group that is never scored)"""
 
-    def __init__(self, oracle, refs, qrys=None):
+    def __init__(self, oracle, refs, qrys=None, ssd=SEED, flt=True, chk=None):
         self.oracle = oracle
         self.refs = refs
         self.qrys = refs if qrys is None else qrys
-        bk, sid, pos = [], [], []
+        self.ssd, self.flt = ssd, flt
+        bk, sid, pos, drop, raw = [], [], [], [], []
         for s, seq in enumerate(refs):
-            b, p = windows(oracle, seq)
+            b, p = windows(oracle, seq, ssd=ssd)
+            raw.append(p)
             z = p == 0   # (the offset-0 entry: see the head of the file)
             bk.append(b), pos.append(np.where(z, len(refs[s - 1]) if s else 0, p)), sid.append(np.where(z, s - 1, s).astype(np.int64))
-        bk, sid, pos = np.concatenate(bk), np.concatenate(sid), np.concatenate(pos)
+            drop.append(z & ((s % chk == 0) if chk else (s == 0)))
+        bk, sid, pos, drop = np.concatenate(bk), np.concatenate(sid), np.concatenate(pos), np.concatenate(drop)
+        # the reference never reads the last slot of a chunk's index: the smallest entry (subject, position) of the chunk's highest bucket
+        # is no hit for anybody (tests/test_gpu_parity.py check_index)
+        own = np.repeat(np.arange(len(refs)), [len(x) for x in raw])
+        raw = np.concatenate(raw)
+        keep = np.ones(len(bk), dtype=bool)
+        for c in np.unique(own // chk if chk else own * 0):
+            i = np.flatnonzero((own // chk if chk else own * 0) == c)
+            i = i[bk[i] == bk[i].max()]
+            keep[i[np.lexsort((raw[i], own[i]))[0]]] = False
+        bk, sid, pos, drop = bk[keep], sid[keep], pos[keep], drop[keep]
         o = np.argsort(bk, kind="stable")
-        self.bk, self.sid, self.pos = bk[o], sid[o], pos[o]
-        self._d = {}
+        self.bk, self.sid, self.pos, self.drop = bk[o], sid[o], pos[o], drop[o]
+        self._d, self._h = {}, {}
+
+    def hits(self, q):
+        """(subject, subject position, query position, dropped by the library) of every hit of query q"""
+        if q not in self._h:
+            b, p = windows(self.oracle, self.qrys[q], self.flt, self.ssd)
+            lo, hi = np.searchsorted(self.bk, b, "left"), np.searchsorted(self.bk, b, "right")
+            n = hi - lo
+            at = np.repeat(lo, n) + (np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n))
+            self._h[q] = (self.sid[at], self.pos[at], np.repeat(p, n), self.drop[at])
+        return self._h[q]
 
     def diagonals(self, q):
         """(keys, sizes) of all diagonals of query q; key = subject << DSH | (diagonal + 2^(DSH - 1))"""
         if q not in self._d:
-            b, p = windows(self.oracle, self.qrys[q], True)
-            lo, hi = np.searchsorted(self.bk, b, "left"), np.searchsorted(self.bk, b, "right")
-            n = hi - lo
-            at = np.repeat(lo, n) + (np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n))
-            key = (self.sid[at] << DSH) | (self.pos[at] - np.repeat(p, n) + (1 << (DSH - 1)))
+            sid, pos, qp, _ = self.hits(q)
+            key = (sid << DSH) | (pos - qp + (1 << (DSH - 1)))
             self._d[q] = np.unique(key, return_counts=True)
         return self._d[q]
 
@@ -240,7 +262,7 @@ def tier_set(oracle, limits, seed=30312, n_back=256):
     raise AssertionError("the families keep meeting chance matches")
 
 
-def band_set(oracle, seed=30313, n_q=260, slen=6000):
+def band_set(oracle, seed=30313, n_q=260, slen=6000, ssd=SEED):
     """(reference fasta, query fasta, model): n_q queries of 60 .. 200 residues against themselves and ONE subject of `slen` residues that
     holds a 40-residue segment of every fourth query: a subject too long for one diagonal band, with groups in every part of it"""
     rng = np.random.default_rng(seed)
@@ -250,7 +272,7 @@ def band_set(oracle, seed=30313, n_q=260, slen=6000):
         at = 20 + k * ((slen - 100) // (len(qs[::4])))
         _plant(big, at, q, 10, 40)
     refs = qs + [big]
-    return to_fasta(refs), to_fasta(qs), ChainModel(oracle, refs, qs)
+    return to_fasta(refs), to_fasta(qs), ChainModel(oracle, refs, qs, ssd=ssd)
 
 
 def cap_set(oracle, seed=30314, n_back=256):
