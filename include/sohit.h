@@ -600,6 +600,47 @@ int so_operon_pairs(int device, int64_t n_ops, const int64_t *start, const int32
 void so_operon_free(so_operon_result *result);
 const char *so_operon_last_error(void);
 
+/* The core-gene supermatrix from the hits' own alignments, and the counts its distances are made from, on the device (csrc/phy.hip).
+ * Replaces: the second half of scripts/rbh2phy.py (the aligner it shells out to, and its join of the family alignments) by what
+ * swiftortho_amd/phy.py `pick_rows()`, `project()`, `supermatrix()` and `pair_counts()` define, array for array.  Integer and byte work only.
+ * so_phy_rows: n hit rows as host columns q, s (name codes) and score, in any order, and n_pairs wanted (pair_q, pair_s) pairs ->
+ *   row[n_pairs]: the row with q == pair_q, s == pair_s and the highest score, the lowest such row among equal scores (0.0 == -0.0), -1
+ *   when there is none.  A pair listed twice gets the same answer twice.  Refused: a NaN score, a negative code in a wanted pair, n or
+ *   n_pairs >= 2^31, flags != 0.
+ * so_phy_build: n_fam families, family f owning columns col_off[f] .. col_off[f + 1] (its anchor's length) of n_taxa rows; every task fills
+ *   the block (fam, slot), at most one task per block, a block without a task stays '-':
+ *     kind 1  the anchor itself: the block's row is residues[res_off .. res_off + res_len), res_len == the block's length;
+ *     kind 0  a member: walk the runs runs[run_off[t] .. run_off[t + 1]) (length << 4 | op; 0 M, 1 I, 2 D) from anchor position qst - 1
+ *             and member position sst - 1: M copies residues, I leaves the columns '-', D drops residues.
+ *   Then gaps[c] = the '-' of column c, keep = the ascending columns with gaps[c] <= floor(gap_share * n_taxa), and over the kept columns
+ *   cmp[a * n_taxa + b] = columns where neither row is '-', same[a * n_taxa + b] = those of them where the two bytes are equal.
+ *   flags bit 0: no matrix in the result (the counts only).  n_keep entries of keep are valid.
+ *   Refused with a message (so_phy_last_error) and nothing left allocated: n_taxa or n_fam of 0, more than 2^31 - 1 columns, 46341 taxa
+ *   and more, offsets that do not rise from 0 or leave their arrays, a family or slot out of range, two tasks for one block, a gap share
+ *   outside [0, 1], and -- found on the device, before the task stores anything -- qst or sst < 1, a run of length 0 or an unknown
+ *   operation, runs that lead past the anchor or past the member, an anchor whose residues are not as many as its columns; the message names
+ *   the lowest such task.
+ * One result type for both calls (a call fills what it computes, the other arrays are empty); waits: host waits of the call.
+ * No so_ctx: the calls read the SOHIT_* switches themselves (SOHIT_POISON). */
+typedef struct so_phy_result {
+    int64_t n_pairs, n_taxa, n_cols, n_keep;
+    int32_t waits;
+    int32_t reserved;
+    int64_t *row;                 /* so_phy_rows: n_pairs */
+    uint8_t *matrix;              /* n_taxa * n_cols, or empty (flags bit 0) */
+    int32_t *gaps;                /* n_cols */
+    int32_t *keep;                /* n_cols allocated, n_keep valid */
+    int64_t *cmp, *same;          /* n_taxa * n_taxa */
+} so_phy_result;
+int so_phy_rows(int device, int64_t n, const int32_t *q, const int32_t *s, const double *score, int64_t n_pairs, const int32_t *pair_q,
+                const int32_t *pair_s, int32_t flags, so_phy_result *out);
+int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t *col_off, int64_t n_tasks, const int32_t *fam, const int32_t *slot,
+                 const uint8_t *kind, const int64_t *res_off, const int32_t *res_len, const int32_t *qst, const int32_t *sst,
+                 const int64_t *run_off, const uint32_t *runs, int64_t n_runs, const uint8_t *residues, int64_t n_res, double gap_share,
+                 int32_t flags, so_phy_result *out);
+void so_phy_free(so_phy_result *result);
+const char *so_phy_last_error(void);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

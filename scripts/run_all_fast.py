@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Counterpart of the search + orthology + clustering steps of SwiftOrtho's scripts/run_all_fast.py (95-193): duplicate
 collapse, all-vs-all search on the GPU, expansion, find_orth, clustering.  Same flags for those steps (-i -s -a -v -c -y -n -A -I),
-same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the species-tree step of the reference (external tools: trimal, fasttree) is
-outside SURVEY.md section 8 and is not run.  The operon step (241-255) runs when `-p foo.operon` names a file: scripts/operon_cluster.py
+same files under <fasta>_results/ (.sc, .opc, .xyz, .clsr); the species-tree step of the reference (external tools: famsa, trimal, fasttree) is
+outside SURVEY.md section 8 and is not run as such: `-t T` (below) builds the tree from the search's own alignments instead.  The operon step (241-255) runs when `-p foo.operon` names a file: scripts/operon_cluster.py
 on the .clsr file and the operon file writes <operon name>.xyz (with `-G T`: the shared-family counts on the GPU), and
 `bin/find_cluster.py -i` that file with the wrapper's -A, -I and -G writes <operon name>.clsr.  This wrapper keeps its intermediates --
 the reference removes every .xyz at its end --, so both files stay.  Without -p nothing of this happens.
 The pan-genome step (204-214) runs on request: `-P T` (default `F`: the files and the output above, nothing more) runs scripts/pan_genome.py on the .clsr file after the clustering step and leaves
 <name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.
+The species-tree step runs on request as well: `-t T` (default `F`) leaves <name>.aln (the core-gene supermatrix of the reference taxon -r,
+FASTA, taxa in slot order), <name>.aln.trim (the columns whose share of gaps is at most `-g`, default 1: the same file) and <name>.nwk
+(neighbour joining over the `-m p|poisson` distances).  The reference shells out to famsa, trimal and fasttree here; this step aligns
+nothing: it joins the families along the alignments the search itself made (swiftortho_amd/phy.py), in one process that searches the
+proteome once more with a CIGAR on every row; with `-G T` the matrix and the pair counts are built on the GPU.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
 (<name>.xyz, three columns), THAT file is clustered, and the numbers are mapped back into <name>.clsr (the .grp file in between is
@@ -32,7 +37,7 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-t': 'F', '-g': '1', '-m': 'p'}
 
 
 def main(argv):
@@ -88,6 +93,21 @@ def main(argv):
         with open('%s_results/%s.pan' % (fas, name), 'wb') as o:
             subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'pan_genome.py'), '-i', fas, '-g', clsr, '-G', a['-G']], stdout=o, check=True)
         print('pan-genome analysis time:', time() - t)
+    if a['-t'].upper()[:1] == 'T':
+        # species tree (run_all_fast.py:216-239, without famsa, trimal and fasttree): one process searches the proteome with a CIGAR on every
+        # row and joins the core families of -r along those alignments; <name>.aln, <name>.aln.trim (the columns -g keeps) and <name>.nwk
+        t = time()
+        from swiftortho_amd import phy, pipeline
+        newick, sm, _ = pipeline.species_tree_from_search(fas, reference=a['-r'], gap_share=float(a['-g']), model=a['-m'],
+                                                          device_stage=a['-G'].upper()[:1] == 'T', **nr.collapsed_search_kw(a['-s'], a['-v']))
+        aln = '%s_results/%s.aln' % (fas, name)
+        with open(aln, 'wb') as o:
+            o.write(phy.supermatrix_fasta(sm.taxa, sm.matrix, range(sm.matrix.shape[1])))
+        with open(aln + '.trim', 'wb') as o:
+            o.write(phy.supermatrix_fasta(sm.taxa, sm.matrix, sm.keep))
+        with open('%s_results/%s.nwk' % (fas, name), 'wb') as o:
+            o.write(newick + b'\n')
+        print('species tree time:', time() - t)
     if os.path.isfile(a['-p']):
         # operon clustering (run_all_fast.py:241-255): scored operon pairs from the gene families, then the same clustering as above
         t = time()

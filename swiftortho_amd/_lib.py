@@ -57,7 +57,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error",
-           "so_operon_pairs", "so_operon_free", "so_operon_last_error"]
+           "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -122,6 +122,12 @@ class SoOperonResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_ops", "n_pairs", "n_candidates", "n_expansions")] + \
                [("batches", C.c_int32), ("waits", C.c_int32), ("i", C.POINTER(C.c_int32)), ("j", C.POINTER(C.c_int32)),
                 ("nshr", C.POINTER(C.c_int32)), ("cand_start", C.POINTER(C.c_int64))]
+
+
+class SoPhyResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_pairs", "n_taxa", "n_cols", "n_keep")] + \
+               [("waits", C.c_int32), ("reserved", C.c_int32), ("row", C.POINTER(C.c_int64)), ("matrix", C.POINTER(C.c_uint8)),
+                ("gaps", C.POINTER(C.c_int32)), ("keep", C.POINTER(C.c_int32)), ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64))]
 
 
 _lib = None
@@ -275,6 +281,10 @@ def load():
     L.so_operon_pairs.argtypes = [C.c_int, i64, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(SoOperonResult)]
     L.so_operon_free.argtypes = [C.POINTER(SoOperonResult)]
     L.so_operon_last_error.restype = cp
+    L.so_phy_rows.argtypes = [C.c_int, i64, vp, vp, vp, i64, vp, vp, C.c_int32, C.POINTER(SoPhyResult)]
+    L.so_phy_build.argtypes = [C.c_int, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, C.c_double, C.c_int32, C.POINTER(SoPhyResult)]
+    L.so_phy_free.argtypes = [C.POINTER(SoPhyResult)]
+    L.so_phy_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

@@ -1,0 +1,440 @@
+// phy.hip -- the core-gene supermatrix from the hits' own alignments, on the device: what swiftortho_amd/phy.py `pick_rows()`, `project()`,
+// `supermatrix()` and `pair_counts()` define.  Every member of a core family is the best hit of the family's anchor gene in its taxon, so the
+// search has aligned exactly that pair: the member's residues are laid onto the anchor's coordinates along the row's CIGAR (M: copied,
+// I: the columns stay '-', D: the residues are dropped), the blocks of the families side by side are the supermatrix, and the counts of
+// compared and equal columns per pair of taxa are what the distances are made from.
+//
+// The numpy functions are the definition; all of it is integer and byte work, so every result is exact whatever the scheduling:
+//   so_phy_rows   the wanted (anchor, member) pairs as 64-bit keys, sorted once; every hit row finds its key by binary search.  Pass 1: an
+//                 integer atomicMax of the order-preserving bit pattern of the score (-0.0 counts as 0.0); pass 2: an atomicMin of the
+//                 row number among the rows that hold the maximum.  No float is ever compared on the device.
+//   so_phy_build  k_phy_project   a wave per (family, slot) task: the run lengths are summed and checked against both sequences BEFORE any
+//                                 store (a bad task flags itself and writes nothing), a wave-wide scan gives every run its two starts,
+//                                 and the wave copies the M runs one after the other, a byte per lane;
+//                 k_phy_gaps      '-' per column and the keep flag gaps <= floor(g * T); scan_u32 + k_phy_keep compact the kept columns;
+//                 k_phy_gather    the kept columns of every taxon side by side, padded with '-' to a multiple of 16 bytes;
+//                 k_phy_pairs     a workgroup owns a tile of 64 x 64 taxon pairs and a range of kept columns, staged chunk by chunk in the
+//                                 LDS as [word][row] with the non-gap masks next to them; four residues per 32-bit word: a byte is
+//                                 non-zero where ((x & 0x7f7f7f7f) + 0x7f7f7f7f | x) has its top bit; counts in registers, one flush per
+//                                 workgroup with 64-bit integer atomics.  Only tiles I <= J are walked; the flush writes both halves.
+// One host wait per call (DeviceCall, device_call.h), counted.
+#include "hit_table.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+typedef unsigned long long ull;
+
+#define PHY_DASH 0x2Du
+#define PHY_DASH4 0x2D2D2D2Du
+enum { PHY_E_START = 1, PHY_E_RUN = 2, PHY_E_QEND = 4, PHY_E_SEND = 8, PHY_E_ANCHOR = 16 };
+
+// ---- so_phy_rows ---------------------------------------------------------------------------------------------------------------------
+// the bits of a double (no NaN) -> an unsigned number that orders like the value; -0.0 and 0.0 give the same number, every number is > 0
+__device__ __forceinline__ ull score_order(ull bits) {
+    if (bits == 0x8000000000000000ull) bits = 0ull;
+    return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
+}
+// first position of key among the m sorted keys, or NONE32
+__device__ __forceinline__ u32 phy_find(const ull* __restrict__ sk, u32 m, ull key) {
+    u32 lo = 0, hi = m;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] < key) lo = mid + 1u;
+        else hi = mid;
+    }
+    return (lo < m && sk[lo] == key) ? lo : NONE32;
+}
+__device__ __forceinline__ ull phy_key(int q, int s) { return ((ull)(u32)q << 32) | (ull)(u32)s; }
+
+__global__ __launch_bounds__(256) void k_phy_row_max(u32 n, const int* __restrict__ q, const int* __restrict__ s, const ull* __restrict__ score, const ull* __restrict__ sk,
+                                                     u32 m, u32* __restrict__ slot_of, ull* __restrict__ best) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u32 slot = phy_find(sk, m, phy_key(q[i], s[i]));
+    slot_of[i] = slot;
+    if (slot != NONE32) atomicMax(best + slot, score_order(score[i]));
+}
+__global__ __launch_bounds__(256) void k_phy_row_first(u32 n, const ull* __restrict__ score, const u32* __restrict__ slot_of, const ull* __restrict__ best,
+                                                       u32* __restrict__ first) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u32 slot = slot_of[i];
+    if (slot != NONE32 && score_order(score[i]) == best[slot]) atomicMin(first + slot, i);
+}
+__global__ __launch_bounds__(256) void k_phy_row_out(u32 np, const ull* __restrict__ pkey, const ull* __restrict__ sk, const u32* __restrict__ first, u32* __restrict__ row) {
+    const u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= np) return;
+    const u32 slot = phy_find(sk, np, pkey[p]);   // (always found: sk holds the same keys)
+    row[p] = slot == NONE32 ? NONE32 : first[slot];
+}
+
+// ---- so_phy_build ----------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 wave_incl_scan(u32 v, u32 lane) {
+#pragma unroll
+    for (u32 d = 1; d < 64u; d <<= 1) {
+        const u32 t = (u32)__shfl_up((int)v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ ull wave_sum64(ull v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += (ull)__shfl_xor((long long)v, d, 64);
+    return v;
+}
+
+struct PhyTasks {
+    const int *fam, *slot, *res_len, *qst, *sst;
+    const u8* kind;
+    const i64 *res_off, *run_off;
+};
+
+// a wave per task.  The host has checked what a task names (family, slot, its slice of the residues and of the runs); the wave checks what
+// the runs do inside the block and inside the member before it stores anything.  err[0]: the PHY_E_* bits, err[1]: the lowest bad task.
+__global__ __launch_bounds__(256) void k_phy_project(u32 n_tasks, PhyTasks tk, const u32* __restrict__ runs, const u8* __restrict__ res, const i64* __restrict__ col_off, u64 L,
+                                                     u8* __restrict__ matrix, u32* __restrict__ err) {
+    const u32 t = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (t >= n_tasks) return;   // (a whole wave)
+    const u32 lane = threadIdx.x & 63u;
+    const int f = tk.fam[t];
+    const i64 c0 = col_off[f];
+    const u32 alen = (u32)(col_off[f + 1] - c0), rlen = (u32)tk.res_len[t];
+    u8* dst = matrix + (size_t)tk.slot[t] * L + (size_t)c0;
+    const u8* src = res + tk.res_off[t];
+    u32 bad = 0;
+    if (tk.kind[t]) {   // the anchor itself: its residues are the block's row
+        if (rlen != alen) bad = PHY_E_ANCHOR;
+        else
+            for (u32 x = lane; x < alen; x += 64u) dst[x] = src[x];
+    } else {
+        const i64 r0 = tk.run_off[t];
+        const u64 nr = (u64)(tk.run_off[t + 1] - r0);
+        const int qs = tk.qst[t], ss = tk.sst[t];
+        if (qs < 1 || ss < 1) bad |= PHY_E_START;
+        ull qsum = 0, ssum = 0;
+        bool badrun = false;
+        for (u64 k = lane; k < nr; k += 64u) {
+            const u32 v = runs[r0 + (i64)k], len = v >> 4, op = v & 15u;
+            if (len == 0u || op > 2u) badrun = true;
+            else {
+                if (op != 2u) qsum += len;
+                if (op != 1u) ssum += len;
+            }
+        }
+        qsum = wave_sum64(qsum), ssum = wave_sum64(ssum);
+        if (__any(badrun)) bad |= PHY_E_RUN;
+        if (!bad) {
+            if ((ull)(qs - 1) + qsum > (ull)alen) bad |= PHY_E_QEND;
+            if ((ull)(ss - 1) + ssum > (ull)rlen) bad |= PHY_E_SEND;
+        }
+        if (!bad) {   // (wave-uniform: every sum above is)
+            u32 qp = (u32)(qs - 1), sp = (u32)(ss - 1);
+            for (u64 base = 0; base < nr; base += 64u) {
+                const u64 k = base + lane;
+                const u32 v = k < nr ? runs[r0 + (i64)k] : 0u, len = v >> 4, op = v & 15u;
+                const u32 qa = op != 2u ? len : 0u, sa = op != 1u ? len : 0u;
+                const u32 qi = wave_incl_scan(qa, lane), si = wave_incl_scan(sa, lane);
+                const u32 my_q = qp + qi - qa, my_s = sp + si - sa;
+                ull m = __ballot(k < nr && op == 0u);
+                while (m) {   // the M runs of these 64, one after the other, the wave copying each
+                    const int j = __ffsll((long long)m) - 1;
+                    m &= m - 1ull;
+                    const u32 n = (u32)__shfl((int)len, j, 64), q0 = (u32)__shfl((int)my_q, j, 64), s0 = (u32)__shfl((int)my_s, j, 64);
+                    for (u32 x = lane; x < n; x += 64u) dst[q0 + x] = src[s0 + x];
+                }
+                qp += (u32)__shfl((int)qi, 63, 64), sp += (u32)__shfl((int)si, 63, 64);
+            }
+        }
+    }
+    if (bad && lane == 0u) {
+        atomicOr(err, bad);
+        atomicMin(err + 1, t);
+    }
+}
+
+// a lane per column: the '-' of the column and whether it is kept
+__global__ __launch_bounds__(256) void k_phy_gaps(const u8* __restrict__ matrix, u32 T, u32 L, u32 gmax, int* __restrict__ gaps, u32* __restrict__ flag) {
+    const u32 c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= L) return;
+    u32 g = 0;
+    for (u32 t = 0; t < T; ++t) g += matrix[(size_t)t * L + c] == PHY_DASH ? 1u : 0u;
+    gaps[c] = (int)g;
+    flag[c] = g <= gmax ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_phy_keep(const u32* __restrict__ flag, const u32* __restrict__ pos, u32 L, int* __restrict__ keep) {
+    const u32 c = blockIdx.x * 256u + threadIdx.x;
+    if (c < L && flag[c]) keep[pos[c]] = (int)c;
+}
+// grid (columns of the padded row, taxa): the kept columns side by side, '-' behind them
+__global__ __launch_bounds__(256) void k_phy_gather(const u8* __restrict__ matrix, u32 L, u32 Lp, const int* __restrict__ keep, const u32* __restrict__ d_nk, u8* __restrict__ K) {
+    const u32 j = blockIdx.x * 256u + threadIdx.x, t = blockIdx.y;
+    if (j >= Lp) return;
+    K[(size_t)t * Lp + j] = j < *d_nk ? matrix[(size_t)t * L + (u32)keep[j]] : (u8)PHY_DASH;
+}
+
+// 0x80 in every byte of x that is not 0 (no carry leaves a byte: 0x7f + 0x7f < 0x100)
+__device__ __forceinline__ u32 nonzero_bytes(u32 x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
+
+// grid (nt * nt tiles of 64 x 64 pairs, ranges of `wps` words); K: T rows of Lpw words (Lpw a multiple of 4), '-' behind the kept columns.
+// lane (ty, tx) of the 16 x 16 holds rows I * 64 + ty * 4 + r against rows J * 64 + tx * 4 + c.
+__global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u32 T, u32 Lpw, const u32* __restrict__ d_nk, u32 nt, u32 wps, ull* __restrict__ cmp,
+                                                   ull* __restrict__ same) {
+    __shared__ __attribute__((aligned(16))) u32 sA[PHY_CHUNK_WORDS][PHY_TILE];
+    __shared__ __attribute__((aligned(16))) u32 sNA[PHY_CHUNK_WORDS][PHY_TILE];
+    __shared__ __attribute__((aligned(16))) u32 sB[PHY_CHUNK_WORDS][PHY_TILE];
+    __shared__ __attribute__((aligned(16))) u32 sNB[PHY_CHUNK_WORDS][PHY_TILE];
+    const u32 I = blockIdx.x / nt, J = blockIdx.x % nt;
+    if (I > J) return;
+    const u32 nkw = min(Lpw, (*d_nk + 3u) >> 2);   // words that hold a kept column; the last one may be partial: its tail is '-'
+    const u32 w_begin = blockIdx.y * wps, w_end = min(nkw, w_begin + wps);
+    if (w_begin >= w_end) return;   // (the whole workgroup)
+    const u32 tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const u32 lrow = threadIdx.x & 63u, lpart = threadIdx.x >> 6;
+    const u32 ra = I * PHY_TILE + lrow, rb = J * PHY_TILE + lrow;
+    u32 cs[4][4], ss[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cs[r][c] = 0u, ss[r][c] = 0u;
+    for (u32 w0 = w_begin; w0 < w_end; w0 += PHY_CHUNK_WORDS) {
+        __syncthreads();   // the last chunk's readers are done
+        for (u32 qd = lpart; qd < PHY_CHUNK_WORDS / 4u; qd += 4u) {
+            const u32 w = w0 + qd * 4u;   // a multiple of 4 below Lpw, itself one: the 16 bytes lie inside the row
+            uint4 va = make_uint4(PHY_DASH4, PHY_DASH4, PHY_DASH4, PHY_DASH4), vb = va;
+            if (w < w_end) {
+                if (ra < T) va = *reinterpret_cast<const uint4*>(K + (size_t)ra * Lpw + w);
+                if (rb < T) vb = *reinterpret_cast<const uint4*>(K + (size_t)rb * Lpw + w);
+            }
+            const u32 a4[4] = {va.x, va.y, va.z, va.w}, b4[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+            for (u32 i = 0; i < 4u; ++i) {
+                sA[qd * 4u + i][lrow] = a4[i], sNA[qd * 4u + i][lrow] = nonzero_bytes(a4[i] ^ PHY_DASH4);
+                sB[qd * 4u + i][lrow] = b4[i], sNB[qd * 4u + i][lrow] = nonzero_bytes(b4[i] ^ PHY_DASH4);
+            }
+        }
+        __syncthreads();
+        const u32 nw = min((u32)PHY_CHUNK_WORDS, w_end - w0);
+        for (u32 w = 0; w < nw; ++w) {
+            const uint4 a = *reinterpret_cast<const uint4*>(&sA[w][ty * 4u]), na = *reinterpret_cast<const uint4*>(&sNA[w][ty * 4u]);
+            const uint4 b = *reinterpret_cast<const uint4*>(&sB[w][tx * 4u]), nb = *reinterpret_cast<const uint4*>(&sNB[w][tx * 4u]);
+            const u32 av[4] = {a.x, a.y, a.z, a.w}, nav[4] = {na.x, na.y, na.z, na.w}, bv[4] = {b.x, b.y, b.z, b.w}, nbv[4] = {nb.x, nb.y, nb.z, nb.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    cs[r][c] += (u32)__popc(nav[r] & nbv[c]);
+                    ss[r][c] += (u32)__popc(nav[r] & ~nonzero_bytes(av[r] ^ bv[c]));   // equal bytes that are not '-' (then neither is the other)
+                }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32 x = I * PHY_TILE + ty * 4u + (u32)r, y = J * PHY_TILE + tx * 4u + (u32)c;
+            if (x >= T || y >= T) continue;
+            if (cs[r][c]) {
+                atomicAdd(cmp + (size_t)x * T + y, (ull)cs[r][c]);
+                if (I != J) atomicAdd(cmp + (size_t)y * T + x, (ull)cs[r][c]);
+            }
+            if (ss[r][c]) {
+                atomicAdd(same + (size_t)x * T + y, (ull)ss[r][c]);
+                if (I != J) atomicAdd(same + (size_t)y * T + x, (ull)ss[r][c]);
+            }
+        }
+}
+
+thread_local std::string g_phy_err;
+
+auto slots(so_phy_result* r) { return result_slots(&r->row, &r->matrix, &r->gaps, &r->keep, &r->cmp, &r->same); }
+
+}  // namespace
+
+extern "C" {
+
+const char* so_phy_last_error(void) { return g_phy_err.c_str(); }
+
+void so_phy_free(so_phy_result* r) {
+    if (r) release_slots(r, slots(r));
+}
+
+int so_phy_rows(int device, int64_t n, const int32_t* q, const int32_t* s, const double* score, int64_t n_pairs, const int32_t* pair_q, const int32_t* pair_s, int32_t flags,
+                so_phy_result* out) {
+    const std::string who = "so_phy_rows";
+    return guarded_call(g_phy_err, out, so_phy_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags != 0) throw SoError(who + ": flags is reserved and must be 0");
+        if (n < 0 || n_pairs < 0) throw SoError(who + ": bad arguments");
+        if (n >= (1ll << 31)) throw SoError(who + ": 2^31 rows and more are not supported (32-bit row numbers)");
+        if (n_pairs >= (1ll << 31)) throw SoError(who + ": 2^31 wanted pairs and more are not supported");
+        if (n > 0 && (!q || !s || !score)) throw SoError(who + ": a hit column is NULL");
+        if (n_pairs > 0 && (!pair_q || !pair_s)) throw SoError(who + ": a pair column is NULL");
+        for (i64 i = 0; i < n; ++i)
+            if (score[i] != score[i]) throw SoError(who + ": row " + std::to_string(i) + " has a NaN score");
+        std::vector<u64> key((size_t)n_pairs);
+        for (i64 p = 0; p < n_pairs; ++p) {
+            if (pair_q[p] < 0 || pair_s[p] < 0) throw SoError(who + ": wanted pair " + std::to_string(p) + " holds a negative name code");
+            key[(size_t)p] = ((u64)(u32)pair_q[p] << 32) | (u64)(u32)pair_s[p];
+        }
+        out->n_pairs = n_pairs;
+        check_device(who.c_str(), device);
+        out->row = host_array<int64_t>(who.c_str(), (size_t)n_pairs);
+        for (i64 p = 0; p < n_pairs; ++p) out->row[p] = -1;
+        if (n == 0 || n_pairs == 0) {   // nothing to launch
+            fill_empty_slots(slots(out));
+            return;
+        }
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        const u32 N = (u32)n, P = (u32)n_pairs;
+        DevBuf<int> d_q, d_s;
+        DevBuf<ull> d_score, d_pkey, d_skey, best;
+        DevBuf<u32> slot_of, first, d_row;
+        DevBuf<u8> sort_tmp;
+        static_assert(sizeof(ull) == sizeof(double) && sizeof(ull) == sizeof(u64), "scores travel as their bits");
+        upload(d_q, q, (size_t)n, st), upload(d_s, s, (size_t)n, st), upload(d_score, reinterpret_cast<const ull*>(score), (size_t)n, st);
+        upload(d_pkey, reinterpret_cast<const ull*>(key.data()), key.size(), st);
+        d_skey.ensure((size_t)P + 2), best.ensure((size_t)P + 2), first.ensure((size_t)P + 2), d_row.ensure((size_t)P + 2), slot_of.ensure((size_t)N + 2);
+        const size_t tb = sort_keys_u64_temp_bytes(P, 64);
+        sort_tmp.ensure(tb + 16);
+        sort_keys_u64(sort_tmp.p, tb, reinterpret_cast<const u64*>(d_pkey.p), reinterpret_cast<u64*>(d_skey.p), P, 0, 64, st);
+        HIP_CHECK(hipMemsetAsync(best.p, 0, (size_t)P * sizeof(ull), st));          // below every score's number
+        HIP_CHECK(hipMemsetAsync(first.p, 0xFF, (size_t)P * sizeof(u32), st));      // NONE32: no row
+        hipLaunchKernelGGL(k_phy_row_max, grid256(N), dim3(256), 0, st, N, d_q.p, d_s.p, d_score.p, d_skey.p, P, slot_of.p, best.p);
+        hipLaunchKernelGGL(k_phy_row_first, grid256(N), dim3(256), 0, st, N, d_score.p, slot_of.p, best.p, first.p);
+        hipLaunchKernelGGL(k_phy_row_out, grid256(P), dim3(256), 0, st, P, d_pkey.p, d_skey.p, first.p, d_row.p);
+        HIP_CHECK(hipGetLastError());
+        std::vector<u32> row((size_t)P);
+        call.fetch(row.data(), d_row.p, (size_t)P);
+        call.wait();
+        out->waits = call.waits;
+        for (size_t p = 0; p < (size_t)P; ++p) out->row[p] = row[p] == NONE32 ? -1 : (int64_t)row[p];
+        fill_empty_slots(slots(out));
+    });
+}
+
+int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t* col_off, int64_t n_tasks, const int32_t* fam, const int32_t* slot, const uint8_t* kind,
+                 const int64_t* res_off, const int32_t* res_len, const int32_t* qst, const int32_t* sst, const int64_t* run_off, const uint32_t* runs, int64_t n_runs,
+                 const uint8_t* residues, int64_t n_res, double gap_share, int32_t flags, so_phy_result* out) {
+    const std::string who = "so_phy_build";
+    return guarded_call(g_phy_err, out, so_phy_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: no matrix in the result)");
+        if (n_taxa < 0 || n_fam < 0 || n_tasks < 0 || n_runs < 0 || n_res < 0) throw SoError(who + ": bad arguments");
+        if (n_taxa == 0) throw SoError(who + ": no taxa (n_taxa is 0)");
+        if (n_fam == 0) throw SoError(who + ": no families (n_fam is 0)");
+        if (!(gap_share >= 0. && gap_share <= 1.)) throw SoError(who + ": the gap share must lie in [0, 1]");
+        if (n_taxa >= 46341) throw SoError(who + ": 46341 taxa and more (2^31 pairs) are not supported");
+        if (n_fam >= (1ll << 31) || n_tasks >= (1ll << 31)) throw SoError(who + ": 2^31 families or tasks and more are not supported");
+        if (!col_off) throw SoError(who + ": col_off is NULL");
+        if (n_tasks > 0 && (!fam || !slot || !kind || !res_off || !res_len || !qst || !sst || !run_off)) throw SoError(who + ": a task column is NULL");
+        if ((n_runs > 0 && !runs) || (n_res > 0 && !residues)) throw SoError(who + ": runs or residues is NULL");
+        if (col_off[0] != 0) throw SoError(who + ": inconsistent offsets: col_off does not start at 0");
+        for (i64 f = 0; f < n_fam; ++f) {
+            if (col_off[f + 1] < col_off[f]) throw SoError(who + ": inconsistent offsets: col_off falls at family " + std::to_string(f));
+            if (col_off[f + 1] > 0x7FFFFFFFll) throw SoError(who + ": more than 2^31 - 1 columns are not supported");
+        }
+        const i64 L64 = col_off[n_fam];
+        if (n_tasks > 0 && run_off[0] != 0) throw SoError(who + ": inconsistent offsets: run_off does not start at 0");
+        {
+            std::vector<u64> cell((size_t)n_tasks);
+            for (i64 t = 0; t < n_tasks; ++t) {
+                const std::string task = "task " + std::to_string(t);
+                if (fam[t] < 0 || fam[t] >= n_fam) throw SoError(who + ": " + task + " names a family outside 0 .. n_fam - 1");
+                if (slot[t] < 0 || slot[t] >= n_taxa) throw SoError(who + ": " + task + " names a slot outside 0 .. n_taxa - 1");
+                if (res_len[t] < 0 || res_off[t] < 0 || res_off[t] > n_res || (i64)res_len[t] > n_res - res_off[t])
+                    throw SoError(who + ": inconsistent offsets: the residues of " + task + " lie outside the residue blob");
+                if (run_off[t + 1] < run_off[t] || run_off[t + 1] > n_runs) throw SoError(who + ": inconsistent offsets: the runs of " + task + " lie outside the run array");
+                cell[(size_t)t] = (u64)fam[t] * (u64)n_taxa + (u64)slot[t];
+            }
+            if (n_tasks > 0 && run_off[n_tasks] != n_runs) throw SoError(who + ": inconsistent offsets: run_off does not end at n_runs");
+            std::sort(cell.begin(), cell.end());
+            const auto dup = std::adjacent_find(cell.begin(), cell.end());
+            if (dup != cell.end())
+                throw SoError(who + ": two tasks fill family " + std::to_string(*dup / (u64)n_taxa) + ", slot " + std::to_string(*dup % (u64)n_taxa));
+        }
+        const bool want_matrix = !(flags & 1);
+        const u32 T = (u32)n_taxa, L = (u32)L64, NT = (u32)n_tasks;
+        const size_t cells = (size_t)T * L, TT = (size_t)T * T;
+        out->n_taxa = n_taxa, out->n_cols = L64;
+        check_device(who.c_str(), device);
+        const char* w = who.c_str();
+        if (L == 0) {   // families without a column: nothing to launch (a task then has an anchor of length 0: only empty tasks pass)
+            for (i64 t = 0; t < n_tasks; ++t)
+                if (kind[t] ? res_len[t] != 0 : (run_off[t + 1] != run_off[t] || qst[t] != 1 || sst[t] < 1 || sst[t] - 1 > res_len[t]))
+                    throw SoError(who + ": task " + std::to_string(t) + " (family " + std::to_string(fam[t]) + ", slot " + std::to_string(slot[t]) + ") runs past its anchor");
+            out->cmp = host_array<int64_t>(w, TT), out->same = host_array<int64_t>(w, TT);
+            memset(out->cmp, 0, TT * 8), memset(out->same, 0, TT * 8);
+            fill_empty_slots(slots(out));
+            return;
+        }
+        const u32 gmax = (u32)std::floor(gap_share * (double)T);   // (as Python evaluates floor(g * T): one IEEE product)
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<int> d_fam, d_slot, d_rlen, d_qst, d_sst, d_gaps, d_keep;
+        DevBuf<u8> d_kind, d_res, matrix, kept;
+        DevBuf<i64> d_roff, d_runoff, d_coloff;
+        DevBuf<u32> d_runs, err, flag, pos, scan_tmp;
+        DevBuf<ull> d_cmp, d_same;
+        upload(d_coloff, col_off, (size_t)n_fam + 1, st);
+        if (NT) {
+            upload(d_fam, fam, NT, st), upload(d_slot, slot, NT, st), upload(d_kind, kind, NT, st), upload(d_roff, res_off, NT, st), upload(d_rlen, res_len, NT, st);
+            upload(d_qst, qst, NT, st), upload(d_sst, sst, NT, st), upload(d_runoff, run_off, (size_t)NT + 1, st);
+        }
+        upload(d_runs, runs, (size_t)n_runs, st), upload(d_res, residues, (size_t)n_res, st);
+        const u32 Lp = (L + 15u) & ~15u, Lpw = Lp / 4u;   // (L <= 2^31 - 1: Lp <= 2^31)
+        matrix.ensure(cells + 16), kept.ensure((size_t)T * Lp + 16), d_gaps.ensure((size_t)L + 2), d_keep.ensure((size_t)L + 2), flag.ensure((size_t)L + 2), pos.ensure((size_t)L + 2);
+        scan_tmp.ensure(scan_u32_temp_elems(L) + 2), err.ensure(4), d_cmp.ensure(TT + 2), d_same.ensure(TT + 2);
+        HIP_CHECK(hipMemsetAsync(matrix.p, (int)PHY_DASH, cells, st));
+        HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(u32), st));
+        HIP_CHECK(hipMemsetAsync(err.p + 1, 0xFF, sizeof(u32), st));
+        HIP_CHECK(hipMemsetAsync(d_cmp.p, 0, TT * sizeof(ull), st));
+        HIP_CHECK(hipMemsetAsync(d_same.p, 0, TT * sizeof(ull), st));
+        if (NT) {
+            const PhyTasks tk = {d_fam.p, d_slot.p, d_rlen.p, d_qst.p, d_sst.p, d_kind.p, d_roff.p, d_runoff.p};
+            hipLaunchKernelGGL(k_phy_project, dim3((NT + 3u) / 4u), dim3(256), 0, st, NT, tk, d_runs.p, d_res.p, d_coloff.p, (u64)L, matrix.p, err.p);
+        }
+        hipLaunchKernelGGL(k_phy_gaps, grid256(L), dim3(256), 0, st, matrix.p, T, L, gmax, d_gaps.p, flag.p);
+        const u32* d_nk = scan_u32(flag.p, pos.p, L, false, scan_tmp.p, st);
+        hipLaunchKernelGGL(k_phy_keep, grid256(L), dim3(256), 0, st, flag.p, pos.p, L, d_keep.p);
+        hipLaunchKernelGGL(k_phy_gather, dim3((Lp + 255u) / 256u, T), dim3(256), 0, st, matrix.p, L, Lp, d_keep.p, d_nk, kept.p);
+        {
+            const u32 nt = (T + PHY_TILE - 1u) / PHY_TILE, tiles = nt * (nt + 1u) / 2u;
+            const u32 chunks = (Lpw + PHY_CHUNK_WORDS - 1u) / PHY_CHUNK_WORDS;
+            const u32 want = std::min(chunks, std::max(1u, (PHY_TARGET_WGS + tiles - 1u) / tiles));
+            const u32 wps = ((chunks + want - 1u) / want) * PHY_CHUNK_WORDS;   // words per range: whole chunks
+            const u32 ranges = (Lpw + wps - 1u) / wps;
+            hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges), dim3(256), 0, st, reinterpret_cast<const u32*>(kept.p), T, Lpw, d_nk, nt, wps, d_cmp.p, d_same.p);
+        }
+        HIP_CHECK(hipGetLastError());
+        u32 e[2] = {0, 0}, nk = 0;
+        call.fetch(e, err.p, 2), call.fetch(&nk, d_nk);
+        if (want_matrix) out->matrix = host_copy(w, matrix.p, cells, st);
+        out->gaps = host_copy(w, d_gaps.p, (size_t)L, st);
+        out->keep = host_copy(w, d_keep.p, (size_t)L, st);   // (the first n_keep entries are written)
+        static_assert(sizeof(ull) == sizeof(int64_t), "the counters are copied out as int64");
+        out->cmp = (int64_t*)host_copy(w, d_cmp.p, TT, st);
+        out->same = (int64_t*)host_copy(w, d_same.p, TT, st);
+        call.wait();
+        out->waits = call.waits;
+        if (e[0]) {
+            const u32 t = e[1];
+            const std::string task = "task " + std::to_string(t) + " (family " + std::to_string(fam[t]) + ", slot " + std::to_string(slot[t]) + ")";
+            if (kind[t]) throw SoError(who + ": " + task + " is the anchor, and its residues are not as many as the family's columns");
+            if (qst[t] < 1 || sst[t] < 1) throw SoError(who + ": " + task + " starts before the first residue (qst or sst < 1)");
+            throw SoError(who + ": " + task + " has a run of length 0 or of an unknown operation, or its runs lead past the anchor or past the member");
+        }
+        out->n_keep = nk;
+        fill_empty_slots(slots(out));
+    });
+}
+
+}  // extern "C"

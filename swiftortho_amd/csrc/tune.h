@@ -98,6 +98,14 @@ static inline int orth_tier_of(const char* v) {
 // (u64 key, u32 payload) for input and output each, so 2^28 expansions are about 6 GB of keys, payloads and sort scratch ----
 #define OPERON_EXPAND_DEFAULT (1ull << 28)
 
+// ---- supermatrix and pair counts (phy.hip): the tile of k_phy_pairs.  64 x 64 taxon pairs per workgroup, a 4 x 4 block per lane; a chunk
+// of 32 words (128 kept columns) of both row sets and their non-gap masks is 32 KiB of LDS, five workgroups to a CU.  The LDS image is
+// [word][row]: a lane's four rows are one 16-byte read, the 16 lanes of a row group read 256 consecutive bytes (no bank is asked twice)
+// and the four row groups of the other side read one address each (a broadcast) ----
+#define PHY_TILE 64u
+#define PHY_CHUNK_WORDS 32u
+#define PHY_TARGET_WGS 1024u   // the kept columns are cut into ranges until about this many workgroups exist (each flushes its counts once)
+
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;
 #define X_I(f, d) long long f = (d);

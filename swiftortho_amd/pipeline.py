@@ -255,3 +255,47 @@ def pan_genome_from_search(fasta_path, ts=.05, tc=.95, taxa=None, pan_device=Tru
     res = pan.pan_genome(table, len(taxa), ts, tc, device_stage=pan_device, want_counts=False, device=groups_from_search_kw.get('device', 0))
     t['pan'] = time.time() - t0
     return list(taxa), res.types, res.totals, (res.core, res.spec, res.panz), t
+
+
+def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', **search_kw):
+    """one process from a FASTA file to the species tree of its taxa: self-search on the GPU with a CIGAR on every row, the core-gene
+    table of `reference` (default: the taxon with most genes), the core-gene supermatrix from the rows' own alignments (swiftortho_amd.phy:
+    no aligner runs), the distances over its kept columns (`gap_share`, `model` 'p' or 'poisson') and neighbour joining -- what
+    `bin/find_hit.py -C T ... && scripts/rbh2phy.py -A T -t x.nwk` write.  device_stage: the table, the picked rows, the matrix and the
+    pair counts on the GPU (so_rbh_cols, so_phy_rows, so_phy_build), else by the numpy definitions; the records and the CIGARs are the host
+    copies either way.
+    -> (Newick bytes, phy.Supermatrix, dict of stage wall times in seconds: load, search, rbh, supermatrix, tree, and the counts rows,
+    families, columns, kept)"""
+    from . import find_orth, fsearch, phy, rbh
+    t = {}
+    t0 = time.time()
+    full = open(fasta_path, 'rb').read()
+    ids = find_orth.fasta_ids(full)
+    s = fsearch.Searcher(device=device, **search_kw)
+    try:
+        s.load_ref_bytes(full)
+        s.load_queries_bytes(full)
+        t['load'] = time.time() - t0
+        t0 = time.time()
+        hits = s.search(cigar=True)
+        try:
+            rec = hits.array()
+            t['search'] = time.time() - t0
+            t0 = time.time()
+            cols = find_orth.columns_from_records(rec, ids, ids)
+            table = rbh.device_core_table(cols, full, reference, sep, device) if device_stage else rbh.core_table(cols, full, reference, sep)
+            t['rbh'] = time.time() - t0
+            t0 = time.time()
+            ops, off = hits.cigar_buffer()
+            rows = phy.RecordRows(cols, rec['qst'], rec['sst'], ops, off)
+            sm = phy.supermatrix(cols.names, table, rbh.fasta_records(full), rows, gap_share, device_stage, device=device)
+            t['supermatrix'] = time.time() - t0
+        finally:
+            hits.close()
+    finally:
+        s.close()
+    t0 = time.time()
+    newick = phy.tree(sm, model)
+    t['tree'] = time.time() - t0
+    t['rows'], t['families'], t['columns'], t['kept'] = len(rec), len(sm.col_off) - 1, len(sm.gaps), len(sm.keep)
+    return newick, sm, t

@@ -378,17 +378,35 @@ def main_rbh2phy(argv=None):
     import os
     from .fsearch import parse_flags
     argv = list(sys.argv if argv is None else argv)
-    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': ''})
+    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p'})
     if args['-i'] == '' or args['-f'] == '':
-        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv]')
+        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson]]')
         print(' -i: blast -m8 or find_hit .sc file; ids are taxon|gene\n -f: the FASTA file the search read\n -r: reference taxon (default: the taxon with most genes)')
         print(' -G: the winner list and the table on the GPU [T|F]. Default: F\n -o: also write one tab-separated line of ids per group')
+        print(' -A: join the families into the core-gene supermatrix from the CIGARs of the rows (find_hit.py -C T) and print it as FASTA [T|F]. Default: F')
+        print(' -g: with -A T, keep the columns whose share of gaps is at most this. Default: 1 (every column)')
+        print(' -t: with -A T, write the neighbour-joining tree of the taxa to this file\n -m: distance of the tree [p|poisson]. Default: p')
         raise SystemExit()
     with open(args['-i'], 'rb') as f:
-        cols = find_orth.columns_from_text(f.read())
+        sc = f.read()
+    cols = find_orth.columns_from_text(sc)
     with open(args['-f'], 'rb') as f:
         fasta = f.read()
     table = device_core_table(cols, fasta, args['-r']) if _gpu_flag(args['-G']) else core_table(cols, fasta, args['-r'])
+    if _gpu_flag(args['-A']):
+        from . import phy
+        try:
+            share = float(args['-g'])
+            sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']))
+        except phy.MissingCigar as e:
+            sys.stderr.write('rbh2phy: %s\n' % e)
+            return 2
+        except ValueError as e:
+            sys.stderr.write('rbh2phy: %s\n' % e)
+            return 1
+        sys.stderr.write('rbh2phy: %d core families of reference taxon %s joined into %d columns (%d kept) for %d taxa\n'
+                         % (len(sm.col_off) - 1, table.reference.decode('utf-8', 'replace'), len(sm.gaps), len(sm.keep), len(sm.taxa)))
+        return 0
     groups = core_groups(cols.names, table)
     recs = fasta_records(fasta)
     d = '%s_alns_tmp' % args['-i']
