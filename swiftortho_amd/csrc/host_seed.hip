@@ -743,6 +743,11 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     u32 *c_qp = nullptr, *c_recp = nullptr;
     u32 NS = 0, maxseg = 0xFFFFFFFFu;  // candidates of the pass; the longest per-query segment (sparse path only)
     int cand_idx_bits = 0, cand_ftw = 0;   // > 0: k_bkt_best wrote sort words (first-touch word << idx_bits | position in the query's segment)
+    // (tests: which candidate-order path the pass took -- every pass that leaves candidates counts under exactly one of the keys, the
+    // per-query flow's redo on top of the path that redid it; tools/diag/README.md)
+    auto took = [&](const char* path) {
+        if (c->profile) c->tm[std::string("group.order_") + path + "_launches"] += 1;
+    };
     for (;;) {
         // contiguous pass list; the group counters and the pass total come back in one synchronisation
         u32* shard_off = b.shard.p + UG_SHARDS;
@@ -837,6 +842,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
                     launch_q_emit(b.bcnt.p, qa, nqp, NP, b.pidx2.p, qcnt, b.bccnt.p, b.order2.p, b.c_rec.p, b.cand_q.p + base, b.cand_rec.p + 4 * (size_t)base, c->st);
                     b.chunk_base.back() = base + NS;
                     c->cnt.candidates += NS;
+                    took("per_query");
                 }
                 sc.lap("group.best_order");
                 c->cnt.seed_ms += (t1 - t0) * 1e3;
@@ -845,6 +851,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
             }
             // (a query above the LDS instance: k_q_best has written counts for the others -- the path below writes every query's again)
             NS = 0;
+            took("per_query_redo");
         }
         // best diagonal per (query, subject): sort pass records by (q, subject)
         b.pidx.ensure((size_t)NP + 2), b.pidx2.ensure((size_t)NP + 2), b.p_qs2.ensure((size_t)NP + 2);
@@ -880,6 +887,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         b.cand_q.ensure((size_t)base + NS + 4, true, c->st);
         b.cand_rec.ensure(4 * ((size_t)base + NS) + 16, true, c->st);
         launch_cand_order_lds(c_ftp, c_recp, b.qseg.p, qa, qb, maxseg, bsp, b.cand_q.p + base, b.cand_rec.p + 4 * (size_t)base, qcnt, c->st);
+        took(maxseg <= 256 ? "lds256" : "lds2048");   // (launch_cand_order_lds's choice)
         b.chunk_base.back() = base + NS;
         c->cnt.candidates += NS;
         sc.lap("group.best_order");
@@ -898,7 +906,9 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
         HIP_CHECK(hipMemsetAsync(b.bflag.p, 0, sizeof(u32), c->st));
         launch_cand_order_seg(c_ftp, b.qseg.p, bL.nqp, bL.qa, cand_idx_bits, cand_idx_bits + cand_ftw, c_recp, b.cand_q.p + base, b.cand_rec.p + 4 * (size_t)base,
                               qcnt, b.bflag.p, c->st);
-        if (d2h_u32(c, b.bflag.p) != 0) {   // a digit group above the LDS sort (never seen): the library's segmented radix sort redoes the pass's order
+        const bool resort = d2h_u32(c, b.bflag.p) != 0;
+        took(resort ? "bucket_seg_resort" : "bucket_seg");
+        if (resort) {   // a digit group above the LDS sort (tests/cand_order_inputs.py builds one): the library's segmented radix sort redoes the pass's order
             ensure_sort_tmp(c, sort_cand_keys_seg_temp_bytes(NS, bL.nqp, cand_idx_bits, cand_idx_bits + cand_ftw));
             sort_cand_keys_seg(c->d_sort_tmp.p, c->d_sort_tmp.cap, c_ftp, b.tmp64.p, NS, bL.nqp, b.qseg.p, cand_idx_bits, cand_idx_bits + cand_ftw, c->st);
             launch_emit_cands_seg(b.tmp64.p, b.qseg.p, bL.nqp, bL.qa, cand_idx_bits, c_recp, b.cand_q.p + base, b.cand_rec.p + 4 * (size_t)base, qcnt, c->st);
@@ -935,6 +945,7 @@ void seed_pass(so_ctx* c, Batch& b, int ci, u32 qa, u32 qb, double t0, StageCloc
     b.cand_rec.ensure(4 * ((size_t)base + NS) + 16, true, c->st);
     b.segfirst.ensure((size_t)b.nq + 4);
     launch_emit_cands(b.order.p, NS, b.c_ft2.p, qshift, c_recp, b.cand_q.p + base, b.cand_rec.p + 4 * (size_t)base, qcnt, b.segfirst.p, c->st);
+    took(bbest ? "bucket_sort" : ftbits + kl.bq <= 64 ? "sort1" : "sort2");
     b.chunk_base.back() = base + NS;
     c->cnt.candidates += NS;
     sc.lap("group.best_order");  // (synchronises when profiling; otherwise the next pass is queued behind this one)

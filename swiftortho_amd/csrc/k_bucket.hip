@@ -963,8 +963,8 @@ __global__ __launch_bounds__(256) void k_emit_cands_seg(const u64* __restrict__ 
 // CO_DBITS bits (count, scan, scatter: the words land grouped by that digit), then every word finds its rank inside its digit's group
 // by comparing with the group's other words (neighbouring threads read the same LDS words: broadcasts) -- digit group start + rank is
 // the candidate's final place, and its record is copied there at once.  A query with more than CO_CAP candidates in one chunk is done
-// in sub-passes over ranges of the digit; a single digit group above CO_CAP words (never seen: the frequency cap bounds the hits of one
-// query position) raises `fallback` and the host orders the pass with the library sort.
+// in sub-passes over ranges of the digit; a single digit group above CO_CAP words (never seen in a proteome: the frequency cap bounds the
+// hits of one query position; tests/cand_order_inputs.py builds one) raises `fallback` and the host orders the pass with the library sort.
 // Before: segmented library radix sort 1.76 ms + gather kernel 1.32 ms per 928 M-hit pass; this kernel: see DESIGN.md.
 #define CO_THREADS 1024
 #define CO_CAP 16384
