@@ -641,6 +641,42 @@ int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t *col_o
 void so_phy_free(so_phy_result *result);
 const char *so_phy_last_error(void);
 
+/* Bootstrap support for the neighbour-joining tree over the kept columns of a supermatrix, on the device (csrc/phy.hip): what
+ * swiftortho_amd/phy.py `boot_columns()`, `boot_counts()`, `nj_splits()`, `split_support()` and `bootstrap()` define, array for array
+ * (integers and bit sets; the float64 walk of nj_splits is the same sequence of IEEE operations).
+ * matrix: n_taxa rows of n_cols bytes (host); keep: n_keep columns in 0 .. n_cols - 1; replicate b draws n_keep of them with replacement:
+ *   draw k = ((z >> 32) * n_keep) >> 32 with z = splitmix64's output for the counter (b << 32) + k + 1 added to `seed`.
+ * so_phy_boot_counts: cmp, same [n_reps][n_taxa][n_taxa] of the replicates b0 .. b0 + n_reps - 1 (the pair counts of so_phy_build over
+ *   the drawn columns).  flags must be 0.
+ * so_phy_nj_splits: D [n_reps][n_taxa][n_taxa] float64 (host), each finite and symmetric bit for bit -> splits [n_reps][n_taxa - 3][n_words],
+ *   n_words = ceil(n_taxa / 64): the clade every join of the neighbour-joining walk makes (bit t = taxon t), complemented inside n_taxa
+ *   bits where it holds taxon 0, in join order.  Row sums run left to right over the live nodes in ascending order; Q = ((n - 2) * D[i][j] -
+ *   r[i]) - r[j], the minimum over i < j with ties to the lowest (i, j); the new row is ((D[i] + D[j]) - D[i][j]) / 2 at position i.
+ *   A workgroup per matrix.  n_taxa < 4: no splits.  flags bit 0 (tests): the clade bit sets in global scratch whatever n_taxa.
+ * so_phy_boot: the fused path of the p distance -- per replicate the counts, D = 1 - same / cmp, the walk and the comparison with the
+ *   n_taxa - 3 splits of the printed tree (ref_splits, the same form) stay in device memory.  ok[b] = 0: a pair of replicate b shares no
+ *   compared column, the replicate is dropped; valid = the others; count[s] = the valid replicates whose tree holds ref split s.
+ *   flags bit 0: splits [n_reps][n_taxa - 3][n_words] of every replicate come back too (zeros for a dropped one); bit 1: events around the
+ *   stages of every batch -- counts_ms (columns, pair counts, distances), trees_ms, support_ms.  Replicates run in
+ *   batches sized from the free device memory (SOHIT_PHY_BOOT_BATCH forces the size), one host wait per batch: waits == batches.
+ * Refused with a message (so_phy_last_error) and nothing left allocated: n_taxa below 2 or above 4096, n_keep of 0, n_reps below 1 or
+ * b0 + n_reps above 2^31, a keep entry outside 0 .. n_cols - 1, a D that is not finite or not symmetric, unknown flag bits. */
+typedef struct so_phy_boot_result {
+    int64_t n_taxa, n_reps, n_splits, n_words, valid;
+    int32_t waits, batches;
+    double counts_ms, trees_ms, support_ms;   /* so_phy_boot with flags bit 1: device time of the three stages, summed over the batches */
+    int64_t *cmp, *same;          /* so_phy_boot_counts: n_reps * n_taxa * n_taxa */
+    uint64_t *splits;             /* so_phy_nj_splits, so_phy_boot with flags bit 0: n_reps * n_splits * n_words */
+    int32_t *count;               /* so_phy_boot: n_splits */
+    uint8_t *ok;                  /* so_phy_boot: n_reps */
+} so_phy_boot_result;
+int so_phy_boot_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, uint64_t seed,
+                       int64_t b0, int64_t n_reps, int32_t flags, so_phy_boot_result *out);
+int so_phy_nj_splits(int device, int64_t n_reps, int64_t n_taxa, const double *D, int32_t flags, so_phy_boot_result *out);
+int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, uint64_t seed,
+                int64_t n_reps, const uint64_t *ref_splits, int32_t flags, so_phy_boot_result *out);
+void so_phy_boot_free(so_phy_boot_result *result);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

@@ -12,7 +12,9 @@ The species-tree step runs on request as well: `-t T` (default `F`) leaves <name
 FASTA, taxa in slot order), <name>.aln.trim (the columns whose share of gaps is at most `-g`, default 1: the same file) and <name>.nwk
 (neighbour joining over the `-m p|poisson` distances).  The reference shells out to famsa, trimal and fasttree here; this step aligns
 nothing: it joins the families along the alignments the search itself made (swiftortho_amd/phy.py), in one process that searches the
-proteome once more with a CIGAR on every row; with `-G T` the matrix and the pair counts are built on the GPU.
+proteome once more with a CIGAR on every row; with `-G T` the matrix and the pair counts are built on the GPU.  `-B n` (default 0: the
+bare tree) labels the tree's nodes with their bootstrap support over n replicates of the kept columns, drawn from the seed `-S` (default 1)
+-- what the reference gets from `fasttree -boot`; with `-G T` the replicates run on the GPU.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
 (<name>.xyz, three columns), THAT file is clustered, and the numbers are mapped back into <name>.clsr (the .grp file in between is
@@ -37,11 +39,14 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-t': 'F', '-g': '1', '-m': 'p'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1'}
 
 
 def main(argv):
     a = parse_flags(argv, ARGS)
+    if not (a['-B'].isdigit() and a['-S'].isdigit() and int(a['-B']) < 2 ** 31 and int(a['-S']) < 2 ** 64):
+        sys.stderr.write('run_all_fast: -B takes a whole number of replicates from 0 to 2^31 - 1, -S a seed from 0 to 2^64 - 1\n')
+        return 2
     if a['-i'] == '':
         print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon]' % argv[0])
         raise SystemExit()
@@ -99,7 +104,7 @@ def main(argv):
         t = time()
         from swiftortho_amd import phy, pipeline
         newick, sm, _ = pipeline.species_tree_from_search(fas, reference=a['-r'], gap_share=float(a['-g']), model=a['-m'],
-                                                          device_stage=a['-G'].upper()[:1] == 'T', **nr.collapsed_search_kw(a['-s'], a['-v']))
+                                                          device_stage=a['-G'].upper()[:1] == 'T', boot=int(a['-B']), boot_seed=int(a['-S']), **nr.collapsed_search_kw(a['-s'], a['-v']))
         aln = '%s_results/%s.aln' % (fas, name)
         with open(aln, 'wb') as o:
             o.write(phy.supermatrix_fasta(sm.taxa, sm.matrix, range(sm.matrix.shape[1])))

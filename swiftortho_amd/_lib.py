@@ -57,7 +57,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error",
-           "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error"]
+           "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
+           "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free"]
 
 
 class SoMclResult(C.Structure):
@@ -128,6 +129,13 @@ class SoPhyResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_pairs", "n_taxa", "n_cols", "n_keep")] + \
                [("waits", C.c_int32), ("reserved", C.c_int32), ("row", C.POINTER(C.c_int64)), ("matrix", C.POINTER(C.c_uint8)),
                 ("gaps", C.POINTER(C.c_int32)), ("keep", C.POINTER(C.c_int32)), ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64))]
+
+
+class SoPhyBootResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_reps", "n_splits", "n_words", "valid")] + \
+               [("waits", C.c_int32), ("batches", C.c_int32), ("counts_ms", C.c_double), ("trees_ms", C.c_double), ("support_ms", C.c_double),
+                ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64)),
+                ("splits", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)), ("ok", C.POINTER(C.c_uint8))]
 
 
 _lib = None
@@ -285,6 +293,10 @@ def load():
     L.so_phy_build.argtypes = [C.c_int, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, C.c_double, C.c_int32, C.POINTER(SoPhyResult)]
     L.so_phy_free.argtypes = [C.POINTER(SoPhyResult)]
     L.so_phy_last_error.restype = cp
+    L.so_phy_boot_counts.argtypes = [C.c_int, i64, i64, vp, i64, vp, C.c_uint64, i64, i64, C.c_int32, C.POINTER(SoPhyBootResult)]
+    L.so_phy_nj_splits.argtypes = [C.c_int, i64, i64, vp, C.c_int32, C.POINTER(SoPhyBootResult)]
+    L.so_phy_boot.argtypes = [C.c_int, i64, i64, vp, i64, vp, C.c_uint64, i64, vp, C.c_int32, C.POINTER(SoPhyBootResult)]
+    L.so_phy_boot_free.argtypes = [C.POINTER(SoPhyBootResult)]
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

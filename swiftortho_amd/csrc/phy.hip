@@ -18,6 +18,19 @@
 //                                 non-zero where ((x & 0x7f7f7f7f) + 0x7f7f7f7f | x) has its top bit; counts in registers, one flush per
 //                                 workgroup with 64-bit integer atomics.  Only tiles I <= J are walked; the flush writes both halves.
 // One host wait per call (DeviceCall, device_call.h), counted.
+//
+// Bootstrap support of the neighbour-joining tree (phy.py boot_columns, boot_counts, nj_splits, split_support, bootstrap):
+//   so_phy_boot_counts  k_phy_boot_gather  a lane per drawn column: the draw is splitmix64 of (replicate, column) in 64-bit integers, scaled by
+//                                          a multiply and a shift; the replicate's columns side by side, padded as k_phy_gather pads;
+//                       k_phy_pairs        the same tiles, the replicates of a batch along the grid's third dimension.
+//   so_phy_nj_splits    k_phy_nj           a workgroup per matrix.  D stays in global memory; the live list, the row sums and the clade bit
+//                                          sets are LDS (the bit sets move to global scratch beyond 640 taxa).  A row sum runs left to right
+//                                          over the live nodes -- the one order a lane can reproduce --, the minimum of (Q, i, j) is a
+//                                          lexicographic reduction, the new row is written on both sides of the diagonal.  Plain IEEE
+//                                          doubles, nothing fused: the splits equal numpy's bit for bit.
+//   so_phy_boot         the fused path of the p distance: gather, pairs, k_phy_boot_dist (D = 1 - same / cmp; a pair without a compared
+//                       column drops the replicate), k_phy_nj, k_phy_boot_support (a lane per split of the printed tree).  Batches of
+//                       replicates sized from the free device memory (SOHIT_PHY_BOOT_BATCH), one host wait per batch.
 #include "hit_table.h"
 
 #include <algorithm>
@@ -183,8 +196,10 @@ __device__ __forceinline__ u32 nonzero_bytes(u32 x) { return (((x & 0x7F7F7F7Fu)
 
 // grid (nt * nt tiles of 64 x 64 pairs, ranges of `wps` words); K: T rows of Lpw words (Lpw a multiple of 4), '-' behind the kept columns.
 // lane (ty, tx) of the 16 x 16 holds rows I * 64 + ty * 4 + r against rows J * 64 + tx * 4 + c.
+// blockIdx.z: the replicate of a bootstrap batch -- its rows lie krep words, its counters orep elements behind the last one's (0, 0: one matrix).
 __global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u32 T, u32 Lpw, const u32* __restrict__ d_nk, u32 nt, u32 wps, ull* __restrict__ cmp,
-                                                   ull* __restrict__ same) {
+                                                   ull* __restrict__ same, size_t krep, size_t orep) {
+    K += (size_t)blockIdx.z * krep, cmp += (size_t)blockIdx.z * orep, same += (size_t)blockIdx.z * orep;
     __shared__ __attribute__((aligned(16))) u32 sA[PHY_CHUNK_WORDS][PHY_TILE];
     __shared__ __attribute__((aligned(16))) u32 sNA[PHY_CHUNK_WORDS][PHY_TILE];
     __shared__ __attribute__((aligned(16))) u32 sB[PHY_CHUNK_WORDS][PHY_TILE];
@@ -250,9 +265,226 @@ __global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u3
         }
 }
 
+// the grid of k_phy_pairs over T taxa, rows of Lpw words and `reps` matrices: tiles per side, words per column range (whole chunks), ranges
+void pair_grid(u32 T, u32 Lpw, u32 reps, u32& nt, u32& wps, u32& ranges) {
+    nt = (T + PHY_TILE - 1u) / PHY_TILE;
+    const u64 tiles = (u64)(nt * (nt + 1u) / 2u) * reps;
+    const u32 chunks = (Lpw + PHY_CHUNK_WORDS - 1u) / PHY_CHUNK_WORDS;
+    const u32 want = std::min(chunks, std::max(1u, (u32)((PHY_TARGET_WGS + tiles - 1u) / tiles)));
+    wps = ((chunks + want - 1u) / want) * PHY_CHUNK_WORDS;
+    ranges = (Lpw + wps - 1u) / wps;
+}
+
+// ---- bootstrap: so_phy_boot_counts, so_phy_nj_splits, so_phy_boot -------------------------------------------------------------------------
+// draw k of replicate b from K columns: phy.py boot_columns(), in 64-bit integers that wrap
+__device__ __forceinline__ u32 boot_draw(ull seed, ull b, ull k, u32 K) {
+    ull z = seed + ((b << 32) + k + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (u32)(((z >> 32) * (ull)K) >> 32);   // < K: the left factor is below 2^32
+}
+
+// grid (columns of the padded row, groups of PHY_BOOT_TAXA taxa, replicates): replicate b0 + z's drawn columns side by side, '-' behind them
+// as k_phy_gather leaves them.  keep[] lies inside [0, L) (the host has checked), a draw inside [0, K).
+__global__ __launch_bounds__(256) void k_phy_boot_gather(const u8* __restrict__ matrix, u32 T, u32 L, u32 K, u32 Kp, const int* __restrict__ keep, ull seed, u32 b0,
+                                                         u8* __restrict__ out) {
+    const u32 j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= Kp) return;
+    const u32 t0 = blockIdx.y * PHY_BOOT_TAXA, t1 = min(T, t0 + PHY_BOOT_TAXA);
+    u8* dst = out + (size_t)blockIdx.z * T * Kp + j;
+    if (j >= K) {
+        for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = (u8)PHY_DASH;
+        return;
+    }
+    const u32 c = (u32)keep[boot_draw(seed, (ull)b0 + blockIdx.z, j, K)];
+    for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = matrix[(size_t)t * L + c];
+}
+
+// grid (pairs, replicates): D = 1 - same / cmp in IEEE doubles, as numpy divides; a pair without a compared column clears the replicate's ok
+__global__ __launch_bounds__(256) void k_phy_boot_dist(const ull* __restrict__ cmp, const ull* __restrict__ same, u32 TT, double* __restrict__ D, u8* __restrict__ ok) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= TT) return;
+    const size_t at = (size_t)blockIdx.y * TT + i;
+    const ull c = cmp[at];
+    if (c == 0ull) ok[blockIdx.y] = 0;   // (every writer stores the same byte)
+    D[at] = 1. - (double)same[at] / (double)c;
+}
+
+__device__ __forceinline__ bool nj_before(double q, u32 a, u32 b, double q2, u32 a2, u32 b2) { return q < q2 || (q == q2 && (a < a2 || (a == a2 && b < b2))); }
+
+// phy.py nj_splits(): a workgroup per replicate, T >= 4.  D (the replicate's own T x T doubles, symmetric bit for bit, changed in place) stays
+// in global memory; the row sums r, the two live lists (positions -> original rows, ascending; u16: T <= 4096) and -- where `scratch` is
+// null -- the clade bit sets are LDS: r[T] | clade[T * W] | live[2][T].  Every index is a position below n <= T or an entry of the live
+// list, which only ever holds 0 .. T - 1; out is written at step * W + w with step < T - 3, w < W.
+// Plain IEEE + - * / on doubles in the order of the definition (the build passes -ffp-contract=off: nothing is fused).
+__global__ __launch_bounds__(PHY_NJ_THREADS) void k_phy_nj(double* Dall, u32 T, u32 W, const u8* __restrict__ ok, ull* __restrict__ splits, ull* scratch) {
+    extern __shared__ __attribute__((aligned(16))) u8 nj_lds[];
+    __shared__ double red_q[PHY_NJ_THREADS / 64u];
+    __shared__ u32 red_a[PHY_NJ_THREADS / 64u], red_b[PHY_NJ_THREADS / 64u], pick[2];
+    const u32 tid = threadIdx.x, S = T - 3u;
+    const size_t rep = blockIdx.x;
+    ull* out = splits + rep * S * W;
+    if (ok && !ok[rep]) {   // a dropped replicate: no tree (the whole workgroup)
+        for (u32 x = tid; x < S * W; x += PHY_NJ_THREADS) out[x] = 0ull;
+        return;
+    }
+    double* D = Dall + rep * T * T;
+    double* r = reinterpret_cast<double*>(nj_lds);
+    ull* clade = scratch ? scratch + rep * T * W : reinterpret_cast<ull*>(r + T);
+    unsigned short* live = reinterpret_cast<unsigned short*>(r + T + (scratch ? 0u : T * W));
+    unsigned short* next = live + T;
+    for (u32 k = tid; k < T; k += PHY_NJ_THREADS) live[k] = (unsigned short)k;
+    for (u32 x = tid; x < T * W; x += PHY_NJ_THREADS) {
+        const u32 t = x / W, w = x % W;
+        clade[x] = (t >> 6) == w ? 1ull << (t & 63u) : 0ull;
+    }
+    const ull last_mask = (T & 63u) ? (1ull << (T & 63u)) - 1ull : ~0ull;
+    __syncthreads();
+    u32 n = T;
+    for (u32 step = 0; step < S; ++step, --n) {
+        // r[a]: the row of position a summed left to right over the live nodes; D[k][i] for D[i][k]: the wave reads consecutive addresses
+        for (u32 a = tid; a < n; a += PHY_NJ_THREADS) {
+            const u32 i = live[a];
+            double s = 0.;
+            for (u32 b = 0; b < n; ++b) s = s + D[(size_t)live[b] * T + i];
+            r[a] = s;
+        }
+        __syncthreads();
+        // the smallest (Q, a, b) over a < b; a lane owns the columns b, so it meets its pairs in ascending (b, a) and compares in full
+        const double nm2 = (double)(n - 2u);
+        double bq = INFINITY;
+        u32 ba = 0u, bb = 1u;
+        for (u32 b = tid; b < n; b += PHY_NJ_THREADS) {
+            const u32 j = live[b];
+            const double rb = r[b];
+            for (u32 a = 0; a < b; ++a) {
+                const double q = (nm2 * D[(size_t)live[a] * T + j] - r[a]) - rb;
+                if (nj_before(q, a, b, bq, ba, bb)) bq = q, ba = a, bb = b;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const double q2 = __shfl_xor(bq, d, 64);
+            const u32 a2 = (u32)__shfl_xor((int)ba, d, 64), b2 = (u32)__shfl_xor((int)bb, d, 64);
+            if (nj_before(q2, a2, b2, bq, ba, bb)) bq = q2, ba = a2, bb = b2;
+        }
+        if ((tid & 63u) == 0u) red_q[tid >> 6] = bq, red_a[tid >> 6] = ba, red_b[tid >> 6] = bb;
+        __syncthreads();
+        if (tid == 0u) {
+            for (u32 v = 1; v < PHY_NJ_THREADS / 64u; ++v)
+                if (nj_before(red_q[v], red_a[v], red_b[v], bq, ba, bb)) bq = red_q[v], ba = red_a[v], bb = red_b[v];
+            pick[0] = ba, pick[1] = bb;
+        }
+        __syncthreads();
+        const u32 pa = pick[0], pb = pick[1];   // pa < pb < n
+        const u32 I = live[pa], J = live[pb];
+        const double dij = D[(size_t)I * T + J];
+        // the new node's row at position pa: a lane owns the columns k, reads rows I and J there and writes (I, k) and (k, I); nobody
+        // writes row J or (I, J)
+        for (u32 c = tid; c < n; c += PHY_NJ_THREADS) {
+            const u32 k = live[c];
+            if (k == J) continue;
+            if (k == I) {
+                D[(size_t)I * T + I] = 0.;
+                continue;
+            }
+            const double v = ((D[(size_t)I * T + k] + D[(size_t)J * T + k]) - dij) / 2.;
+            D[(size_t)I * T + k] = v, D[(size_t)k * T + I] = v;
+        }
+        // the clades: position 0 is never removed and every join keeps the lower position, so taxon 0 sits in row 0's clade and nowhere else
+        for (u32 w = tid; w < W; w += PHY_NJ_THREADS) {
+            const ull c = clade[(size_t)I * W + w] | clade[(size_t)J * W + w];
+            clade[(size_t)I * W + w] = c;
+            out[(size_t)step * W + w] = I == 0u ? ~c & (w == W - 1u ? last_mask : ~0ull) : c;
+        }
+        for (u32 c = tid; c + 1u < n; c += PHY_NJ_THREADS) next[c] = c < pb ? live[c] : live[c + 1u];
+        __syncthreads();
+        unsigned short* t = live;
+        live = next, next = t;
+    }
+}
+
+// grid (splits of the printed tree, replicates): does the replicate's tree hold the split?  (its T - 3 splits are distinct: one per inner edge)
+__global__ __launch_bounds__(256) void k_phy_boot_support(const ull* __restrict__ ref, const ull* __restrict__ splits, u32 S, u32 W, const u8* __restrict__ ok,
+                                                          u32* __restrict__ count) {
+    const u32 s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= S || !ok[blockIdx.y]) return;
+    const ull* rep = splits + (size_t)blockIdx.y * S * W;
+    const ull* want = ref + (size_t)s * W;
+    bool found = false;
+    for (u32 x = 0; x < S && !found; ++x) {
+        bool eq = true;
+        for (u32 w = 0; w < W && eq; ++w) eq = rep[(size_t)x * W + w] == want[w];
+        found = eq;
+    }
+    if (found) atomicAdd(count + s, 1u);
+}
+
 thread_local std::string g_phy_err;
 
 auto slots(so_phy_result* r) { return result_slots(&r->row, &r->matrix, &r->gaps, &r->keep, &r->cmp, &r->same); }
+auto slots(so_phy_boot_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->count, &r->ok); }
+
+// four marks around the three stages of a batch (flags bit 1 of so_phy_boot): recorded on the stream, read after the batch's wait
+struct StageEvents {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit StageEvents(bool on) {
+        if (on)
+            for (hipEvent_t& x : e) HIP_CHECK(hipEventCreate(&x));
+    }
+    ~StageEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    StageEvents(const StageEvents&) = delete;
+    StageEvents& operator=(const StageEvents&) = delete;
+    void mark(int k, hipStream_t st) {
+        if (e[k]) HIP_CHECK(hipEventRecord(e[k], st));
+    }
+    double ms(int k) {   // between mark k and mark k + 1, both reached: the stream has been waited for
+        float v = 0.f;
+        if (e[k]) HIP_CHECK(hipEventElapsedTime(&v, e[k], e[k + 1]));
+        return v;
+    }
+};
+
+// what the two calls that draw columns check before anything touches the device -> keep as the 32-bit columns the kernels read
+std::vector<int> boot_check(const std::string& who, i64 n_taxa, i64 n_cols, const u8* matrix, i64 n_keep, const i64* keep, i64 b0, i64 n_reps) {
+    if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+    if (n_cols < 0 || n_cols > 0x7FFFFFFFll) throw SoError(who + ": more than 2^31 - 1 columns are not supported");
+    if (n_keep <= 0) throw SoError(who + ": no kept column to draw from (n_keep is 0)");
+    if (n_keep > 0x7FFFFFFFll - 16) throw SoError(who + ": more than 2^31 - 17 kept columns are not supported");
+    if (n_reps < 1) throw SoError(who + ": a replicate at least (n_reps is " + std::to_string(n_reps) + ")");
+    if (b0 < 0 || b0 >= (1ll << 31) || n_reps >= (1ll << 31) || b0 + n_reps > (1ll << 31))
+        throw SoError(who + ": replicates beyond 2^31 - 1 are not supported");
+    if (!matrix || !keep) throw SoError(who + ": matrix or keep is NULL");
+    std::vector<int> k32((size_t)n_keep);
+    for (i64 k = 0; k < n_keep; ++k) {
+        if (keep[k] < 0 || keep[k] >= n_cols) throw SoError(who + ": keep[" + std::to_string(k) + "] lies outside 0 .. n_cols - 1");
+        k32[(size_t)k] = (int)keep[k];
+    }
+    return k32;
+}
+
+// one batch: the drawn columns of nb replicates from b0 on side by side, then their pair counts (cmp, same: nb * T * T, zeroed here)
+void boot_counts_batch(hipStream_t st, const u8* matrix, u32 T, u32 L, u32 K, const int* keep, const u32* d_K, ull seed, u32 b0, u32 nb, u8* cols, ull* cmp, ull* same) {
+    const u32 Kp = (K + 15u) & ~15u, Kpw = Kp / 4u;
+    const size_t TT = (size_t)T * T;
+    HIP_CHECK(hipMemsetAsync(cmp, 0, (size_t)nb * TT * sizeof(ull), st));
+    HIP_CHECK(hipMemsetAsync(same, 0, (size_t)nb * TT * sizeof(ull), st));
+    hipLaunchKernelGGL(k_phy_boot_gather, dim3((Kp + 255u) / 256u, (T + PHY_BOOT_TAXA - 1u) / PHY_BOOT_TAXA, nb), dim3(256), 0, st, matrix, T, L, K, Kp, keep, seed, b0, cols);
+    u32 nt, wps, ranges;
+    pair_grid(T, Kpw, nb, nt, wps, ranges);
+    hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges, nb), dim3(256), 0, st, reinterpret_cast<const u32*>(cols), T, Kpw, d_K, nt, wps, cmp, same, (size_t)T * Kpw, TT);
+}
+
+// the walk of nb matrices; clades: the scratch of the bit sets (nb * T * W words) or null where they fit the LDS
+size_t nj_lds_bytes(u32 T, u32 W, bool in_lds) { return (size_t)T * 8u + (in_lds ? (size_t)T * W * 8u : 0u) + (size_t)T * 4u; }
+bool nj_clades_fit(u32 T, u32 W) { return nj_lds_bytes(T, W, true) <= PHY_NJ_LDS_BYTES; }
+void nj_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, ull* splits, ull* clades) {
+    hipLaunchKernelGGL(k_phy_nj, dim3(nb), dim3(PHY_NJ_THREADS), nj_lds_bytes(T, W, clades == nullptr), st, D, T, W, ok, splits, clades);
+}
 
 }  // namespace
 
@@ -407,12 +639,10 @@ int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t* col_o
         hipLaunchKernelGGL(k_phy_keep, grid256(L), dim3(256), 0, st, flag.p, pos.p, L, d_keep.p);
         hipLaunchKernelGGL(k_phy_gather, dim3((Lp + 255u) / 256u, T), dim3(256), 0, st, matrix.p, L, Lp, d_keep.p, d_nk, kept.p);
         {
-            const u32 nt = (T + PHY_TILE - 1u) / PHY_TILE, tiles = nt * (nt + 1u) / 2u;
-            const u32 chunks = (Lpw + PHY_CHUNK_WORDS - 1u) / PHY_CHUNK_WORDS;
-            const u32 want = std::min(chunks, std::max(1u, (PHY_TARGET_WGS + tiles - 1u) / tiles));
-            const u32 wps = ((chunks + want - 1u) / want) * PHY_CHUNK_WORDS;   // words per range: whole chunks
-            const u32 ranges = (Lpw + wps - 1u) / wps;
-            hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges), dim3(256), 0, st, reinterpret_cast<const u32*>(kept.p), T, Lpw, d_nk, nt, wps, d_cmp.p, d_same.p);
+            u32 nt, wps, ranges;
+            pair_grid(T, Lpw, 1u, nt, wps, ranges);
+            hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges), dim3(256), 0, st, reinterpret_cast<const u32*>(kept.p), T, Lpw, d_nk, nt, wps, d_cmp.p, d_same.p, (size_t)0,
+                               (size_t)0);
         }
         HIP_CHECK(hipGetLastError());
         u32 e[2] = {0, 0}, nk = 0;
@@ -433,6 +663,160 @@ int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t* col_o
             throw SoError(who + ": " + task + " has a run of length 0 or of an unknown operation, or its runs lead past the anchor or past the member");
         }
         out->n_keep = nk;
+        fill_empty_slots(slots(out));
+    });
+}
+
+void so_phy_boot_free(so_phy_boot_result* r) {
+    if (r) release_slots(r, slots(r));
+}
+
+int so_phy_boot_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, uint64_t seed, int64_t b0, int64_t n_reps,
+                       int32_t flags, so_phy_boot_result* out) {
+    const std::string who = "so_phy_boot_counts";
+    return guarded_call(g_phy_err, out, so_phy_boot_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags != 0) throw SoError(who + ": flags is reserved and must be 0");
+        const std::vector<int> k32 = boot_check(who, n_taxa, n_cols, matrix, n_keep, keep, b0, n_reps);
+        if (n_reps > PHY_BOOT_MAX_BATCH) throw SoError(who + ": more than " + std::to_string(PHY_BOOT_MAX_BATCH) + " replicates in one call are not supported");
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, K = (u32)n_keep, nb = (u32)n_reps, Kp = (K + 15u) & ~15u;
+        const size_t TT = (size_t)T * T;
+        out->n_taxa = n_taxa, out->n_reps = n_reps;
+        check_device(who.c_str(), device);
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<u8> d_matrix, cols;
+        DevBuf<int> d_keep;
+        DevBuf<u32> d_K;
+        DevBuf<ull> d_cmp, d_same;
+        upload(d_matrix, matrix, (size_t)T * L, st), upload(d_keep, k32.data(), k32.size(), st), upload(d_K, &K, 1, st);
+        cols.ensure((size_t)nb * T * Kp + 16), d_cmp.ensure((size_t)nb * TT + 2), d_same.ensure((size_t)nb * TT + 2);
+        boot_counts_batch(st, d_matrix.p, T, L, K, d_keep.p, d_K.p, (ull)seed, (u32)b0, nb, cols.p, d_cmp.p, d_same.p);
+        HIP_CHECK(hipGetLastError());
+        out->cmp = (int64_t*)host_copy(who.c_str(), d_cmp.p, (size_t)nb * TT, st);
+        out->same = (int64_t*)host_copy(who.c_str(), d_same.p, (size_t)nb * TT, st);
+        call.wait();
+        out->waits = call.waits, out->batches = 1;
+        fill_empty_slots(slots(out));
+    });
+}
+
+int so_phy_nj_splits(int device, int64_t n_reps, int64_t n_taxa, const double* D, int32_t flags, so_phy_boot_result* out) {
+    const std::string who = "so_phy_nj_splits";
+    return guarded_call(g_phy_err, out, so_phy_boot_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: the clade bit sets in global scratch)");
+        if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+        if (n_reps < 1 || n_reps >= (1ll << 31)) throw SoError(who + ": the matrices number 1 .. 2^31 - 1 (n_reps is " + std::to_string(n_reps) + ")");
+        if (!D) throw SoError(who + ": D is NULL");
+        const u32 T = (u32)n_taxa, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
+        const size_t TT = (size_t)T * T;
+        for (i64 b = 0; b < n_reps; ++b) {
+            const double* M = D + (size_t)b * TT;
+            for (u32 i = 0; i < T; ++i)
+                for (u32 j = 0; j < T; ++j) {
+                    if (!std::isfinite(M[(size_t)i * T + j])) throw SoError(who + ": matrix " + std::to_string(b) + " holds a value that is not finite");
+                    if (j < i && memcmp(&M[(size_t)i * T + j], &M[(size_t)j * T + i], sizeof(double)) != 0)
+                        throw SoError(who + ": matrix " + std::to_string(b) + " is not symmetric bit for bit");
+                }
+        }
+        out->n_taxa = n_taxa, out->n_reps = n_reps, out->n_splits = S, out->n_words = W;
+        check_device(who.c_str(), device);
+        if (S == 0) {   // two or three taxa: one topology, no split
+            fill_empty_slots(slots(out));
+            return;
+        }
+        const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<double> d_D;
+        DevBuf<ull> d_splits, clades;
+        const size_t per_call = PHY_BOOT_MAX_BATCH;
+        out->splits = host_array<uint64_t>(who.c_str(), (size_t)n_reps * S * W);
+        static_assert(sizeof(ull) == sizeof(uint64_t), "the bit sets are copied out as uint64");
+        for (size_t b0 = 0; b0 < (size_t)n_reps; b0 += per_call) {
+            const u32 nb = (u32)std::min(per_call, (size_t)n_reps - b0);
+            upload(d_D, D + b0 * TT, (size_t)nb * TT, st);
+            d_splits.ensure((size_t)nb * S * W + 2);
+            if (!in_lds) clades.ensure((size_t)nb * T * W + 2);
+            nj_launch(st, d_D.p, T, W, nb, nullptr, d_splits.p, in_lds ? nullptr : clades.p);
+            HIP_CHECK(hipGetLastError());
+            call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * S * W, d_splits.p, (size_t)nb * S * W);
+            call.wait();
+            ++out->batches;
+        }
+        out->waits = call.waits;
+        fill_empty_slots(slots(out));
+    });
+}
+
+int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, uint64_t seed, int64_t n_reps,
+                const uint64_t* ref_splits, int32_t flags, so_phy_boot_result* out) {
+    const std::string who = "so_phy_boot";
+    return guarded_call(g_phy_err, out, so_phy_boot_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~3) throw SoError(who + ": unknown flag bits (bit 0: every replicate's splits in the result, bit 1: the stages timed by events)");
+        const std::vector<int> k32 = boot_check(who, n_taxa, n_cols, matrix, n_keep, keep, 0, n_reps);
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, K = (u32)n_keep, Kp = (K + 15u) & ~15u, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
+        if (S && !ref_splits) throw SoError(who + ": ref_splits is NULL");
+        const bool want_splits = flags & 1, timed = flags & 2;
+        const size_t TT = (size_t)T * T, B = (size_t)n_reps, SW = (size_t)S * W;
+        out->n_taxa = n_taxa, out->n_reps = n_reps, out->n_splits = S, out->n_words = W;
+        check_device(who.c_str(), device);
+        const char* w = who.c_str();
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<u8> d_matrix, cols, d_ok;
+        DevBuf<int> d_keep;
+        DevBuf<u32> d_K, d_count;
+        DevBuf<ull> d_cmp, d_same, d_ref, d_splits, clades;
+        DevBuf<double> d_D;
+        upload(d_matrix, matrix, (size_t)T * L, st), upload(d_keep, k32.data(), k32.size(), st), upload(d_K, &K, 1, st);
+        if (S) upload(d_ref, reinterpret_cast<const ull*>(ref_splits), SW, st);
+        d_count.ensure((size_t)S + 2);
+        HIP_CHECK(hipMemsetAsync(d_count.p, 0, ((size_t)S + 2) * sizeof(u32), st));
+        // a batch: the drawn columns, two counters and a distance per pair, the splits and the bit sets of every replicate
+        const bool in_lds = S && nj_clades_fit(T, W);
+        const size_t per_rep = (size_t)T * Kp + 3u * TT * 8u + SW * 8u + (S && !in_lds ? (size_t)T * W * 8u : 0u) + 1u;
+        size_t batch = (size_t)call.tn.phy_boot_batch;
+        if (call.tn.phy_boot_batch <= 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            batch = std::max<size_t>(1, free_b / 2 / (per_rep + per_rep / 8));   // (a DevBuf takes an eighth more than it is asked for)
+        }
+        batch = std::min(std::min(batch, B), (size_t)PHY_BOOT_MAX_BATCH);
+        cols.ensure(batch * T * Kp + 16), d_cmp.ensure(batch * TT + 2), d_same.ensure(batch * TT + 2), d_D.ensure(batch * TT + 2), d_ok.ensure(batch + 2);
+        d_splits.ensure(batch * SW + 2);
+        if (S && !in_lds) clades.ensure(batch * T * W + 2);
+        out->ok = host_array<uint8_t>(w, B);
+        if (want_splits) out->splits = host_array<uint64_t>(w, B * SW);
+        out->count = host_array<int32_t>(w, S);
+        static_assert(sizeof(u32) == sizeof(int32_t) && sizeof(ull) == sizeof(uint64_t), "counts and bit sets are copied out as they are");
+        StageEvents ev(timed);
+        for (size_t b0 = 0; b0 < B; b0 += batch) {
+            const u32 nb = (u32)std::min(batch, B - b0);
+            ev.mark(0, st);
+            boot_counts_batch(st, d_matrix.p, T, L, K, d_keep.p, d_K.p, (ull)seed, (u32)b0, nb, cols.p, d_cmp.p, d_same.p);
+            HIP_CHECK(hipMemsetAsync(d_ok.p, 1, nb, st));
+            hipLaunchKernelGGL(k_phy_boot_dist, dim3((unsigned)((TT + 255) / 256), nb), dim3(256), 0, st, d_cmp.p, d_same.p, (u32)TT, d_D.p, d_ok.p);
+            ev.mark(1, st);
+            if (S) nj_launch(st, d_D.p, T, W, nb, d_ok.p, d_splits.p, in_lds ? nullptr : clades.p);
+            ev.mark(2, st);
+            if (S) hipLaunchKernelGGL(k_phy_boot_support, dim3((S + 255u) / 256u, nb), dim3(256), 0, st, d_ref.p, d_splits.p, S, W, d_ok.p, d_count.p);
+            ev.mark(3, st);
+            HIP_CHECK(hipGetLastError());
+            call.fetch(out->ok + b0, d_ok.p, nb);
+            if (want_splits && S) call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * SW, d_splits.p, (size_t)nb * SW);
+            if (b0 + nb == B && S) call.fetch(reinterpret_cast<u32*>(out->count), d_count.p, S);
+            call.wait();   // the one wait of the batch: its buffers are the next batch's
+            ++out->batches;
+            out->counts_ms += ev.ms(0), out->trees_ms += ev.ms(1), out->support_ms += ev.ms(2);
+        }
+        out->waits = call.waits;
+        for (size_t b = 0; b < B; ++b) out->valid += out->ok[b] ? 1 : 0;
         fill_empty_slots(slots(out));
     });
 }

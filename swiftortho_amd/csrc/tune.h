@@ -63,6 +63,8 @@
     X(T, pan_tier, "SOHIT_PAN_TIER", 0, "tests: lds = what auto does where the taxa fit the LDS of k_pan_curve, global = words, orders and counters in global memory (0 = auto: by the number of taxa)") \
     /* ---- operon pairs (so_operon_pairs: read per call) ---- */                                                                                               \
     X(I, operon_expand, "SOHIT_OPERON_EXPAND", -1, "tests: expansions per batch (-1: 2^28)")                                                                   \
+    /* ---- bootstrap of the species tree (so_phy_boot: read per call) ---- */                                                                                  \
+    X(I, phy_boot_batch, "SOHIT_PHY_BOOT_BATCH", 0, "replicates per batch (0: what half of the free device memory holds; tests move the batch edges)")        \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \
@@ -105,6 +107,14 @@ static inline int orth_tier_of(const char* v) {
 #define PHY_TILE 64u
 #define PHY_CHUNK_WORDS 32u
 #define PHY_TARGET_WGS 1024u   // the kept columns are cut into ranges until about this many workgroups exist (each flushes its counts once)
+// ... and the bootstrap on top of them: k_phy_boot_gather walks the taxa in groups of PHY_BOOT_TAXA per workgroup (a draw is computed once per
+// group); k_phy_nj keeps the clade bit sets of a replicate in the LDS while row sums, live lists and bit sets fit PHY_NJ_LDS_BYTES (T <= 640),
+// beyond that in global scratch; a batch holds at most PHY_BOOT_MAX_BATCH replicates (a grid dimension)
+#define PHY_BOOT_TAXA 32u
+#define PHY_NJ_THREADS 256u
+#define PHY_NJ_LDS_BYTES 61440u
+#define PHY_BOOT_MAX_BATCH 32768
+#define PHY_MAX_TAXA 4096
 
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;

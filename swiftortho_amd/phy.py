@@ -23,6 +23,15 @@ csrc/phy.hip) equal them array for array.
   * pair_counts: cmp[a, b] = kept columns where neither row is '-', same[a, b] = those where the bytes are equal; diagonal included.
   * host only: distances (p = 1 - same / cmp; poisson: -log(1 - p)), neighbor_joining (Saitou-Nei, float64, Newick with %.6f) and
     supermatrix_fasta (`>taxon\\nrow\\n` per taxon in SLOT order; the reference prints in the iteration order of a set).
+  * bootstrap support (off unless asked for; the reference gets it from `fasttree -boot`): replicate b draws the K kept columns with
+    replacement (boot_columns: splitmix64 of (b, k), scaled by a multiply and a shift), its pair counts (boot_counts) give distances
+    (boot_distances: distances() that drops the replicate where it would refuse) and a topology (nj_splits: the T - 3 clades the joins
+    make, as bit sets over the taxa, the side without taxon 0).  nj_splits is neighbor_joining's walk with SEQUENTIAL row sums -- the
+    one summation order a GPU lane reproduces bit for bit; the printed tree keeps its own summation (tree_splits hands out its
+    clades), so the supports always refer to the tree that is printed.  split_support counts, per clade of the printed tree, the kept
+    replicates that hold it; bootstrap -> (count, valid); tree(boot=B) labels the nodes with count / valid, %.3f.  On the device
+    (so_phy_boot_counts, so_phy_nj_splits, so_phy_boot) the counts are integers and the walks the same IEEE operations in the same
+    order: every array equals numpy's.
 """
 import math
 import sys
@@ -458,20 +467,29 @@ def distances(cmp, same, model='p', names=None):
     return -np.log(1. - p) + np.zeros((T, T))
 
 
-def neighbor_joining(D, names):
-    """Saitou-Nei over float64 -> Newick bytes.  The pair with the smallest Q is joined, ties to the lexicographically lowest (i, j) in
-    the current node order; the new node takes position i, j is removed; the last three nodes are a trifurcation; T = 2 is
-    (A:d/2,B:d/2); branch lengths %.6f, negative ones as they come."""
+def _clade_words(c, T):
+    """a clade (Python int, bit t = taxon t) -> its canonical uint64[W] words: complemented inside T bits where it holds taxon 0"""
+    if c & 1:
+        c = ~c & ((1 << T) - 1)
+    return [(c >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range((T + 63) // 64)]
+
+
+def _nj_walk(D, names, support=None):
+    """the walk of neighbor_joining -> (Newick bytes, uint64[T - 3, W] splits of the joins in join order, canonical as nj_splits' are).
+    support[t] (a share in [0, 1]) labels the node join t makes, %.3f as fasttree prints it"""
     D = np.array(D, dtype=np.float64)
-    n = len(names)
+    n = T = len(names)
     if D.shape != (n, n):
         raise ValueError('neighbor_joining: D is not a square matrix over the names')
     if n < 2:
         raise ValueError('neighbor_joining: a tree needs two taxa at least')
+    if support is not None and len(support) != max(T - 3, 0):
+        raise ValueError('neighbor_joining: %d supports for %d joins' % (len(support), max(T - 3, 0)))
     node = [_label(x) for x in names]
+    clade, splits = [1 << k for k in range(T)], []
     fmt = lambda s, l: '%s:%.6f' % (s, l)
     if n == 2:
-        return ('(%s,%s);' % (fmt(node[0], D[0, 1] / 2.), fmt(node[1], D[0, 1] / 2.))).encode('utf-8')
+        return ('(%s,%s);' % (fmt(node[0], D[0, 1] / 2.), fmt(node[1], D[0, 1] / 2.))).encode('utf-8'), np.zeros((0, 1), dtype=np.uint64)
     while n > 3:
         r = D.sum(1)
         Q = (n - 2) * D - r[:, None] - r[None, :]
@@ -484,13 +502,260 @@ def neighbor_joining(D, names):
         D[i, :], D[:, i] = du, du
         D[i, i] = 0.
         D = np.delete(np.delete(D, j, 0), j, 1)
-        node[i] = '(%s,%s)' % (fmt(node[i], li), fmt(node[j], lj))
-        del node[j]
+        node[i] = '(%s,%s)%s' % (fmt(node[i], li), fmt(node[j], lj), '' if support is None else '%.3f' % support[len(splits)])
+        clade[i] |= clade[j]
+        splits.append(_clade_words(clade[i], T))
+        del node[j], clade[j]
         n -= 1
     la = (D[0, 1] + D[0, 2] - D[1, 2]) / 2.
     lb = (D[0, 1] + D[1, 2] - D[0, 2]) / 2.
     lc = (D[0, 2] + D[1, 2] - D[0, 1]) / 2.
-    return ('(%s,%s,%s);' % (fmt(node[0], la), fmt(node[1], lb), fmt(node[2], lc))).encode('utf-8')
+    newick = ('(%s,%s,%s);' % (fmt(node[0], la), fmt(node[1], lb), fmt(node[2], lc))).encode('utf-8')
+    return newick, np.array(splits, dtype=np.uint64).reshape(len(splits), (T + 63) // 64)
+
+
+def neighbor_joining(D, names, support=None):
+    """Saitou-Nei over float64 -> Newick bytes.  The pair with the smallest Q is joined, ties to the lexicographically lowest (i, j) in
+    the current node order; the new node takes position i, j is removed; the last three nodes are a trifurcation; T = 2 is
+    (A:d/2,B:d/2); branch lengths %.6f, negative ones as they come.  support (None: no labels): float[T - 3], support[t] labels the node
+    join t makes, as in (A:0.100000,B:0.200000)0.950:0.300000 -- %.3f, the way fasttree prints it; the last trifurcation has no label."""
+    return _nj_walk(D, names, support)[0]
+
+
+def tree_splits(D):
+    """-> uint64[T - 3, W]: the splits of the tree neighbor_joining(D, ...) prints, join by join, in the canonical form of nj_splits"""
+    return _nj_walk(D, [''] * len(D))[1]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# bootstrap support: columns drawn with replacement, a tree per replicate, the share of the trees that hold a split
+# ---------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def boot_columns(seed, b, K):
+    """-> int64[K]: the K draws of replicate b from K kept columns.  Draw k is splitmix64 of the counter (b << 32) + k + 1 in wrapping
+    uint64 arithmetic (seed: any uint64, b < 2^31, K < 2^31), its high 32 bits scaled into [0, K) by a multiply and a shift:
+    ((z >> 32) * K) >> 32.  The multiply-shift is off from uniform by at most K / 2^32 per column."""
+    seed, b, K = int(seed), int(b), int(K)
+    if not (0 <= seed <= _M64 and 0 <= b < 2 ** 31 and 0 <= K < 2 ** 31):
+        raise ValueError('boot_columns: seed is a uint64, b and K lie below 2^31')
+    u = np.uint64
+    with np.errstate(over='ignore'):
+        ctr = np.arange(1, K + 1, dtype=np.uint64) + u((b << 32) & _M64)
+        z = u(seed) + ctr * u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        z ^= z >> u(31)
+        return (((z >> u(32)) * u(K)) >> u(32)).astype(np.int64)
+
+
+def boot_counts(matrix, keep, seed, b):
+    """-> (cmp, same) int64[T, T] of replicate b: pair_counts over keep[boot_columns(seed, b, len(keep))] (the order of the draws does
+    not matter, a column drawn twice counts twice)"""
+    keep = np.asarray(keep, dtype=np.int64)
+    return pair_counts(matrix, keep[boot_columns(seed, b, len(keep))])
+
+
+def boot_distances(cmp, same, model='p'):
+    """-> (D float64[T, T], ok): distances() without its refusals.  ok is False when a pair has no compared column, under poisson also
+    when a pair has p >= 1: such a replicate is dropped, not refused (its D holds NaN or inf there)."""
+    if model not in ('p', 'poisson'):
+        raise ValueError("distances: the model is 'p' or 'poisson'")
+    cmp, same = np.asarray(cmp, dtype=np.int64), np.asarray(same, dtype=np.int64)
+    ok = not (cmp == 0).any()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        p = 1. - same.astype(np.float64) / cmp.astype(np.float64)
+        if model == 'p':
+            return p, ok
+        ok = ok and not (p >= 1.).any()
+        return -np.log(1. - p) + np.zeros(p.shape), ok
+
+
+def nj_splits(D):
+    """-> uint64[T - 3, W], W = ceil(T / 64): the non-trivial splits of the neighbour-joining topology of D in join order.  The walk of
+    neighbor_joining with ONE difference, which makes it reproducible on a GPU: the row sums are sequential -- r[i] is the left-to-right
+    float64 sum over the live nodes in ascending order (np.cumsum(D, 1)[:, -1]), not D.sum(1), whose pairwise order no kernel shares.
+    Q = ((n - 2) * D[i, j] - r[i]) - r[j], the minimum over i < j with ties to the lowest (i, j); the new row is
+    ((D[i] + D[j]) - D[i, j]) / 2., it takes position i, j is removed.  A node's clade is a bit set over the taxa in slot order; a join
+    ORs the two clades and emits the result, complemented inside T bits where it holds taxon 0.  T < 4: no split.  A non-finite D is
+    refused."""
+    D = np.array(D, dtype=np.float64)
+    T = len(D)
+    if D.ndim != 2 or D.shape != (T, T):
+        raise ValueError('nj_splits: D is not a square matrix')
+    if not np.isfinite(D).all():
+        raise ValueError('nj_splits: D holds a value that is not finite')
+    W = (T + 63) // 64
+    clade, splits, n = [1 << k for k in range(T)], [], T
+    while n > 3:
+        r = np.cumsum(D, axis=1)[:, -1]
+        Q = ((n - 2) * D - r[:, None]) - r[None, :]
+        Q[np.tril_indices(n)] = np.inf
+        i, j = divmod(int(np.argmin(Q)), n)
+        du = ((D[i] + D[j]) - D[i, j]) / 2.
+        D[i, :], D[:, i] = du, du
+        D[i, i] = 0.
+        D = np.delete(np.delete(D, j, 0), j, 1)
+        clade[i] |= clade[j]
+        splits.append(_clade_words(clade[i], T))
+        del clade[j]
+        n -= 1
+    return np.array(splits, dtype=np.uint64).reshape(len(splits), W)
+
+
+def split_support(ref_splits, rep_splits, ok):
+    """-> int32[T - 3]: per split of the printed tree (ref_splits uint64[S, W]) the number of ok replicates whose tree holds it
+    (rep_splits uint64[B, S, W], ok bool[B])"""
+    ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
+    rep = np.ascontiguousarray(rep_splits, dtype=np.uint64)
+    out = np.zeros(len(ref), dtype=np.int32)
+    keys = [row.tobytes() for row in ref]
+    for b in np.flatnonzero(np.asarray(ok, dtype=bool)).tolist():
+        held = {row.tobytes() for row in rep[b]}
+        for s, k in enumerate(keys):
+            if k in held:
+                out[s] += 1
+    return out
+
+
+def _boot_batch(B, per_rep_bytes):
+    """replicates per device call of the poisson path: SOHIT_PHY_BOOT_BATCH, else what about 2^30 bytes of counts and columns hold"""
+    import os
+    forced = int(os.environ.get('SOHIT_PHY_BOOT_BATCH', '0') or 0)
+    return max(1, min(B, 32768, forced if forced > 0 else (1 << 30) // max(1, per_rep_bytes)))   # (32768: the most a device call takes)
+
+
+def device_boot_counts(matrix, keep, seed, b0, nb, device=0):
+    """boot_counts() of replicates b0 .. b0 + nb - 1 in one device call (so_phy_boot_counts) -> (cmp, same) int64[nb, T, T]"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('device_boot_counts: the matrix has two dimensions')
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    T, nc = matrix.shape
+    res = _lib.SoPhyBootResult()
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    if L.so_phy_boot_counts(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(b0), int(nb), 0, C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        return (_lib.result_array(res.cmp, nb * T * T, np.int64).reshape(nb, T, T), _lib.result_array(res.same, nb * T * T, np.int64).reshape(nb, T, T))
+    finally:
+        L.so_phy_boot_free(C.byref(res))
+
+
+def device_nj_splits(D, device=0, clades_in_global=False):
+    """nj_splits() of nb matrices D float64[nb, T, T] in one device call (so_phy_nj_splits), a workgroup per matrix -> uint64[nb, T - 3, W].
+    The device reads D[k][i] for D[i][k]: a D that is not symmetric bit for bit is refused, as a non-finite one is.  clades_in_global
+    (tests): the clade bit sets in global scratch, where the call keeps them once they outgrow the LDS"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.ndim != 3 or D.shape[1] != D.shape[2]:
+        raise ValueError('device_nj_splits: D is float64[nb, T, T]')
+    nb, T = D.shape[0], D.shape[1]
+    res = _lib.SoPhyBootResult()
+    if L.so_phy_nj_splits(int(device), nb, T, C.c_void_p(D.ctypes.data), 1 if clades_in_global else 0, C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        S, W = max(T - 3, 0), (T + 63) // 64
+        return _lib.result_array(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
+    finally:
+        L.so_phy_boot_free(C.byref(res))
+
+
+def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, stats=None, timed=False):
+    """the fused bootstrap of model p (so_phy_boot): counts, D = 1 - same / cmp, the trees and their comparison with ref_splits stay on
+    the device, in batches of replicates with one host wait each -> (count int32[T - 3], valid, ok bool[B], splits uint64[B, T - 3, W] or
+    None); a dropped replicate's splits are zeros.  stats: 'waits', 'batches'; timed: also 'counts_ms', 'trees_ms', 'support_ms', the
+    device time of the stages by events"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('device_boot: the matrix has two dimensions')
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    T, nc = matrix.shape
+    S, W = max(T - 3, 0), (T + 63) // 64
+    ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
+    if ref.size != S * W:
+        raise ValueError('device_boot: the printed tree has %d splits of %d words' % (S, W))
+    res = _lib.SoPhyBootResult()
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    if L.so_phy_boot(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(B), ptr(ref), (1 if want_splits else 0) | (2 if timed else 0),
+                     C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        if stats is not None:
+            stats['waits'], stats['batches'] = int(res.waits), int(res.batches)
+            if timed:
+                stats['counts_ms'], stats['trees_ms'], stats['support_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.support_ms)
+        splits = _lib.result_array(res.splits, B * S * W, np.uint64).reshape(B, S, W) if want_splits else None
+        return _lib.result_array(res.count, S, np.int32), int(res.valid), _lib.result_array(res.ok, B, np.uint8).astype(bool), splits
+    finally:
+        L.so_phy_boot_free(C.byref(res))
+
+
+def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0, stats=None, want_splits=True):
+    """-> (count int32[T - 3], valid, ok bool[B], splits uint64[B, T - 3, W] or None): everything bootstrap() is made from.  Host: the
+    numpy definitions replicate by replicate.  device_stage, model p: so_phy_boot; poisson: the counts of a batch by so_phy_boot_counts,
+    the distances on the host (the device's log is not numpy's), the trees by so_phy_nj_splits, the support by split_support."""
+    B, seed = int(B), int(seed)
+    if not 1 <= B < 2 ** 31:
+        raise ValueError('bootstrap: B lies in 1 .. 2^31 - 1')
+    if sm.matrix is None:
+        raise ValueError('bootstrap: the supermatrix was built without its matrix')
+    T = len(sm.taxa)
+    S, W = max(T - 3, 0), (T + 63) // 64
+    ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa)) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
+    if len(sm.keep) == 0:
+        raise ValueError('bootstrap: no kept column to draw from')
+    if device_stage and model == 'p':
+        try:
+            return device_boot(sm.matrix, sm.keep, seed, B, ref, want_splits, device, stats)
+        except RuntimeError as e:
+            raise ValueError('bootstrap: %s' % e)
+    ok, splits = np.zeros(B, dtype=bool), np.zeros((B, S, W), dtype=np.uint64)
+    if device_stage:
+        Kp = (len(sm.keep) + 15) & ~15
+        step = _boot_batch(B, T * Kp + 16 * T * T)
+        calls = 0
+        for b0 in range(0, B, step):
+            nb = min(step, B - b0)
+            try:
+                cmp_, same = device_boot_counts(sm.matrix, sm.keep, seed, b0, nb, device)
+                dist = [boot_distances(cmp_[k], same[k], model) for k in range(nb)]
+                good = [k for k in range(nb) if dist[k][1]]
+                calls += 1
+                if good and S:
+                    splits[[b0 + k for k in good]] = device_nj_splits(np.stack([dist[k][0] for k in good]), device)
+                    calls += 1
+            except RuntimeError as e:
+                raise ValueError('bootstrap: %s' % e)
+            ok[[b0 + k for k in good]] = True
+        if stats is not None:
+            stats['calls'] = calls
+    else:
+        for b in range(B):
+            D, ok[b] = boot_distances(*boot_counts(sm.matrix, sm.keep, seed, b), model=model)
+            if ok[b]:
+                splits[b] = nj_splits(D)
+    return split_support(ref, splits, ok), int(ok.sum()), ok, splits if want_splits else None
+
+
+def bootstrap(sm, B, seed=1, model='p', device_stage=False, device=0, stats=None):
+    """Felsenstein's bootstrap of the neighbour-joining tree over the kept columns -> (count int32[T - 3], valid): B replicates draw the
+    kept columns with replacement (boot_columns), each gives pair counts (boot_counts), distances (boot_distances) and a topology
+    (nj_splits); a replicate that leaves a pair without a distance is dropped; count[t] = the valid replicates that hold the split join t
+    of the printed tree makes (tree_splits).  No valid replicate: ValueError."""
+    count, valid = bootstrap_replicates(sm, B, seed, model, device_stage, device, stats, want_splits=False)[:2]
+    if valid == 0:
+        raise ValueError('bootstrap: none of the %d replicates gives every pair of taxa a distance' % int(B))
+    return count, valid
 
 
 def supermatrix_fasta(taxa, matrix, keep):
@@ -499,19 +764,27 @@ def supermatrix_fasta(taxa, matrix, keep):
     return b''.join(b'>' + (t if isinstance(t, bytes) else str(t).encode('utf-8')) + b'\n' + matrix[k, keep].tobytes() + b'\n' for k, t in enumerate(taxa))
 
 
-def tree(sm, model='p'):
-    """Supermatrix -> Newick bytes over its taxa"""
-    return neighbor_joining(distances(sm.cmp, sm.same, model, sm.taxa), sm.taxa)
+def tree(sm, model='p', boot=0, seed=1, device_stage=False, device=0, stats=None):
+    """Supermatrix -> Newick bytes over its taxa; boot > 0: every node a join makes carries the share of the valid bootstrap replicates
+    that hold its split (bootstrap(); stats: 'boot', 'boot_valid' and the device's counters)"""
+    D = distances(sm.cmp, sm.same, model, sm.taxa)
+    if int(boot) <= 0:
+        return neighbor_joining(D, sm.taxa)
+    count, valid = bootstrap(sm, boot, seed, model, device_stage, device, stats)
+    if stats is not None:
+        stats['boot'], stats['boot_valid'] = int(boot), valid
+    return neighbor_joining(D, sm.taxa, count / float(valid))
 
 
 # ---------------------------------------------------------------------------------------------------------
 # scripts/rbh2phy.py -A T
 # ---------------------------------------------------------------------------------------------------------
-def run_align(sc_bytes, fasta_bytes, cols, table, gap_share=1.0, model='p', tree_path='', device_stage=False, out=None):
-    """the -A T half of rbh2phy.py: the supermatrix FASTA to `out` (default: stdout), the tree to `tree_path` when named -> Supermatrix"""
+def run_align(sc_bytes, fasta_bytes, cols, table, gap_share=1.0, model='p', tree_path='', device_stage=False, out=None, boot=0, seed=1):
+    """the -A T half of rbh2phy.py: the supermatrix FASTA to `out` (default: stdout), the tree to `tree_path` when named -> Supermatrix;
+    boot > 0: the tree's nodes carry their bootstrap support over `boot` replicates drawn from `seed` (sm.stats: boot, boot_valid)"""
     rows_src = TextRows(sc_bytes, cols.names)
     sm = supermatrix(cols.names, table, rbh.fasta_records(fasta_bytes), rows_src, gap_share, device_stage)
-    newick = tree(sm, model) if tree_path else None      # (before anything is printed: a refusal leaves no half output)
+    newick = tree(sm, model, boot, seed, device_stage, stats=sm.stats) if tree_path else None      # (before anything is printed: a refusal leaves no half output)
     o = out if out is not None else sys.stdout.buffer
     o.write(supermatrix_fasta(sm.taxa, sm.matrix, sm.keep))
     o.flush()

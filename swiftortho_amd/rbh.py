@@ -358,6 +358,12 @@ def _gpu_flag(v):
     return str(v).upper()[:1] == 'T'
 
 
+def _count_flag(v, most):
+    """the value of a flag that takes a whole number in 0 .. most, or None"""
+    v = str(v).strip()
+    return int(v) if v.isdigit() and v.isascii() and int(v) <= most else None
+
+
 def main_get_rbh(argv=None):
     from .fsearch import parse_flags
     argv = list(sys.argv if argv is None else argv)
@@ -378,15 +384,24 @@ def main_rbh2phy(argv=None):
     import os
     from .fsearch import parse_flags
     argv = list(sys.argv if argv is None else argv)
-    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p'})
+    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p', '-B': '0', '-S': '1'})
     if args['-i'] == '' or args['-f'] == '':
-        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson]]')
+        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson] [-B replicates] [-S seed]]')
         print(' -i: blast -m8 or find_hit .sc file; ids are taxon|gene\n -f: the FASTA file the search read\n -r: reference taxon (default: the taxon with most genes)')
         print(' -G: the winner list and the table on the GPU [T|F]. Default: F\n -o: also write one tab-separated line of ids per group')
         print(' -A: join the families into the core-gene supermatrix from the CIGARs of the rows (find_hit.py -C T) and print it as FASTA [T|F]. Default: F')
         print(' -g: with -A T, keep the columns whose share of gaps is at most this. Default: 1 (every column)')
         print(' -t: with -A T, write the neighbour-joining tree of the taxa to this file\n -m: distance of the tree [p|poisson]. Default: p')
+        print(' -B: with -t, label the tree\'s nodes with their bootstrap support over this many replicates (with -G T: on the GPU). Default: 0 (no labels)')
+        print(' -S: seed of the bootstrap\'s column draws, 0 .. 2^64 - 1. Default: 1')
         raise SystemExit()
+    boot, seed = _count_flag(args['-B'], 2 ** 31 - 1), _count_flag(args['-S'], 2 ** 64 - 1)
+    if boot is None or seed is None:
+        sys.stderr.write('rbh2phy: -B takes a whole number of replicates from 0 to 2^31 - 1, -S a seed from 0 to 2^64 - 1\n')
+        return 2
+    if boot > 0 and args['-t'] == '':
+        sys.stderr.write('rbh2phy: -B labels the tree that -t writes: name a tree file with -t (and join the families with -A T)\n')
+        return 2
     with open(args['-i'], 'rb') as f:
         sc = f.read()
     cols = find_orth.columns_from_text(sc)
@@ -397,7 +412,7 @@ def main_rbh2phy(argv=None):
         from . import phy
         try:
             share = float(args['-g'])
-            sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']))
+            sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']), boot=boot, seed=seed)
         except phy.MissingCigar as e:
             sys.stderr.write('rbh2phy: %s\n' % e)
             return 2
