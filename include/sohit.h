@@ -677,6 +677,33 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matri
                 int64_t n_reps, const uint64_t *ref_splits, int32_t flags, so_phy_boot_result *out);
 void so_phy_boot_free(so_phy_boot_result *result);
 
+/* The substitution-count tensor of a supermatrix on the matrix cores (csrc/phy.hip): what swiftortho_amd/phy.py `subst_counts()` and
+ * `boot_subst()` define, integer for integer.  It is what the Kimura and LogDet distances of the species tree are made from.
+ * Residue code a = the index of a byte in ARNDCQEGHILKMFPSTWYV; every other byte ('-', X, B, Z, U, '*', lower case, 0x00, 0xFF) is uncoded.
+ * The pairs (i, j), i < j, of n_taxa taxa in row-major order: (0,1), (0,2), .., (n_taxa - 2, n_taxa - 1); n_pairs = n_taxa (n_taxa - 1) / 2.
+ * so_phy_subst: subst[t][p][a][b] = the columns k of tensor t where taxon i of pair p holds residue a and taxon j residue b; a column where
+ *   either byte is uncoded adds nothing to the pair.  n_reps == 0: one tensor over the kept columns (seed and b0 are not read); n_reps >= 1:
+ *   the tensors of the bootstrap replicates b0 .. b0 + n_reps - 1, their columns drawn as so_phy_boot_counts draws them.
+ *   k_phy_code writes the codes (0xFF: uncoded, and the padding of a row to the k-step of the product), k_phy_subst is the product
+ *   N = E E^T of the one-hot matrix E (row 20 i + a over the columns is code[i][k] == a) by v_mfma_i32_32x32x32_i8 with 32-bit integer
+ *   accumulators: E is never written -- a lane builds its operand bytes from 16 staged codes by a byte-wise compare --, only tiles that hold
+ *   a pair i < j are walked, the columns are cut into ranges that flush with integer atomics.  No floating point: determinants and
+ *   logarithms are the host's (numpy's), so the distances are the same bytes with and without the device.
+ *   flags bit 0: no tensor in the result (measurements); bit 1: events around the two passes -- code_ms, product_ms.  One host wait.
+ * Refused with a message (so_phy_last_error) and nothing left allocated: n_taxa below 2 or above 4096, n_keep of 0, a keep entry outside
+ * 0 .. n_cols - 1, n_reps below 0 or above 32768, b0 + n_reps above 2^31, a tensor that does not fit half of the free device memory (the
+ * message says how many bytes it would take), no device, unknown flag bits. */
+typedef struct so_phy_subst_result {
+    int64_t n_taxa, n_pairs, n_reps, bytes;   /* n_reps: the tensors in subst (1 for the kept columns); bytes: their size */
+    int32_t waits;
+    int32_t reserved;
+    double code_ms, product_ms;   /* flags bit 1: device time of the coding pass and of the product */
+    int32_t *subst;               /* n_reps * n_pairs * 400, or empty (flags bit 0) */
+} so_phy_subst_result;
+int so_phy_subst(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, uint64_t seed,
+                 int64_t b0, int64_t n_reps, int32_t flags, so_phy_subst_result *out);
+void so_phy_subst_free(so_phy_subst_result *result);
+
 /* The expansion of a collapsed search on the device (csrc/nr.hip).  Replaces: scripts/nr2full.py (14-44) -- every row of the search of
  * the collapsed proteome multiplied out to the cross product of the ';;;'-joined query ids and subject ids (23-33), inside a run of
  * rows of one collapsed query the expanded rows grouped by individual query in order of first appearance (35-44) -- as

@@ -10,7 +10,7 @@ The pan-genome step (204-214) runs on request: `-P T` (default `F`: the files an
 <name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.
 The species-tree step runs on request as well: `-t T` (default `F`) leaves <name>.aln (the core-gene supermatrix of the reference taxon -r,
 FASTA, taxa in slot order), <name>.aln.trim (the columns whose share of gaps is at most `-g`, default 1: the same file) and <name>.nwk
-(neighbour joining over the `-m p|poisson` distances).  The reference shells out to famsa, trimal and fasttree here; this step aligns
+(neighbour joining over the `-m p|poisson|kimura|logdet` distances).  The reference shells out to famsa, trimal and fasttree here; this step aligns
 nothing: it joins the families along the alignments the search itself made (swiftortho_amd/phy.py), in one process that searches the
 proteome once more with a CIGAR on every row; with `-G T` the matrix and the pair counts are built on the GPU.  `-B n` (default 0: the
 bare tree) labels the tree's nodes with their bootstrap support over n replicates of the kept columns, drawn from the seed `-S` (default 1)

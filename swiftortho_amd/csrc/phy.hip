@@ -31,6 +31,13 @@
 //   so_phy_boot         the fused path of the p distance: gather, pairs, k_phy_boot_dist (D = 1 - same / cmp; a pair without a compared
 //                       column drops the replicate), k_phy_nj, k_phy_boot_support (a lane per split of the printed tree).  Batches of
 //                       replicates sized from the free device memory (SOHIT_PHY_BOOT_BATCH), one host wait per batch.
+//
+// The substitution counts the Kimura and LogDet distances need (phy.py subst_counts, boot_subst):
+//   so_phy_subst        k_phy_code         a lane per kept (or drawn) column: the residue codes 0 .. 19, 0xFF for every other byte and for the
+//                                          padding of a row to the k-step;
+//                       k_phy_subst        N = E E^T on the matrix cores (v_mfma_i32_32x32x32_i8, i32 accumulators), E the one-hot matrix
+//                                          of 20 rows per taxon, never written: a lane compares 16 staged codes with its row's residue.
+//                                          Integers only; determinants and logarithms stay on the host.
 #include "hit_table.h"
 
 #include <algorithm>
@@ -421,8 +428,128 @@ __global__ __launch_bounds__(256) void k_phy_boot_support(const ull* __restrict_
     if (found) atomicAdd(count + s, 1u);
 }
 
+// ---- so_phy_subst: the 20 x 20 table of residue pairs per pair of taxa -------------------------------------------------------------------
+// grid (columns of the padded row, groups of PHY_BOOT_TAXA taxa, tensors): the residue codes of the kept columns (draw == 0) or of replicate
+// b0 + z's drawn columns side by side: the index in ARNDCQEGHILKMFPSTWYV, 0xFF for every other byte and behind the K columns up to Kp (a
+// multiple of the k-step: the padding never counts).  keep[] lies inside [0, L) (the host has checked), a draw inside [0, K).
+__global__ __launch_bounds__(256) void k_phy_code(const u8* __restrict__ matrix, u32 T, u32 L, u32 K, u32 Kp, const int* __restrict__ keep, ull seed, u32 b0, u32 draw,
+                                                  u8* __restrict__ out) {
+    __shared__ u8 lut[256];
+    lut[threadIdx.x] = 0xFFu;
+    __syncthreads();
+    if (threadIdx.x < 20u) lut[(u8)"ARNDCQEGHILKMFPSTWYV"[threadIdx.x]] = (u8)threadIdx.x;
+    __syncthreads();
+    const u32 j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= Kp) return;
+    const u32 t0 = blockIdx.y * PHY_BOOT_TAXA, t1 = min(T, t0 + PHY_BOOT_TAXA);
+    u8* dst = out + (size_t)blockIdx.z * T * Kp + j;
+    if (j >= K) {
+        for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = 0xFFu;
+        return;
+    }
+    const u32 c = (u32)keep[draw ? boot_draw(seed, (ull)b0 + blockIdx.z, j, K) : j];
+    for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = lut[matrix[(size_t)t * L + c]];
+}
+
+typedef int phs_v4 __attribute__((ext_vector_type(4)));
+typedef int phs_v16 __attribute__((ext_vector_type(16)));
+
+// 0x01 in every byte of w that equals the splat's byte: four entries of a row of E
+__device__ __forceinline__ u32 onehot4(u32 w, u32 splat) { return (~nonzero_bytes(w ^ splat) & 0x80808080u) >> 7; }
+// the 16 operand bytes of a lane: row 20 i + a of E over 16 columns is (code[i][k] == a); p: the 16 codes of taxon i in the LDS
+__device__ __forceinline__ phs_v4 subst_frag(const u8* p, u32 splat) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    phs_v4 f;
+    f.x = (int)onehot4(v.x, splat), f.y = (int)onehot4(v.y, splat), f.z = (int)onehot4(v.z, splat), f.w = (int)onehot4(v.w, splat);
+    return f;
+}
+
+// grid (nt * nt tiles of PHS_TILE x PHS_TILE of N = E E^T, ranges of `cps` columns, tensors); code: T rows of Kp bytes (Kp a multiple of 32,
+// cps a multiple of PHS_CHUNK_COLS), 0xFF behind the K columns.  Only tiles I <= J hold a pair i < j.  Wave (wr, wc) of the 2 x 2 owns rows
+// I * 128 + wr * 64 .. + 63 against columns J * 128 + wc * 64 .. + 63 as 2 x 2 MFMA tiles.  v_mfma_i32_32x32x32_i8: lane l holds row (A) or
+// column (B) l & 31 over the 16 columns 16 (l >> 5) .. + 15 of the k-step -- A and B are built by the same function from the same bytes, so
+// the k order inside a lane does not matter --; accumulator register g of lane l is row (g & 3) + 8 (g >> 2) + 4 (l >> 5), column l & 31.
+// A row of E beyond 20 T reads a staged row of 0xFF and stays 0; the flush keeps i < j < T only.  out: [pair][20][20], zeroed by the host;
+// blockIdx.z: its code rows lie crep bytes, its tensor orep elements behind the last one's.
+__global__ __launch_bounds__(256) void k_phy_subst(const u8* __restrict__ code, u32 T, u32 Kp, u32 nt, u32 cps, int* __restrict__ out, size_t crep, size_t orep) {
+    code += (size_t)blockIdx.z * crep, out += (size_t)blockIdx.z * orep;
+    __shared__ __attribute__((aligned(16))) u8 sA[PHS_TAXA * PHS_CHUNK_COLS];
+    __shared__ __attribute__((aligned(16))) u8 sB[PHS_TAXA * PHS_CHUNK_COLS];
+    const u32 I = blockIdx.x / nt, J = blockIdx.x % nt;
+    if (I > J) return;
+    const u32 c_begin = blockIdx.y * cps, c_end = min(Kp, c_begin + cps);   // multiples of 32
+    if (c_begin >= c_end) return;   // (the whole workgroup)
+    const u32 tA0 = I * PHS_TILE / 20u, tB0 = J * PHS_TILE / 20u;
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1u, r = lane & 31u, h = lane >> 5;
+    const bool live = I != J || wr <= wc;   // (wave-uniform) below the diagonal of a diagonal tile no pair has i < j
+    u32 aoff[2], asplat[2], boff[2], bsplat[2];
+#pragma unroll
+    for (u32 m = 0; m < 2u; ++m) {
+        const u32 ra = I * PHS_TILE + wr * 64u + m * 32u + r, rb = J * PHS_TILE + wc * 64u + m * 32u + r;   // ra / 20 - tA0 < PHS_TAXA
+        aoff[m] = (ra / 20u - tA0) * PHS_CHUNK_COLS + 16u * h, asplat[m] = (ra % 20u) * 0x01010101u;
+        boff[m] = (rb / 20u - tB0) * PHS_CHUNK_COLS + 16u * h, bsplat[m] = (rb % 20u) * 0x01010101u;
+    }
+    phs_v16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
+    static_assert(PHS_TAXA * (PHS_CHUNK_COLS / 16u) == 256u, "a lane stages 16 bytes of each side per chunk");
+    const u32 st = threadIdx.x / (PHS_CHUNK_COLS / 16u), sp = (threadIdx.x % (PHS_CHUNK_COLS / 16u)) * 16u;
+    for (u32 c0 = c_begin; c0 < c_end; c0 += PHS_CHUNK_COLS) {
+        __syncthreads();   // the last chunk's readers are done
+        uint4 va = make_uint4(~0u, ~0u, ~0u, ~0u), vb = va;
+        if (c0 + sp < c_end) {   // c0 + sp a multiple of 16 below c_end <= Kp, itself a multiple of 32: the 16 bytes lie inside the row
+            if (tA0 + st < T) va = *reinterpret_cast<const uint4*>(code + (size_t)(tA0 + st) * Kp + c0 + sp);
+            if (tB0 + st < T) vb = *reinterpret_cast<const uint4*>(code + (size_t)(tB0 + st) * Kp + c0 + sp);
+        }
+        *reinterpret_cast<uint4*>(sA + st * PHS_CHUNK_COLS + sp) = va;
+        *reinterpret_cast<uint4*>(sB + st * PHS_CHUNK_COLS + sp) = vb;
+        __syncthreads();
+        if (!live) continue;
+        const u32 steps = min((u32)PHS_CHUNK_COLS, c_end - c0) / 32u;
+        for (u32 kk = 0; kk < steps; ++kk) {
+            const phs_v4 a0 = subst_frag(sA + aoff[0] + kk * 32u, asplat[0]), a1 = subst_frag(sA + aoff[1] + kk * 32u, asplat[1]);
+            const phs_v4 b0 = subst_frag(sB + boff[0] + kk * 32u, bsplat[0]), b1 = subst_frag(sB + boff[1] + kk * 32u, bsplat[1]);
+            acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const u32 col = J * PHS_TILE + wc * 64u + (u32)n * 32u + r, j = col / 20u, b = col % 20u;
+            if (j >= T) continue;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const u32 row = I * PHS_TILE + wr * 64u + (u32)m * 32u + (u32)(g & 3) + 8u * (u32)(g >> 2) + 4u * h, i = row / 20u, a = row % 20u;
+                const int v = acc[m][n][g];
+                if (v == 0 || i >= j) continue;   // i < j < T: the pair's number lies below T (T - 1) / 2
+                const size_t p = (size_t)(i * (2u * T - i - 1u) / 2u + (j - i - 1u));
+                atomicAdd(out + p * 400u + a * 20u + b, v);
+            }
+        }
+}
+
+// the grid of k_phy_subst over T taxa, rows of Kp codes and `reps` tensors: tiles per side, columns per range (whole chunks), ranges
+void subst_grid(u32 T, u32 Kp, u32 reps, u32& nt, u32& cps, u32& ranges) {
+    nt = (20u * T + PHS_TILE - 1u) / PHS_TILE;
+    const u64 tiles = (u64)nt * (nt + 1u) / 2u * reps;
+    const u32 chunks = (Kp + PHS_CHUNK_COLS - 1u) / PHS_CHUNK_COLS;
+    const u32 want = std::min(chunks, std::max(1u, (u32)((PHS_TARGET_WGS + tiles - 1u) / tiles)));
+    cps = ((chunks + want - 1u) / want) * PHS_CHUNK_COLS;
+    ranges = (Kp + cps - 1u) / cps;
+}
+
 thread_local std::string g_phy_err;
 
+auto slots(so_phy_subst_result* r) { return result_slots(&r->subst); }
 auto slots(so_phy_result* r) { return result_slots(&r->row, &r->matrix, &r->gaps, &r->keep, &r->cmp, &r->same); }
 auto slots(so_phy_boot_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->count, &r->ok); }
 
@@ -698,6 +825,59 @@ int so_phy_boot_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t
         out->same = (int64_t*)host_copy(who.c_str(), d_same.p, (size_t)nb * TT, st);
         call.wait();
         out->waits = call.waits, out->batches = 1;
+        fill_empty_slots(slots(out));
+    });
+}
+
+void so_phy_subst_free(so_phy_subst_result* r) {
+    if (r) release_slots(r, slots(r));
+}
+
+int so_phy_subst(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, uint64_t seed, int64_t b0, int64_t n_reps,
+                 int32_t flags, so_phy_subst_result* out) {
+    const std::string who = "so_phy_subst";
+    return guarded_call(g_phy_err, out, so_phy_subst_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~3) throw SoError(who + ": unknown flag bits (bit 0: no tensor in the result, bit 1: the two passes timed by events)");
+        if (n_reps < 0) throw SoError(who + ": n_reps is 0 (the kept columns) or the number of replicates (n_reps is " + std::to_string(n_reps) + ")");
+        const bool draw = n_reps > 0;
+        const std::vector<int> k32 = boot_check(who, n_taxa, n_cols, matrix, n_keep, keep, draw ? b0 : 0, draw ? n_reps : 1);
+        if (n_reps > PHY_BOOT_MAX_BATCH) throw SoError(who + ": more than " + std::to_string(PHY_BOOT_MAX_BATCH) + " replicates in one call are not supported");
+        const bool want_tensor = !(flags & 1), timed = flags & 2;
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, K = (u32)n_keep, nb = draw ? (u32)n_reps : 1u, Kp = (K + 31u) & ~31u;
+        const size_t P = (size_t)T * (T - 1u) / 2u, per = P * 400u, bytes = (size_t)nb * per * sizeof(int);
+        out->n_taxa = n_taxa, out->n_pairs = (int64_t)P, out->n_reps = nb, out->bytes = (int64_t)bytes;
+        check_device(who.c_str(), device);
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        {
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            if (bytes + bytes / 8 > free_b / 2)   // (a DevBuf takes an eighth more than it is asked for)
+                throw SoError(who + ": the tensor of " + std::to_string(nb) + " x " + std::to_string(P) + " pairs would take " + std::to_string(bytes) +
+                              " bytes, more than half of the free device memory (" + std::to_string(free_b) + " bytes free): ask for fewer replicates per call");
+        }
+        DevBuf<u8> d_matrix, codes;
+        DevBuf<int> d_keep, d_out;
+        upload(d_matrix, matrix, (size_t)T * L, st), upload(d_keep, k32.data(), k32.size(), st);
+        codes.ensure((size_t)nb * T * Kp + 16), d_out.ensure((size_t)nb * per + 2);
+        StageEvents ev(timed);
+        HIP_CHECK(hipMemsetAsync(d_out.p, 0, bytes, st));
+        ev.mark(0, st);
+        hipLaunchKernelGGL(k_phy_code, dim3((Kp + 255u) / 256u, (T + PHY_BOOT_TAXA - 1u) / PHY_BOOT_TAXA, nb), dim3(256), 0, st, d_matrix.p, T, L, K, Kp, d_keep.p, (ull)seed,
+                           (u32)(draw ? b0 : 0), draw ? 1u : 0u, codes.p);
+        ev.mark(1, st);
+        u32 nt, cps, ranges;
+        subst_grid(T, Kp, nb, nt, cps, ranges);
+        hipLaunchKernelGGL(k_phy_subst, dim3(nt * nt, ranges, nb), dim3(256), 0, st, codes.p, T, Kp, nt, cps, d_out.p, (size_t)T * Kp, per);
+        ev.mark(2, st);
+        HIP_CHECK(hipGetLastError());
+        static_assert(sizeof(int) == sizeof(int32_t), "the counts are copied out as int32");
+        if (want_tensor) out->subst = host_copy(who.c_str(), d_out.p, (size_t)nb * per, st);
+        call.wait();
+        out->waits = call.waits;
+        out->code_ms = ev.ms(0), out->product_ms = ev.ms(1);
         fill_empty_slots(slots(out));
     });
 }

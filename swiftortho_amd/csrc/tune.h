@@ -115,6 +115,14 @@ static inline int orth_tier_of(const char* v) {
 #define PHY_NJ_LDS_BYTES 61440u
 #define PHY_BOOT_MAX_BATCH 32768
 #define PHY_MAX_TAXA 4096
+// ... and the substitution counts (k_phy_subst): the one-hot matrix E has 20 rows per taxon; a workgroup owns PHS_TILE x PHS_TILE of
+// N = E E^T, its four waves 64 x 64 each as 2 x 2 tiles of v_mfma_i32_32x32x32_i8.  PHS_TILE rows of E touch at most PHS_TAXA taxa
+// ((PHS_TILE + 18) / 20 + 1), whose codes are staged in the LDS PHS_CHUNK_COLS columns at a time (a multiple of the k-step 32; 2 x 4 KiB);
+// the kept columns are cut into ranges of whole chunks until about PHS_TARGET_WGS workgroups exist
+#define PHS_TILE 128u
+#define PHS_TAXA 8u
+#define PHS_CHUNK_COLS 512u
+#define PHS_TARGET_WGS 1024u
 
 struct Tune {
 #define X_B(f, d) bool f = (d) != 0;

@@ -32,6 +32,12 @@ csrc/phy.hip) equal them array for array.
     replicates that hold it; bootstrap -> (count, valid); tree(boot=B) labels the nodes with count / valid, %.3f.  On the device
     (so_phy_boot_counts, so_phy_nj_splits, so_phy_boot) the counts are integers and the walks the same IEEE operations in the same
     order: every array equals numpy's.
+  * substitution counts (pair_index, subst_counts, boot_subst): per pair of taxa i < j the 20 x 20 table N[a, b] of the kept columns where
+    taxon i holds residue a and taxon j residue b (AA20 order; any other byte is uncoded and adds nothing).  Two more distances follow,
+    neither of which needs a rate matrix: kimura, -log(1 - p - p * p / 5) from the pair counts, and logdet (Lake; Lockhart et al.),
+    -(log det N - (sum log r + sum log c) / 2) / 20 with r, c the row and column sums of N, additive under a general Markov model,
+    composition bias included.  The tensor is N = E E^T of one-hot matrices: on the device (so_phy_subst) a product on the matrix cores
+    in 32-bit integers; determinants and logarithms stay numpy's, so the distances are the same bytes with and without the device.
 """
 import math
 import sys
@@ -45,7 +51,9 @@ GAP = 45   # '-'
 
 class Supermatrix:
     """`taxa` (bytes, slot order), `matrix` uint8[T, L] (None when a device call was asked for the counts only), `col_off` int64[F + 1],
-    `gaps` int32[L], `keep` int64[L'], `cmp` / `same` int64[T, T] over the kept columns, `anchors` (name codes, family order), `stats`"""
+    `gaps` int32[L], `keep` int64[L'], `cmp` / `same` int64[T, T] over the kept columns, `anchors` (name codes, family order), `stats`;
+    `subst` int32[P, 20, 20]: the substitution counts over the kept columns, None until a model asks for them (tree(), model logdet)"""
+    subst = None
 
     def __init__(self, taxa, matrix, col_off, gaps, keep, cmp, same, anchors=None, stats=None):
         self.taxa, self.matrix, self.col_off, self.gaps, self.keep, self.cmp, self.same = taxa, matrix, col_off, gaps, keep, cmp, same
@@ -448,19 +456,122 @@ def _label(x):
     return x.decode('utf-8', 'replace') if isinstance(x, bytes) else str(x)
 
 
-def distances(cmp, same, model='p', names=None):
-    """-> float64[T, T]: p = 1 - same / cmp, or -log(1 - p) (poisson); a pair without a compared column, or poisson with p >= 1, refuses"""
-    if model not in ('p', 'poisson'):
-        raise ValueError("distances: the model is 'p' or 'poisson'")
+AA20 = b'ARNDCQEGHILKMFPSTWYV'   # residue code a = the index in it; every other byte is uncoded
+MODELS = ('p', 'poisson', 'kimura', 'logdet')
+_NO_MODEL = "distances: the model is 'p', 'poisson', 'kimura' or 'logdet'"
+
+
+class DistanceRefused(ValueError):
+    """a pair of taxa has no kimura or logdet distance (rbh2phy.py exits with code 2)"""
+
+
+def residue_codes(matrix):
+    """-> uint8 like matrix: the index in AA20, 0xFF for every uncoded byte"""
+    lut = np.full(256, 0xFF, dtype=np.uint8)
+    lut[np.frombuffer(AA20, dtype=np.uint8)] = np.arange(20, dtype=np.uint8)
+    return lut[np.asarray(matrix, dtype=np.uint8)]
+
+
+def pair_index(T):
+    """-> int64[P, 2], P = T (T - 1) / 2: the pairs (i, j), i < j, row-major -- (0, 1), (0, 2), .., (T - 2, T - 1)"""
+    i, j = np.triu_indices(int(T), 1)
+    return np.stack([i, j], 1).astype(np.int64)
+
+
+def subst_counts(matrix, keep):
+    """-> int32[P, 20, 20]: N[p, a, b] = the kept columns where taxon i of pair p holds residue a and taxon j residue b (pair_index);
+    a column where either byte is uncoded adds nothing to the pair.  N = E E^T of the one-hot matrix E (row 20 i + a over the columns
+    is code[i] == a), in float32 over at most 2^20 columns at a time (fewer for many taxa: E is held whole): every partial count is an
+    integer below 2^24, so the sums are exact."""
+    matrix = np.asarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('subst_counts: the matrix has two dimensions')
+    T = matrix.shape[0]
+    keep = np.asarray(keep, dtype=np.int64)
+    if len(keep) >= 2 ** 31:
+        raise ValueError('subst_counts: 2^31 kept columns and more are not supported (32-bit counts)')
+    pi = pair_index(T)
+    N = np.zeros((len(pi), 20, 20), dtype=np.int64)
+    step = max(1024, min(1 << 20, (1 << 26) // max(1, 20 * T)))
+    res = np.arange(20, dtype=np.uint8)
+    for c0 in range(0, len(keep), step):
+        code = residue_codes(matrix[:, keep[c0:c0 + step]])
+        E = (code[:, None, :] == res[None, :, None]).astype(np.float32).reshape(20 * T, -1)
+        G = np.rint(E @ E.T).astype(np.int64).reshape(T, 20, T, 20)
+        N += G[pi[:, 0], :, pi[:, 1], :]
+    return N.astype(np.int32)
+
+
+def boot_subst(matrix, keep, seed, b):
+    """-> int32[P, 20, 20] of replicate b: subst_counts over keep[boot_columns(seed, b, len(keep))], as boot_counts draws them"""
+    keep = np.asarray(keep, dtype=np.int64)
+    return subst_counts(matrix, keep[boot_columns(seed, b, len(keep))])
+
+
+def _logdet_pair(N):
+    """one 20 x 20 table -> (d, None), or (nan, why) where the pair has no logdet distance"""
+    N = np.asarray(N).astype(np.float64)
+    r, c = N.sum(1), N.sum(0)
+    if (r == 0).any() or (c == 0).any():
+        a = int(np.flatnonzero((r == 0) | (c == 0))[0])
+        return np.nan, 'residue %s never occurs in one of the two over the columns they share' % AA20[a:a + 1].decode()
+    sign, ld = np.linalg.slogdet(N)
+    if not sign > 0:
+        return np.nan, 'their table of residue pairs is singular (or its determinant is negative)'
+    return ((np.log(r).sum() + np.log(c).sum()) / 2. - ld) / 20., None      # = -(ld - (..) / 2) / 20, and 0.0 (not -0.0) where the two are equal
+
+
+def _logdet(subst, T):
+    """-> (D float64[T, T], first bad (i, j, why) or None): every pair once, mirrored, the diagonal 0.0 -- symmetric bit for bit"""
+    if subst is None:
+        raise ValueError("distances: model 'logdet' needs the substitution counts (subst_counts)")
+    subst = np.asarray(subst)
+    pi = pair_index(T)
+    if subst.shape != (len(pi), 20, 20):
+        raise ValueError('distances: the substitution counts are not [%d, 20, 20]' % len(pi))
+    D, bad = np.zeros((T, T), dtype=np.float64), None
+    for (i, j), N in zip(pi.tolist(), subst):
+        d, why = _logdet_pair(N)
+        if why is not None and bad is None:
+            bad = (i, j, why)
+        D[i, j] = D[j, i] = d
+    return D, bad
+
+
+def _kimura(p):
+    """-> (D, argwhere of the pairs without a distance): -log(1 - p - p * p / 5)"""
+    q = (1. - p) - p * p / 5.
+    bad = np.argwhere(~(q > 0.))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return -np.log(q) + np.zeros(p.shape), bad
+
+
+def distances(cmp, same, model='p', names=None, subst=None):
+    """-> float64[T, T]: p = 1 - same / cmp; poisson: -log(1 - p); kimura: -log(1 - p - p * p / 5); logdet: from `subst` (subst_counts),
+    per pair -(log det N - (sum log r + sum log c) / 2) / 20 with r, c the row and column sums of N (the column total cancels: no
+    frequencies are formed).  A pair without a compared column, poisson with p >= 1, kimura with 1 - p - p * p / 5 <= 0 and logdet with a
+    residue that one of the two taxa never shows, or with a singular table, refuse (the last two as DistanceRefused)"""
+    if model not in MODELS:
+        raise ValueError(_NO_MODEL)
     cmp, same = np.asarray(cmp, dtype=np.int64), np.asarray(same, dtype=np.int64)
     T = len(cmp)
     who = lambda k: _label(names[k]) if names is not None else str(k)
     bad = np.argwhere(cmp == 0)
     if len(bad):
-        raise ValueError('distances: taxa %s and %s share no compared column' % (who(bad[0][0]), who(bad[0][1])))
+        raise (ValueError if model in ('p', 'poisson') else DistanceRefused)('distances: taxa %s and %s share no compared column' % (who(bad[0][0]), who(bad[0][1])))
+    if model == 'logdet':
+        D, bad = _logdet(subst, T)
+        if bad is not None:
+            raise DistanceRefused('distances: taxa %s and %s have no logdet distance: %s' % (who(bad[0]), who(bad[1]), bad[2]))
+        return D
     p = 1. - same.astype(np.float64) / cmp.astype(np.float64)
     if model == 'p':
         return p
+    if model == 'kimura':
+        D, bad = _kimura(p)
+        if len(bad):
+            raise DistanceRefused('distances: taxa %s and %s differ in too many compared columns (p = %.4f): no kimura distance' % (who(bad[0][0]), who(bad[0][1]), p[tuple(bad[0])]))
+        return D
     bad = np.argwhere(p >= 1.)
     if len(bad):
         raise ValueError('distances: taxa %s and %s differ in every compared column: no poisson distance' % (who(bad[0][0]), who(bad[0][1])))
@@ -557,17 +668,24 @@ def boot_counts(matrix, keep, seed, b):
     return pair_counts(matrix, keep[boot_columns(seed, b, len(keep))])
 
 
-def boot_distances(cmp, same, model='p'):
+def boot_distances(cmp, same, model='p', subst=None):
     """-> (D float64[T, T], ok): distances() without its refusals.  ok is False when a pair has no compared column, under poisson also
-    when a pair has p >= 1: such a replicate is dropped, not refused (its D holds NaN or inf there)."""
-    if model not in ('p', 'poisson'):
-        raise ValueError("distances: the model is 'p' or 'poisson'")
+    when a pair has p >= 1, under kimura when 1 - p - p * p / 5 <= 0, under logdet when a pair's table lacks a residue on one side or is
+    singular: such a replicate is dropped, not refused (its D holds NaN or inf there)."""
+    if model not in MODELS:
+        raise ValueError(_NO_MODEL)
     cmp, same = np.asarray(cmp, dtype=np.int64), np.asarray(same, dtype=np.int64)
     ok = not (cmp == 0).any()
+    if model == 'logdet':
+        D, bad = _logdet(subst, len(cmp))
+        return D, ok and bad is None
     with np.errstate(divide='ignore', invalid='ignore'):
         p = 1. - same.astype(np.float64) / cmp.astype(np.float64)
         if model == 'p':
             return p, ok
+        if model == 'kimura':
+            D, bad = _kimura(p)
+            return D, ok and not len(bad)
         ok = ok and not (p >= 1.).any()
         return -np.log(1. - p) + np.zeros(p.shape), ok
 
@@ -646,6 +764,59 @@ def device_boot_counts(matrix, keep, seed, b0, nb, device=0):
         L.so_phy_boot_free(C.byref(res))
 
 
+def _device_subst(who, matrix, keep, seed, b0, nb, device, stats=None, want=True, timed=False):
+    """so_phy_subst -> int32[max(nb, 1), P, 20, 20] (None without `want`); nb = 0: the kept columns"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('%s: the matrix has two dimensions' % who)
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    T, nc = matrix.shape
+    res = _lib.SoPhySubstResult()
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    flags = (0 if want else 1) | (2 if timed else 0)
+    if L.so_phy_subst(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(b0), int(nb), flags, C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        if stats is not None:
+            stats['waits'], stats['bytes'] = int(res.waits), int(res.bytes)
+            if timed:
+                stats['code_ms'], stats['product_ms'] = float(res.code_ms), float(res.product_ms)
+        n, P = int(res.n_reps), int(res.n_pairs)
+        return _lib.result_array(res.subst, n * P * 400, np.int32).reshape(n, P, 20, 20) if want else None
+    finally:
+        L.so_phy_subst_free(C.byref(res))
+
+
+def device_subst_counts(matrix, keep, device=0, stats=None):
+    """subst_counts() in one device call (so_phy_subst) -> int32[P, 20, 20]; a refusal raises RuntimeError with the library's message"""
+    return _device_subst('device_subst_counts', matrix, keep, 0, 0, 0, device, stats)[0]
+
+
+def device_boot_subst(matrix, keep, seed, b0, nb, device=0, stats=None):
+    """boot_subst() of replicates b0 .. b0 + nb - 1 in one device call (so_phy_subst) -> int32[nb, P, 20, 20]"""
+    if int(nb) < 1:
+        raise ValueError('device_boot_subst: a replicate at least')
+    return _device_subst('device_boot_subst', matrix, keep, seed, b0, nb, device, stats)
+
+
+def model_subst(sm, model, device_stage=False, device=0):
+    """the substitution counts `model` needs over sm's kept columns (None for every model but logdet), computed once and kept in
+    sm.subst: device_stage: so_phy_subst, else subst_counts"""
+    if model != 'logdet':
+        return None
+    if getattr(sm, 'subst', None) is None:
+        if sm.matrix is None:
+            raise ValueError('tree: the supermatrix was built without its matrix')
+        try:
+            sm.subst = device_subst_counts(sm.matrix, sm.keep, device) if device_stage else subst_counts(sm.matrix, sm.keep)
+        except RuntimeError as e:
+            raise ValueError('tree: %s' % e)
+    return sm.subst
+
+
 def device_nj_splits(D, device=0, clades_in_global=False):
     """nj_splits() of nb matrices D float64[nb, T, T] in one device call (so_phy_nj_splits), a workgroup per matrix -> uint64[nb, T - 3, W].
     The device reads D[k][i] for D[i][k]: a D that is not symmetric bit for bit is refused, as a non-finite one is.  clades_in_global
@@ -703,7 +874,8 @@ def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, 
 def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0, stats=None, want_splits=True):
     """-> (count int32[T - 3], valid, ok bool[B], splits uint64[B, T - 3, W] or None): everything bootstrap() is made from.  Host: the
     numpy definitions replicate by replicate.  device_stage, model p: so_phy_boot; poisson: the counts of a batch by so_phy_boot_counts,
-    the distances on the host (the device's log is not numpy's), the trees by so_phy_nj_splits, the support by split_support."""
+    the distances on the host (the device's log is not numpy's), the trees by so_phy_nj_splits, the support by split_support; kimura
+    goes poisson's way, logdet too, with the tensors of the batch by so_phy_subst and the determinants on the host."""
     B, seed = int(B), int(seed)
     if not 1 <= B < 2 ** 31:
         raise ValueError('bootstrap: B lies in 1 .. 2^31 - 1')
@@ -711,7 +883,8 @@ def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0,
         raise ValueError('bootstrap: the supermatrix was built without its matrix')
     T = len(sm.taxa)
     S, W = max(T - 3, 0), (T + 63) // 64
-    ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa)) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
+    logdet = model == 'logdet'
+    ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa, model_subst(sm, model, device_stage, device))) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
     if len(sm.keep) == 0:
         raise ValueError('bootstrap: no kept column to draw from')
     if device_stage and model == 'p':
@@ -722,15 +895,16 @@ def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0,
     ok, splits = np.zeros(B, dtype=bool), np.zeros((B, S, W), dtype=np.uint64)
     if device_stage:
         Kp = (len(sm.keep) + 15) & ~15
-        step = _boot_batch(B, T * Kp + 16 * T * T)
+        step = _boot_batch(B, T * Kp + 16 * T * T + (2 * T * Kp + 800 * T * (T - 1) if logdet else 0))   # (logdet: codes and the tensor, 1600 bytes a pair)
         calls = 0
         for b0 in range(0, B, step):
             nb = min(step, B - b0)
             try:
                 cmp_, same = device_boot_counts(sm.matrix, sm.keep, seed, b0, nb, device)
-                dist = [boot_distances(cmp_[k], same[k], model) for k in range(nb)]
+                sub = device_boot_subst(sm.matrix, sm.keep, seed, b0, nb, device) if logdet else [None] * nb
+                dist = [boot_distances(cmp_[k], same[k], model, sub[k]) for k in range(nb)]
                 good = [k for k in range(nb) if dist[k][1]]
-                calls += 1
+                calls += 2 if logdet else 1
                 if good and S:
                     splits[[b0 + k for k in good]] = device_nj_splits(np.stack([dist[k][0] for k in good]), device)
                     calls += 1
@@ -741,7 +915,7 @@ def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0,
             stats['calls'] = calls
     else:
         for b in range(B):
-            D, ok[b] = boot_distances(*boot_counts(sm.matrix, sm.keep, seed, b), model=model)
+            D, ok[b] = boot_distances(*boot_counts(sm.matrix, sm.keep, seed, b), model=model, subst=boot_subst(sm.matrix, sm.keep, seed, b) if logdet else None)
             if ok[b]:
                 splits[b] = nj_splits(D)
     return split_support(ref, splits, ok), int(ok.sum()), ok, splits if want_splits else None
@@ -767,7 +941,7 @@ def supermatrix_fasta(taxa, matrix, keep):
 def tree(sm, model='p', boot=0, seed=1, device_stage=False, device=0, stats=None):
     """Supermatrix -> Newick bytes over its taxa; boot > 0: every node a join makes carries the share of the valid bootstrap replicates
     that hold its split (bootstrap(); stats: 'boot', 'boot_valid' and the device's counters)"""
-    D = distances(sm.cmp, sm.same, model, sm.taxa)
+    D = distances(sm.cmp, sm.same, model, sm.taxa, model_subst(sm, model, device_stage, device))
     if int(boot) <= 0:
         return neighbor_joining(D, sm.taxa)
     count, valid = bootstrap(sm, boot, seed, model, device_stage, device, stats)

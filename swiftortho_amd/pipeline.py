@@ -260,7 +260,7 @@ def pan_genome_from_search(fasta_path, ts=.05, tc=.95, taxa=None, pan_device=Tru
 def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', boot=0, boot_seed=1, **search_kw):
     """one process from a FASTA file to the species tree of its taxa: self-search on the GPU with a CIGAR on every row, the core-gene
     table of `reference` (default: the taxon with most genes), the core-gene supermatrix from the rows' own alignments (swiftortho_amd.phy:
-    no aligner runs), the distances over its kept columns (`gap_share`, `model` 'p' or 'poisson') and neighbour joining -- what
+    no aligner runs), the distances over its kept columns (`gap_share`, `model` 'p', 'poisson', 'kimura' or 'logdet' -- the last from the substitution counts, device_stage: so_phy_subst) and neighbour joining -- what
     `bin/find_hit.py -C T ... && scripts/rbh2phy.py -A T -t x.nwk` write.  device_stage: the table, the picked rows, the matrix and the
     pair counts on the GPU (so_rbh_cols, so_phy_rows, so_phy_build), else by the numpy definitions; the records and the CIGARs are the host
     copies either way.  boot > 0: the tree's nodes carry their bootstrap support over `boot` replicates of the kept columns drawn from

@@ -386,12 +386,13 @@ def main_rbh2phy(argv=None):
     argv = list(sys.argv if argv is None else argv)
     args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p', '-B': '0', '-S': '1'})
     if args['-i'] == '' or args['-f'] == '':
-        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson] [-B replicates] [-S seed]]')
+        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson|kimura|logdet] [-B replicates] [-S seed]]')
         print(' -i: blast -m8 or find_hit .sc file; ids are taxon|gene\n -f: the FASTA file the search read\n -r: reference taxon (default: the taxon with most genes)')
         print(' -G: the winner list and the table on the GPU [T|F]. Default: F\n -o: also write one tab-separated line of ids per group')
         print(' -A: join the families into the core-gene supermatrix from the CIGARs of the rows (find_hit.py -C T) and print it as FASTA [T|F]. Default: F')
         print(' -g: with -A T, keep the columns whose share of gaps is at most this. Default: 1 (every column)')
-        print(' -t: with -A T, write the neighbour-joining tree of the taxa to this file\n -m: distance of the tree [p|poisson]. Default: p')
+        print(' -t: with -A T, write the neighbour-joining tree of the taxa to this file\n -m: distance of the tree [p|poisson|kimura|logdet]. Default: p')
+        print('     kimura: -log(1 - p - p*p/5); logdet: the paralinear distance from the 20 x 20 residue-pair table of every pair of taxa (with -G T: on the GPU)')
         print(' -B: with -t, label the tree\'s nodes with their bootstrap support over this many replicates (with -G T: on the GPU). Default: 0 (no labels)')
         print(' -S: seed of the bootstrap\'s column draws, 0 .. 2^64 - 1. Default: 1')
         raise SystemExit()
@@ -413,7 +414,7 @@ def main_rbh2phy(argv=None):
         try:
             share = float(args['-g'])
             sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']), boot=boot, seed=seed)
-        except phy.MissingCigar as e:
+        except (phy.MissingCigar, phy.DistanceRefused) as e:
             sys.stderr.write('rbh2phy: %s\n' % e)
             return 2
         except ValueError as e:
