@@ -659,6 +659,8 @@ const char *so_phy_last_error(void);
  *   flags bit 0: splits [n_reps][n_taxa - 3][n_words] of every replicate come back too (zeros for a dropped one); bit 1: events around the
  *   stages of every batch -- counts_ms (columns, pair counts, distances), trees_ms, support_ms.  Replicates run in
  *   batches sized from the free device memory (SOHIT_PHY_BOOT_BATCH forces the size), one host wait per batch: waits == batches.
+ * nj_tier (both calls that walk): 1 while row sums, live lists and clade bit sets fit the walk's LDS budget (n_taxa <= 640), 2 beyond it or
+ *   under so_phy_nj_splits' flags bit 0 (the bit sets in global scratch), 0 where n_taxa < 4 leaves nothing to walk.
  * Refused with a message (so_phy_last_error) and nothing left allocated: n_taxa below 2 or above 4096, n_keep of 0, n_reps below 1 or
  * b0 + n_reps above 2^31, a keep entry outside 0 .. n_cols - 1, a D that is not finite or not symmetric, unknown flag bits. */
 typedef struct so_phy_boot_result {
@@ -669,6 +671,8 @@ typedef struct so_phy_boot_result {
     uint64_t *splits;             /* so_phy_nj_splits, so_phy_boot with flags bit 0: n_reps * n_splits * n_words */
     int32_t *count;               /* so_phy_boot: n_splits */
     uint8_t *ok;                  /* so_phy_boot: n_reps */
+    int32_t nj_tier;              /* so_phy_nj_splits, so_phy_boot: where the walk kept its clade bit sets -- 0: no walk (n_taxa < 4), 1: LDS, 2: global scratch */
+    int32_t reserved;
 } so_phy_boot_result;
 int so_phy_boot_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, uint64_t seed,
                        int64_t b0, int64_t n_reps, int32_t flags, so_phy_boot_result *out);

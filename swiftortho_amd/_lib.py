@@ -135,7 +135,8 @@ class SoPhyBootResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_reps", "n_splits", "n_words", "valid")] + \
                [("waits", C.c_int32), ("batches", C.c_int32), ("counts_ms", C.c_double), ("trees_ms", C.c_double), ("support_ms", C.c_double),
                 ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64)),
-                ("splits", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)), ("ok", C.POINTER(C.c_uint8))]
+                ("splits", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)), ("ok", C.POINTER(C.c_uint8)),
+                ("nj_tier", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SoPhySubstResult(C.Structure):

@@ -607,6 +607,7 @@ void boot_counts_batch(hipStream_t st, const u8* matrix, u32 T, u32 L, u32 K, co
 }
 
 // the walk of nb matrices; clades: the scratch of the bit sets (nb * T * W words) or null where they fit the LDS
+static_assert(sizeof(so_phy_boot_result) == 120, "nj_tier and its pad word follow the pointers: swiftortho_amd/_lib.py SoPhyBootResult mirrors the layout");
 size_t nj_lds_bytes(u32 T, u32 W, bool in_lds) { return (size_t)T * 8u + (in_lds ? (size_t)T * W * 8u : 0u) + (size_t)T * 4u; }
 bool nj_clades_fit(u32 T, u32 W) { return nj_lds_bytes(T, W, true) <= PHY_NJ_LDS_BYTES; }
 void nj_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, ull* splits, ull* clades) {
@@ -909,6 +910,7 @@ int so_phy_nj_splits(int device, int64_t n_reps, int64_t n_taxa, const double* D
             return;
         }
         const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
+        out->nj_tier = in_lds ? 1 : 2;
         DeviceCall call(device);
         hipStream_t st = call.st;
         DevBuf<double> d_D;
@@ -960,6 +962,7 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
         HIP_CHECK(hipMemsetAsync(d_count.p, 0, ((size_t)S + 2) * sizeof(u32), st));
         // a batch: the drawn columns, two counters and a distance per pair, the splits and the bit sets of every replicate
         const bool in_lds = S && nj_clades_fit(T, W);
+        out->nj_tier = S ? (in_lds ? 1 : 2) : 0;
         const size_t per_rep = (size_t)T * Kp + 3u * TT * 8u + SW * 8u + (S && !in_lds ? (size_t)T * W * 8u : 0u) + 1u;
         size_t batch = (size_t)call.tn.phy_boot_batch;
         if (call.tn.phy_boot_batch <= 0) {

@@ -817,10 +817,11 @@ def model_subst(sm, model, device_stage=False, device=0):
     return sm.subst
 
 
-def device_nj_splits(D, device=0, clades_in_global=False):
+def device_nj_splits(D, device=0, clades_in_global=False, stats=None):
     """nj_splits() of nb matrices D float64[nb, T, T] in one device call (so_phy_nj_splits), a workgroup per matrix -> uint64[nb, T - 3, W].
     The device reads D[k][i] for D[i][k]: a D that is not symmetric bit for bit is refused, as a non-finite one is.  clades_in_global
-    (tests): the clade bit sets in global scratch, where the call keeps them once they outgrow the LDS"""
+    (tests): the clade bit sets in global scratch, where the call keeps them once they outgrow the LDS.  stats: 'nj_tier', where they were
+    kept (0: T < 4, no walk; 1: LDS; 2: global scratch)"""
     import ctypes as C
     from . import _lib
     L = _lib.load()
@@ -832,6 +833,8 @@ def device_nj_splits(D, device=0, clades_in_global=False):
     if L.so_phy_nj_splits(int(device), nb, T, C.c_void_p(D.ctypes.data), 1 if clades_in_global else 0, C.byref(res)) != 0:
         raise RuntimeError(L.so_phy_last_error().decode())
     try:
+        if stats is not None:
+            stats['nj_tier'] = int(res.nj_tier)
         S, W = max(T - 3, 0), (T + 63) // 64
         return _lib.result_array(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
     finally:
@@ -841,8 +844,9 @@ def device_nj_splits(D, device=0, clades_in_global=False):
 def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, stats=None, timed=False):
     """the fused bootstrap of model p (so_phy_boot): counts, D = 1 - same / cmp, the trees and their comparison with ref_splits stay on
     the device, in batches of replicates with one host wait each -> (count int32[T - 3], valid, ok bool[B], splits uint64[B, T - 3, W] or
-    None); a dropped replicate's splits are zeros.  stats: 'waits', 'batches'; timed: also 'counts_ms', 'trees_ms', 'support_ms', the
-    device time of the stages by events"""
+    None); a dropped replicate's splits are zeros.  stats: 'waits', 'batches'; a stats that comes with the key 'nj_tier' gets it filled
+    (device_nj_splits: where the walk kept its bit sets; the callers that compare or print the whole dict see no new key); timed: also
+    'counts_ms', 'trees_ms', 'support_ms', the device time of the stages by events"""
     import ctypes as C
     from . import _lib
     L = _lib.load()
@@ -863,6 +867,8 @@ def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, 
     try:
         if stats is not None:
             stats['waits'], stats['batches'] = int(res.waits), int(res.batches)
+            if 'nj_tier' in stats:
+                stats['nj_tier'] = int(res.nj_tier)
             if timed:
                 stats['counts_ms'], stats['trees_ms'], stats['support_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.support_ms)
         splits = _lib.result_array(res.splits, B * S * W, np.uint64).reshape(B, S, W) if want_splits else None

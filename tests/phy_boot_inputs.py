@@ -1,6 +1,13 @@
 """Designed inputs of the bootstrap of the species tree (swiftortho_amd/phy.py boot_columns .. bootstrap, csrc/phy.hip so_phy_boot*) and
 the literal restatements its tests compare with: Python-int splitmix64, a neighbour-joining walk over Python floats and lists, the
-bootstrap replicate by replicate.  Shared by tests/test_phy_boot.py (numpy definitions) and tests/test_gpu_phy_boot.py (device == numpy)."""
+bootstrap replicate by replicate.  Shared by tests/test_phy_boot.py (numpy definitions) and tests/test_gpu_phy_boot.py (device == numpy).
+
+The wide inputs (NJ_WIDE_TAXA, cherries, wide_boot_case) take k_phy_nj past one pass of its 256 lanes and to both sides of its LDS limit.
+Not run, on purpose:
+  * 4096 taxa, the end of the u16 live list.  The numpy walk is cubic: 0.08 s per matrix at 257 taxa, 1.3 s at 641, 5.9 s at 1025, so
+    about 5.9 * 4 ** 3 = 380 s at 4096 -- per matrix, before the device is asked anything.  641 is the widest input here.
+  * a finite D so large that (n - 2) * D overflows.  Every Q is then inf or NaN; numpy's argmin over an all-inf Q gives its first entry,
+    (0, 0), where the kernel starts from (inf, 0, 1) and never replaces it: the two disagree and neither is a tree.  Out of scope."""
 import functools
 
 import numpy as np
@@ -146,6 +153,98 @@ def nj_gpu_stack(T, nb):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# wide matrices: beyond one pass of the walk's 256 lanes, and its LDS limit
+# ---------------------------------------------------------------------------------------------------------
+NJ_THREADS = 256          # csrc/tune.h PHY_NJ_THREADS
+NJ_LDS_BYTES = 61440      # csrc/tune.h PHY_NJ_LDS_BYTES
+NJ_WIDE_TAXA = (255, 256, 257, 513, 640, 641)   # one below, at and one above a pass; a third pass of one column; the two sides of the LDS limit
+NJ_WIDE_KINDS = ("random", "additive", "all_equal", "duplicated")
+
+
+def nj_lds_bytes(T, in_lds=True):
+    """csrc/phy.hip nj_lds_bytes: the row sums (T doubles), the clade bit sets (T * W words, where they are in the LDS), two u16 live lists"""
+    W = (T + 63) // 64
+    return T * 8 + (T * W * 8 if in_lds else 0) + T * 4
+
+
+def nj_tier(T, forced_global=False):
+    """what so_phy_boot_result.nj_tier must say: 0 no walk, 1 clades in the LDS, 2 in global scratch"""
+    if T < 4:
+        return 0
+    return 1 if not forced_global and nj_lds_bytes(T) <= NJ_LDS_BYTES else 2
+
+
+def nj_wide_stack(T):
+    """four matrices of T taxa, NJ_WIDE_KINDS: random (every rounding counts), additive (the tree is known), all equal (every step a tie),
+    duplicated taxa (zero distances)"""
+    return np.stack([random_symmetric(T, 1), additive(T)[1], all_equal(T), duplicated(T)])
+
+
+@functools.lru_cache(maxsize=None)
+def nj_wide_want(T, k):
+    """phy.nj_splits of member k of nj_wide_stack(T), computed once per process: uint64[T - 3, W], not to be written to"""
+    from swiftortho_amd import phy
+    out = phy.nj_splits(nj_wide_stack(T)[k])
+    out.setflags(write=False)
+    return out
+
+
+def additive_inner_splits(T):
+    """the inner edges of the tree additive(T) was made from, as canonical word tuples"""
+    edges, _ = additive(T)
+    return {canonical(s, T) for s in pin.tree_splits(edges, T) if 1 < len(s) < T - 1}
+
+
+def cherries(T, pairs):
+    """a star of T leaves at distance 10 from the centre; each pair (x, y) is a cherry: two leaves of length 1 on a node 9 from the centre.
+    D is 2 inside a cherry and 20 everywhere else off the diagonal: small integers, every Q exact, two cherries tie bit for bit"""
+    D = np.full((T, T), 20.)
+    np.fill_diagonal(D, 0.)
+    for x, y in pairs:
+        D[x, y] = D[y, x] = 2.
+    return D
+
+
+# (pairs, the first join, the second join): two tied cherries, the lexicographically lowest (row, column) first.  The joins are written down
+# from the definition, not taken from an implementation.  At T = 600 a lane of the walk owns the columns b, b + 256, b + 512:
+CHERRY_T = 600
+CHERRY_CASES = (
+    (((300, 301), (5, 557)), {5, 557}, {300, 301}),     # columns 301 and 557 are one lane's (45 mod 256): it meets the loser first
+    (((5, 301), (300, 557)), {5, 301}, {300, 557}),     # the same lane: it meets the winner first
+    (((7, 520), (8, 264)), {7, 520}, {8, 264}),         # the same lane (8 mod 256): the larger column wins on the lower row
+    (((7, 450), (8, 70)), {7, 450}, {8, 70}),           # lanes 194 and 70, waves 3 and 1: the reduction across waves decides
+)
+# the same relative layouts on 12 taxa, for the literal walk
+CHERRY_SMALL_T = 12
+CHERRY_SMALL_CASES = (
+    (((6, 7), (1, 11)), {1, 11}, {6, 7}),
+    (((1, 7), (6, 11)), {1, 7}, {6, 11}),
+    (((2, 10), (3, 5)), {2, 10}, {3, 5}),
+    (((2, 9), (3, 4)), {2, 9}, {3, 4}),
+)
+assert all(x % NJ_THREADS == y % NJ_THREADS for (_, x), (_, y) in (c[0] for c in CHERRY_CASES[:3]))
+assert [[(y % NJ_THREADS) // 64 for _, y in c[0]] for c in CHERRY_CASES[3:]] == [[3, 1]]
+
+
+@functools.lru_cache(maxsize=None)
+def cherry_want(k):
+    """phy.nj_splits of cherries(CHERRY_T, CHERRY_CASES[k][0]), computed once per process; not to be written to"""
+    from swiftortho_amd import phy
+    out = phy.nj_splits(cherries(CHERRY_T, CHERRY_CASES[k][0]))
+    out.setflags(write=False)
+    return out
+
+
+def first_difference(got, want):
+    """-> (join, got words, want words) of the first row where two split arrays differ, None where they are equal"""
+    bad = np.flatnonzero((np.asarray(got) != np.asarray(want)).any(axis=1))
+    if not len(bad):
+        return None
+    j = int(bad[0])
+    return j, [hex(int(x)) for x in got[j]], [hex(int(x)) for x in want[j]]
+
+
+# ---------------------------------------------------------------------------------------------------------
 # matrices to draw columns from
 # ---------------------------------------------------------------------------------------------------------
 class Sm:
@@ -208,6 +307,31 @@ def boot_cases():
             ("T65", Sm(pin.gap_matrix(np.random.RandomState(22), 65, 333, .1)), 7, 0, True),
             ("T4", Sm(pin.gap_matrix(np.random.RandomState(23), 4, 50, .1)), 7, 2, True),
             ("T3", Sm(pin.gap_matrix(np.random.RandomState(24), 3, 50, .1)), 7, 2, True))
+
+
+WIDE_BOOT = ((257, 96, 8), (641, 80, 3))      # (taxa, columns, replicates), seed 1
+
+
+@functools.lru_cache(maxsize=None)
+def wide_boot_case(T, K, seed=1):
+    """T taxa over K columns, 5 % gaps; column 0 holds one residue in every row, taxon T - 2 is gapped over columns 1 .. K / 2 - 1 and
+    taxon T - 1 from column K / 2 on: the two share exactly ONE compared column, and a replicate that does not draw it is dropped
+    -> Sm (with .seed)"""
+    m = pin.gap_matrix(np.random.RandomState(40 + T), T, K, .05)
+    m[:, 0] = pin.AA[0]
+    m[T - 2, 1:K // 2] = GAP
+    m[T - 1, K // 2:] = GAP
+    sm = Sm(m)
+    sm.seed = seed
+    return sm
+
+
+@functools.lru_cache(maxsize=None)
+def wide_boot_want(T, K, B, model="p"):
+    """-> (Sm, seed, phy.bootstrap_replicates on the host), computed once per process"""
+    from swiftortho_amd import phy
+    sm = wide_boot_case(T, K)
+    return sm, sm.seed, phy.bootstrap_replicates(sm, B, sm.seed, model)
 
 
 COUNT_TAXA = (2, 63, 64, 65, 129)

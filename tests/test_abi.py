@@ -37,6 +37,9 @@ def test_struct_layouts_match_header(lib):
     assert C.sizeof(lib.SoHit) == 80
     assert C.sizeof(lib.SoParams) == 2 * C.sizeof(C.c_void_p) + 5 * 8 + 2 * 8 + 2 * 4
     assert lib.load().so_abi_version() == 3
+    # so_phy_boot_result: 5 x i64, 2 x i32, 3 x f64, 5 ptr, then nj_tier and its pad word (appended: every earlier offset stays)
+    assert C.sizeof(lib.SoPhyBootResult) == 5 * 8 + 2 * 4 + 3 * 8 + 5 * C.sizeof(C.c_void_p) + 2 * 4 == 120
+    assert lib.SoPhyBootResult.ok.offset == 104 and lib.SoPhyBootResult.nj_tier.offset == 112
 
 
 def test_no_cpu_fallback(lib):

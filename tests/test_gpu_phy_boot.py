@@ -1,7 +1,15 @@
 """The bootstrap of the species tree on the GPU (csrc/phy.hip, include/sohit.h so_phy_boot_counts / so_phy_nj_splits / so_phy_boot) against
 the numpy definitions (swiftortho_amd/phy.py) array for array and bit set for bit set, on the designed inputs of tests/phy_boot_inputs.py:
 device memory poisoned, every call twice in one process, every batch edge, every refusal; then scripts/rbh2phy.py -B on a proteome of six
-taxa.
+taxa.  The walk (k_phy_nj) is also run beyond one pass of its 256 lanes and on both sides of its LDS limit: test_nj_splits_wide,
+test_nj_ties_across_a_lanes_columns, test_boot_wide; nj_tier in the result says where the clade bit sets were kept.
+
+Observed on an MI355X, numpy reference included (it is nearly all of it: one device call of the four wide matrices takes 0.014 s at 257
+taxa and 0.14 s at 641, in either tier):
+test_nj_splits_wide 0.4 s at 255 - 257 taxa, 2.1 s at 513, 3.6 s at 640, 3.7 s at 641; test_nj_ties_across_a_lanes_columns 1.9 s;
+test_boot_wide 0.6 s at 257 x 96 and 1.8 s at 641 x 80.  No path disagreed with numpy.  Deviation check, each change alone in the kernel:
+a lane's argmin that replaces only on a smaller Q fails test_nj_ties_across_a_lanes_columns and nothing else; a cross-wave pick on Q
+alone fails that test and the stacks of 128, 129, 256, 513, 640 and 641 taxa.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_phy_boot.py -m gpu -q
 """
@@ -92,6 +100,54 @@ def test_nj_splits(phy, T):
             assert (got == want).all(), (T, nb, in_global, np.argwhere((got != want).any(axis=(1, 2))).ravel().tolist())
 
 
+def same_walk(got, want, label):
+    """word for word; a mismatch names the input and the first join that differs"""
+    assert got.dtype == np.uint64 and got.shape == want.shape, (label, got.shape, want.shape)
+    assert (got == want).all(), (label, "first differing join, device words, numpy words:", bin_.first_difference(got, want))
+
+
+@pytest.mark.parametrize("T", bin_.NJ_WIDE_TAXA)
+def test_nj_splits_wide(phy, T):
+    """more taxa than the walk has lanes: second and third passes of the row sums, the argmin, the new row and the live list, five to eleven
+    clade words, and the two sides of the LDS limit -- 640 taxa ask for 58880 bytes of LDS, 641 would need 64100 and go to global scratch by
+    themselves; nj_tier says which one ran"""
+    D = bin_.nj_wide_stack(T)
+    want = np.stack([bin_.nj_wide_want(T, k) for k in range(len(D))])
+    assert want.shape == (4, T - 3, (T + 63) // 64)
+    for in_global in (False, True):
+        stats = {}
+        got = phy.device_nj_splits(D, clades_in_global=in_global, stats=stats)
+        assert stats == {"nj_tier": bin_.nj_tier(T, in_global)}, (T, in_global, stats)
+        assert stats["nj_tier"] == (2 if in_global or T > 640 else 1)
+        assert got.shape == want.shape
+        for k, kind in enumerate(bin_.NJ_WIDE_KINDS):
+            same_walk(got[k], want[k], (T, kind, "global" if in_global else "default"))
+        assert set(bin_.as_tuples(got[bin_.NJ_WIDE_KINDS.index("additive")])) == bin_.additive_inner_splits(T), (T, in_global)
+
+
+def test_nj_ties_across_a_lanes_columns(phy):
+    """two cherries tie bit for bit; the winner has the lowest (row, column).  A lane owns columns b, b + 256, b + 512 and meets the loser
+    before the winner, the winner before the loser, or the winner on the larger column; or the two sit in different waves.  The first two
+    joins are the input file's literal sets; the rest of the walk (ties at every later step) is numpy's"""
+    T = bin_.CHERRY_T
+    D = np.stack([bin_.cherries(T, pairs) for pairs, _, _ in bin_.CHERRY_CASES])
+    for in_global in (False, True):
+        stats = {}
+        got = phy.device_nj_splits(D, clades_in_global=in_global, stats=stats)
+        assert stats == {"nj_tier": 2 if in_global else 1}
+        for k, (pairs, first, second) in enumerate(bin_.CHERRY_CASES):
+            assert bin_.as_tuples(got[k, :2]) == [bin_.canonical(first, T), bin_.canonical(second, T)], (pairs, in_global, bin_.as_tuples(got[k, :2]))
+            same_walk(got[k], bin_.cherry_want(k), (T, pairs, in_global))
+
+
+def test_nj_tier_of_the_narrow_calls(phy):
+    """no walk below four taxa; the LDS where nothing asks otherwise; the scratch under the flag"""
+    for T, in_global, want in ((3, False, 0), (3, True, 0), (4, False, 1), (4, True, 2), (129, False, 1)):
+        stats = {}
+        phy.device_nj_splits(bin_.nj_gpu_stack(T, 1) if T > 3 else np.zeros((1, 3, 3)), clades_in_global=in_global, stats=stats)
+        assert stats == {"nj_tier": want} and want == bin_.nj_tier(T, in_global), (T, in_global, stats)
+
+
 def test_nj_splits_small_cases(phy):
     for _, D in bin_.nj_cases():
         got = phy.device_nj_splits(D[None])
@@ -167,6 +223,30 @@ def test_boot_poisson(phy, monkeypatch, key):
         same_boot(phy.bootstrap_replicates(sm, B, seed, "poisson", device_stage=True), want)
     monkeypatch.delenv("SOHIT_PHY_BOOT_BATCH")
     assert phy.tree(sm, "poisson", B, seed, True) == phy.tree(sm, "poisson", B, seed)
+
+
+@pytest.mark.parametrize("T,K,B", bin_.WIDE_BOOT)
+def test_boot_wide(phy, monkeypatch, T, K, B):
+    """the fused path beyond one pass of the walk's lanes and beyond its LDS limit: replicates are dropped (their S * W > 256 zero words take
+    more than one pass), two workgroups of k_phy_boot_support at 641 taxa; at 257 also in batches of 3, each of which starts on a dropped
+    replicate, and the poisson path, whose trees are so_phy_nj_splits'"""
+    sm, seed, want = bin_.wide_boot_want(T, K, B)
+    assert 0 < want[1] < B and want[3].shape[1] * want[3].shape[2] > 256
+    for batch in ("", "3") if T == 257 else ("",):
+        monkeypatch.setenv("SOHIT_PHY_BOOT_BATCH", batch)
+        stats = {"nj_tier": None}
+        got = phy.bootstrap_replicates(sm, B, seed, device_stage=True, stats=stats)
+        for b in np.flatnonzero(got[2] & want[2]).tolist():
+            same_walk(got[3][b], want[3][b], (T, K, "replicate %d" % b, batch))
+        same_boot(got, want)
+        assert all((got[3][b] == 0).all() for b in range(B) if not want[2][b])
+        n = -(-B // 3) if batch else 1
+        assert stats == {"waits": n, "batches": n, "nj_tier": bin_.nj_tier(T)}, stats
+    monkeypatch.delenv("SOHIT_PHY_BOOT_BATCH")
+    if T == 257:
+        want = bin_.wide_boot_want(T, K, B, "poisson")[2]
+        assert want[1] > 0
+        same_boot(phy.bootstrap_replicates(sm, B, seed, "poisson", device_stage=True), want)
 
 
 def test_boot_refusals(phy):

@@ -93,6 +93,49 @@ def test_nj_splits_recover_an_additive_tree(phy, T):
     assert set(bin_.as_tuples(phy.tree_splits(D))) == want
 
 
+def test_cherries_tie_to_the_lowest_row_then_column(phy):
+    """two cherries with the same Q bit for bit: the literal walk joins the one of the lowest (row, column) first, then the other"""
+    T = bin_.CHERRY_SMALL_T
+    for pairs, first, second in bin_.CHERRY_SMALL_CASES:
+        D = bin_.cherries(T, pairs)
+        assert sorted(set(D[np.triu_indices(T, 1)].tolist())) == [2., 20.] and (D == D.T).all()
+        walk = bin_.literal_nj_splits(D.tolist())
+        assert walk[:2] == [bin_.canonical(first, T), bin_.canonical(second, T)], pairs
+        assert bin_.as_tuples(phy.nj_splits(D)) == walk, pairs
+
+
+def test_cherries_at_600_taxa(phy):
+    """the same ties where a lane of the device's walk owns three columns: the definition gives the joins the input file states"""
+    T = bin_.CHERRY_T
+    for k, (pairs, first, second) in enumerate(bin_.CHERRY_CASES):
+        got = bin_.as_tuples(bin_.cherry_want(k)[:2])
+        assert got == [bin_.canonical(first, T), bin_.canonical(second, T)], pairs
+
+
+@pytest.mark.parametrize("T", [257, 641])
+def test_nj_splits_recover_a_wide_additive_tree(phy, T):
+    """beyond 256 taxa and beyond the LDS limit of the device's walk: the additive member of the wide stack gives its own tree"""
+    want = bin_.additive_inner_splits(T)
+    got = bin_.as_tuples(bin_.nj_wide_want(T, bin_.NJ_WIDE_KINDS.index("additive")))
+    assert len(want) == T - 3 and len(got) == T - 3 and set(got) == want
+
+
+def test_wide_taxa_sit_on_the_walks_edges():
+    """csrc/tune.h and csrc/phy.hip restated: 640 taxa are the last whose clade bit sets fit the LDS budget of the walk.  A change of
+    PHY_NJ_LDS_BYTES, PHY_NJ_THREADS or nj_lds_bytes has to move NJ_WIDE_TAXA along"""
+    tune = open(os.path.join(ROOT, "swiftortho_amd", "csrc", "tune.h")).read()
+    assert int(re.search(r"#define PHY_NJ_THREADS (\d+)u", tune).group(1)) == bin_.NJ_THREADS == 256
+    assert int(re.search(r"#define PHY_NJ_LDS_BYTES (\d+)u", tune).group(1)) == bin_.NJ_LDS_BYTES == 61440
+    src = open(os.path.join(ROOT, "swiftortho_amd", "csrc", "phy.hip")).read()
+    assert "return (size_t)T * 8u + (in_lds ? (size_t)T * W * 8u : 0u) + (size_t)T * 4u;" in src
+    assert bin_.nj_lds_bytes(640) == 58880 <= bin_.NJ_LDS_BYTES < 64100 == bin_.nj_lds_bytes(641)
+    assert bin_.nj_lds_bytes(641, False) == 641 * 12 and bin_.nj_lds_bytes(129) < 4700
+    assert [bin_.nj_tier(T) for T in (3, 4, 640, 641)] == [0, 1, 1, 2] and bin_.nj_tier(4, True) == 2 and bin_.nj_tier(3, True) == 0
+    T = bin_.NJ_WIDE_TAXA
+    assert T == (255, 256, 257, 513, 640, 641) and [-(-t // 256) for t in T] == [1, 1, 2, 3, 3, 3] and [(t + 63) // 64 for t in T] == [4, 4, 5, 9, 10, 11]
+    assert all(t - 3 > 256 for t, _, _ in bin_.WIDE_BOOT[1:]) and (257 - 3) * 5 > 256       # two workgroups of splits; a dropped replicate's zeros: two passes
+
+
 def test_nj_splits_small_and_refusals(phy):
     assert phy.nj_splits(np.zeros((3, 3))).shape == (0, 1) and phy.nj_splits(np.zeros((2, 2))).shape == (0, 1)
     assert bin_.as_tuples(phy.nj_splits(bin_.two_minima())) == [(0b111100,), (0b001100,), (0b110000,)]      # (0, 1) first, the lowest of the equal minima: its clade holds taxon 0 and is complemented
@@ -202,6 +245,21 @@ def test_sparse_matrix_drops_replicates(phy):
     for model in ("p", "poisson"):
         c, valid = phy.bootstrap(sm, B, seed, model)
         assert valid <= sum(ok) and (c <= valid).all()
+
+
+@pytest.mark.parametrize("T,K,B", bin_.WIDE_BOOT)
+def test_wide_boot_cases_drop_and_keep(phy, T, K, B):
+    """what the device test of these inputs rests on, from the numpy reference alone: the two last taxa share one compared column; a
+    replicate is dropped, one is kept, and a split of the printed tree is counted"""
+    sm, seed, (count, valid, ok, splits) = bin_.wide_boot_want(T, K, B)
+    assert sm.cmp[T - 2, T - 1] == 1 and (sm.cmp > 0).all()
+    assert 0 < valid == int(ok.sum()) < B and (count > 0).any() and (count <= valid).all()
+    assert all((splits[b] == 0).all() == (not ok[b]) for b in range(B)) and splits.shape[1] * splits.shape[2] > 256
+    if (T, K, B) == (257, 96, 8):
+        assert ok.tolist() == [False, True, True, False, True, True, False, True]         # batches of 3: each starts on a dropped replicate
+        assert 0 < bin_.wide_boot_want(T, K, B, "poisson")[2][1] <= valid
+    else:
+        assert ok.tolist() == [False, True, True]
 
 
 def test_every_other_input_keeps_every_replicate(phy):
