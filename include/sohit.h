@@ -566,6 +566,36 @@ int so_pan_genome(int device, int64_t m, const int32_t *row, const int32_t *taxo
 void so_pan_free(so_pan_result *result);
 const char *so_pan_last_error(void);
 
+/* The families every pair of genomes shares, on the device (csrc/pan.hip): what swiftortho_amd/pan.py `shared_counts()` and `boot_shared()`
+ * define, integer for integer -- the numbers the gene-content distances (Jaccard; overlap, Snel et al. 1999) and the gene-content tree with
+ * its bootstrap support are made from.  The reference has no such product; the numpy functions are the definition.
+ * Input as for so_pan_genome: m members as pairs (row[k], taxon[k]) (a pair listed twice counts once here), n_rows rows, n_taxa taxa.
+ * n_reps == 0: shared[a * n_taxa + b] = the rows present in both a and b over all rows (seed and b0 are not read); n_reps >= 1: the matrices
+ * of the bootstrap replicates b0 .. b0 + n_reps - 1, replicate b over the n_rows rows drawn with replacement as so_phy_boot_counts draws
+ * columns: draw k = ((z >> 32) * n_rows) >> 32 with z = splitmix64's output for the counter (b << 32) + k + 1 added to `seed`; a row drawn
+ * twice counts twice.  The full symmetric matrix with its diagonal (the families of a genome); every entry lies below 2^31.
+ * flags bit 0: no matrix in the result (measurements); bit 1: events around the passes -- draw_ms, product_ms, summed over the batches.
+ * Output (allocated by the library, released with so_pan_shared_free()): shared[max(n_reps, 1) * n_taxa * n_taxa]; n_reps: the matrices
+ * in it; bytes: their size; batches: the groups of replicates whose presence words lay in device memory together (sized from the free
+ * device memory, SOHIT_PAN_BOOT_BATCH forces the size); ranges: the ranges the row words of the last launch were cut into
+ * (SOHIT_PAN_SHARED_RANGES forces the number); waits: host waits of the call -- one, whatever the batches.  n_rows = 0 with n_reps = 0 is
+ * served and launches nothing.  Integers only: nothing depends on scheduling.
+ * Refused with a message (so_pan_last_error) and nothing left allocated: a row or taxon out of range, n_taxa below 1 or above 4096, n_rows
+ * or m >= 2^31, n_reps below 0 or above 32768, b0 + n_reps above 2^31, n_reps >= 1 with n_rows == 0, a result that does not fit half of
+ * the free device memory (the message says how many bytes it would take), unknown flag bits, no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON, SOHIT_PAN_BOOT_BATCH, SOHIT_PAN_SHARED_RANGES). */
+typedef struct so_pan_shared_result {
+    int64_t n_taxa, n_reps, bytes;
+    int32_t waits, batches;
+    int32_t ranges;
+    int32_t reserved;
+    double draw_ms, product_ms;   /* flags bit 1: device time of the draws and of the products */
+    int32_t *shared;              /* n_reps * n_taxa * n_taxa, or empty (flags bit 0) */
+} so_pan_shared_result;
+int so_pan_shared(int device, int64_t m, const int32_t *row, const int32_t *taxon, int64_t n_rows, int64_t n_taxa, uint64_t seed, int64_t b0,
+                  int64_t n_reps, int32_t flags, so_pan_shared_result *out);
+void so_pan_shared_free(so_pan_shared_result *result);
+
 /* The operon pairs of the operon-clustering step on the device (csrc/operon.hip).  Replaces: the pair loop of scripts/operon_cluster.py
  * `operon_clust()` (136-168) -- for every operon the operons listed under the families of its genes, and per such pair the size of the
  * intersection of the two family sets -- as swiftortho_amd/operon.py `candidate_pairs()` restates it, count for count.  All of it is

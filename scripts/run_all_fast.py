@@ -7,7 +7,9 @@ on the .clsr file and the operon file writes <operon name>.xyz (with `-G T`: the
 `bin/find_cluster.py -i` that file with the wrapper's -A, -I and -G writes <operon name>.clsr.  This wrapper keeps its intermediates --
 the reference removes every .xyz at its end --, so both files stay.  Without -p nothing of this happens.
 The pan-genome step (204-214) runs on request: `-P T` (default `F`: the files and the output above, nothing more) runs scripts/pan_genome.py on the .clsr file after the clustering step and leaves
-<name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.
+<name>.pan and <name>.clsr_xy.txt; with `-G T` its counting and rarefaction run on the GPU.  `-C T` (default `F`; with `-P T`) makes that
+command also write the gene-content tree of the genomes, <name>.gc.nwk, and the table of the families every pair of genomes shares,
+<name>.gc.tsv (pan_genome.py -t -d; Jaccard distances, or `-m overlap`); `-B` and `-S` give the tree bootstrap support as below, with `-G T` on the GPU.
 The species-tree step runs on request as well: `-t T` (default `F`) leaves <name>.aln (the core-gene supermatrix of the reference taxon -r,
 FASTA, taxa in slot order), <name>.aln.trim (the columns whose share of gaps is at most `-g`, default 1: the same file) and <name>.nwk
 (neighbour joining over the `-m p|poisson|kimura|logdet` distances).  The reference shells out to famsa, trimal and fasttree here; this step aligns
@@ -39,7 +41,7 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1'}
 
 
 def main(argv):
@@ -96,7 +98,11 @@ def main(argv):
         # statistics of the pan-genome (run_all_fast.py:204-214): the report into <name>.pan, the curves into <name>.clsr_xy.txt
         t = time()
         with open('%s_results/%s.pan' % (fas, name), 'wb') as o:
-            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'pan_genome.py'), '-i', fas, '-g', clsr, '-G', a['-G']], stdout=o, check=True)
+            content = []
+            if a['-C'].upper()[:1] == 'T':
+                gc = '%s_results/%s.gc' % (fas, name)
+                content = ['-t', gc + '.nwk', '-d', gc + '.tsv', '-m', a['-m'] if a['-m'] in ('jaccard', 'overlap') else 'jaccard', '-B', a['-B'], '-S', a['-S']]
+            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'pan_genome.py'), '-i', fas, '-g', clsr, '-G', a['-G']] + content, stdout=o, check=True)
         print('pan-genome analysis time:', time() - t)
     if a['-t'].upper()[:1] == 'T':
         # species tree (run_all_fast.py:216-239, without famsa, trimal and fasttree): one process searches the proteome with a CIGAR on every

@@ -56,7 +56,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_candidates_cols", "so_orth_candidates_records", "so_orth_free", "so_orth_last_error",
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
-           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error",
+           "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error", "so_pan_shared", "so_pan_shared_free",
            "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
            "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free"]
 
@@ -117,6 +117,12 @@ class SoPanResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_rows", "n_taxa", "size", "n_core", "n_share", "n_spec")] + \
                [("waits", C.c_int32), ("tier", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("type", C.POINTER(C.c_uint8)),
                 ("core", C.POINTER(C.c_int64)), ("spec", C.POINTER(C.c_int64)), ("panz", C.POINTER(C.c_int64))]
+
+
+class SoPanSharedResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_reps", "bytes")] + \
+               [("waits", C.c_int32), ("batches", C.c_int32), ("ranges", C.c_int32), ("reserved", C.c_int32), ("draw_ms", C.c_double), ("product_ms", C.c_double),
+                ("shared", C.POINTER(C.c_int32))]
 
 
 class SoOperonResult(C.Structure):
@@ -292,6 +298,8 @@ def load():
     L.so_pan_genome.argtypes = [C.c_int, i64, vp, vp, i64, i64, i64, C.c_int32, C.c_int32, i64, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(SoPanResult)]
     L.so_pan_free.argtypes = [C.POINTER(SoPanResult)]
     L.so_pan_last_error.restype = cp
+    L.so_pan_shared.argtypes = [C.c_int, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, C.c_int32, C.POINTER(SoPanSharedResult)]
+    L.so_pan_shared_free.argtypes = [C.POINTER(SoPanSharedResult)]
     L.so_operon_pairs.argtypes = [C.c_int, i64, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(SoOperonResult)]
     L.so_operon_free.argtypes = [C.POINTER(SoOperonResult)]
     L.so_operon_last_error.restype = cp

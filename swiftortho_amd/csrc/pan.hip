@@ -21,6 +21,15 @@
 //                are flushed once per workgroup with integer atomics (tune.h PAN_LDS_BYTES bounds the taxa);
 //   global tier  words, orders and thresholds are read where they lie and every step adds to the global counters.
 // SOHIT_PAN_TIER forces either (the LDS tier only where it fits).  One host wait per call (DeviceCall, device_call.h), counted.
+//
+// so_pan_shared: what pan.py `shared_counts()` and `boot_shared()` define -- S[a][b] = the rows present in both a and b, over all rows or
+// over the rows a bootstrap replicate draws (a row drawn twice counts twice).  S = P^T P of the presence bits is AND + popcount over the
+// tile-major words: k_pan_shared, a workgroup per 64 x 64 tile of taxon pairs (the upper triangle of tiles only) and range of row words,
+// 4 x 4 sums per lane, integer adds into the int32 result.  A replicate is a presence matrix of its own: k_pan_rowbits writes the bits
+// row-major, k_pan_draw draws 64 rows per wave (phy.py boot_columns with K = n_rows), reads each drawn row's word for a block of 64 taxa
+// and transposes the 64 x 64 bits with 64 ballots into the replicate's tile-major words.  Replicates run along the grid, in batches whose
+// words fit half of the free device memory (SOHIT_PAN_BOOT_BATCH forces the size); SOHIT_PAN_SHARED_RANGES forces the number of ranges.
+// Integers only, one host wait per call whatever the number of batches.
 #include "device_call.h"
 #include "../../include/sohit.h"
 
@@ -153,9 +162,141 @@ __global__ __launch_bounds__(256) void k_pan_curve(const ull* __restrict__ bits,
     }
 }
 
+// ---- so_pan_shared: the families every pair of genomes shares, S = P^T P of the presence matrix, for the table or for bootstrap replicates ----
+// the row-major twin of k_pan_bits: bit t & 63 of rowbits[r * TW + (t >> 6)] is the presence of taxon t in row r (TW = ceil(T / 64))
+__global__ __launch_bounds__(256) void k_pan_rowbits(u32 m, const int* __restrict__ row, const int* __restrict__ tax, u32 n_rows, u32 T, u32 TW, ull* __restrict__ rowbits,
+                                                     u32* __restrict__ err) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    u32 r, t;
+    if (i < m && pan_pair(i, row, tax, n_rows, T, r, t, err)) atomicOr(rowbits + (size_t)r * TW + (t >> 6), 1ull << (t & 63u));
+}
+
+// draw k of replicate b from K rows: phy.py boot_columns(), in 64-bit integers that wrap (phy.hip boot_draw restated)
+__device__ __forceinline__ u32 pan_draw(ull seed, ull b, ull k, u32 K) {
+    ull z = seed + ((b << 32) + k + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (u32)(((z >> 32) * (ull)K) >> 32);   // < K: the left factor is below 2^32
+}
+
+// grid (groups of 4 draw tiles, groups of PAN_DRAW_BLOCKS blocks of 64 taxa, replicates); a wave per tile of 64 draws, a draw per lane.
+// Lane k reads the row-major word of its drawn row for a block of 64 taxa; ballot j is then bit j of all 64 lanes -- the tile-major word
+// of taxon 64 tb + j over the 64 drawn rows, which lane j keeps and stores: words[z][w * T + t] as k_pan_bits writes them.  A lane behind
+// the last draw holds 0, so the bits behind the last row stay 0.  A draw lies below R and tb below TW: every read is inside rowbits.
+__global__ __launch_bounds__(256) void k_pan_draw(const ull* __restrict__ rowbits, u32 R, u32 T, u32 TW, ull seed, u32 b0, ull* __restrict__ words, size_t wrep) {
+    const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (w >= (R + 63u) / 64u) return;   // (a whole wave)
+    const u32 lane = threadIdx.x & 63u, d = w * 64u + lane;
+    const bool live = d < R;
+    const ull* src = rowbits + (live ? (size_t)pan_draw(seed, (ull)b0 + blockIdx.z, d, R) * TW : 0);
+    ull* dst = words + (size_t)blockIdx.z * wrep + (size_t)w * T;
+    const u32 tb0 = blockIdx.y * PAN_DRAW_BLOCKS, tb1 = min(TW, tb0 + PAN_DRAW_BLOCKS);
+    for (u32 tb = tb0; tb < tb1; ++tb) {   // (the same bounds for every lane: the ballots are met by the whole wave)
+        const ull word = live ? src[tb] : 0ull;
+        ull mine = 0ull;
+#pragma unroll
+        for (u32 j = 0; j < 64u; ++j) {
+            const ull bal = __ballot((word >> j) & 1ull);
+            if (lane == j) mine = bal;
+        }
+        const u32 t = tb * 64u + lane;
+        if (t < T) dst[t] = mine;
+    }
+}
+
+// S += A^T B over a range of row words.  grid (tiles of 64 x 64 taxon pairs with I <= J, ranges of `wps` row words, matrices); words: per
+// matrix W row words of T taxa, tile-major.  Lane (ty, tx) of the 16 x 16 holds taxa I * 64 + ty * 4 + r against J * 64 + tx * 4 + c.  A
+// chunk of PAN_SH_CHUNK row words of both sides lies in the LDS as [word][taxon]: a lane's four taxa are 32 consecutive bytes, the 16
+// lanes of one ty read one address (a broadcast).  The range's sums (below 2^31: 64 per word, fewer than 2^25 words) flush with integer
+// adds, the mirror entry too; a diagonal tile holds both (x, y) and (y, x) itself and writes each once.
+__global__ __launch_bounds__(256) void k_pan_shared(const ull* __restrict__ words, u32 W, u32 T, u32 nt, u32 wps, int* __restrict__ out, size_t wrep, size_t orep) {
+    words += (size_t)blockIdx.z * wrep, out += (size_t)blockIdx.z * orep;
+    __shared__ __attribute__((aligned(16))) ull sA[PAN_SH_CHUNK][PAN_SH_TILE];
+    __shared__ __attribute__((aligned(16))) ull sB[PAN_SH_CHUNK][PAN_SH_TILE];
+    u32 I = 0, J = blockIdx.x;   // the blockIdx.x-th pair I <= J in row-major order
+    while (J >= nt - I) J -= nt - I, ++I;
+    J += I;
+    const u32 w_begin = blockIdx.y * wps, w_end = min(W, w_begin + wps);
+    if (w_begin >= w_end) return;   // (the whole workgroup)
+    const u32 tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const u32 lcol = threadIdx.x & 63u, lpart = threadIdx.x >> 6;
+    const u32 ta = I * PAN_SH_TILE + lcol, tb = J * PAN_SH_TILE + lcol;
+    u32 acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0u;
+    for (u32 w0 = w_begin; w0 < w_end; w0 += PAN_SH_CHUNK) {
+        const u32 nw = min((u32)PAN_SH_CHUNK, w_end - w0);
+        __syncthreads();   // the last chunk's readers are done
+        for (u32 k = lpart; k < nw; k += 4u) {
+            const ull* src = words + (size_t)(w0 + k) * T;   // w0 + k < w_end <= W
+            sA[k][lcol] = ta < T ? src[ta] : 0ull;
+            sB[k][lcol] = tb < T ? src[tb] : 0ull;
+        }
+        __syncthreads();
+        for (u32 k = 0; k < nw; ++k) {
+            const ulonglong2 a0 = *reinterpret_cast<const ulonglong2*>(&sA[k][ty * 4u]), a1 = *reinterpret_cast<const ulonglong2*>(&sA[k][ty * 4u + 2u]);
+            const ulonglong2 b0 = *reinterpret_cast<const ulonglong2*>(&sB[k][tx * 4u]), b1 = *reinterpret_cast<const ulonglong2*>(&sB[k][tx * 4u + 2u]);
+            const ull av[4] = {a0.x, a0.y, a1.x, a1.y}, bv[4] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] += (u32)__popcll(av[r] & bv[c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32 x = I * PAN_SH_TILE + ty * 4u + (u32)r, y = J * PAN_SH_TILE + tx * 4u + (u32)c;
+            if (x >= T || y >= T || !acc[r][c]) continue;
+            atomicAdd(out + (size_t)x * T + y, (int)acc[r][c]);
+            if (I != J) atomicAdd(out + (size_t)y * T + x, (int)acc[r][c]);
+        }
+}
+
+// the grid of k_pan_shared over W row words and `reps` matrices of nt x nt tiles: row words per range and ranges.  forced > 0: that many
+// ranges (as far as there are words); else whole chunks, until about PAN_SH_TARGET_WGS workgroups exist.  Never more than 2^23 workgroups.
+void shared_grid(u32 W, u32 nt, u32 reps, long long forced, u32& wps, u32& ranges) {
+    const u64 tiles = (u64)(nt * (nt + 1u) / 2u) * reps;
+    const u32 most = (u32)std::max<u64>(1, std::min<u64>(65535, (1ull << 23) / tiles));
+    if (forced > 0) {
+        const u32 want = (u32)std::min<u64>({(u64)forced, (u64)W, (u64)most});
+        wps = (W + want - 1u) / want;
+    } else {
+        const u32 chunks = (W + PAN_SH_CHUNK - 1u) / PAN_SH_CHUNK;
+        const u32 want = std::min({chunks, most, std::max(1u, (u32)((PAN_SH_TARGET_WGS + tiles - 1u) / tiles))});
+        wps = ((chunks + want - 1u) / want) * PAN_SH_CHUNK;
+    }
+    ranges = (W + wps - 1u) / wps;
+}
+
+// marks around the draw and the product of every batch (flags bit 1 of so_pan_shared): recorded on the stream, read after the call's wait
+struct BatchEvents {
+    std::vector<hipEvent_t> e;
+    ~BatchEvents() {
+        for (hipEvent_t x : e) (void)hipEventDestroy(x);
+    }
+    void mark(bool on, hipStream_t st) {
+        if (!on) return;
+        hipEvent_t x = nullptr;
+        HIP_CHECK(hipEventCreate(&x));
+        e.push_back(x);
+        HIP_CHECK(hipEventRecord(x, st));
+    }
+    double ms(size_t k) {   // between mark k and mark k + 1, both reached: the stream has been waited for
+        float v = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&v, e[k], e[k + 1]));
+        return v;
+    }
+};
+
 thread_local std::string g_pan_err;
 
 auto slots(so_pan_result* r) { return result_slots(&r->counts, &r->type, &r->core, &r->spec, &r->panz); }
+auto slots(so_pan_shared_result* r) { return result_slots(&r->shared); }
 
 }  // namespace
 
@@ -258,6 +399,114 @@ int so_pan_genome(int device, int64_t m, const int32_t* row, const int32_t* taxo
         if (e & 1u) throw SoError(who + ": a row outside 0 .. n_rows - 1");
         if (e & 2u) throw SoError(who + ": a taxon outside 0 .. n_taxa - 1");
         out->n_core = (i64)tot[0], out->n_share = (i64)tot[1], out->n_spec = (i64)tot[2];
+        fill_empty_slots(slots(out));
+    });
+}
+
+void so_pan_shared_free(so_pan_shared_result* r) {
+    if (r) release_slots(r, slots(r));
+}
+
+int so_pan_shared(int device, int64_t m, const int32_t* row, const int32_t* taxon, int64_t n_rows, int64_t n_taxa, uint64_t seed, int64_t b0, int64_t n_reps, int32_t flags,
+                  so_pan_shared_result* out) {
+    const std::string who = "so_pan_shared";
+    return guarded_call(g_pan_err, out, so_pan_shared_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~3) throw SoError(who + ": unknown flag bits (bit 0: no matrix in the result, bit 1: draw and product timed by events)");
+        if (m < 0 || n_rows < 0) throw SoError(who + ": bad arguments");
+        if (n_taxa < 1 || n_taxa > PAN_MAX_TAXA) throw SoError(who + ": the taxa number 1 .. " + std::to_string(PAN_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+        if (n_rows >= (1ll << 31)) throw SoError(who + ": 2^31 rows and more are not supported");
+        if (m >= (1ll << 31)) throw SoError(who + ": 2^31 members and more are not supported");
+        if (n_reps < 0) throw SoError(who + ": n_reps is 0 (all rows) or the number of replicates (n_reps is " + std::to_string(n_reps) + ")");
+        if (n_reps > PAN_BOOT_MAX_REPS) throw SoError(who + ": more than " + std::to_string(PAN_BOOT_MAX_REPS) + " replicates in one call are not supported");
+        const bool draw = n_reps > 0;
+        if (draw && (b0 < 0 || b0 >= (1ll << 31) || b0 + n_reps > (1ll << 31))) throw SoError(who + ": replicates beyond 2^31 - 1 are not supported");
+        if (draw && n_rows == 0) throw SoError(who + ": no row to draw from (n_rows is 0)");
+        if (m > 0 && (!row || !taxon)) throw SoError(who + ": a member column is NULL");
+        if (m > 0 && n_rows == 0) throw SoError(who + ": a row outside 0 .. n_rows - 1");
+        const bool want = !(flags & 1), timed = flags & 2;
+        const u32 M = (u32)m, R = (u32)n_rows, T = (u32)n_taxa, W = (R + 63u) / 64u, TW = (T + 63u) / 64u, nrep = draw ? (u32)n_reps : 1u;
+        const size_t TT = (size_t)T * T, bytes = (size_t)nrep * TT * sizeof(int);
+        out->n_taxa = n_taxa, out->n_reps = nrep, out->bytes = (int64_t)bytes;
+        check_device(who.c_str(), device);
+        if (n_rows == 0) {   // nothing to launch: no rows, every count 0
+            if (want) {
+                out->shared = host_array<int32_t>(who.c_str(), TT);
+                memset(out->shared, 0, TT * sizeof(int32_t));
+            }
+            fill_empty_slots(slots(out));
+            return;
+        }
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (bytes + bytes / 8 > free_b / 2)   // (a DevBuf takes an eighth more than it is asked for)
+            throw SoError(who + ": the result of " + std::to_string(nrep) + " x " + std::to_string(T) + " x " + std::to_string(T) + " counts would take " + std::to_string(bytes) +
+                          " bytes, more than half of the free device memory (" + std::to_string(free_b) + " bytes free): ask for fewer replicates per call");
+        DevBuf<int> d_row, d_tax, d_out;
+        DevBuf<ull> bits, words;
+        DevBuf<u32> err;
+        upload(d_row, row, (size_t)m, st), upload(d_tax, taxon, (size_t)m, st);
+        const size_t per = (size_t)W * T, nbits = draw ? (size_t)R * TW : per;   // words of one matrix; of the presence bits (row-major for the draws)
+        d_out.ensure((size_t)nrep * TT + 2), bits.ensure(nbits + 2), err.ensure(4);
+        HIP_CHECK(hipMemsetAsync(d_out.p, 0, bytes, st));
+        HIP_CHECK(hipMemsetAsync(bits.p, 0, nbits * sizeof(ull), st));
+        HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(u32), st));
+        if (M) {
+            if (draw)
+                hipLaunchKernelGGL(k_pan_rowbits, grid256(M), dim3(256), 0, st, M, d_row.p, d_tax.p, R, T, TW, bits.p, err.p);
+            else
+                hipLaunchKernelGGL(k_pan_bits, grid256(M), dim3(256), 0, st, M, d_row.p, d_tax.p, R, T, bits.p, err.p);
+        }
+        const u32 nt = (T + PAN_SH_TILE - 1u) / PAN_SH_TILE;
+        BatchEvents ev;
+        u32 wps = 0, ranges = 0;
+        if (!draw) {
+            shared_grid(W, nt, 1u, call.tn.pan_shared_ranges, wps, ranges);
+            ev.mark(timed, st);
+            hipLaunchKernelGGL(k_pan_shared, dim3(nt * (nt + 1u) / 2u, ranges, 1u), dim3(256), 0, st, bits.p, W, T, nt, wps, d_out.p, (size_t)0, (size_t)0);
+            ev.mark(timed, st);
+            out->batches = 1;
+        } else {
+            // a batch: as many replicates' words as half of what is free now holds, below 2^31 words and 2^22 tiles (grid sizes)
+            size_t batch = call.tn.pan_boot_batch > 0 ? (size_t)call.tn.pan_boot_batch : 0;
+            if (!batch) {
+                HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+                batch = (free_b / 2) / ((per + per / 8 + 64) * sizeof(ull));
+            }
+            batch = std::min({batch, (size_t)nrep, ((size_t)1 << 31) / per, ((size_t)1 << 22) / (nt * (nt + 1u) / 2u)});
+            batch = std::max<size_t>(batch, 1);
+            words.ensure(batch * per + 2);
+            for (u32 r0 = 0; r0 < nrep; r0 += (u32)batch) {
+                const u32 nb = std::min((u32)batch, nrep - r0);
+                shared_grid(W, nt, nb, call.tn.pan_shared_ranges, wps, ranges);
+                ev.mark(timed, st);
+                hipLaunchKernelGGL(k_pan_draw, dim3((W + 3u) / 4u, (TW + PAN_DRAW_BLOCKS - 1u) / PAN_DRAW_BLOCKS, nb), dim3(256), 0, st, bits.p, R, T, TW, (ull)seed,
+                                   (u32)b0 + r0, words.p, per);
+                ev.mark(timed, st);
+                hipLaunchKernelGGL(k_pan_shared, dim3(nt * (nt + 1u) / 2u, ranges, nb), dim3(256), 0, st, words.p, W, T, nt, wps, d_out.p + (size_t)r0 * TT, per, TT);
+                ev.mark(timed, st);
+                ++out->batches;
+            }
+        }
+        out->ranges = (int32_t)ranges;
+        HIP_CHECK(hipGetLastError());
+        u32 e = 0;
+        call.fetch(&e, err.p);
+        static_assert(sizeof(int) == sizeof(int32_t), "the counts are copied out as int32");
+        if (want) out->shared = host_copy(who.c_str(), d_out.p, (size_t)nrep * TT, st);
+        call.wait();
+        out->waits = call.waits;
+        if (e & 1u) throw SoError(who + ": a row outside 0 .. n_rows - 1");
+        if (e & 2u) throw SoError(who + ": a taxon outside 0 .. n_taxa - 1");
+        if (timed) {
+            if (!draw)
+                out->product_ms = ev.ms(0);
+            else
+                for (size_t k = 0; k + 2 < ev.e.size(); k += 3) out->draw_ms += ev.ms(k), out->product_ms += ev.ms(k + 1);
+        }
         fill_empty_slots(slots(out));
     });
 }

@@ -61,6 +61,8 @@
     X(T, rbh_tier, "SOHIT_RBH_TIER", 0, "tests: wave = runs of up to 64 rows through k_rbh_run_wave (what auto does), long or sort = every run through the sorted tier (0 = auto: by run length)") \
     /* ---- pan-genome statistics (so_pan_genome: read per call) ---- */                                                                                        \
     X(T, pan_tier, "SOHIT_PAN_TIER", 0, "tests: lds = what auto does where the taxa fit the LDS of k_pan_curve, global = words, orders and counters in global memory (0 = auto: by the number of taxa)") \
+    X(I, pan_boot_batch, "SOHIT_PAN_BOOT_BATCH", 0, "so_pan_shared: replicates whose presence words are in device memory at a time (0: what half of the free device memory holds; tests move the batch edges)") \
+    X(I, pan_shared_ranges, "SOHIT_PAN_SHARED_RANGES", 0, "so_pan_shared: ranges the row words of k_pan_shared are cut into (0: whole chunks until about 1024 workgroups exist; tests make a small input walk several)") \
     /* ---- operon pairs (so_operon_pairs: read per call) ---- */                                                                                               \
     X(I, operon_expand, "SOHIT_OPERON_EXPAND", -1, "tests: expansions per batch (-1: 2^28)")                                                                   \
     /* ---- bootstrap of the species tree (so_phy_boot: read per call) ---- */                                                                                  \
@@ -95,6 +97,15 @@ static inline int orth_tier_of(const char* v) {
 // ---- pan-genome statistics (pan.hip): SOHIT_PAN_TIER is read with orth_tier_of -- l[ds] = 2; g[lobal] (3) = the tier without LDS tables ----
 #define PAN_LDS_BYTES 65536u  // most LDS k_pan_curve asks for: 80 bytes per taxon (a tile's words, four orders, thresholds, 12 counters per step)
 #define PAN_TILE_RANGES 256u  // ranges the row tiles are cut into: a workgroup walks one range for four orders and flushes its counters once
+// ... and the shared-family counts (k_pan_shared): 64 x 64 taxon pairs per workgroup, a 4 x 4 block per lane; a chunk of 32 row words (2048
+// rows) of both sides is 32 KiB of LDS; the row words are cut into ranges of whole chunks until about PAN_SH_TARGET_WGS workgroups exist.
+// k_pan_draw walks PAN_DRAW_BLOCKS blocks of 64 taxa per wave: the 64 bytes of a drawn row's words that share a cache line
+#define PAN_SH_TILE 64u
+#define PAN_SH_CHUNK 32u
+#define PAN_SH_TARGET_WGS 1024u
+#define PAN_DRAW_BLOCKS 8u
+#define PAN_MAX_TAXA 4096
+#define PAN_BOOT_MAX_REPS 32768
 
 // ---- operon pairs (operon.hip): expansions of one batch.  A memory bound, not a tuned value: the sort helpers take 12 bytes per element
 // (u64 key, u32 payload) for input and output each, so 2^28 expansions are about 6 GB of keys, payloads and sort scratch ----

@@ -29,6 +29,15 @@ tools/refharness/make_pan_goldens.py runs the REAL script):
     script then dies in its fit).  Here the file is always kept (the script removes it when Rscript is installed).
 Not provided: the three curve fits of the report (scipy's solver is not reproducible bit for bit; _xy.txt is their whole input, and a
 line of the report says so), the R plot, the temporary pan.npy / type.txt.
+
+Added, with no counterpart in the reference (-t, -d, -m, -B, -S; off unless asked for): the gene content of the genomes.  shared_counts:
+S[a, b] = the rows present in both genomes a and b (all rows, presence = count > 0), S[a, a] = the families of a; boot_shared: the same
+over the rows a bootstrap replicate draws (phy.boot_columns over the rows; a row drawn twice counts twice); content_distances: jaccard,
+1 - S_ab / (S_aa + S_bb - S_ab), or overlap, 1 - S_ab / min(S_aa, S_bb) (Snel et al. 1999), in float64 from the exact integers;
+content_tree: phy.neighbor_joining over them, with bootstrap support over the families as phy.tree labels it.  Tree and table list the
+taxa in SORTED order of their names, so the files repeat from run to run.  The numpy functions are the definition; the device call
+(device_shared_counts, device_boot_shared: include/sohit.h so_pan_shared) equals them integer for integer, and the replicates' trees
+come from the existing so_phy_nj_splits.
 """
 import math
 import random
@@ -268,6 +277,200 @@ def pan_genome(table, n_taxa, ts=.05, tc=.95, size=SIZE, device_stage=False, wan
 
 
 # ---------------------------------------------------------------------------------------------------------
+# gene content: the families every pair of genomes shares, the distances made from them, the tree of the genomes.  The reference has no
+# such product: these numpy functions are the definition, the device call (so_pan_shared) equals them integer for integer.
+# ---------------------------------------------------------------------------------------------------------
+METRICS = ('jaccard', 'overlap')
+_NO_METRIC = "content_distances: the metric is 'jaccard' or 'overlap'"
+_ROW_STEP = 1 << 16   # rows per float64 product: every partial count is an integer far below 2^53, so the sums are exact
+
+
+def _weighted_shared(counts, weight=None):
+    x = np.asarray(counts)
+    if x.ndim != 2:
+        raise ValueError('shared_counts: the count table has two dimensions')
+    R, T = x.shape
+    S = np.zeros((T, T), dtype=np.int64)
+    for r0 in range(0, R, _ROW_STEP):
+        P = (x[r0:r0 + _ROW_STEP] > 0).astype(np.float64)
+        S += np.rint(P.T @ (P if weight is None else P * weight[r0:r0 + _ROW_STEP, None])).astype(np.int64)
+    return S
+
+
+def shared_counts(counts):
+    """-> int64[T, T]: S[a, b] = the rows (file rows and the one-gene rows behind them) present in both a and b, presence = count > 0 (a
+    member listed twice counts once); S[a, a] = the families of genome a.  S = P^T P in float64, exact"""
+    return _weighted_shared(counts)
+
+
+def boot_shared(counts, seed, b):
+    """-> int64[T, T] of replicate b: shared_counts over the rows phy.boot_columns(seed, b, n_rows) -- a row drawn twice counts twice
+    (the order of the draws does not matter: S = P^T diag(times drawn) P)"""
+    from . import phy
+    R = len(np.asarray(counts))
+    return _weighted_shared(counts, np.bincount(phy.boot_columns(seed, b, R), minlength=R).astype(np.float64))
+
+
+def _content(S, metric):
+    """-> (D, argwhere of the zero denominators): the diagonal's denominator counts -- a genome without a family has no distance at all"""
+    if metric not in METRICS:
+        raise ValueError(_NO_METRIC)
+    S = np.asarray(S, dtype=np.int64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError('content_distances: S is a square matrix')
+    d = np.diagonal(S)
+    den = (d[:, None] + d[None, :] - S) if metric == 'jaccard' else np.minimum(d[:, None], d[None, :])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        D = 1. - S.astype(np.float64) / den.astype(np.float64)
+    np.fill_diagonal(D, 0.)
+    return D, np.argwhere(den == 0)
+
+
+def content_distances(S, metric='jaccard', names=None):
+    """-> float64[T, T] from the exact integers: jaccard 1 - S_ab / (S_aa + S_bb - S_ab); overlap 1 - S_ab / min(S_aa, S_bb), the
+    gene-content distance of Snel et al. 1999; the diagonal is 0.  A pair whose denominator is 0 -- under jaccard two genomes without a
+    family, under overlap one; a genome without a family has none to itself either -- raises phy.DistanceRefused"""
+    from . import phy
+    D, bad = _content(S, metric)
+    if len(bad):
+        off = bad[bad[:, 0] != bad[:, 1]]      # the first pair of two taxa; under jaccard a lone empty genome has only itself: any other names the pair
+        a, b = (int(off[0][0]), int(off[0][1])) if len(off) else (int(bad[0][0]), 0 if bad[0][0] or len(D) == 1 else 1)
+        who = lambda k: phy._label(names[k]) if names is not None else str(k)
+        raise phy.DistanceRefused('content_distances: taxa %s and %s have no %s distance: its denominator is 0 (a genome without a family)' % (who(a), who(b), metric))
+    return D
+
+
+def boot_content_distances(S, metric='jaccard'):
+    """-> (D float64[T, T], ok): content_distances() without its refusal.  ok is False where a denominator is 0: such a replicate is
+    dropped, not refused (its D holds NaN or inf there; the diagonal is 0 all the same)"""
+    D, bad = _content(S, metric)
+    return D, not len(bad)
+
+
+def _device_shared(who, row, taxon, n_rows, n_taxa, seed, b0, nb, device, stats=None, want=True, timed=False):
+    """so_pan_shared -> int32[max(nb, 1), T, T] (None without `want`); nb = 0: all rows"""
+    import ctypes as C_
+    from . import _lib
+    L = _lib.load()
+    row32, tax32 = np.ascontiguousarray(row, dtype=np.int32), np.ascontiguousarray(taxon, dtype=np.int32)
+    if len(row32) != len(tax32):
+        raise ValueError('%s: row and taxon differ in length' % who)
+    ptr = lambda a: C_.c_void_p(a.ctypes.data)
+    res = _lib.SoPanSharedResult()
+    flags = (0 if want else 1) | (2 if timed else 0)
+    if L.so_pan_shared(int(device), len(row32), ptr(row32), ptr(tax32), int(n_rows), int(n_taxa), C_.c_uint64(int(seed) & (2 ** 64 - 1)), int(b0), int(nb), flags,
+                       C_.byref(res)) != 0:
+        raise RuntimeError(L.so_pan_last_error().decode())
+    try:
+        if stats is not None:
+            stats['waits'], stats['batches'], stats['ranges'], stats['bytes'] = int(res.waits), int(res.batches), int(res.ranges), int(res.bytes)
+            if timed:
+                stats['draw_ms'], stats['product_ms'] = float(res.draw_ms), float(res.product_ms)
+        n, T = int(res.n_reps), int(n_taxa)
+        return _lib.result_array(res.shared, n * T * T, np.int32).reshape(n, T, T) if want else None
+    finally:
+        L.so_pan_shared_free(C_.byref(res))
+
+
+def device_shared_counts(row, taxon, n_rows, n_taxa, device=0, stats=None):
+    """shared_counts(count_matrix(row, taxon, n_rows, n_taxa)) in one device call (so_pan_shared), never through the count table ->
+    int64[T, T]; a refusal raises RuntimeError with the library's message"""
+    return _device_shared('device_shared_counts', row, taxon, n_rows, n_taxa, 0, 0, 0, device, stats)[0].astype(np.int64)
+
+
+def device_boot_shared(row, taxon, n_rows, n_taxa, seed, b0, nb, device=0, stats=None):
+    """boot_shared() of replicates b0 .. b0 + nb - 1 in one device call (so_pan_shared) -> int64[nb, T, T]"""
+    if int(nb) < 1:
+        raise ValueError('device_boot_shared: a replicate at least')
+    return _device_shared('device_boot_shared', row, taxon, n_rows, n_taxa, seed, b0, nb, device, stats).astype(np.int64)
+
+
+class TooFewTaxa(ValueError):
+    """fewer than two taxa: no pair, no tree (pan_genome.py exits with code 2)"""
+
+
+def _content_batch(B, T):
+    """replicates per device call of content_tree: what about 2^30 bytes of counts (int32 and int64) and distances hold"""
+    return max(1, min(B, 32768, (1 << 30) // max(1, 20 * T * T)))   # (32768: the most a device call takes)
+
+
+def content_tree(table, taxa, metric='jaccard', boot=0, seed=1, device_stage=False, device=0, stats=None):
+    """MemberTable + the names of its taxon codes -> (Newick bytes, S int64[T, T], D float64[T, T]): the neighbour-joining tree
+    (phy.neighbor_joining) of the gene-content distances.  Tree, S and D list the taxa in SORTED order of their names, whatever order the
+    table codes them in.  boot > 0: every node a join makes carries the share of the valid bootstrap replicates that hold its split, as
+    phy.tree labels them: replicate b draws the rows with replacement (boot_shared), a replicate with a zero denominator is dropped
+    (boot_content_distances), the others give a topology (phy.nj_splits); no valid replicate: ValueError.  device_stage: S and the
+    replicates' matrices by so_pan_shared, the replicates' trees by so_phy_nj_splits (no fallback); the distances divide exact integers
+    on the host either way, so the bytes are the same.  stats: 'boot', 'boot_valid', 'calls' (device calls of the bootstrap)"""
+    from . import phy
+    if metric not in METRICS:
+        raise ValueError(_NO_METRIC)
+    boot, seed, T = int(boot), int(seed), len(taxa)
+    if not 0 <= boot < 2 ** 31:
+        raise ValueError('content_tree: boot lies in 0 .. 2^31 - 1')
+    if T < 2:
+        raise TooFewTaxa('content_tree: the gene-content tree and table need two taxa at least (there %s)' % ('is 1' if T == 1 else 'are none'))
+    order = sorted(range(T), key=lambda k: taxa[k])
+    names = [taxa[k] for k in order]
+    rank = np.zeros(T, dtype=np.int32)
+    rank[order] = np.arange(T, dtype=np.int32)
+    tax = rank[np.asarray(table.taxon, dtype=np.int64)] if len(table.taxon) else np.zeros(0, dtype=np.int32)
+    R = table.n_rows
+    try:
+        if device_stage:
+            counts, S = None, device_shared_counts(table.row, tax, R, T, device)
+        else:
+            counts = count_matrix(table.row, tax, R, T)
+            S = shared_counts(counts)
+        D = content_distances(S, metric, names)
+        if boot <= 0:
+            return phy.neighbor_joining(D, names), S, D
+        if R == 0:
+            raise ValueError('content_tree: no row to draw from')
+        ref = phy.tree_splits(D)
+        ns, W = max(T - 3, 0), (T + 63) // 64
+        ok, splits = np.zeros(boot, dtype=bool), np.zeros((boot, ns, W), dtype=np.uint64)
+        if device_stage:
+            step, calls = _content_batch(boot, T), 0
+            for b0 in range(0, boot, step):
+                nb = min(step, boot - b0)
+                Sb = device_boot_shared(table.row, tax, R, T, seed, b0, nb, device)
+                calls += 1
+                dist = [boot_content_distances(Sb[k], metric) for k in range(nb)]
+                good = [k for k in range(nb) if dist[k][1]]
+                if good and ns:
+                    splits[[b0 + k for k in good]] = phy.device_nj_splits(np.stack([dist[k][0] for k in good]), device)
+                    calls += 1
+                ok[[b0 + k for k in good]] = True
+            if stats is not None:
+                stats['calls'] = calls
+        else:
+            for b in range(boot):
+                Db, ok[b] = boot_content_distances(boot_shared(counts, seed, b), metric)
+                if ok[b]:
+                    splits[b] = phy.nj_splits(Db)
+    except RuntimeError as e:
+        raise ValueError('content_tree: %s' % e)
+    valid = int(ok.sum())
+    if valid == 0:
+        raise ValueError('content_tree: none of the %d replicates gives every pair of taxa a distance' % boot)
+    if stats is not None:
+        stats['boot'], stats['boot_valid'] = boot, valid
+    return phy.neighbor_joining(D, names, phy.split_support(ref, splits, ok) / float(valid)), S, D
+
+
+def content_table_text(names, S, D):
+    """-> the text of the -d file: per pair a < b of the sorted taxa `taxon_a taxon_b families_a families_b shared distance`, tab-separated,
+    the distance as repr(float)"""
+    S, D = np.asarray(S).tolist(), np.asarray(D).tolist()
+    out = []
+    for a in range(len(names)):
+        for b in range(a + 1, len(names)):
+            out.append('%s\t%s\t%d\t%d\t%d\t%s\n' % (names[a], names[b], S[a][a], S[b][b], S[a][b], repr(float(D[a][b]))))
+    return ''.join(out)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # text
 # ---------------------------------------------------------------------------------------------------------
 def xy_text(core, spec, panz):
@@ -311,19 +514,39 @@ def report_lines(taxa, res, n_file_rows, xy_name):
 # ---------------------------------------------------------------------------------------------------------
 def manual_print():
     print('Usage:')
-    print('  python this_script.py -i foo.pep.fsa -g foo.mcl [-l .05] [-u .95] [-r taxa.txt] [-G T]')
+    print('  python this_script.py -i foo.pep.fsa -g foo.mcl [-l .05] [-u .95] [-r taxa.txt] [-G T] [-t tree.nwk] [-d pairs.tsv] [-m jaccard|overlap] [-B replicates] [-S seed]')
     print('Parameters:')
     print(' -i: protein/gene fasta file; a header reads taxon|identifier')
     print(' -g: groups file, one protein/gene group per line, tab-separated')
     print(' -l: at most this share (below 1) or number of taxa: a specific family. Default 0.05')
     print(' -u: at least this share (below 1) or number of taxa: a core family. Default 0.95')
     print(' -r: a file of taxon names, one per line: only these take part')
-    print(' -G: count table, types and rarefaction on the GPU [T|F]. Default: F')
+    print(' -G: count table, types and rarefaction on the GPU [T|F]; with -t or -d also the shared-family counts and the bootstrap replicates. Default: F')
+    print(' -t: write the gene-content tree of the genomes (neighbour joining, Newick, taxa in sorted order) to this file')
+    print(' -d: write one line per pair of genomes to this file: taxon_a taxon_b families_a families_b shared distance (tab-separated, taxa in sorted order)')
+    print(' -m: gene-content distance [jaccard|overlap]: 1 - shared / (families_a + families_b - shared), or 1 - shared / min(families_a, families_b). Default: jaccard')
+    print(' -B: with -t, label the tree\'s nodes with their bootstrap support over this many replicates of the families. Default: 0 (no labels)')
+    print(' -S: seed of the bootstrap\'s draws, 0 .. 2^64 - 1. Default: 1')
 
 
-def run(fasta_path, groups_path, ts=.05, tc=.95, allow_path=None, device_stage=False, taxa=None):
+def write_content(table, taxa, tree_path='', dist_path='', metric='jaccard', boot=0, seed=1, device_stage=False, device=0, stats=None):
+    """content_tree() to files: the tree (Newick and a newline) to `tree_path`, content_table_text() to `dist_path`, each when named;
+    nothing is written before both are computed -> (sorted taxa, Newick bytes, S, D)"""
+    newick, S, D = content_tree(table, taxa, metric, boot if tree_path else 0, seed, device_stage, device, stats)
+    names = sorted(taxa)
+    if tree_path:
+        with open(tree_path, 'wb') as o:
+            o.write(newick + b'\n')
+    if dist_path:
+        with open(dist_path, 'w') as o:
+            o.write(content_table_text(names, S, D))
+    return names, newick, S, D
+
+
+def run(fasta_path, groups_path, ts=.05, tc=.95, allow_path=None, device_stage=False, taxa=None, content=None):
     """the script on two files -> the report lines; writes <groups_path>_xy.txt.  taxa: the column order (None: Python's set order of
-    the names, as the script has it)"""
+    the names, as the script has it).  content: the keywords of write_content() (-t, -d, -m, -B, -S) -- the gene-content tree and table
+    are computed before anything is written, so a refusal leaves no half output"""
     allow = read_allow(allow_path)
     with open(fasta_path, 'r') as f:
         fasta = f.read()
@@ -333,7 +556,9 @@ def run(fasta_path, groups_path, ts=.05, tc=.95, allow_path=None, device_stage=F
         taxa = list(set(taxa_of_fasta(fasta, allow)))
     table = member_table(fasta, groups, taxa, allow)
     res = pan_genome(table, len(taxa), ts, tc, device_stage=device_stage)
-    xy = groups_path + '_xy.txt'
+    if content:
+        write_content(table, taxa, device_stage=device_stage, **content)
+    xy =groups_path + '_xy.txt'
     with open(xy, 'w') as o:
         o.write(xy_text(res.core, res.spec, res.panz))
     return report_lines(taxa, res, table.n_file_rows, xy)
@@ -342,7 +567,7 @@ def run(fasta_path, groups_path, ts=.05, tc=.95, allow_path=None, device_stage=F
 def main(argv=None):
     from .fsearch import parse_flags
     argv = list(sys.argv if argv is None else argv)
-    args = parse_flags(argv, {'-i': '', '-g': '', '-l': .05, '-u': .95, '-r': None, '-G': 'F'})
+    args = parse_flags(argv, {'-i': '', '-g': '', '-l': .05, '-u': .95, '-r': None, '-G': 'F', '-t': '', '-d': '', '-m': 'jaccard', '-B': '0', '-S': '1'})
     if args['-i'] == '' or args['-g'] == '':
         manual_print()
         raise SystemExit()
@@ -351,7 +576,28 @@ def main(argv=None):
     except ValueError:
         manual_print()
         raise SystemExit()
-    lines = run(args['-i'], args['-g'], ts, tc, args['-r'], str(args['-G']).upper()[:1] == 'T')
+    gpu = str(args['-G']).upper()[:1] == 'T'
+    if args['-t'] == '' and args['-d'] == '' and (args['-B'], args['-S'], args['-m']) == ('0', '1', 'jaccard'):
+        lines = run(args['-i'], args['-g'], ts, tc, args['-r'], gpu)
+    else:
+        from .phy import DistanceRefused
+        from .rbh import _count_flag
+        boot, seed = _count_flag(args['-B'], 2 ** 31 - 1), _count_flag(args['-S'], 2 ** 64 - 1)
+        if boot is None or seed is None:
+            sys.stderr.write('pan_genome: -B takes a whole number of replicates from 0 to 2^31 - 1, -S a seed from 0 to 2^64 - 1\n')
+            return 2
+        if args['-m'] not in METRICS:
+            sys.stderr.write('pan_genome: -m names the gene-content distance, jaccard or overlap\n')
+            return 2
+        if boot > 0 and args['-t'] == '':
+            sys.stderr.write('pan_genome: -B labels the tree that -t writes: name a tree file with -t\n')
+            return 2
+        content = dict(tree_path=args['-t'], dist_path=args['-d'], metric=args['-m'], boot=boot, seed=seed) if args['-t'] or args['-d'] else None
+        try:
+            lines = run(args['-i'], args['-g'], ts, tc, args['-r'], gpu, content=content)
+        except (DistanceRefused, TooFewTaxa) as e:
+            sys.stderr.write('pan_genome: %s\n' % e)
+            return 2
     sys.stdout.write(''.join(l + '\n' for l in lines))
     sys.stdout.flush()
     return 0

@@ -302,3 +302,25 @@ def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p',
     t['boot'], t['boot_valid'] = boot_stats.get('boot', 0), boot_stats.get('boot_valid', 0)
     t['rows'], t['families'], t['columns'], t['kept'] = len(rec), len(sm.col_off) - 1, len(sm.gaps), len(sm.keep)
     return newick, sm, t
+
+
+def gene_content_tree_from_search(fasta_path, metric='jaccard', boot=0, boot_seed=1, pan_device=True, **groups_from_search_kw):
+    """one process from a FASTA file to the gene-content tree of its genomes: groups_from_search(fasta_path, **groups_from_search_kw),
+    then pan.content_tree on those groups -- what `scripts/pan_genome.py -i x.fsa -g x.clsr -t x.nwk -d x.tsv -m metric -B boot -S
+    boot_seed` writes on the groups file of the same search, with no groups text in between.  pan_device: the shared-family counts and
+    the bootstrap replicates on the device (pan.device_shared_counts, so_pan_shared; the replicates' trees by so_phy_nj_splits), else by
+    the numpy definitions.
+    -> (taxa in sorted order, Newick bytes, S int64[T, T] (the families every pair shares), D float64[T, T], the dict of
+    groups_from_search with pan_host (ids and taxa coded on the host) and content (the stage) added, in seconds)"""
+    from . import pan
+    groups, t = groups_from_search(fasta_path, **groups_from_search_kw)
+    t0 = time.time()
+    with open(fasta_path, 'r') as f:
+        text = f.read()
+    taxa = pan.taxa_of_fasta(text)
+    table = pan.member_table_of(groups, pan.fasta_ids(text), taxa)
+    t['pan_host'] = time.time() - t0
+    t0 = time.time()
+    newick, S, D = pan.content_tree(table, taxa, metric, boot, boot_seed, device_stage=pan_device, device=groups_from_search_kw.get('device', 0))
+    t['content'] = time.time() - t0
+    return sorted(taxa), newick, S, D, t
