@@ -711,6 +711,52 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matri
                 int64_t n_reps, const uint64_t *ref_splits, int32_t flags, so_phy_boot_result *out);
 void so_phy_boot_free(so_phy_boot_result *result);
 
+/* Gene concordance factors of the species tree on the device (csrc/phy.hip): what swiftortho_amd/phy.py `family_counts()`,
+ * `family_present()`, `gene_distances()` (model p), `nj_splits_subset()` and `concordance()` define, array for array.  For every inner branch
+ * of the printed tree: the families able to decide it, and those among them whose own neighbour-joining tree holds it.
+ * matrix: n_taxa rows of n_cols bytes (host); keep: n_keep columns in 0 .. n_cols - 1; family f owns keep[fam_off[f] .. fam_off[f + 1]) (fam_off
+ *   rises from 0 to n_keep; a family may own nothing).  Taxon t is PRESENT in family f iff one of the family's kept columns holds a byte other
+ *   than '-' in row t (cmp[f][t][t] > 0); bit sets are n_words = ceil(n_taxa / 64) words, bit t & 63 of word t >> 6.
+ * so_phy_gene_counts: cmp, same [n][n_taxa][n_taxa] of the families f0 .. f0 + n - 1 (the pair counts of so_phy_build over each family's kept
+ *   columns): k_phy_fam_gather lays the families' columns side by side, each padded with '-' to a multiple of 16 bytes; k_phy_fam_pairs is
+ *   k_phy_pairs' tile walk with a workgroup per (tile, family) and plain 32-bit stores.  flags must be 0.
+ * so_phy_nj_subsets: D [n_reps][n_taxa][n_taxa] float64 and present [n_reps][n_words] (host) -> splits [n_reps][n_taxa - 3][n_words]: the walk
+ *   of so_phy_nj_splits over the present taxa alone (the same body: the live list starts as the present taxa, ascending), each clade in the
+ *   original bits, complemented inside the present set where it holds the LOWEST PRESENT taxon; with n present taxa the rows n - 3 .. are zeros,
+ *   n < 4: all zeros.  Only present x present of D is read: there it is finite and symmetric bit for bit.  flags bit 0 (tests): the clade bit
+ *   sets in global scratch whatever n_taxa.
+ * so_phy_gene: the fused path of the p distance -- per family the counts, D = 1 - same / cmp, the present words, n_present, the walk and the
+ *   comparison with the n_taxa - 3 splits of the printed tree (ref_splits, so_phy_nj_splits' form) stay in device memory.  ok[f] = 0: two
+ *   present taxa of family f share no compared column, the family is dropped (its splits are zeros).  For split s with clade C and an ok
+ *   family with present set P: A = C & P, B = P & ~C; decisive[s] counts the families where both hold two taxa, concordant[s] those among them
+ *   whose tree holds the one of A and B without P's lowest taxon.  flags bit 0: present [n_fam][n_words] and splits [n_fam][n_taxa - 3][n_words]
+ *   come back too; bit 1: events around the stages of every batch -- counts_ms (the gather, pair counts, distances and presence), trees_ms,
+ *   concord_ms.  Families run in batches sized from the free device memory (SOHIT_PHY_GENE_BATCH forces the size), one host wait per batch:
+ *   waits == batches.  nj_tier: as so_phy_boot's.
+ * Refused with a message (so_phy_last_error) and nothing left allocated: n_taxa below 2 or above 4096, n_fam below 1, a fam_off that does not
+ * rise from 0 to n_keep, a keep entry outside 0 .. n_cols - 1, families outside 0 .. n_fam - 1 or more than 32768 of them in so_phy_gene_counts,
+ * padded rows beyond 2^31 - 16 bytes, a present bit at n_taxa or beyond, a D that is not finite or not symmetric between present taxa, unknown
+ * flag bits, no device. */
+typedef struct so_phy_gene_result {
+    int64_t n_taxa, n_fam, n_splits, n_words;   /* n_fam: the families (so_phy_nj_subsets: the matrices) of the result */
+    int32_t waits, batches;
+    double counts_ms, trees_ms, concord_ms;   /* so_phy_gene with flags bit 1: device time of the three stages, summed over the batches */
+    int64_t *cmp, *same;          /* so_phy_gene_counts: n_fam * n_taxa * n_taxa */
+    uint64_t *splits;             /* so_phy_nj_subsets, so_phy_gene with flags bit 0: n_fam * n_splits * n_words */
+    uint64_t *present;            /* so_phy_gene with flags bit 0: n_fam * n_words */
+    int32_t *decisive, *concordant;   /* so_phy_gene: n_splits */
+    int32_t *n_present;           /* so_phy_gene: n_fam */
+    uint8_t *ok;                  /* so_phy_gene: n_fam */
+    int32_t nj_tier;              /* so_phy_nj_subsets, so_phy_gene: 0: no walk (n_taxa < 4), 1: clade bit sets in the LDS, 2: in global scratch */
+    int32_t reserved;
+} so_phy_gene_result;
+int so_phy_gene_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, int64_t n_fam,
+                       const int64_t *fam_off, int64_t f0, int64_t n, int32_t flags, so_phy_gene_result *out);
+int so_phy_nj_subsets(int device, int64_t n_reps, int64_t n_taxa, const double *D, const uint64_t *present, int32_t flags, so_phy_gene_result *out);
+int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t *matrix, int64_t n_keep, const int64_t *keep, int64_t n_fam,
+                const int64_t *fam_off, const uint64_t *ref_splits, int32_t flags, so_phy_gene_result *out);
+void so_phy_gene_free(so_phy_gene_result *result);
+
 /* The substitution-count tensor of a supermatrix on the matrix cores (csrc/phy.hip): what swiftortho_amd/phy.py `subst_counts()` and
  * `boot_subst()` define, integer for integer.  It is what the Kimura and LogDet distances of the species tree are made from.
  * Residue code a = the index of a byte in ARNDCQEGHILKMFPSTWYV; every other byte ('-', X, B, Z, U, '*', lower case, 0x00, 0xFF) is uncoded.

@@ -16,7 +16,9 @@ FASTA, taxa in slot order), <name>.aln.trim (the columns whose share of gaps is 
 nothing: it joins the families along the alignments the search itself made (swiftortho_amd/phy.py), in one process that searches the
 proteome once more with a CIGAR on every row; with `-G T` the matrix and the pair counts are built on the GPU.  `-B n` (default 0: the
 bare tree) labels the tree's nodes with their bootstrap support over n replicates of the kept columns, drawn from the seed `-S` (default 1)
--- what the reference gets from `fasttree -boot`; with `-G T` the replicates run on the GPU.
+-- what the reference gets from `fasttree -boot`; with `-G T` the replicates run on the GPU.  `-K T` labels the nodes with their gene
+concordance factors (the share of the core families able to decide a branch whose own tree holds it; `boot/gcf` with `-B`) and writes
+the table of them to <name>.gcf.tsv.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
 (<name>.xyz, three columns), THAT file is clustered, and the numbers are mapped back into <name>.clsr (the .grp file in between is
@@ -41,7 +43,7 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1', '-K': 'F'}
 
 
 def main(argv):
@@ -109,8 +111,10 @@ def main(argv):
         # row and joins the core families of -r along those alignments; <name>.aln, <name>.aln.trim (the columns -g keeps) and <name>.nwk
         t = time()
         from swiftortho_amd import phy, pipeline
-        newick, sm, _ = pipeline.species_tree_from_search(fas, reference=a['-r'], gap_share=float(a['-g']), model=a['-m'],
-                                                          device_stage=a['-G'].upper()[:1] == 'T', boot=int(a['-B']), boot_seed=int(a['-S']), **nr.collapsed_search_kw(a['-s'], a['-v']))
+        gcf = a['-K'].upper()[:1] == 'T'
+        newick, sm, st = pipeline.species_tree_from_search(fas, reference=a['-r'], gap_share=float(a['-g']), model=a['-m'],
+                                                           device_stage=a['-G'].upper()[:1] == 'T', boot=int(a['-B']), boot_seed=int(a['-S']),
+                                                           **dict(nr.collapsed_search_kw(a['-s'], a['-v']), **({'concordance': True} if gcf else {})))
         aln = '%s_results/%s.aln' % (fas, name)
         with open(aln, 'wb') as o:
             o.write(phy.supermatrix_fasta(sm.taxa, sm.matrix, range(sm.matrix.shape[1])))
@@ -118,6 +122,9 @@ def main(argv):
             o.write(phy.supermatrix_fasta(sm.taxa, sm.matrix, sm.keep))
         with open('%s_results/%s.nwk' % (fas, name), 'wb') as o:
             o.write(newick + b'\n')
+        if gcf:
+            with open('%s_results/%s.gcf.tsv' % (fas, name), 'wb') as o:
+                o.write(phy.gcf_table(sm.taxa, st['gcf']['splits'], st['gcf']['decisive'], st['gcf']['concordant']))
         print('species tree time:', time() - t)
     if os.path.isfile(a['-p']):
         # operon clustering (run_all_fast.py:241-255): scored operon pairs from the gene families, then the same clustering as above

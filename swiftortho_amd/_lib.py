@@ -58,7 +58,8 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error", "so_pan_shared", "so_pan_shared_free",
            "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
-           "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free"]
+           "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free",
+           "so_phy_gene", "so_phy_gene_counts", "so_phy_nj_subsets", "so_phy_gene_free"]
 
 
 class SoMclResult(C.Structure):
@@ -142,6 +143,14 @@ class SoPhyBootResult(C.Structure):
                [("waits", C.c_int32), ("batches", C.c_int32), ("counts_ms", C.c_double), ("trees_ms", C.c_double), ("support_ms", C.c_double),
                 ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64)),
                 ("splits", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)), ("ok", C.POINTER(C.c_uint8)),
+                ("nj_tier", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SoPhyGeneResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_fam", "n_splits", "n_words")] + \
+               [("waits", C.c_int32), ("batches", C.c_int32), ("counts_ms", C.c_double), ("trees_ms", C.c_double), ("concord_ms", C.c_double),
+                ("cmp", C.POINTER(C.c_int64)), ("same", C.POINTER(C.c_int64)), ("splits", C.POINTER(C.c_uint64)), ("present", C.POINTER(C.c_uint64)),
+                ("decisive", C.POINTER(C.c_int32)), ("concordant", C.POINTER(C.c_int32)), ("n_present", C.POINTER(C.c_int32)), ("ok", C.POINTER(C.c_uint8)),
                 ("nj_tier", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -313,6 +322,10 @@ def load():
     L.so_phy_boot_free.argtypes = [C.POINTER(SoPhyBootResult)]
     L.so_phy_subst.argtypes = [C.c_int, i64, i64, vp, i64, vp, C.c_uint64, i64, i64, C.c_int32, C.POINTER(SoPhySubstResult)]
     L.so_phy_subst_free.argtypes = [C.POINTER(SoPhySubstResult)]
+    L.so_phy_gene.argtypes = [C.c_int, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int32, C.POINTER(SoPhyGeneResult)]
+    L.so_phy_gene_counts.argtypes = [C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, i64, C.c_int32, C.POINTER(SoPhyGeneResult)]
+    L.so_phy_nj_subsets.argtypes = [C.c_int, i64, i64, vp, vp, C.c_int32, C.POINTER(SoPhyGeneResult)]
+    L.so_phy_gene_free.argtypes = [C.POINTER(SoPhyGeneResult)]
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

@@ -38,6 +38,18 @@
 //                       k_phy_subst        N = E E^T on the matrix cores (v_mfma_i32_32x32x32_i8, i32 accumulators), E the one-hot matrix
 //                                          of 20 rows per taxon, never written: a lane compares 16 staged codes with its row's residue.
 //                                          Integers only; determinants and logarithms stay on the host.
+//
+// Gene concordance factors of the species tree (phy.py family_counts, family_present, gene_distances, nj_splits_subset, concordance):
+//   so_phy_gene_counts  k_phy_fam_gather   the kept columns family by family, each family's range padded with '-' to a multiple of 16 bytes;
+//                       k_phy_fam_pairs    the tile walk of k_phy_pairs (pairs_tile_walk) over one family's words, a workgroup per (tile,
+//                                          family): plain 32-bit stores, no atomics, nothing to clear.
+//   so_phy_nj_subsets   k_phy_nj_subset    the walk of k_phy_nj (nj_walk) over the taxa a family holds: the live list starts as the present
+//                                          bits, a clade with the lowest present taxon is complemented inside the present set.
+//   so_phy_gene         the fused path of the p distance: gather, pairs, k_phy_gene_dist (D = 1 - same / cmp among the present taxa, the present
+//                       words and their count from the diagonal; two present taxa without a compared column drop the family), k_phy_nj_subset,
+//                       k_phy_gene_concord (a lane per (split of the printed tree, family): popcounts, the canonical side, a search in the
+//                       family's splits, integer atomicAdd).  Batches of families sized from the free device memory
+//                       (SOHIT_PHY_GENE_BATCH), one host wait per batch.
 #include "hit_table.h"
 
 #include <algorithm>
@@ -201,29 +213,17 @@ __global__ __launch_bounds__(256) void k_phy_gather(const u8* __restrict__ matri
 // 0x80 in every byte of x that is not 0 (no carry leaves a byte: 0x7f + 0x7f < 0x100)
 __device__ __forceinline__ u32 nonzero_bytes(u32 x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
 
-// grid (nt * nt tiles of 64 x 64 pairs, ranges of `wps` words); K: T rows of Lpw words (Lpw a multiple of 4), '-' behind the kept columns.
-// lane (ty, tx) of the 16 x 16 holds rows I * 64 + ty * 4 + r against rows J * 64 + tx * 4 + c.
-// blockIdx.z: the replicate of a bootstrap batch -- its rows lie krep words, its counters orep elements behind the last one's (0, 0: one matrix).
-__global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u32 T, u32 Lpw, const u32* __restrict__ d_nk, u32 nt, u32 wps, ull* __restrict__ cmp,
-                                                   ull* __restrict__ same, size_t krep, size_t orep) {
-    K += (size_t)blockIdx.z * krep, cmp += (size_t)blockIdx.z * orep, same += (size_t)blockIdx.z * orep;
+// The walk of one tile of 64 x 64 taxon pairs over the words [w_begin, w_end) of K: T rows of Lpw words (Lpw and w_begin multiples of 4),
+// staged chunk by chunk in the LDS.  lane (ty, tx) of the 16 x 16 holds rows I * 64 + ty * 4 + r against rows J * 64 + tx * 4 + c; a row
+// beyond T is staged as '-' and counts nothing.  The whole workgroup calls it (it synchronises); cs, ss: the lane's 4 x 4 sums, added to.
+__device__ __forceinline__ void pairs_tile_walk(const u32* __restrict__ K, u32 T, u32 Lpw, u32 I, u32 J, u32 w_begin, u32 w_end, u32 (&cs)[4][4], u32 (&ss)[4][4]) {
     __shared__ __attribute__((aligned(16))) u32 sA[PHY_CHUNK_WORDS][PHY_TILE];
     __shared__ __attribute__((aligned(16))) u32 sNA[PHY_CHUNK_WORDS][PHY_TILE];
     __shared__ __attribute__((aligned(16))) u32 sB[PHY_CHUNK_WORDS][PHY_TILE];
     __shared__ __attribute__((aligned(16))) u32 sNB[PHY_CHUNK_WORDS][PHY_TILE];
-    const u32 I = blockIdx.x / nt, J = blockIdx.x % nt;
-    if (I > J) return;
-    const u32 nkw = min(Lpw, (*d_nk + 3u) >> 2);   // words that hold a kept column; the last one may be partial: its tail is '-'
-    const u32 w_begin = blockIdx.y * wps, w_end = min(nkw, w_begin + wps);
-    if (w_begin >= w_end) return;   // (the whole workgroup)
     const u32 tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
     const u32 lrow = threadIdx.x & 63u, lpart = threadIdx.x >> 6;
     const u32 ra = I * PHY_TILE + lrow, rb = J * PHY_TILE + lrow;
-    u32 cs[4][4], ss[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) cs[r][c] = 0u, ss[r][c] = 0u;
     for (u32 w0 = w_begin; w0 < w_end; w0 += PHY_CHUNK_WORDS) {
         __syncthreads();   // the last chunk's readers are done
         for (u32 qd = lpart; qd < PHY_CHUNK_WORDS / 4u; qd += 4u) {
@@ -255,6 +255,25 @@ __global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u3
                 }
         }
     }
+}
+
+// grid (nt * nt tiles of 64 x 64 pairs, ranges of `wps` words); K: T rows of Lpw words (Lpw a multiple of 4), '-' behind the kept columns.
+// blockIdx.z: the replicate of a bootstrap batch -- its rows lie krep words, its counters orep elements behind the last one's (0, 0: one matrix).
+__global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u32 T, u32 Lpw, const u32* __restrict__ d_nk, u32 nt, u32 wps, ull* __restrict__ cmp,
+                                                   ull* __restrict__ same, size_t krep, size_t orep) {
+    K += (size_t)blockIdx.z * krep, cmp += (size_t)blockIdx.z * orep, same += (size_t)blockIdx.z * orep;
+    const u32 I = blockIdx.x / nt, J = blockIdx.x % nt;
+    if (I > J) return;
+    const u32 nkw = min(Lpw, (*d_nk + 3u) >> 2);   // words that hold a kept column; the last one may be partial: its tail is '-'
+    const u32 w_begin = blockIdx.y * wps, w_end = min(nkw, w_begin + wps);
+    if (w_begin >= w_end) return;   // (the whole workgroup)
+    const u32 tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    u32 cs[4][4], ss[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cs[r][c] = 0u, ss[r][c] = 0u;
+    pairs_tile_walk(K, T, Lpw, I, J, w_begin, w_end, cs, ss);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -320,36 +339,41 @@ __global__ __launch_bounds__(256) void k_phy_boot_dist(const ull* __restrict__ c
 
 __device__ __forceinline__ bool nj_before(double q, u32 a, u32 b, double q2, u32 a2, u32 b2) { return q < q2 || (q == q2 && (a < a2 || (a == a2 && b < b2))); }
 
-// phy.py nj_splits(): a workgroup per replicate, T >= 4.  D (the replicate's own T x T doubles, symmetric bit for bit, changed in place) stays
-// in global memory; the row sums r, the two live lists (positions -> original rows, ascending; u16: T <= 4096) and -- where `scratch` is
-// null -- the clade bit sets are LDS: r[T] | clade[T * W] | live[2][T].  Every index is a position below n <= T or an entry of the live
-// list, which only ever holds 0 .. T - 1; out is written at step * W + w with step < T - 3, w < W.
+// phy.py nj_splits() and nj_splits_subset(): the walk of one workgroup over one matrix, T >= 4.  D (the matrix's own T x T doubles,
+// symmetric bit for bit where it is read, changed in place) stays in global memory; the row sums r, the two live lists (positions ->
+// original rows, ascending; u16: T <= 4096) and -- where `scratch` is null -- the clade bit sets are LDS: r[T] | clade[T * W] | live[2][T].
+// present == null: every taxon is live, n0 == T.  Else the live list starts as the n0 >= 4 set bits of present[W], ascending, and the rows
+// and columns of D outside them are never read; a clade that holds the lowest live taxon is complemented inside the live set (inside the
+// T bits without `present`: the same rule), and the rows n0 - 3 .. T - 4 of out are zeroed.
+// Every index is a position below n <= n0 <= T or an entry of the live list, which only ever holds 0 .. T - 1 (a present bit at T or
+// beyond is refused by the host); out is written at step * W + w with step < T - 3, w < W.
 // Plain IEEE + - * / on doubles in the order of the definition (the build passes -ffp-contract=off: nothing is fused).
-__global__ __launch_bounds__(PHY_NJ_THREADS) void k_phy_nj(double* Dall, u32 T, u32 W, const u8* __restrict__ ok, ull* __restrict__ splits, ull* scratch) {
+__device__ __forceinline__ void nj_walk(double* D, u32 T, u32 W, ull* out, ull* clade_scratch, const ull* __restrict__ present, u32 n0) {
     extern __shared__ __attribute__((aligned(16))) u8 nj_lds[];
     __shared__ double red_q[PHY_NJ_THREADS / 64u];
     __shared__ u32 red_a[PHY_NJ_THREADS / 64u], red_b[PHY_NJ_THREADS / 64u], pick[2];
-    const u32 tid = threadIdx.x, S = T - 3u;
-    const size_t rep = blockIdx.x;
-    ull* out = splits + rep * S * W;
-    if (ok && !ok[rep]) {   // a dropped replicate: no tree (the whole workgroup)
-        for (u32 x = tid; x < S * W; x += PHY_NJ_THREADS) out[x] = 0ull;
-        return;
-    }
-    double* D = Dall + rep * T * T;
+    const u32 tid = threadIdx.x;
     double* r = reinterpret_cast<double*>(nj_lds);
-    ull* clade = scratch ? scratch + rep * T * W : reinterpret_cast<ull*>(r + T);
-    unsigned short* live = reinterpret_cast<unsigned short*>(r + T + (scratch ? 0u : T * W));
+    ull* clade = clade_scratch ? clade_scratch : reinterpret_cast<ull*>(r + T);
+    unsigned short* live = reinterpret_cast<unsigned short*>(r + T + (clade_scratch ? 0u : T * W));
     unsigned short* next = live + T;
-    for (u32 k = tid; k < T; k += PHY_NJ_THREADS) live[k] = (unsigned short)k;
+    for (u32 k = tid; k < T; k += PHY_NJ_THREADS) {
+        if (!present) live[k] = (unsigned short)k;
+        else if ((present[k >> 6] >> (k & 63u)) & 1ull) {   // its position: the present taxa below it (fewer than n0)
+            u32 pos = (u32)__popcll(present[k >> 6] & ((1ull << (k & 63u)) - 1ull));
+            for (u32 w = 0; w < (k >> 6); ++w) pos += (u32)__popcll(present[w]);
+            live[pos] = (unsigned short)k;
+        }
+    }
     for (u32 x = tid; x < T * W; x += PHY_NJ_THREADS) {
         const u32 t = x / W, w = x % W;
         clade[x] = (t >> 6) == w ? 1ull << (t & 63u) : 0ull;
     }
     const ull last_mask = (T & 63u) ? (1ull << (T & 63u)) - 1ull : ~0ull;
     __syncthreads();
-    u32 n = T;
-    for (u32 step = 0; step < S; ++step, --n) {
+    u32 n = n0;
+    const u32 steps = n0 - 3u;
+    for (u32 step = 0; step < steps; ++step, --n) {
         // r[a]: the row of position a summed left to right over the live nodes; D[k][i] for D[i][k]: the wave reads consecutive addresses
         for (u32 a = tid; a < n; a += PHY_NJ_THREADS) {
             const u32 i = live[a];
@@ -399,17 +423,46 @@ __global__ __launch_bounds__(PHY_NJ_THREADS) void k_phy_nj(double* Dall, u32 T, 
             const double v = ((D[(size_t)I * T + k] + D[(size_t)J * T + k]) - dij) / 2.;
             D[(size_t)I * T + k] = v, D[(size_t)k * T + I] = v;
         }
-        // the clades: position 0 is never removed and every join keeps the lower position, so taxon 0 sits in row 0's clade and nowhere else
+        // the clades: position 0 is never removed and every join keeps the lower position, so the lowest live taxon (taxon 0 when all
+        // are live) sits in position 0's clade and nowhere else
         for (u32 w = tid; w < W; w += PHY_NJ_THREADS) {
             const ull c = clade[(size_t)I * W + w] | clade[(size_t)J * W + w];
             clade[(size_t)I * W + w] = c;
-            out[(size_t)step * W + w] = I == 0u ? ~c & (w == W - 1u ? last_mask : ~0ull) : c;
+            out[(size_t)step * W + w] = pa == 0u ? ~c & (present ? present[w] : (w == W - 1u ? last_mask : ~0ull)) : c;
         }
         for (u32 c = tid; c + 1u < n; c += PHY_NJ_THREADS) next[c] = c < pb ? live[c] : live[c + 1u];
         __syncthreads();
         unsigned short* t = live;
         live = next, next = t;
     }
+    for (u32 x = steps * W + tid; x < (T - 3u) * W; x += PHY_NJ_THREADS) out[x] = 0ull;   // (nothing without `present`: steps == T - 3)
+}
+
+// a workgroup per replicate over all T >= 4 taxa; ok (may be null): a dropped replicate has no tree, its splits are zeros
+__global__ __launch_bounds__(PHY_NJ_THREADS) void k_phy_nj(double* Dall, u32 T, u32 W, const u8* __restrict__ ok, ull* __restrict__ splits, ull* scratch) {
+    const u32 S = T - 3u;
+    const size_t rep = blockIdx.x;
+    ull* out = splits + rep * S * W;
+    if (ok && !ok[rep]) {   // (the whole workgroup)
+        for (u32 x = threadIdx.x; x < S * W; x += PHY_NJ_THREADS) out[x] = 0ull;
+        return;
+    }
+    nj_walk(Dall + rep * T * T, T, W, out, scratch ? scratch + rep * T * W : nullptr, nullptr, T);
+}
+
+// a workgroup per family over its present taxa (present[fam][W], n_present[fam] of them); a dropped family and one with fewer than four
+// present taxa have no split: zeros
+__global__ __launch_bounds__(PHY_NJ_THREADS) void k_phy_nj_subset(double* Dall, u32 T, u32 W, const u8* __restrict__ ok, const u32* __restrict__ n_present,
+                                                                  const ull* __restrict__ present, ull* __restrict__ splits, ull* scratch) {
+    const u32 S = T - 3u;
+    const size_t fam = blockIdx.x;
+    ull* out = splits + fam * S * W;
+    const u32 n0 = n_present[fam];
+    if ((ok && !ok[fam]) || n0 < 4u || n0 > T) {   // (the whole workgroup; n0 <= T always: a count of bits below T)
+        for (u32 x = threadIdx.x; x < S * W; x += PHY_NJ_THREADS) out[x] = 0ull;
+        return;
+    }
+    nj_walk(Dall + fam * T * T, T, W, out, scratch ? scratch + fam * T * W : nullptr, present + fam * W, n0);
 }
 
 // grid (splits of the printed tree, replicates): does the replicate's tree hold the split?  (its T - 3 splits are distinct: one per inner edge)
@@ -426,6 +479,100 @@ __global__ __launch_bounds__(256) void k_phy_boot_support(const ull* __restrict_
         found = eq;
     }
     if (found) atomicAdd(count + s, 1u);
+}
+
+// ---- gene concordance: so_phy_gene, so_phy_gene_counts, so_phy_nj_subsets ------------------------------------------------------------------
+// grid (bytes of the padded row, taxa): the kept columns family by family, each family's range padded with '-' to a multiple of 16 bytes, so
+// that no family shares a 16-byte fragment with its neighbour.  src[j]: the matrix column of byte j of the row, -1 for padding (from the
+// host, which has checked every column against L).
+__global__ __launch_bounds__(256) void k_phy_fam_gather(const u8* __restrict__ matrix, u32 L, u32 Lp, const int* __restrict__ src, u8* __restrict__ K) {
+    const u32 j = blockIdx.x * 256u + threadIdx.x, t = blockIdx.y;
+    if (j >= Lp) return;
+    const int c = src[j];
+    K[(size_t)t * Lp + j] = c >= 0 ? matrix[(size_t)t * L + (u32)c] : (u8)PHY_DASH;
+}
+
+// grid (nt * nt tiles, 1, families of the batch): the pair counts of family f0 + z over the words [woff[z], woff[z + 1]) of the gathered
+// rows (multiples of 4, rising, the last one at most Lpw: the host has made them).  One workgroup owns a (tile, family): plain 32-bit stores,
+// both halves of the matrix (a family has fewer than 2^31 columns), zeros included -- no atomics, nothing to clear, an empty family too.
+__global__ __launch_bounds__(256) void k_phy_fam_pairs(const u32* __restrict__ K, u32 T, u32 Lpw, const u32* __restrict__ woff, u32 nt, u32* __restrict__ cmp,
+                                                       u32* __restrict__ same) {
+    const u32 I = blockIdx.x / nt, J = blockIdx.x % nt;
+    if (I > J) return;   // (tile (J, I) writes this one's elements)
+    const size_t at = (size_t)blockIdx.z * T * T;
+    const u32 tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    u32 cs[4][4], ss[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cs[r][c] = 0u, ss[r][c] = 0u;
+    pairs_tile_walk(K, T, Lpw, I, J, woff[blockIdx.z], min(Lpw, woff[blockIdx.z + 1u]), cs, ss);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32 x = I * PHY_TILE + ty * 4u + (u32)r, y = J * PHY_TILE + tx * 4u + (u32)c;
+            if (x >= T || y >= T) continue;
+            cmp[at + (size_t)x * T + y] = cs[r][c], same[at + (size_t)x * T + y] = ss[r][c];
+            if (I != J) cmp[at + (size_t)y * T + x] = cs[r][c], same[at + (size_t)y * T + x] = ss[r][c];
+        }
+}
+
+// grid (pairs, families): D = 1 - same / cmp in IEEE doubles, as k_phy_boot_dist divides, where both taxa are present (cmp[t][t] > 0), 0.0
+// elsewhere (nothing reads it); two present taxa without a compared column clear the family's ok (every writer stores the same byte).
+// The first wave of the first workgroup of a family also writes its present words and n_present.
+__global__ __launch_bounds__(256) void k_phy_gene_dist(const u32* __restrict__ cmp, const u32* __restrict__ same, u32 T, u32 W, double* __restrict__ D, u8* __restrict__ ok,
+                                                       ull* __restrict__ present, u32* __restrict__ n_present) {
+    const u32 TT = T * T, i = blockIdx.x * 256u + threadIdx.x;
+    const size_t base = (size_t)blockIdx.y * TT;
+    if (blockIdx.x == 0u && threadIdx.x < 64u) {
+        u32 cnt = 0;
+        for (u32 w = threadIdx.x; w < W; w += 64u) {
+            ull bits = 0ull;
+            for (u32 t = w * 64u; t < min(T, w * 64u + 64u); ++t) bits |= cmp[base + (size_t)t * T + t] ? 1ull << (t & 63u) : 0ull;
+            present[(size_t)blockIdx.y * W + w] = bits;
+            cnt += (u32)__popcll(bits);
+        }
+        cnt = (u32)wave_sum64((ull)cnt);
+        if (threadIdx.x == 0u) n_present[blockIdx.y] = cnt;
+    }
+    if (i >= TT) return;
+    const u32 x = i / T, y = i % T, c = cmp[base + i];
+    const bool both = cmp[base + (size_t)x * T + x] && cmp[base + (size_t)y * T + y];
+    if (both && c == 0u) ok[blockIdx.y] = 0;
+    D[base + i] = both ? 1. - (double)same[base + i] / (double)c : 0.;
+}
+
+// grid (splits of the printed tree, families): clade C of split s against the present set P of an ok family: A = C & P, B = P & ~C; decisive
+// iff both hold two taxa; concordant iff the family's tree holds the one of A and B without P's lowest taxon -- the form its own splits
+// have (rows n_present - 3 .. are zeros and match nothing: a side holds two taxa).  Integer atomics: the sums do not depend on the order.
+__global__ __launch_bounds__(256) void k_phy_gene_concord(const ull* __restrict__ ref, const ull* __restrict__ splits, u32 S, u32 W, const u8* __restrict__ ok,
+                                                          const u32* __restrict__ n_present, const ull* __restrict__ present, u32* __restrict__ decisive,
+                                                          u32* __restrict__ concordant) {
+    const u32 s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= S || !ok[blockIdx.y]) return;
+    const u32 n = n_present[blockIdx.y];
+    if (n < 4u) return;
+    const ull* P = present + (size_t)blockIdx.y * W;
+    const ull* C = ref + (size_t)s * W;
+    u32 na = 0, nb = 0;
+    bool seen = false, a_low = false;
+    for (u32 w = 0; w < W; ++w) {
+        const ull p = P[w], a = C[w] & p;
+        na += (u32)__popcll(a), nb += (u32)__popcll(p & ~C[w]);
+        if (!seen && p) seen = true, a_low = (a & (p & (~p + 1ull))) != 0ull;
+    }
+    if (na < 2u || nb < 2u) return;
+    atomicAdd(decisive + s, 1u);
+    const ull* fam = splits + (size_t)blockIdx.y * S * W;
+    const u32 rows = min(S, n - 3u);
+    bool found = false;
+    for (u32 x = 0; x < rows && !found; ++x) {
+        bool eq = true;
+        for (u32 w = 0; w < W && eq; ++w) eq = fam[(size_t)x * W + w] == (a_low ? P[w] & ~C[w] : C[w] & P[w]);
+        found = eq;
+    }
+    if (found) atomicAdd(concordant + s, 1u);
 }
 
 // ---- so_phy_subst: the 20 x 20 table of residue pairs per pair of taxa -------------------------------------------------------------------
@@ -552,6 +699,7 @@ thread_local std::string g_phy_err;
 auto slots(so_phy_subst_result* r) { return result_slots(&r->subst); }
 auto slots(so_phy_result* r) { return result_slots(&r->row, &r->matrix, &r->gaps, &r->keep, &r->cmp, &r->same); }
 auto slots(so_phy_boot_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->count, &r->ok); }
+auto slots(so_phy_gene_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->present, &r->decisive, &r->concordant, &r->n_present, &r->ok); }
 
 // four marks around the three stages of a batch (flags bit 1 of so_phy_boot): recorded on the stream, read after the batch's wait
 struct StageEvents {
@@ -612,6 +760,48 @@ size_t nj_lds_bytes(u32 T, u32 W, bool in_lds) { return (size_t)T * 8u + (in_lds
 bool nj_clades_fit(u32 T, u32 W) { return nj_lds_bytes(T, W, true) <= PHY_NJ_LDS_BYTES; }
 void nj_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, ull* splits, ull* clades) {
     hipLaunchKernelGGL(k_phy_nj, dim3(nb), dim3(PHY_NJ_THREADS), nj_lds_bytes(T, W, clades == nullptr), st, D, T, W, ok, splits, clades);
+}
+void nj_subset_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, const u32* n_present, const ull* present, ull* splits, ull* clades) {
+    hipLaunchKernelGGL(k_phy_nj_subset, dim3(nb), dim3(PHY_NJ_THREADS), nj_lds_bytes(T, W, clades == nullptr), st, D, T, W, ok, n_present, present, splits, clades);
+}
+
+// ---- gene concordance ----
+static_assert(sizeof(so_phy_gene_result) == 136, "swiftortho_amd/_lib.py SoPhyGeneResult mirrors the layout");
+// what the calls over families check before anything touches the device
+void gene_check(const std::string& who, i64 n_taxa, i64 n_cols, const u8* matrix, i64 n_keep, const i64* keep, i64 n_fam, const i64* fam_off) {
+    if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+    if (n_cols < 0 || n_cols > 0x7FFFFFFFll) throw SoError(who + ": more than 2^31 - 1 columns are not supported");
+    if (n_keep < 0 || n_keep > 0x7FFFFFFFll - 16) throw SoError(who + ": more than 2^31 - 17 kept columns are not supported");
+    if (n_fam < 1 || n_fam >= (1ll << 31)) throw SoError(who + ": the families number 1 .. 2^31 - 1 (n_fam is " + std::to_string(n_fam) + ")");
+    if (!fam_off || (n_keep > 0 && !keep) || ((i64)n_taxa * n_cols > 0 && !matrix)) throw SoError(who + ": matrix, keep or fam_off is NULL");
+    if (fam_off[0] != 0) throw SoError(who + ": inconsistent offsets: fam_off does not start at 0");
+    for (i64 f = 0; f < n_fam; ++f)
+        if (fam_off[f + 1] < fam_off[f]) throw SoError(who + ": inconsistent offsets: fam_off falls at family " + std::to_string(f));
+    if (fam_off[n_fam] != n_keep) throw SoError(who + ": inconsistent offsets: fam_off does not end at n_keep");
+    for (i64 k = 0; k < n_keep; ++k)
+        if (keep[k] < 0 || keep[k] >= n_cols) throw SoError(who + ": keep[" + std::to_string(k) + "] lies outside 0 .. n_cols - 1");
+}
+// the gathered row of the families f0 .. f0 + nf - 1: src[j] = the matrix column of byte j, -1 where a family's range is padded to a
+// multiple of 16 bytes; woff[z] = the first 32-bit word of family f0 + z (nf + 1 of them, multiples of 4)
+void gene_layout(const std::string& who, const i64* keep, const i64* fam_off, i64 f0, i64 nf, std::vector<int>& src, std::vector<u32>& woff) {
+    u64 bytes = 0;
+    for (i64 f = f0; f < f0 + nf; ++f) bytes += ((u64)(fam_off[f + 1] - fam_off[f]) + 15u) & ~15ull;
+    if (bytes > 0x7FFFFFF0ull) throw SoError(who + ": the families' padded columns take more than 2^31 - 16 bytes a row: ask for fewer families per call");
+    src.assign((size_t)bytes, -1), woff.assign((size_t)nf + 1, 0u);
+    size_t at = 0;
+    for (i64 z = 0; z < nf; ++z) {
+        const i64 k0 = fam_off[f0 + z], k1 = fam_off[f0 + z + 1];
+        for (i64 k = k0; k < k1; ++k) src[at + (size_t)(k - k0)] = (int)keep[k];
+        at += ((size_t)(k1 - k0) + 15u) & ~(size_t)15u;
+        woff[(size_t)z + 1] = (u32)(at / 4u);
+    }
+}
+// the gathered rows of such a layout (T rows of src.size() bytes) in K
+void gene_gather(hipStream_t st, const u8* matrix, u32 T, u32 L, const std::vector<int>& src, DevBuf<int>& d_src, DevBuf<u8>& K) {
+    const u32 Lp = (u32)src.size();
+    upload(d_src, src.data(), src.size(), st);
+    K.ensure((size_t)T * Lp + 16);
+    if (Lp) hipLaunchKernelGGL(k_phy_fam_gather, dim3((Lp + 255u) / 256u, T), dim3(256), 0, st, matrix, L, Lp, d_src.p, K.p);
 }
 
 }  // namespace
@@ -1000,6 +1190,186 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
         }
         out->waits = call.waits;
         for (size_t b = 0; b < B; ++b) out->valid += out->ok[b] ? 1 : 0;
+        fill_empty_slots(slots(out));
+    });
+}
+
+void so_phy_gene_free(so_phy_gene_result* r) {
+    if (r) release_slots(r, slots(r));
+}
+
+int so_phy_gene_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, int64_t n_fam, const int64_t* fam_off,
+                       int64_t f0, int64_t n, int32_t flags, so_phy_gene_result* out) {
+    const std::string who = "so_phy_gene_counts";
+    return guarded_call(g_phy_err, out, so_phy_gene_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags != 0) throw SoError(who + ": unknown flag bits (flags is reserved and must be 0)");
+        gene_check(who, n_taxa, n_cols, matrix, n_keep, keep, n_fam, fam_off);
+        if (f0 < 0 || n < 1 || f0 > n_fam || n > n_fam - f0) throw SoError(who + ": the families f0 .. f0 + n - 1 lie outside 0 .. n_fam - 1");
+        if (n > PHY_BOOT_MAX_BATCH) throw SoError(who + ": more than " + std::to_string(PHY_BOOT_MAX_BATCH) + " families in one call are not supported");
+        std::vector<int> src;
+        std::vector<u32> woff;
+        gene_layout(who, keep, fam_off, f0, n, src, woff);
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, nf = (u32)n, nt = (T + PHY_TILE - 1u) / PHY_TILE;
+        const size_t TT = (size_t)T * T;
+        out->n_taxa = n_taxa, out->n_fam = n;
+        check_device(who.c_str(), device);
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<u8> d_matrix, K;
+        DevBuf<int> d_src;
+        DevBuf<u32> d_woff, d_cmp, d_same;
+        upload(d_matrix, matrix, (size_t)T * L, st), upload(d_woff, woff.data(), woff.size(), st);
+        gene_gather(st, d_matrix.p, T, L, src, d_src, K);
+        d_cmp.ensure((size_t)nf * TT + 2), d_same.ensure((size_t)nf * TT + 2);
+        hipLaunchKernelGGL(k_phy_fam_pairs, dim3(nt * nt, 1, nf), dim3(256), 0, st, reinterpret_cast<const u32*>(K.p), T, (u32)(src.size() / 4u), d_woff.p, nt, d_cmp.p, d_same.p);
+        HIP_CHECK(hipGetLastError());
+        std::vector<u32> c32((size_t)nf * TT), s32((size_t)nf * TT);
+        call.fetch(c32.data(), d_cmp.p, c32.size()), call.fetch(s32.data(), d_same.p, s32.size());
+        call.wait();
+        out->cmp = host_array<int64_t>(who.c_str(), c32.size()), out->same = host_array<int64_t>(who.c_str(), s32.size());
+        for (size_t i = 0; i < c32.size(); ++i) out->cmp[i] = c32[i], out->same[i] = s32[i];
+        out->waits = call.waits, out->batches = 1;
+        fill_empty_slots(slots(out));
+    });
+}
+
+int so_phy_nj_subsets(int device, int64_t n_reps, int64_t n_taxa, const double* D, const uint64_t* present, int32_t flags, so_phy_gene_result* out) {
+    const std::string who = "so_phy_nj_subsets";
+    return guarded_call(g_phy_err, out, so_phy_gene_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: the clade bit sets in global scratch)");
+        if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+        if (n_reps < 1 || n_reps >= (1ll << 31)) throw SoError(who + ": the matrices number 1 .. 2^31 - 1 (n_reps is " + std::to_string(n_reps) + ")");
+        if (!D || !present) throw SoError(who + ": D or present is NULL");
+        const u32 T = (u32)n_taxa, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
+        const size_t TT = (size_t)T * T;
+        const u64 last_mask = (T & 63u) ? (1ull << (T & 63u)) - 1ull : ~0ull;
+        std::vector<u32> npres((size_t)n_reps);
+        std::vector<u32> rows;
+        for (i64 b = 0; b < n_reps; ++b) {
+            const double* M = D + (size_t)b * TT;
+            const uint64_t* P = present + (size_t)b * W;
+            if (P[W - 1u] & ~last_mask) throw SoError(who + ": the present words of matrix " + std::to_string(b) + " name a taxon beyond n_taxa - 1");
+            rows.clear();
+            for (u32 t = 0; t < T; ++t)
+                if ((P[t >> 6] >> (t & 63u)) & 1ull) rows.push_back(t);
+            npres[(size_t)b] = (u32)rows.size();
+            for (u32 i : rows)
+                for (u32 j : rows) {
+                    if (!std::isfinite(M[(size_t)i * T + j])) throw SoError(who + ": matrix " + std::to_string(b) + " holds a value that is not finite between two present taxa");
+                    if (j < i && memcmp(&M[(size_t)i * T + j], &M[(size_t)j * T + i], sizeof(double)) != 0)
+                        throw SoError(who + ": matrix " + std::to_string(b) + " is not symmetric bit for bit between two present taxa");
+                }
+        }
+        out->n_taxa = n_taxa, out->n_fam = n_reps, out->n_splits = S, out->n_words = W;
+        check_device(who.c_str(), device);
+        if (S == 0) {   // two or three taxa: one topology, no split
+            fill_empty_slots(slots(out));
+            return;
+        }
+        const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
+        out->nj_tier = in_lds ? 1 : 2;
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<double> d_D;
+        DevBuf<ull> d_splits, clades, d_present;
+        DevBuf<u32> d_np;
+        const size_t per_call = PHY_BOOT_MAX_BATCH;
+        out->splits = host_array<uint64_t>(who.c_str(), (size_t)n_reps * S * W);
+        for (size_t b0 = 0; b0 < (size_t)n_reps; b0 += per_call) {
+            const u32 nb = (u32)std::min(per_call, (size_t)n_reps - b0);
+            upload(d_D, D + b0 * TT, (size_t)nb * TT, st), upload(d_present, reinterpret_cast<const ull*>(present) + b0 * W, (size_t)nb * W, st);
+            upload(d_np, npres.data() + b0, nb, st);
+            d_splits.ensure((size_t)nb * S * W + 2);
+            if (!in_lds) clades.ensure((size_t)nb * T * W + 2);
+            nj_subset_launch(st, d_D.p, T, W, nb, nullptr, d_np.p, d_present.p, d_splits.p, in_lds ? nullptr : clades.p);
+            HIP_CHECK(hipGetLastError());
+            call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * S * W, d_splits.p, (size_t)nb * S * W);
+            call.wait();
+            ++out->batches;
+        }
+        out->waits = call.waits;
+        fill_empty_slots(slots(out));
+    });
+}
+
+int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, int64_t n_fam, const int64_t* fam_off,
+                const uint64_t* ref_splits, int32_t flags, so_phy_gene_result* out) {
+    const std::string who = "so_phy_gene";
+    return guarded_call(g_phy_err, out, so_phy_gene_free, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~3) throw SoError(who + ": unknown flag bits (bit 0: every family's present words and splits in the result, bit 1: the stages timed by events)");
+        gene_check(who, n_taxa, n_cols, matrix, n_keep, keep, n_fam, fam_off);
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u, nt = (T + PHY_TILE - 1u) / PHY_TILE;
+        if (S && !ref_splits) throw SoError(who + ": ref_splits is NULL");
+        std::vector<int> src;
+        std::vector<u32> woff;
+        gene_layout(who, keep, fam_off, 0, n_fam, src, woff);
+        const bool want_all = flags & 1, timed = flags & 2;
+        const size_t TT = (size_t)T * T, F = (size_t)n_fam, SW = (size_t)S * W;
+        out->n_taxa = n_taxa, out->n_fam = n_fam, out->n_splits = S, out->n_words = W;
+        check_device(who.c_str(), device);
+        const char* w = who.c_str();
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<u8> d_matrix, K, d_ok;
+        DevBuf<int> d_src;
+        DevBuf<u32> d_woff, d_cmp, d_same, d_np, d_dec, d_con;
+        DevBuf<ull> d_ref, d_present, d_splits, clades;
+        DevBuf<double> d_D;
+        upload(d_matrix, matrix, (size_t)T * L, st), upload(d_woff, woff.data(), woff.size(), st);
+        if (S) upload(d_ref, reinterpret_cast<const ull*>(ref_splits), SW, st);
+        d_dec.ensure((size_t)S + 2), d_con.ensure((size_t)S + 2);
+        HIP_CHECK(hipMemsetAsync(d_dec.p, 0, ((size_t)S + 2) * sizeof(u32), st));
+        HIP_CHECK(hipMemsetAsync(d_con.p, 0, ((size_t)S + 2) * sizeof(u32), st));
+        StageEvents ev(timed);
+        ev.mark(0, st);
+        gene_gather(st, d_matrix.p, T, L, src, d_src, K);   // (the first batch's counts stage is timed from here)
+        // a batch: two 32-bit counters and a distance per pair, the present words, the splits and the bit sets of every family
+        const bool in_lds = S && nj_clades_fit(T, W);
+        out->nj_tier = S ? (in_lds ? 1 : 2) : 0;
+        const size_t per_fam = 2u * TT * 4u + TT * 8u + SW * 8u + (S && !in_lds ? (size_t)T * W * 8u : 0u) + (size_t)W * 8u + 5u;
+        size_t batch = (size_t)call.tn.phy_gene_batch;
+        if (call.tn.phy_gene_batch <= 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            batch = std::max<size_t>(1, free_b / 2 / (per_fam + per_fam / 8));   // (a DevBuf takes an eighth more than it is asked for)
+        }
+        batch = std::min(std::min(batch, F), (size_t)PHY_BOOT_MAX_BATCH);
+        d_cmp.ensure(batch * TT + 2), d_same.ensure(batch * TT + 2), d_D.ensure(batch * TT + 2), d_ok.ensure(batch + 2), d_np.ensure(batch + 2);
+        d_present.ensure(batch * W + 2), d_splits.ensure(batch * SW + 2);
+        if (S && !in_lds) clades.ensure(batch * T * W + 2);
+        out->ok = host_array<uint8_t>(w, F), out->n_present = host_array<int32_t>(w, F);
+        if (want_all) out->present = host_array<uint64_t>(w, F * W), out->splits = host_array<uint64_t>(w, F * SW);
+        out->decisive = host_array<int32_t>(w, S), out->concordant = host_array<int32_t>(w, S);
+        static_assert(sizeof(u32) == sizeof(int32_t) && sizeof(ull) == sizeof(uint64_t), "counts and bit sets are copied out as they are");
+        for (size_t f0 = 0; f0 < F; f0 += batch) {
+            const u32 nb = (u32)std::min(batch, F - f0);
+            if (f0) ev.mark(0, st);
+            hipLaunchKernelGGL(k_phy_fam_pairs, dim3(nt * nt, 1, nb), dim3(256), 0, st, reinterpret_cast<const u32*>(K.p), T, (u32)(src.size() / 4u), d_woff.p + f0, nt, d_cmp.p,
+                               d_same.p);
+            HIP_CHECK(hipMemsetAsync(d_ok.p, 1, nb, st));
+            hipLaunchKernelGGL(k_phy_gene_dist, dim3((unsigned)((TT + 255) / 256), nb), dim3(256), 0, st, d_cmp.p, d_same.p, T, W, d_D.p, d_ok.p, d_present.p, d_np.p);
+            ev.mark(1, st);
+            if (S) nj_subset_launch(st, d_D.p, T, W, nb, d_ok.p, d_np.p, d_present.p, d_splits.p, in_lds ? nullptr : clades.p);
+            ev.mark(2, st);
+            if (S)
+                hipLaunchKernelGGL(k_phy_gene_concord, dim3((S + 255u) / 256u, nb), dim3(256), 0, st, d_ref.p, d_splits.p, S, W, d_ok.p, d_np.p, d_present.p, d_dec.p, d_con.p);
+            ev.mark(3, st);
+            HIP_CHECK(hipGetLastError());
+            call.fetch(out->ok + f0, d_ok.p, nb), call.fetch(reinterpret_cast<u32*>(out->n_present) + f0, d_np.p, nb);
+            if (want_all) call.fetch(reinterpret_cast<ull*>(out->present) + f0 * W, d_present.p, (size_t)nb * W);
+            if (want_all && S) call.fetch(reinterpret_cast<ull*>(out->splits) + f0 * SW, d_splits.p, (size_t)nb * SW);
+            if (f0 + nb == F && S) call.fetch(reinterpret_cast<u32*>(out->decisive), d_dec.p, S), call.fetch(reinterpret_cast<u32*>(out->concordant), d_con.p, S);
+            call.wait();   // the one wait of the batch: its buffers are the next batch's
+            ++out->batches;
+            out->counts_ms += ev.ms(0), out->trees_ms += ev.ms(1), out->concord_ms += ev.ms(2);
+        }
+        out->waits = call.waits;
         fill_empty_slots(slots(out));
     });
 }

@@ -67,6 +67,8 @@
     X(I, operon_expand, "SOHIT_OPERON_EXPAND", -1, "tests: expansions per batch (-1: 2^28)")                                                                   \
     /* ---- bootstrap of the species tree (so_phy_boot: read per call) ---- */                                                                                  \
     X(I, phy_boot_batch, "SOHIT_PHY_BOOT_BATCH", 0, "replicates per batch (0: what half of the free device memory holds; tests move the batch edges)")        \
+    /* ---- gene concordance factors of the species tree (so_phy_gene: read per call) ---- */                                                                  \
+    X(I, phy_gene_batch, "SOHIT_PHY_GENE_BATCH", 0, "families per batch (0: what half of the free device memory holds; tests move the batch edges)")          \
     /* ---- index ---- */                                                                                                                                       \
     X(P, exact_threshold, "SOHIT_EXACT_THRESHOLD", 0, "threshold always by the sequential fp64 replay")                                                        \
     X(I, dir_max, "SOHIT_DIR_MAX", -1, "largest -M served by the bitmap + rank directory (-1: 2^31)")                                                          \

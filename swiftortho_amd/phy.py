@@ -38,6 +38,21 @@ csrc/phy.hip) equal them array for array.
     -(log det N - (sum log r + sum log c) / 2) / 20 with r, c the row and column sums of N, additive under a general Markov model,
     composition bias included.  The tensor is N = E E^T of one-hot matrices: on the device (so_phy_subst) a product on the matrix cores
     in 32-bit integers; determinants and logarithms stay numpy's, so the distances are the same bytes with and without the device.
+  * gene concordance factors (off unless asked for; the reference has nothing like it -- its alignments come from an external aligner):
+    for every inner branch of the printed tree the share of the single-family trees, among the families that can decide the branch, that
+    hold it.  Family f owns keep[r[f]:r[f + 1]] (family_ranges: searchsorted(keep, col_off)); family_counts = pair_counts per family;
+    taxon t is PRESENT in f iff cmp[f, t, t] > 0 (family_present: bit sets in slot order) -- a family may lack a tenth of the taxa;
+    gene_distances = boot_distances among the present taxa (p, poisson, kimura; logdet is refused: a family's block is where it has no
+    distance); nj_splits_subset = nj_splits over the present taxa with the bits in their original slots, the canonical side the one
+    without the LOWEST PRESENT taxon, rows n - 3 .. zero.  concordance: for clade C of the printed tree (tree_splits) and present set P,
+    A = C & P and B = P & ~C; the family is decisive iff both hold two taxa at least, concordant iff decisive and its tree holds the one
+    of A and B without P's lowest taxon; a family in which a present pair has no distance is dropped.  gene_concordance ->
+    (decisive, concordant, ok, n_present, splits); tree(concordance=True) labels join t with concordant[t] / decisive[t] (%.3f, NA where
+    nobody decides, boot/gcf with boot > 0); gcf_table is what rbh2phy.py -k writes.  On the device (so_phy_gene for p: gather, pair counts
+    per (tile, family), distances and presence, the bootstrap's walk started from the present bits, a (split, family) grid of popcounts
+    and integer atomics, batches with one host wait each; so_phy_gene_counts and so_phy_nj_subsets for poisson and kimura, whose logarithm
+    stays on the host with the printed tree's walk) only integers and bit sets come back: every array equals numpy's.  Refused: T outside
+    2 .. 4096, offsets that do not rise from 0 to the kept columns, a kept column out of range, unknown flags, no device.
 """
 import math
 import sys
@@ -585,9 +600,10 @@ def _clade_words(c, T):
     return [(c >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range((T + 63) // 64)]
 
 
-def _nj_walk(D, names, support=None):
+def _nj_walk(D, names, support=None, labels=None):
     """the walk of neighbor_joining -> (Newick bytes, uint64[T - 3, W] splits of the joins in join order, canonical as nj_splits' are).
-    support[t] (a share in [0, 1]) labels the node join t makes, %.3f as fasttree prints it"""
+    support[t] (a share in [0, 1]) labels the node join t makes, %.3f as fasttree prints it; labels[t]: a ready-made label string
+    instead (not both)"""
     D = np.array(D, dtype=np.float64)
     n = T = len(names)
     if D.shape != (n, n):
@@ -596,6 +612,12 @@ def _nj_walk(D, names, support=None):
         raise ValueError('neighbor_joining: a tree needs two taxa at least')
     if support is not None and len(support) != max(T - 3, 0):
         raise ValueError('neighbor_joining: %d supports for %d joins' % (len(support), max(T - 3, 0)))
+    if labels is not None:
+        if support is not None:
+            raise ValueError('neighbor_joining: supports or ready-made labels, not both')
+        if len(labels) != max(T - 3, 0):
+            raise ValueError('neighbor_joining: %d labels for %d joins' % (len(labels), max(T - 3, 0)))
+    tag = (lambda t: '') if support is None and labels is None else (lambda t: str(labels[t])) if labels is not None else (lambda t: '%.3f' % support[t])
     node = [_label(x) for x in names]
     clade, splits = [1 << k for k in range(T)], []
     fmt = lambda s, l: '%s:%.6f' % (s, l)
@@ -613,7 +635,7 @@ def _nj_walk(D, names, support=None):
         D[i, :], D[:, i] = du, du
         D[i, i] = 0.
         D = np.delete(np.delete(D, j, 0), j, 1)
-        node[i] = '(%s,%s)%s' % (fmt(node[i], li), fmt(node[j], lj), '' if support is None else '%.3f' % support[len(splits)])
+        node[i] = '(%s,%s)%s' % (fmt(node[i], li), fmt(node[j], lj), tag(len(splits)))
         clade[i] |= clade[j]
         splits.append(_clade_words(clade[i], T))
         del node[j], clade[j]
@@ -625,12 +647,13 @@ def _nj_walk(D, names, support=None):
     return newick, np.array(splits, dtype=np.uint64).reshape(len(splits), (T + 63) // 64)
 
 
-def neighbor_joining(D, names, support=None):
+def neighbor_joining(D, names, support=None, labels=None):
     """Saitou-Nei over float64 -> Newick bytes.  The pair with the smallest Q is joined, ties to the lexicographically lowest (i, j) in
     the current node order; the new node takes position i, j is removed; the last three nodes are a trifurcation; T = 2 is
     (A:d/2,B:d/2); branch lengths %.6f, negative ones as they come.  support (None: no labels): float[T - 3], support[t] labels the node
-    join t makes, as in (A:0.100000,B:0.200000)0.950:0.300000 -- %.3f, the way fasttree prints it; the last trifurcation has no label."""
-    return _nj_walk(D, names, support)[0]
+    join t makes, as in (A:0.100000,B:0.200000)0.950:0.300000 -- %.3f, the way fasttree prints it; the last trifurcation has no label.
+    labels (instead of support): str[T - 3], printed as they are -- what tree(concordance=True) hands in."""
+    return _nj_walk(D, names, support, labels)[0]
 
 
 def tree_splits(D):
@@ -938,37 +961,347 @@ def bootstrap(sm, B, seed=1, model='p', device_stage=False, device=0, stats=None
     return count, valid
 
 
+# ---------------------------------------------------------------------------------------------------------
+# gene concordance factors: a tree per core family over the taxa it holds, the share of the deciding families that hold a split
+# ---------------------------------------------------------------------------------------------------------
+GENE_MODELS = ('p', 'poisson', 'kimura')
+_NO_GENE_MODEL = "gene concordance: the model is 'p', 'poisson' or 'kimura' (a family's block is where logdet has no distance)"
+
+
+class ConcordanceRefused(ValueError):
+    """no gene concordance factor can be given (rbh2phy.py exits with code 2)"""
+
+
+def family_ranges(keep, col_off):
+    """-> int64[F + 1]: family f owns keep[r[f]:r[f + 1]], the kept columns of its block col_off[f] .. col_off[f + 1] (keep ascending)"""
+    return np.searchsorted(np.asarray(keep, dtype=np.int64), np.asarray(col_off, dtype=np.int64)).astype(np.int64)
+
+
+def family_counts(matrix, keep, col_off):
+    """-> (cmp, same) int64[F, T, T]: pair_counts over each family's kept columns"""
+    keep = np.asarray(keep, dtype=np.int64)
+    r = family_ranges(keep, col_off)
+    T = np.asarray(matrix).shape[0]
+    cmp_, same = np.zeros((len(r) - 1, T, T), dtype=np.int64), np.zeros((len(r) - 1, T, T), dtype=np.int64)
+    for f in range(len(r) - 1):
+        cmp_[f], same[f] = pair_counts(matrix, keep[r[f]:r[f + 1]])
+    return cmp_, same
+
+
+def _bool_words(flags):
+    """bool[..., T] -> uint64[..., W]: bit t & 63 of word t >> 6 is flag t"""
+    flags = np.asarray(flags, dtype=bool)
+    T = flags.shape[-1]
+    W = (T + 63) // 64
+    bits = np.zeros(flags.shape[:-1] + (W * 64,), dtype=np.uint8)
+    bits[..., :T] = flags
+    return np.ascontiguousarray(np.packbits(bits, axis=-1, bitorder='little')).view(np.uint64).reshape(flags.shape[:-1] + (W,))
+
+
+def _words_bool(words, T):
+    """uint64[..., W] -> bool[..., T]"""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    return np.unpackbits(words.view(np.uint8), axis=-1, bitorder='little')[..., :T].astype(bool)
+
+
+def _popcount(words):
+    """uint64[..., W] -> int64[...]: the bits set over the last axis"""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    return np.unpackbits(words.view(np.uint8), axis=-1).sum(-1, dtype=np.int64)
+
+
+def family_present(cmp):
+    """int64[F, T, T] (or [T, T]) -> uint64[F, W] (or [W]): taxon t is present in family f iff cmp[f, t, t] > 0 -- it holds a byte that is
+    not '-' in a kept column of the block; bit sets in slot order, W = ceil(T / 64)"""
+    cmp = np.asarray(cmp)
+    return _bool_words(np.diagonal(cmp, axis1=-2, axis2=-1) > 0)
+
+
+def gene_distances(cmp_f, same_f, present_f, model='p'):
+    """-> (D float64[T, T], ok): boot_distances restricted to present x present (present_f: uint64[W]).  ok is False when two present taxa
+    share no compared column, or when the model refuses a present pair.  Entries outside present x present are unspecified: nothing reads
+    them.  logdet is refused."""
+    if model not in GENE_MODELS:
+        raise ValueError(_NO_GENE_MODEL)
+    cmp_f, same_f = np.asarray(cmp_f, dtype=np.int64), np.asarray(same_f, dtype=np.int64)
+    T = len(cmp_f)
+    idx = np.flatnonzero(_words_bool(present_f, T))
+    D = np.zeros((T, T), dtype=np.float64)
+    sub, ok = boot_distances(cmp_f[np.ix_(idx, idx)], same_f[np.ix_(idx, idx)], model)
+    D[np.ix_(idx, idx)] = sub
+    return D, bool(ok)
+
+
+def nj_splits_subset(D, present):
+    """-> uint64[T - 3, W]: nj_splits of D[present][:, present] with the clade bits moved back to the original slots (present: uint64[W]).
+    A clade that holds the LOWEST PRESENT taxon is complemented inside the present set (nj_splits complements the clade of its taxon 0
+    inside its own taxa: the same thing).  With n present taxa the rows n - 3 .. are zero; n < 4: all zeros."""
+    D = np.asarray(D, dtype=np.float64)
+    T = len(D)
+    W = (T + 63) // 64
+    out = np.zeros((max(T - 3, 0), W), dtype=np.uint64)
+    idx = np.flatnonzero(_words_bool(present, T))
+    n = len(idx)
+    if n < 4:
+        return out
+    bits = np.zeros((n - 3, W * 64), dtype=bool)
+    bits[:, idx] = _words_bool(nj_splits(D[np.ix_(idx, idx)]), n)
+    out[:n - 3] = _bool_words(bits)
+    return out
+
+
+def concordance(ref_splits, present, gene_splits, ok):
+    """-> (decisive, concordant) int32[S].  For split s of the printed tree (ref_splits uint64[S, W], clade C) and an ok family with present
+    set P (present uint64[F, W]): A = C & P, B = P & ~C; the family is decisive for s iff both hold two taxa at least, and concordant iff it
+    is decisive and its tree (gene_splits uint64[F, S, W], nj_splits_subset) holds whichever of A and B does not contain P's lowest taxon.
+    A dropped family (ok False) is counted nowhere."""
+    ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
+    present = np.ascontiguousarray(present, dtype=np.uint64)
+    gene = np.ascontiguousarray(gene_splits, dtype=np.uint64)
+    S = len(ref)
+    dec, con = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    if S == 0:
+        return dec, con
+    for f in np.flatnonzero(np.asarray(ok, dtype=bool)).tolist():
+        P = present[f]
+        A, B = ref & P, ~ref & P
+        d = (_popcount(A) >= 2) & (_popcount(B) >= 2)
+        if not d.any():
+            continue
+        dec += d
+        w = int(np.flatnonzero(P)[0])                     # (a decisive family has four present taxa at least)
+        low = P[w] & (~P[w] + np.uint64(1))               # the lowest present taxon's bit
+        side = np.where(((A[:, w] & low) != 0)[:, None], B, A)
+        held = {row.tobytes() for row in gene[f]}
+        for s in np.flatnonzero(d).tolist():
+            if side[s].tobytes() in held:
+                con[s] += 1
+    return dec, con
+
+
+def _gene_result(res, L, free, F, S, W, want_splits, stats, timed):
+    from . import _lib
+    try:
+        if stats is not None:
+            stats['waits'], stats['batches'], stats['nj_tier'] = int(res.waits), int(res.batches), int(res.nj_tier)
+            if timed:
+                stats['counts_ms'], stats['trees_ms'], stats['concord_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.concord_ms)
+        arr = _lib.result_array
+        return (arr(res.decisive, S, np.int32), arr(res.concordant, S, np.int32), arr(res.ok, F, np.uint8).astype(bool), arr(res.n_present, F, np.int32),
+                arr(res.present, F * W, np.uint64).reshape(F, W) if want_splits else None, arr(res.splits, F * S * W, np.uint64).reshape(F, S, W) if want_splits else None)
+    finally:
+        free(res)
+
+
+def _gene_args(who, matrix, keep, fam_off):
+    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('%s: the matrix has two dimensions' % who)
+    return matrix, np.ascontiguousarray(keep, dtype=np.int64), np.ascontiguousarray(fam_off, dtype=np.int64)
+
+
+def device_gene(matrix, keep, fam_off, ref_splits, want_splits=False, device=0, stats=None, timed=False):
+    """the fused gene concordance of model p (so_phy_gene): the families' kept columns, their pair counts, D = 1 - same / cmp, presence, the
+    trees over the present taxa and their comparison with ref_splits stay on the device, in batches of families with one host wait each
+    -> (decisive int32[T - 3], concordant int32[T - 3], ok bool[F], n_present int32[F], present uint64[F, W] or None, splits
+    uint64[F, T - 3, W] or None).  stats: 'waits', 'batches', 'nj_tier'; timed: also 'counts_ms', 'trees_ms', 'concord_ms' by events"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    matrix, keep, fam_off = _gene_args('device_gene', matrix, keep, fam_off)
+    T, nc = matrix.shape
+    F, S, W = len(fam_off) - 1, max(T - 3, 0), (T + 63) // 64
+    ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
+    if ref.size != S * W:
+        raise ValueError('device_gene: the printed tree has %d splits of %d words' % (S, W))
+    res = _lib.SoPhyGeneResult()
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    if L.so_phy_gene(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), F, ptr(fam_off), ptr(ref), (1 if want_splits else 0) | (2 if timed else 0), C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    return _gene_result(res, L, lambda r: L.so_phy_gene_free(C.byref(r)), F, S, W, want_splits, stats, timed)
+
+
+def device_gene_counts(matrix, keep, fam_off, f0=0, nf=None, device=0):
+    """family_counts() of the families f0 .. f0 + nf - 1 in one device call (so_phy_gene_counts) -> (cmp, same) int64[nf, T, T]"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    matrix, keep, fam_off = _gene_args('device_gene_counts', matrix, keep, fam_off)
+    T, nc = matrix.shape
+    nf = len(fam_off) - 1 - int(f0) if nf is None else int(nf)
+    res = _lib.SoPhyGeneResult()
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    if L.so_phy_gene_counts(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), len(fam_off) - 1, ptr(fam_off), int(f0), nf, 0, C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        return (_lib.result_array(res.cmp, nf * T * T, np.int64).reshape(nf, T, T), _lib.result_array(res.same, nf * T * T, np.int64).reshape(nf, T, T))
+    finally:
+        L.so_phy_gene_free(C.byref(res))
+
+
+def device_nj_subsets(D, present, device=0, clades_in_global=False, stats=None):
+    """nj_splits_subset() of nb matrices D float64[nb, T, T], each with its own present words uint64[nb, W], in one device call
+    (so_phy_nj_subsets) -> uint64[nb, T - 3, W].  Only present x present is read; there D is finite and symmetric bit for bit, or the
+    call is refused.  clades_in_global, stats['nj_tier']: as device_nj_splits"""
+    import ctypes as C
+    from . import _lib
+    L = _lib.load()
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.ndim != 3 or D.shape[1] != D.shape[2]:
+        raise ValueError('device_nj_subsets: D is float64[nb, T, T]')
+    nb, T = D.shape[0], D.shape[1]
+    S, W = max(T - 3, 0), (T + 63) // 64
+    present = np.ascontiguousarray(present, dtype=np.uint64)
+    if present.shape != (nb, W):
+        raise ValueError('device_nj_subsets: present is uint64[nb, %d]' % W)
+    res = _lib.SoPhyGeneResult()
+    if L.so_phy_nj_subsets(int(device), nb, T, C.c_void_p(D.ctypes.data), C.c_void_p(present.ctypes.data), 1 if clades_in_global else 0, C.byref(res)) != 0:
+        raise RuntimeError(L.so_phy_last_error().decode())
+    try:
+        if stats is not None:
+            stats['nj_tier'] = int(res.nj_tier)
+        return _lib.result_array(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
+    finally:
+        L.so_phy_gene_free(C.byref(res))
+
+
+def _gene_batch(F, per_family_bytes):
+    """families per device call of the poisson and kimura paths: SOHIT_PHY_GENE_BATCH, else what about 2^30 bytes of counts hold"""
+    import os
+    forced = int(os.environ.get('SOHIT_PHY_GENE_BATCH', '0') or 0)
+    return max(1, min(F, 32768, forced if forced > 0 else (1 << 30) // max(1, per_family_bytes)))
+
+
+def gene_concordance(sm, model='p', device_stage=False, device=0, stats=None, want_splits=False):
+    """the gene concordance factors of the printed tree -> (decisive int32[T - 3], concordant int32[T - 3], ok bool[F], n_present int32[F],
+    splits uint64[F, T - 3, W] or None).  Every core family's kept columns (family_ranges) give pair counts (family_counts), the taxa it
+    holds (family_present), distances among them (gene_distances) and a tree over them (nj_splits_subset); concordance() compares the
+    trees with the splits of the printed tree (tree_splits).  A family in which two present taxa share no compared column, or a present
+    pair has no distance under the model, is dropped.  Host: the numpy definitions family by family.  device_stage, model p: so_phy_gene;
+    poisson and kimura: the counts of a batch of families by so_phy_gene_counts, the distances on the host (the device's log is not
+    numpy's), the trees by so_phy_nj_subsets, the comparison by concordance()."""
+    if model not in GENE_MODELS:
+        raise ConcordanceRefused(_NO_GENE_MODEL)
+    if sm.matrix is None:
+        raise ValueError('gene concordance: the supermatrix was built without its matrix')
+    T, F = len(sm.taxa), len(sm.col_off) - 1
+    S, W = max(T - 3, 0), (T + 63) // 64
+    keep = np.asarray(sm.keep, dtype=np.int64)
+    ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa)) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
+    r = family_ranges(keep, sm.col_off)
+    if device_stage and model == 'p':
+        try:
+            dec, con, ok, npres, _, splits = device_gene(sm.matrix, keep, r, ref, want_splits, device, stats)
+        except RuntimeError as e:
+            raise ValueError('gene concordance: %s' % e)
+        return dec, con, ok, npres, splits
+    ok, npres = np.zeros(F, dtype=bool), np.zeros(F, dtype=np.int32)
+    present, splits = np.zeros((F, W), dtype=np.uint64), np.zeros((F, S, W), dtype=np.uint64)
+    step = _gene_batch(F, 16 * T * T) if device_stage else 1
+    calls = 0
+    for f0 in range(0, F, step):
+        nf = min(step, F - f0)
+        try:
+            if device_stage:
+                cmp_, same = device_gene_counts(sm.matrix, keep, r, f0, nf, device)
+                calls += 1
+            else:
+                cmp_, same = family_counts(sm.matrix, keep[r[f0]:r[f0 + nf]], sm.col_off[f0:f0 + nf + 1])
+            present[f0:f0 + nf] = family_present(cmp_)
+            dist = [gene_distances(cmp_[k], same[k], present[f0 + k], model) for k in range(nf)]
+            good = [k for k in range(nf) if dist[k][1]]
+            if good and S:
+                at = [f0 + k for k in good]
+                if device_stage:
+                    splits[at] = device_nj_subsets(np.stack([dist[k][0] for k in good]), present[at], device)
+                    calls += 1
+                else:
+                    for k in good:
+                        splits[f0 + k] = nj_splits_subset(dist[k][0], present[f0 + k])
+        except RuntimeError as e:
+            raise ValueError('gene concordance: %s' % e)
+        ok[[f0 + k for k in good]] = True
+    npres[:] = _popcount(present)
+    if stats is not None and device_stage:
+        stats['calls'] = calls
+    dec, con = concordance(ref, present, splits, ok)
+    return dec, con, ok, npres, splits if want_splits else None
+
+
+def gcf_labels(decisive, concordant):
+    """-> [str]: concordant / decisive as %.3f, NA where no family is decisive"""
+    return ['NA' if d == 0 else '%.3f' % (c / float(d)) for d, c in zip(np.asarray(decisive).tolist(), np.asarray(concordant).tolist())]
+
+
+def gcf_table(taxa, ref_splits, decisive, concordant):
+    """-> bytes: a header line and one line per join of the printed tree, in join order, tab-separated: join, taxa_in_clade, decisive,
+    concordant, gcf (Python's repr of concordant / decisive, NA when undecided) and the clade's taxa in slot order, comma-separated (the
+    clade as tree_splits hands it out: the side without the first taxon)"""
+    T = len(taxa)
+    ref = np.ascontiguousarray(ref_splits, dtype=np.uint64).reshape(len(decisive), (T + 63) // 64)
+    lines = ['join\ttaxa_in_clade\tdecisive\tconcordant\tgcf\ttaxa\n']
+    for t, (d, c) in enumerate(zip(np.asarray(decisive).tolist(), np.asarray(concordant).tolist())):
+        inside = np.flatnonzero(_words_bool(ref[t], T)).tolist()
+        lines.append('%d\t%d\t%d\t%d\t%s\t%s\n' % (t, len(inside), d, c, 'NA' if d == 0 else repr(c / float(d)), ','.join(_label(taxa[k]) for k in inside)))
+    return ''.join(lines).encode('utf-8')
+
+
 def supermatrix_fasta(taxa, matrix, keep):
     """-> bytes: `>taxon\\nrow\\n` per taxon in slot order, the kept columns only"""
     matrix, keep = np.asarray(matrix, dtype=np.uint8), np.asarray(keep, dtype=np.int64)
     return b''.join(b'>' + (t if isinstance(t, bytes) else str(t).encode('utf-8')) + b'\n' + matrix[k, keep].tobytes() + b'\n' for k, t in enumerate(taxa))
 
 
-def tree(sm, model='p', boot=0, seed=1, device_stage=False, device=0, stats=None):
+def tree(sm, model='p', boot=0, seed=1, device_stage=False, device=0, stats=None, concordance=False):
     """Supermatrix -> Newick bytes over its taxa; boot > 0: every node a join makes carries the share of the valid bootstrap replicates
-    that hold its split (bootstrap(); stats: 'boot', 'boot_valid' and the device's counters)"""
+    that hold its split (bootstrap(); stats: 'boot', 'boot_valid' and the device's counters).  concordance: the node of join t carries its
+    gene concordance factor concordant[t] / decisive[t] (gene_concordance(); %.3f, NA where no family decides the branch); with boot > 0
+    as well the label is boot/gcf, as in )0.950/0.812:0.300000.  stats then holds 'gcf': ref splits, decisive, concordant, ok, n_present
+    and the device's counters of that stage.  No family left to ask (every one dropped): ConcordanceRefused."""
+    if concordance and model not in GENE_MODELS:
+        raise ConcordanceRefused(_NO_GENE_MODEL)
     D = distances(sm.cmp, sm.same, model, sm.taxa, model_subst(sm, model, device_stage, device))
-    if int(boot) <= 0:
+    if int(boot) <= 0 and not concordance:
         return neighbor_joining(D, sm.taxa)
+    labels = None
+    if concordance:
+        gs = {}
+        dec, con, ok, npres, _ = gene_concordance(sm, model, device_stage, device, gs)
+        if not ok.any():
+            raise ConcordanceRefused('gene concordance: none of the %d families gives every pair of its taxa a distance' % len(ok))
+        labels = gcf_labels(dec, con)
+        if stats is not None:
+            stats['gcf'] = {'splits': tree_splits(D), 'decisive': dec, 'concordant': con, 'ok': ok, 'n_present': npres, 'device': gs}
+    if int(boot) <= 0:
+        return neighbor_joining(D, sm.taxa, labels=labels)
     count, valid = bootstrap(sm, boot, seed, model, device_stage, device, stats)
     if stats is not None:
         stats['boot'], stats['boot_valid'] = int(boot), valid
-    return neighbor_joining(D, sm.taxa, count / float(valid))
+    if labels is None:
+        return neighbor_joining(D, sm.taxa, count / float(valid))
+    return neighbor_joining(D, sm.taxa, labels=['%.3f/%s' % (b, g) for b, g in zip((count / float(valid)).tolist(), labels)])
 
 
 # ---------------------------------------------------------------------------------------------------------
 # scripts/rbh2phy.py -A T
 # ---------------------------------------------------------------------------------------------------------
-def run_align(sc_bytes, fasta_bytes, cols, table, gap_share=1.0, model='p', tree_path='', device_stage=False, out=None, boot=0, seed=1):
+def run_align(sc_bytes, fasta_bytes, cols, table, gap_share=1.0, model='p', tree_path='', device_stage=False, out=None, boot=0, seed=1, concordance=False, gcf_path=''):
     """the -A T half of rbh2phy.py: the supermatrix FASTA to `out` (default: stdout), the tree to `tree_path` when named -> Supermatrix;
-    boot > 0: the tree's nodes carry their bootstrap support over `boot` replicates drawn from `seed` (sm.stats: boot, boot_valid)"""
+    boot > 0: the tree's nodes carry their bootstrap support over `boot` replicates drawn from `seed` (sm.stats: boot, boot_valid);
+    concordance: they carry their gene concordance factors (tree()), and `gcf_path`, when named, receives gcf_table()"""
+    if concordance and model not in GENE_MODELS:
+        raise ConcordanceRefused(_NO_GENE_MODEL)      # (before the supermatrix is built)
     rows_src = TextRows(sc_bytes, cols.names)
     sm = supermatrix(cols.names, table, rbh.fasta_records(fasta_bytes), rows_src, gap_share, device_stage)
-    newick = tree(sm, model, boot, seed, device_stage, stats=sm.stats) if tree_path else None      # (before anything is printed: a refusal leaves no half output)
+    newick = tree(sm, model, boot, seed, device_stage, stats=sm.stats, **({'concordance': True} if concordance else {})) if tree_path else None      # (before anything is printed: a refusal leaves no half output)
     o = out if out is not None else sys.stdout.buffer
     o.write(supermatrix_fasta(sm.taxa, sm.matrix, sm.keep))
     o.flush()
     if tree_path:
         with open(tree_path, 'wb') as f:
             f.write(newick + b'\n')
+        if concordance and gcf_path:
+            g = sm.stats['gcf']
+            with open(gcf_path, 'wb') as f:
+                f.write(gcf_table(sm.taxa, g['splits'], g['decisive'], g['concordant']))
     return sm

@@ -257,7 +257,7 @@ def pan_genome_from_search(fasta_path, ts=.05, tc=.95, taxa=None, pan_device=Tru
     return list(taxa), res.types, res.totals, (res.core, res.spec, res.panz), t
 
 
-def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', boot=0, boot_seed=1, **search_kw):
+def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', boot=0, boot_seed=1, concordance=False, **search_kw):
     """one process from a FASTA file to the species tree of its taxa: self-search on the GPU with a CIGAR on every row, the core-gene
     table of `reference` (default: the taxon with most genes), the core-gene supermatrix from the rows' own alignments (swiftortho_amd.phy:
     no aligner runs), the distances over its kept columns (`gap_share`, `model` 'p', 'poisson', 'kimura' or 'logdet' -- the last from the substitution counts, device_stage: so_phy_subst) and neighbour joining -- what
@@ -265,6 +265,8 @@ def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p',
     pair counts on the GPU (so_rbh_cols, so_phy_rows, so_phy_build), else by the numpy definitions; the records and the CIGARs are the host
     copies either way.  boot > 0: the tree's nodes carry their bootstrap support over `boot` replicates of the kept columns drawn from
     `boot_seed` (phy.bootstrap; device_stage: so_phy_boot); the dict holds boot and boot_valid, the replicates asked for and kept (0, 0 without).
+    concordance: the nodes carry their gene concordance factors (phy.gene_concordance; device_stage: so_phy_gene; with boot > 0 the label is
+    boot/gcf); the dict then holds 'gcf', what phy.tree leaves under that key (the printed tree's splits, decisive, concordant, ok, n_present).
     -> (Newick bytes, phy.Supermatrix, dict of stage wall times in seconds: load, search, rbh, supermatrix, tree, and the counts rows,
     families, columns, kept)"""
     from . import find_orth, fsearch, phy, rbh
@@ -297,8 +299,10 @@ def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p',
         s.close()
     t0 = time.time()
     boot_stats = {}
-    newick = phy.tree(sm, model, boot, boot_seed, device_stage, device, boot_stats)
+    newick = phy.tree(sm, model, boot, boot_seed, device_stage, device, boot_stats, **({'concordance': True} if concordance else {}))
     t['tree'] = time.time() - t0
+    if concordance:
+        t['gcf'] = boot_stats['gcf']
     t['boot'], t['boot_valid'] = boot_stats.get('boot', 0), boot_stats.get('boot_valid', 0)
     t['rows'], t['families'], t['columns'], t['kept'] = len(rec), len(sm.col_off) - 1, len(sm.gaps), len(sm.keep)
     return newick, sm, t

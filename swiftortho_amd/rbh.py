@@ -384,9 +384,9 @@ def main_rbh2phy(argv=None):
     import os
     from .fsearch import parse_flags
     argv = list(sys.argv if argv is None else argv)
-    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p', '-B': '0', '-S': '1'})
+    args = parse_flags(argv, {'-i': '', '-f': '', '-r': '', '-G': 'F', '-o': '', '-A': 'F', '-g': '1', '-t': '', '-m': 'p', '-B': '0', '-S': '1', '-K': 'F', '-k': ''})
     if args['-i'] == '' or args['-f'] == '':
-        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson|kimura|logdet] [-B replicates] [-S seed]]')
+        print('Usage:\n  python this.py -i foo.sc -f foo.fsa [-r taxon] [-G T] [-o groups.tsv] [-A T [-g share] [-t tree.nwk] [-m p|poisson|kimura|logdet] [-B replicates] [-S seed] [-K T [-k gcf.tsv]]]')
         print(' -i: blast -m8 or find_hit .sc file; ids are taxon|gene\n -f: the FASTA file the search read\n -r: reference taxon (default: the taxon with most genes)')
         print(' -G: the winner list and the table on the GPU [T|F]. Default: F\n -o: also write one tab-separated line of ids per group')
         print(' -A: join the families into the core-gene supermatrix from the CIGARs of the rows (find_hit.py -C T) and print it as FASTA [T|F]. Default: F')
@@ -395,6 +395,9 @@ def main_rbh2phy(argv=None):
         print('     kimura: -log(1 - p - p*p/5); logdet: the paralinear distance from the 20 x 20 residue-pair table of every pair of taxa (with -G T: on the GPU)')
         print(' -B: with -t, label the tree\'s nodes with their bootstrap support over this many replicates (with -G T: on the GPU). Default: 0 (no labels)')
         print(' -S: seed of the bootstrap\'s column draws, 0 .. 2^64 - 1. Default: 1')
+        print(' -K: with -t, label the tree\'s nodes with their gene concordance factors: the share of the core families able to decide a branch whose own')
+        print('     neighbour-joining tree holds it (with -G T: on the GPU; -m p|poisson|kimura; with -B the label is boot/gcf) [T|F]. Default: F')
+        print(' -k: with -K T, write join, taxa_in_clade, decisive, concordant, gcf and the clade\'s taxa per branch to this file')
         raise SystemExit()
     boot, seed = _count_flag(args['-B'], 2 ** 31 - 1), _count_flag(args['-S'], 2 ** 64 - 1)
     if boot is None or seed is None:
@@ -402,6 +405,16 @@ def main_rbh2phy(argv=None):
         return 2
     if boot > 0 and args['-t'] == '':
         sys.stderr.write('rbh2phy: -B labels the tree that -t writes: name a tree file with -t (and join the families with -A T)\n')
+        return 2
+    gcf = _gpu_flag(args['-K'])
+    if gcf and args['-t'] == '':
+        sys.stderr.write('rbh2phy: -K labels the tree that -t writes: name a tree file with -t (and join the families with -A T)\n')
+        return 2
+    if args['-k'] != '' and not gcf:
+        sys.stderr.write('rbh2phy: -k writes the table of the gene concordance factors: ask for them with -K T\n')
+        return 2
+    if gcf and args['-m'] == 'logdet':
+        sys.stderr.write('rbh2phy: -K T takes -m p, poisson or kimura: a single family\'s block is where logdet has no distance\n')
         return 2
     with open(args['-i'], 'rb') as f:
         sc = f.read()
@@ -413,8 +426,9 @@ def main_rbh2phy(argv=None):
         from . import phy
         try:
             share = float(args['-g'])
-            sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']), boot=boot, seed=seed)
-        except (phy.MissingCigar, phy.DistanceRefused) as e:
+            sm = phy.run_align(sc, fasta, cols, table, share, args['-m'], args['-t'], _gpu_flag(args['-G']), boot=boot, seed=seed,
+                               **({'concordance': True, 'gcf_path': args['-k']} if gcf else {}))
+        except (phy.MissingCigar, phy.DistanceRefused, phy.ConcordanceRefused) as e:
             sys.stderr.write('rbh2phy: %s\n' % e)
             return 2
         except ValueError as e:
