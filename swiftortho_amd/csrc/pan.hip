@@ -345,6 +345,13 @@ int so_pan_genome(int device, int64_t m, const int32_t* row, const int32_t* taxo
             fill_empty_slots(slots(out));
             return;
         }
+        if (cells) {   // k_pan_curve's grid is ceil(size / 4) workgroups high: with few taxa the bounds above allow far more than a launch takes
+            int max_y = 0;
+            HIP_CHECK(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, device));   // hipDeviceProp_t::maxGridSize[1]
+            if ((size + 3) / 4 > (i64)max_y)
+                throw SoError(who + ": " + std::to_string(size) + " orders are more than one call serves: the curve kernel's grid is a workgroup per 4 orders and at most " +
+                              std::to_string(max_y) + " high on this device (the largest size served is " + std::to_string(4 * (i64)max_y) + ")");
+        }
         DeviceCall call(device);
         hipStream_t st = call.st;
         const u32 M = (u32)m, R = (u32)n_rows, T = (u32)n_taxa, W = (R + 63u) / 64u;

@@ -58,6 +58,10 @@ GOLDEN_CASES = {
     # 0.07 * 100 > 7 and 0.29 * 100 < 29 in floats: core asks for 8 genomes and new for ys <= 27 at j = 100, where exact fractions give 7 and 28
     'float100': ({'gen': dict(n_taxa=100, n_groups=260, seed=9, n_single=20)}, ['-l.29', '-u.07']),
     'wide65': ({'gen': dict(n_taxa=65, n_groups=129, seed=10, n_single=0)}, []),
+    # -u 0: Tc = 0 at every step, so every row is core, before any genome that holds it has come -- 75 rows, 11 of them in the last 64-row tile, whose other
+    # 53 lanes must not count.  -l 1e12: S is the 32-bit clamp at every step, so every row a genome brings is new
+    'u0': ({'gen': dict(n_taxa=7, n_groups=70, seed=11, n_single=5)}, ['-u', '0']),
+    'l_huge': ({'gen': dict(n_taxa=7, n_groups=70, seed=11, n_single=5)}, ['-l', '1e12']),
 }
 
 

@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import pytest
 
+import pan_curve_inputs as ci
 import pan_inputs as pi
 from test_pan import check_against_golden, library_result, run_script
 
@@ -108,7 +109,11 @@ def test_refusals(pan):
     bad_row[7], bad_tax[11] = t.n_rows, 3
     neg_row, neg_tax = t.row.copy(), t.taxon.copy()
     neg_row[0], neg_tax[0] = -1, -1
-    for change, word in ((dict(row=bad_row), "a row outside"), (dict(row=neg_row), "a row outside"), (dict(taxon=bad_tax), "a taxon outside"),
+    # two taxa and one group of 4 orders more than the grid of k_pan_curve is high: refused before anything is launched
+    limit = ci.served_size_limit(pan.device_pan_genome)
+    too_high = dict(zip(ci.ARG_NAMES, ci.grid_case(limit + 1).args()))
+    for change, word in ((too_high, "the largest size served is %d)" % limit),
+                         (dict(row=bad_row), "a row outside"), (dict(row=neg_row), "a row outside"), (dict(taxon=bad_tax), "a taxon outside"),
                          (dict(taxon=neg_tax), "a taxon outside"), (dict(perm=np.zeros((20, 3), dtype=np.int32)), "not a permutation"),
                          (dict(n_rows=1 << 31), "2^31 rows"), (dict(n_rows=1 << 30), "count matrix of 2^31 cells"), (dict(flags=2), "flags"),
                          (dict(device=1 << 10), "device")):

@@ -64,6 +64,20 @@ def test_goldens_cover_what_they_claim(pan):
         _, table, res = library_result(pan, name)
         assert len(set(res.types[:table.n_file_rows].tolist())) >= 2, name
     assert pi.golden("taxa2")["xy"].count("\n") == 20 and not pi.case_texts("no_newline")[1].endswith("\n")
+    # u0: Tc = 0, so every row is core at every step of every order, also those no genome so far holds, and nothing behind the last
+    # row of the last tile
+    taxa, table, res = library_result(pan, "u0")
+    S, Cc = pan.step_thresholds(*pi.flag_values(pi.case_texts("u0")[3]), n_taxa=len(taxa))
+    assert table.n_rows % 64 != 0 and (table.n_rows, len(taxa)) == (75, 7) and not Cc[1:].any()
+    assert res.core.shape == (20, 6) and (res.core == table.n_rows).all() and (res.panz[:, :-1] < table.n_rows).all()
+    assert [l.split("\t")[1] for l in pi.golden("u0")["xy"].split("\n")[:-1]] == [str(table.n_rows)] * 120
+    assert pan.type_thresholds(.05, 0., 7) == (1, 0) and pi.golden("u0")["number"] == "# Number\t44\t0\t31\t7"
+    # l_huge: S is the 32-bit clamp at every step, so every row the next genome holds is new
+    taxa, table, res = library_result(pan, "l_huge")
+    S, Cc = pan.step_thresholds(*pi.flag_values(pi.case_texts("l_huge")[3]), n_taxa=len(taxa))
+    assert (S[1:] == 2147483647).all() and pan.type_thresholds(1e12, .95, 7)[0] == 2147483647 and res.totals == (0, 0, table.n_file_rows)
+    present = res.counts > 0
+    assert res.spec.tolist() == [[int(present[:, t].sum()) for t in order[1:]] for order in pan.permutations(7).tolist()]
 
 
 def test_member_table_quirks(pan):
@@ -158,6 +172,8 @@ def curves_text(pan, counts, ts, tc, variant=None):
     """_xy.txt by a plain loop; `variant` names ONE deviation from the definition"""
     x = (np.asarray(counts) > 0).astype(np.int64)
     d = x.shape[1]
+    if variant == "mask":             # core counted over whole tiles of 64 rows: the rows behind the table count as zeros
+        x = np.concatenate([x, np.zeros((-len(x) % 64, d), dtype=np.int64)])
     if variant == "fresh_idx":        # every shuffle starts from 0 .. d - 1 instead of from the last order
         rng = random.Random(42)
         perm = []
@@ -186,11 +202,13 @@ def curves_text(pan, counts, ts, tc, variant=None):
             ys = ys + yn
             if variant == "spec_after_add":
                 spec = int(((ys <= cut) & (yn > 0)).sum())
-            rows[(j, p)] = (int((ys >= Tc).sum()), spec, int((ys > 0).sum()))
+            core = int((ys > Tc).sum()) if variant == "core_greater" else int((ys >= Tc).sum())
+            rows[(j, p)] = (core, spec, int((ys > 0).sum()))
     return "".join("%d\t%d\t%d\t%d\n" % ((j,) + rows[(j, p)]) for j in range(2, d + 1) for p in range(20))
 
 
-DEVIATIONS = [("numexpr", "default"), ("less", "frac"), ("spec_after_add", "default"), ("exact", "float100"), ("fresh_idx", "default")]
+DEVIATIONS = [("numexpr", "default"), ("less", "frac"), ("spec_after_add", "default"), ("exact", "float100"), ("fresh_idx", "default"),
+              ("mask", "u0"), ("core_greater", "u0")]
 
 
 @pytest.mark.parametrize("variant,name", DEVIATIONS)

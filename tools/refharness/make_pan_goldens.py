@@ -1,7 +1,9 @@
 """Container-only: goldens for the pan-genome stage (swiftortho_amd/pan.py, csrc/pan.hip).
 
-    python tools/refharness/make_pan_goldens.py
+    python tools/refharness/make_pan_goldens.py [case ...]
 
+Without a case name every case is made again; with names only those (a fixture holds the taxon order of the child that made it, so a
+fixture that is made again differs from the committed one although it says the same: name the new cases and leave the others alone).
 Runs the REAL reference scripts/pan_genome.py on the inputs of tests/pan_inputs.GOLDEN_CASES, each in a child process with a temporary
 working directory (the script leaves pan.npy / type.txt there) and two harness-side stand-ins:
   * Bio.SeqIO (tools/refharness/biostub);
@@ -71,11 +73,14 @@ def run_reference(fasta, groups, allow, flags):
         return r.stdout.decode("utf-8"), open(gr + "_xy.txt").read()
 
 
-def main():
+def main(names=()):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import pan_inputs
-    for name in pan_inputs.golden_names():
+    unknown = sorted(set(names) - set(pan_inputs.golden_names()))
+    if unknown:
+        raise SystemExit("no such case in tests/pan_inputs.GOLDEN_CASES: %s" % ", ".join(unknown))
+    for name in list(names) or pan_inputs.golden_names():
         fasta, groups, allow, flags = pan_inputs.case_texts(name)
         out, xy = run_reference(fasta, groups, allow, flags)
         lines = out.split("\n")
@@ -92,4 +97,4 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
         child(sys.argv[2], sys.argv[3:])
     else:
-        main()
+        main(sys.argv[1:])
