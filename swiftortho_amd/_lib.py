@@ -1,5 +1,6 @@
 """ctypes binding of libsohit.so (include/sohit.h).  No fallback: if the HIP library is
 missing or no GPU is usable, importing/creating a context raises."""
+import contextlib
 import ctypes as C
 import os
 
@@ -192,6 +193,30 @@ def result_array(p, n, dtype=None):
     import numpy as np
     a = np.ctypeslib.as_array(p, shape=(max(int(n), 1),))[:int(n)]
     return a.astype(a.dtype if dtype is None else dtype, copy=True)
+
+
+@contextlib.contextmanager
+def call(fn, result_type, free, last_error, *args):
+    """A device call that fills a result struct, as a `with` block around what reads it: L.<fn>(*args, byref(result)) -- a numpy array
+    among args travels as its data pointer --; a non-zero return raises RuntimeError with L.<last_error>()'s message; the result is
+    released by L.<free> when the block ends, whichever way."""
+    L = load()
+    res = result_type()
+    if getattr(L, fn)(*[C.c_void_p(a.ctypes.data) if hasattr(a, 'ctypes') else a for a in args], C.byref(res)) != 0:
+        raise RuntimeError(getattr(L, last_error)().decode())
+    try:
+        yield res
+    finally:
+        getattr(L, free)(C.byref(res))
+
+
+def matrix2d(who, matrix):
+    """-> the matrix as contiguous uint8[T, L], what the calls over a supermatrix take"""
+    import numpy as np
+    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
+    if matrix.ndim != 2:
+        raise ValueError('%s: the matrix has two dimensions' % who)
+    return matrix
 
 
 def load():

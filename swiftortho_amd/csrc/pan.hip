@@ -30,16 +30,15 @@
 // and transposes the 64 x 64 bits with 64 ballots into the replicate's tile-major words.  Replicates run along the grid, in batches whose
 // words fit half of the free device memory (SOHIT_PAN_BOOT_BATCH forces the size); SOHIT_PAN_SHARED_RANGES forces the number of ranges.
 // Integers only, one host wait per call whatever the number of batches.
-#include "device_call.h"
+#include "tree_stage.h"
 #include "../../include/sohit.h"
 
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace {
-
-typedef unsigned long long ull;
 
 enum { PAN_SPECIFIC = 0, PAN_SHARE = 1, PAN_CORE = 2 };
 enum { PAN_TIER_NONE = 0, PAN_TIER_LDS = 1, PAN_TIER_GLOBAL = 2 };
@@ -171,15 +170,6 @@ __global__ __launch_bounds__(256) void k_pan_rowbits(u32 m, const int* __restric
     if (i < m && pan_pair(i, row, tax, n_rows, T, r, t, err)) atomicOr(rowbits + (size_t)r * TW + (t >> 6), 1ull << (t & 63u));
 }
 
-// draw k of replicate b from K rows: phy.py boot_columns(), in 64-bit integers that wrap (phy.hip boot_draw restated)
-__device__ __forceinline__ u32 pan_draw(ull seed, ull b, ull k, u32 K) {
-    ull z = seed + ((b << 32) + k + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (u32)(((z >> 32) * (ull)K) >> 32);   // < K: the left factor is below 2^32
-}
-
 // grid (groups of 4 draw tiles, groups of PAN_DRAW_BLOCKS blocks of 64 taxa, replicates); a wave per tile of 64 draws, a draw per lane.
 // Lane k reads the row-major word of its drawn row for a block of 64 taxa; ballot j is then bit j of all 64 lanes -- the tile-major word
 // of taxon 64 tb + j over the 64 drawn rows, which lane j keeps and stores: words[z][w * T + t] as k_pan_bits writes them.  A lane behind
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(256) void k_pan_draw(const ull* __restrict__ rowbit
     if (w >= (R + 63u) / 64u) return;   // (a whole wave)
     const u32 lane = threadIdx.x & 63u, d = w * 64u + lane;
     const bool live = d < R;
-    const ull* src = rowbits + (live ? (size_t)pan_draw(seed, (ull)b0 + blockIdx.z, d, R) * TW : 0);
+    const ull* src = rowbits + (live ? (size_t)replicate_draw(seed, (ull)b0 + blockIdx.z, d, R) * TW : 0);
     ull* dst = words + (size_t)blockIdx.z * wrep + (size_t)w * T;
     const u32 tb0 = blockIdx.y * PAN_DRAW_BLOCKS, tb1 = min(TW, tb0 + PAN_DRAW_BLOCKS);
     for (u32 tb = tb0; tb < tb1; ++tb) {   // (the same bounds for every lane: the ballots are met by the whole wave)
@@ -257,41 +247,12 @@ __global__ __launch_bounds__(256) void k_pan_shared(const ull* __restrict__ word
         }
 }
 
-// the grid of k_pan_shared over W row words and `reps` matrices of nt x nt tiles: row words per range and ranges.  forced > 0: that many
+// the grid of k_pan_shared over W row words and `reps` matrices of nt x nt tiles: (row words per range, ranges).  forced > 0: that many
 // ranges (as far as there are words); else whole chunks, until about PAN_SH_TARGET_WGS workgroups exist.  Never more than 2^23 workgroups.
-void shared_grid(u32 W, u32 nt, u32 reps, long long forced, u32& wps, u32& ranges) {
+std::pair<u32, u32> shared_grid(u32 W, u32 nt, u32 reps, long long forced) {
     const u64 tiles = (u64)(nt * (nt + 1u) / 2u) * reps;
-    const u32 most = (u32)std::max<u64>(1, std::min<u64>(65535, (1ull << 23) / tiles));
-    if (forced > 0) {
-        const u32 want = (u32)std::min<u64>({(u64)forced, (u64)W, (u64)most});
-        wps = (W + want - 1u) / want;
-    } else {
-        const u32 chunks = (W + PAN_SH_CHUNK - 1u) / PAN_SH_CHUNK;
-        const u32 want = std::min({chunks, most, std::max(1u, (u32)((PAN_SH_TARGET_WGS + tiles - 1u) / tiles))});
-        wps = ((chunks + want - 1u) / want) * PAN_SH_CHUNK;
-    }
-    ranges = (W + wps - 1u) / wps;
+    return range_grid(W, PAN_SH_CHUNK, tiles, PAN_SH_TARGET_WGS, forced, (u32)std::max<u64>(1, std::min<u64>(65535, (1ull << 23) / tiles)));
 }
-
-// marks around the draw and the product of every batch (flags bit 1 of so_pan_shared): recorded on the stream, read after the call's wait
-struct BatchEvents {
-    std::vector<hipEvent_t> e;
-    ~BatchEvents() {
-        for (hipEvent_t x : e) (void)hipEventDestroy(x);
-    }
-    void mark(bool on, hipStream_t st) {
-        if (!on) return;
-        hipEvent_t x = nullptr;
-        HIP_CHECK(hipEventCreate(&x));
-        e.push_back(x);
-        HIP_CHECK(hipEventRecord(x, st));
-    }
-    double ms(size_t k) {   // between mark k and mark k + 1, both reached: the stream has been waited for
-        float v = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&v, e[k], e[k + 1]));
-        return v;
-    }
-};
 
 thread_local std::string g_pan_err;
 
@@ -447,11 +408,7 @@ int so_pan_shared(int device, int64_t m, const int32_t* row, const int32_t* taxo
         }
         DeviceCall call(device);
         hipStream_t st = call.st;
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        if (bytes + bytes / 8 > free_b / 2)   // (a DevBuf takes an eighth more than it is asked for)
-            throw SoError(who + ": the result of " + std::to_string(nrep) + " x " + std::to_string(T) + " x " + std::to_string(T) + " counts would take " + std::to_string(bytes) +
-                          " bytes, more than half of the free device memory (" + std::to_string(free_b) + " bytes free): ask for fewer replicates per call");
+        refuse_over_half_free(who, "result of " + std::to_string(nrep) + " x " + std::to_string(T) + " x " + std::to_string(T) + " counts", bytes);
         DevBuf<int> d_row, d_tax, d_out;
         DevBuf<ull> bits, words;
         DevBuf<u32> err;
@@ -468,34 +425,29 @@ int so_pan_shared(int device, int64_t m, const int32_t* row, const int32_t* taxo
                 hipLaunchKernelGGL(k_pan_bits, grid256(M), dim3(256), 0, st, M, d_row.p, d_tax.p, R, T, bits.p, err.p);
         }
         const u32 nt = (T + PAN_SH_TILE - 1u) / PAN_SH_TILE;
-        BatchEvents ev;
+        StageEvents ev(timed);   // no draw: marks 0, 1 around the product; else marks 3 k .. 3 k + 2 around the draw and the product of batch k; read behind the call's one wait
         u32 wps = 0, ranges = 0;
         if (!draw) {
-            shared_grid(W, nt, 1u, call.tn.pan_shared_ranges, wps, ranges);
-            ev.mark(timed, st);
+            std::tie(wps, ranges) = shared_grid(W, nt, 1u, call.tn.pan_shared_ranges);
+            ev.mark(0, st);
             hipLaunchKernelGGL(k_pan_shared, dim3(nt * (nt + 1u) / 2u, ranges, 1u), dim3(256), 0, st, bits.p, W, T, nt, wps, d_out.p, (size_t)0, (size_t)0);
-            ev.mark(timed, st);
+            ev.mark(1, st);
             out->batches = 1;
         } else {
             // a batch: as many replicates' words as half of what is free now holds, below 2^31 words and 2^22 tiles (grid sizes)
-            size_t batch = call.tn.pan_boot_batch > 0 ? (size_t)call.tn.pan_boot_batch : 0;
-            if (!batch) {
-                HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-                batch = (free_b / 2) / ((per + per / 8 + 64) * sizeof(ull));
-            }
-            batch = std::min({batch, (size_t)nrep, ((size_t)1 << 31) / per, ((size_t)1 << 22) / (nt * (nt + 1u) / 2u)});
-            batch = std::max<size_t>(batch, 1);
+            const size_t cap = std::min({(size_t)nrep, ((size_t)1 << 31) / per, ((size_t)1 << 22) / (nt * (nt + 1u) / 2u)});
+            const size_t batch = std::max<size_t>(1, device_batch(call, call.tn.pan_boot_batch, (per + 64) * sizeof(ull), cap));
             words.ensure(batch * per + 2);
             for (u32 r0 = 0; r0 < nrep; r0 += (u32)batch) {
                 const u32 nb = std::min((u32)batch, nrep - r0);
-                shared_grid(W, nt, nb, call.tn.pan_shared_ranges, wps, ranges);
-                ev.mark(timed, st);
+                const size_t k = 3u * (size_t)out->batches++;   // the batch's first mark
+                std::tie(wps, ranges) = shared_grid(W, nt, nb, call.tn.pan_shared_ranges);
+                ev.mark(k, st);
                 hipLaunchKernelGGL(k_pan_draw, dim3((W + 3u) / 4u, (TW + PAN_DRAW_BLOCKS - 1u) / PAN_DRAW_BLOCKS, nb), dim3(256), 0, st, bits.p, R, T, TW, (ull)seed,
                                    (u32)b0 + r0, words.p, per);
-                ev.mark(timed, st);
+                ev.mark(k + 1, st);
                 hipLaunchKernelGGL(k_pan_shared, dim3(nt * (nt + 1u) / 2u, ranges, nb), dim3(256), 0, st, words.p, W, T, nt, wps, d_out.p + (size_t)r0 * TT, per, TT);
-                ev.mark(timed, st);
-                ++out->batches;
+                ev.mark(k + 2, st);
             }
         }
         out->ranges = (int32_t)ranges;
@@ -508,12 +460,9 @@ int so_pan_shared(int device, int64_t m, const int32_t* row, const int32_t* taxo
         out->waits = call.waits;
         if (e & 1u) throw SoError(who + ": a row outside 0 .. n_rows - 1");
         if (e & 2u) throw SoError(who + ": a taxon outside 0 .. n_taxa - 1");
-        if (timed) {
-            if (!draw)
-                out->product_ms = ev.ms(0);
-            else
-                for (size_t k = 0; k + 2 < ev.e.size(); k += 3) out->draw_ms += ev.ms(k), out->product_ms += ev.ms(k + 1);
-        }
+        if (!draw) out->product_ms = ev.ms(0);
+        else
+            for (size_t k = 0; k < 3u * (size_t)out->batches; k += 3) out->draw_ms += ev.ms(k), out->product_ms += ev.ms(k + 1);
         fill_empty_slots(slots(out));
     });
 }

@@ -50,17 +50,24 @@
 //                       k_phy_gene_concord (a lane per (split of the printed tree, family): popcounts, the canonical side, a search in the
 //                       family's splits, integer atomicAdd).  Batches of families sized from the free device memory
 //                       (SOHIT_PHY_GENE_BATCH), one host wait per batch.
-#include "hit_table.h"
+//
+// What the bootstrap and the concordance stage share with each other and with pan.hip is in tree_stage.h: the draw (replicate_draw), the
+// grids of the kernels that walk a length in ranges (range_grid), the batch size (device_batch) and the stage timer (StageEvents).  Here:
+// matrix_check (what every call over a matrix and its kept columns checks), nj_call (so_phy_nj_splits and so_phy_nj_subsets: one body) and
+// nj_launch (either kernel of the walk).  The flush of a lane's 4 x 4 block stays written out in k_phy_pairs, k_phy_fam_pairs and
+// k_pan_shared, and the search of a split in k_phy_boot_support and k_phy_gene_concord: through a shared inline function the compiler gave
+// these kernels other code (two more scalar registers in two of them, k_pan_shared's product 4 % slower by events).
+#include "tree_stage.h"
+#include "../../include/sohit.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
-
-typedef unsigned long long ull;
 
 #define PHY_DASH 0x2Du
 #define PHY_DASH4 0x2D2D2D2Du
@@ -291,26 +298,11 @@ __global__ __launch_bounds__(256) void k_phy_pairs(const u32* __restrict__ K, u3
         }
 }
 
-// the grid of k_phy_pairs over T taxa, rows of Lpw words and `reps` matrices: tiles per side, words per column range (whole chunks), ranges
-void pair_grid(u32 T, u32 Lpw, u32 reps, u32& nt, u32& wps, u32& ranges) {
-    nt = (T + PHY_TILE - 1u) / PHY_TILE;
-    const u64 tiles = (u64)(nt * (nt + 1u) / 2u) * reps;
-    const u32 chunks = (Lpw + PHY_CHUNK_WORDS - 1u) / PHY_CHUNK_WORDS;
-    const u32 want = std::min(chunks, std::max(1u, (u32)((PHY_TARGET_WGS + tiles - 1u) / tiles)));
-    wps = ((chunks + want - 1u) / want) * PHY_CHUNK_WORDS;
-    ranges = (Lpw + wps - 1u) / wps;
-}
+// the grid of k_phy_pairs over T taxa, rows of Lpw words and `reps` matrices: tiles per side, (words per column range, ranges)
+u32 pair_tiles(u32 T) { return (T + PHY_TILE - 1u) / PHY_TILE; }
+std::pair<u32, u32> pair_grid(u32 nt, u32 Lpw, u32 reps) { return range_grid(Lpw, PHY_CHUNK_WORDS, (u64)(nt * (nt + 1u) / 2u) * reps, PHY_TARGET_WGS); }
 
 // ---- bootstrap: so_phy_boot_counts, so_phy_nj_splits, so_phy_boot -------------------------------------------------------------------------
-// draw k of replicate b from K columns: phy.py boot_columns(), in 64-bit integers that wrap
-__device__ __forceinline__ u32 boot_draw(ull seed, ull b, ull k, u32 K) {
-    ull z = seed + ((b << 32) + k + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (u32)(((z >> 32) * (ull)K) >> 32);   // < K: the left factor is below 2^32
-}
-
 // grid (columns of the padded row, groups of PHY_BOOT_TAXA taxa, replicates): replicate b0 + z's drawn columns side by side, '-' behind them
 // as k_phy_gather leaves them.  keep[] lies inside [0, L) (the host has checked), a draw inside [0, K).
 __global__ __launch_bounds__(256) void k_phy_boot_gather(const u8* __restrict__ matrix, u32 T, u32 L, u32 K, u32 Kp, const int* __restrict__ keep, ull seed, u32 b0,
@@ -323,7 +315,7 @@ __global__ __launch_bounds__(256) void k_phy_boot_gather(const u8* __restrict__ 
         for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = (u8)PHY_DASH;
         return;
     }
-    const u32 c = (u32)keep[boot_draw(seed, (ull)b0 + blockIdx.z, j, K)];
+    const u32 c = (u32)keep[replicate_draw(seed, (ull)b0 + blockIdx.z, j, K)];
     for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = matrix[(size_t)t * L + c];
 }
 
@@ -594,7 +586,7 @@ __global__ __launch_bounds__(256) void k_phy_code(const u8* __restrict__ matrix,
         for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = 0xFFu;
         return;
     }
-    const u32 c = (u32)keep[draw ? boot_draw(seed, (ull)b0 + blockIdx.z, j, K) : j];
+    const u32 c = (u32)keep[draw ? replicate_draw(seed, (ull)b0 + blockIdx.z, j, K) : j];
     for (u32 t = t0; t < t1; ++t) dst[(size_t)t * Kp] = lut[matrix[(size_t)t * L + c]];
 }
 
@@ -684,16 +676,6 @@ __global__ __launch_bounds__(256) void k_phy_subst(const u8* __restrict__ code, 
         }
 }
 
-// the grid of k_phy_subst over T taxa, rows of Kp codes and `reps` tensors: tiles per side, columns per range (whole chunks), ranges
-void subst_grid(u32 T, u32 Kp, u32 reps, u32& nt, u32& cps, u32& ranges) {
-    nt = (20u * T + PHS_TILE - 1u) / PHS_TILE;
-    const u64 tiles = (u64)nt * (nt + 1u) / 2u * reps;
-    const u32 chunks = (Kp + PHS_CHUNK_COLS - 1u) / PHS_CHUNK_COLS;
-    const u32 want = std::min(chunks, std::max(1u, (u32)((PHS_TARGET_WGS + tiles - 1u) / tiles)));
-    cps = ((chunks + want - 1u) / want) * PHS_CHUNK_COLS;
-    ranges = (Kp + cps - 1u) / cps;
-}
-
 thread_local std::string g_phy_err;
 
 auto slots(so_phy_subst_result* r) { return result_slots(&r->subst); }
@@ -701,85 +683,67 @@ auto slots(so_phy_result* r) { return result_slots(&r->row, &r->matrix, &r->gaps
 auto slots(so_phy_boot_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->count, &r->ok); }
 auto slots(so_phy_gene_result* r) { return result_slots(&r->cmp, &r->same, &r->splits, &r->present, &r->decisive, &r->concordant, &r->n_present, &r->ok); }
 
-// four marks around the three stages of a batch (flags bit 1 of so_phy_boot): recorded on the stream, read after the batch's wait
-struct StageEvents {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    explicit StageEvents(bool on) {
-        if (on)
-            for (hipEvent_t& x : e) HIP_CHECK(hipEventCreate(&x));
-    }
-    ~StageEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    StageEvents(const StageEvents&) = delete;
-    StageEvents& operator=(const StageEvents&) = delete;
-    void mark(int k, hipStream_t st) {
-        if (e[k]) HIP_CHECK(hipEventRecord(e[k], st));
-    }
-    double ms(int k) {   // between mark k and mark k + 1, both reached: the stream has been waited for
-        float v = 0.f;
-        if (e[k]) HIP_CHECK(hipEventElapsedTime(&v, e[k], e[k + 1]));
-        return v;
-    }
-};
-
-// what the two calls that draw columns check before anything touches the device -> keep as the 32-bit columns the kernels read
-std::vector<int> boot_check(const std::string& who, i64 n_taxa, i64 n_cols, const u8* matrix, i64 n_keep, const i64* keep, i64 b0, i64 n_reps) {
+// What every call over a matrix and its kept columns checks before anything touches the device -> keep as the 32-bit columns the kernels
+// read (want32; the calls over families lay their columns out themselves, gene_layout, and take none).  some_keep: a call that draws needs a kept column.  rest(): the caller's own checks (its replicates or families, the NULL
+// pointers), made before keep[] is walked.
+template <class Rest>
+std::vector<int> matrix_check(const std::string& who, i64 n_taxa, i64 n_cols, i64 n_keep, const i64* keep, bool some_keep, bool want32, Rest rest) {
     if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
     if (n_cols < 0 || n_cols > 0x7FFFFFFFll) throw SoError(who + ": more than 2^31 - 1 columns are not supported");
-    if (n_keep <= 0) throw SoError(who + ": no kept column to draw from (n_keep is 0)");
-    if (n_keep > 0x7FFFFFFFll - 16) throw SoError(who + ": more than 2^31 - 17 kept columns are not supported");
-    if (n_reps < 1) throw SoError(who + ": a replicate at least (n_reps is " + std::to_string(n_reps) + ")");
-    if (b0 < 0 || b0 >= (1ll << 31) || n_reps >= (1ll << 31) || b0 + n_reps > (1ll << 31))
-        throw SoError(who + ": replicates beyond 2^31 - 1 are not supported");
-    if (!matrix || !keep) throw SoError(who + ": matrix or keep is NULL");
-    std::vector<int> k32((size_t)n_keep);
+    if (some_keep && n_keep <= 0) throw SoError(who + ": no kept column to draw from (n_keep is 0)");
+    if (n_keep < 0 || n_keep > 0x7FFFFFFFll - 16) throw SoError(who + ": more than 2^31 - 17 kept columns are not supported");
+    rest();
+    std::vector<int> k32(want32 ? (size_t)n_keep : 0);
     for (i64 k = 0; k < n_keep; ++k) {
         if (keep[k] < 0 || keep[k] >= n_cols) throw SoError(who + ": keep[" + std::to_string(k) + "] lies outside 0 .. n_cols - 1");
-        k32[(size_t)k] = (int)keep[k];
+        if (want32) k32[(size_t)k] = (int)keep[k];
     }
     return k32;
+}
+// ... of the calls that draw columns
+std::vector<int> boot_check(const std::string& who, i64 n_taxa, i64 n_cols, const u8* matrix, i64 n_keep, const i64* keep, i64 b0, i64 n_reps) {
+    return matrix_check(who, n_taxa, n_cols, n_keep, keep, true, true, [&] {
+        if (n_reps < 1) throw SoError(who + ": a replicate at least (n_reps is " + std::to_string(n_reps) + ")");
+        if (b0 < 0 || b0 >= (1ll << 31) || n_reps >= (1ll << 31) || b0 + n_reps > (1ll << 31))
+            throw SoError(who + ": replicates beyond 2^31 - 1 are not supported");
+        if (!matrix || !keep) throw SoError(who + ": matrix or keep is NULL");
+    });
 }
 
 // one batch: the drawn columns of nb replicates from b0 on side by side, then their pair counts (cmp, same: nb * T * T, zeroed here)
 void boot_counts_batch(hipStream_t st, const u8* matrix, u32 T, u32 L, u32 K, const int* keep, const u32* d_K, ull seed, u32 b0, u32 nb, u8* cols, ull* cmp, ull* same) {
-    const u32 Kp = (K + 15u) & ~15u, Kpw = Kp / 4u;
+    const u32 Kp = (K + 15u) & ~15u, Kpw = Kp / 4u, nt = pair_tiles(T);
     const size_t TT = (size_t)T * T;
     HIP_CHECK(hipMemsetAsync(cmp, 0, (size_t)nb * TT * sizeof(ull), st));
     HIP_CHECK(hipMemsetAsync(same, 0, (size_t)nb * TT * sizeof(ull), st));
     hipLaunchKernelGGL(k_phy_boot_gather, dim3((Kp + 255u) / 256u, (T + PHY_BOOT_TAXA - 1u) / PHY_BOOT_TAXA, nb), dim3(256), 0, st, matrix, T, L, K, Kp, keep, seed, b0, cols);
-    u32 nt, wps, ranges;
-    pair_grid(T, Kpw, nb, nt, wps, ranges);
+    const auto [wps, ranges] = pair_grid(nt, Kpw, nb);
     hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges, nb), dim3(256), 0, st, reinterpret_cast<const u32*>(cols), T, Kpw, d_K, nt, wps, cmp, same, (size_t)T * Kpw, TT);
 }
 
-// the walk of nb matrices; clades: the scratch of the bit sets (nb * T * W words) or null where they fit the LDS
+// the walk of nb matrices, over all taxa (present null: k_phy_nj) or over each one's present taxa (k_phy_nj_subset); clades: the scratch of
+// the bit sets (nb * T * W words) or null where they fit the LDS
 static_assert(sizeof(so_phy_boot_result) == 120, "nj_tier and its pad word follow the pointers: swiftortho_amd/_lib.py SoPhyBootResult mirrors the layout");
 size_t nj_lds_bytes(u32 T, u32 W, bool in_lds) { return (size_t)T * 8u + (in_lds ? (size_t)T * W * 8u : 0u) + (size_t)T * 4u; }
 bool nj_clades_fit(u32 T, u32 W) { return nj_lds_bytes(T, W, true) <= PHY_NJ_LDS_BYTES; }
-void nj_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, ull* splits, ull* clades) {
-    hipLaunchKernelGGL(k_phy_nj, dim3(nb), dim3(PHY_NJ_THREADS), nj_lds_bytes(T, W, clades == nullptr), st, D, T, W, ok, splits, clades);
-}
-void nj_subset_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, const u32* n_present, const ull* present, ull* splits, ull* clades) {
-    hipLaunchKernelGGL(k_phy_nj_subset, dim3(nb), dim3(PHY_NJ_THREADS), nj_lds_bytes(T, W, clades == nullptr), st, D, T, W, ok, n_present, present, splits, clades);
+void nj_launch(hipStream_t st, double* D, u32 T, u32 W, u32 nb, const u8* ok, const u32* n_present, const ull* present, ull* splits, ull* clades) {
+    const size_t lds = nj_lds_bytes(T, W, clades == nullptr);
+    if (present) hipLaunchKernelGGL(k_phy_nj_subset, dim3(nb), dim3(PHY_NJ_THREADS), lds, st, D, T, W, ok, n_present, present, splits, clades);
+    else hipLaunchKernelGGL(k_phy_nj, dim3(nb), dim3(PHY_NJ_THREADS), lds, st, D, T, W, ok, splits, clades);
 }
 
 // ---- gene concordance ----
 static_assert(sizeof(so_phy_gene_result) == 136, "swiftortho_amd/_lib.py SoPhyGeneResult mirrors the layout");
 // what the calls over families check before anything touches the device
 void gene_check(const std::string& who, i64 n_taxa, i64 n_cols, const u8* matrix, i64 n_keep, const i64* keep, i64 n_fam, const i64* fam_off) {
-    if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
-    if (n_cols < 0 || n_cols > 0x7FFFFFFFll) throw SoError(who + ": more than 2^31 - 1 columns are not supported");
-    if (n_keep < 0 || n_keep > 0x7FFFFFFFll - 16) throw SoError(who + ": more than 2^31 - 17 kept columns are not supported");
-    if (n_fam < 1 || n_fam >= (1ll << 31)) throw SoError(who + ": the families number 1 .. 2^31 - 1 (n_fam is " + std::to_string(n_fam) + ")");
-    if (!fam_off || (n_keep > 0 && !keep) || ((i64)n_taxa * n_cols > 0 && !matrix)) throw SoError(who + ": matrix, keep or fam_off is NULL");
-    if (fam_off[0] != 0) throw SoError(who + ": inconsistent offsets: fam_off does not start at 0");
-    for (i64 f = 0; f < n_fam; ++f)
-        if (fam_off[f + 1] < fam_off[f]) throw SoError(who + ": inconsistent offsets: fam_off falls at family " + std::to_string(f));
-    if (fam_off[n_fam] != n_keep) throw SoError(who + ": inconsistent offsets: fam_off does not end at n_keep");
-    for (i64 k = 0; k < n_keep; ++k)
-        if (keep[k] < 0 || keep[k] >= n_cols) throw SoError(who + ": keep[" + std::to_string(k) + "] lies outside 0 .. n_cols - 1");
+    matrix_check(who, n_taxa, n_cols, n_keep, keep, false, false, [&] {
+        if (n_fam < 1 || n_fam >= (1ll << 31)) throw SoError(who + ": the families number 1 .. 2^31 - 1 (n_fam is " + std::to_string(n_fam) + ")");
+        if (!fam_off || (n_keep > 0 && !keep) || ((i64)n_taxa * n_cols > 0 && !matrix)) throw SoError(who + ": matrix, keep or fam_off is NULL");
+        if (fam_off[0] != 0) throw SoError(who + ": inconsistent offsets: fam_off does not start at 0");
+        for (i64 f = 0; f < n_fam; ++f)
+            if (fam_off[f + 1] < fam_off[f]) throw SoError(who + ": inconsistent offsets: fam_off falls at family " + std::to_string(f));
+        if (fam_off[n_fam] != n_keep) throw SoError(who + ": inconsistent offsets: fam_off does not end at n_keep");
+    });
 }
 // the gathered row of the families f0 .. f0 + nf - 1: src[j] = the matrix column of byte j, -1 where a family's range is padded to a
 // multiple of 16 bytes; woff[z] = the first 32-bit word of family f0 + z (nf + 1 of them, multiples of 4)
@@ -802,6 +766,77 @@ void gene_gather(hipStream_t st, const u8* matrix, u32 T, u32 L, const std::vect
     upload(d_src, src.data(), src.size(), st);
     K.ensure((size_t)T * Lp + 16);
     if (Lp) hipLaunchKernelGGL(k_phy_fam_gather, dim3((Lp + 255u) / 256u, T), dim3(256), 0, st, matrix, L, Lp, d_src.p, K.p);
+}
+
+// so_phy_nj_splits (R so_phy_boot_result, present null) and so_phy_nj_subsets (R so_phy_gene_result, a row of present words per matrix):
+// the walk of n_reps matrices, PHY_BOOT_MAX_BATCH to a launch, one host wait each.  Where the walk reads D -- between two present taxa,
+// everywhere without `present` -- it is finite and symmetric bit for bit, or the call is refused.
+template <class R>
+int nj_call(const std::string& who, int device, i64 n_reps, i64 n_taxa, const double* D, const uint64_t* present, int32_t flags, R* out, void (*free_result)(R*)) {
+    constexpr bool subset = std::is_same<R, so_phy_gene_result>::value;
+    const std::string among = subset ? " between two present taxa" : "";
+    return guarded_call(g_phy_err, out, free_result, [&] {
+        if (!out) throw SoError(who + ": result pointer is NULL");
+        memset(out, 0, sizeof *out);
+        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: the clade bit sets in global scratch)");
+        if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
+        if (n_reps < 1 || n_reps >= (1ll << 31)) throw SoError(who + ": the matrices number 1 .. 2^31 - 1 (n_reps is " + std::to_string(n_reps) + ")");
+        if (!D || (subset && !present)) throw SoError(who + (subset ? ": D or present is NULL" : ": D is NULL"));
+        const u32 T = (u32)n_taxa, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
+        const size_t TT = (size_t)T * T;
+        const u64 last_mask = (T & 63u) ? (1ull << (T & 63u)) - 1ull : ~0ull;
+        std::vector<u32> npres(present ? (size_t)n_reps : 0), rows(T);   // rows: the taxa the walk reads -- all of them, or a matrix's present ones
+        for (u32 t = 0; t < T; ++t) rows[t] = t;
+        for (i64 b = 0; b < n_reps; ++b) {
+            const double* M = D + (size_t)b * TT;
+            if (present) {
+                const uint64_t* P = present + (size_t)b * W;
+                if (P[W - 1u] & ~last_mask) throw SoError(who + ": the present words of matrix " + std::to_string(b) + " name a taxon beyond n_taxa - 1");
+                rows.clear();
+                for (u32 t = 0; t < T; ++t)
+                    if ((P[t >> 6] >> (t & 63u)) & 1ull) rows.push_back(t);
+                npres[(size_t)b] = (u32)rows.size();
+            }
+            for (u32 i : rows)
+                for (u32 j : rows) {
+                    if (!std::isfinite(M[(size_t)i * T + j])) throw SoError(who + ": matrix " + std::to_string(b) + " holds a value that is not finite" + among);
+                    if (j < i && memcmp(&M[(size_t)i * T + j], &M[(size_t)j * T + i], sizeof(double)) != 0)
+                        throw SoError(who + ": matrix " + std::to_string(b) + " is not symmetric bit for bit" + among);
+                }
+        }
+        out->n_taxa = n_taxa, out->n_splits = S, out->n_words = W;
+        if constexpr (subset) out->n_fam = n_reps;
+        else out->n_reps = n_reps;
+        check_device(who.c_str(), device);
+        if (S == 0) {   // two or three taxa: one topology, no split
+            fill_empty_slots(slots(out));
+            return;
+        }
+        const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
+        out->nj_tier = in_lds ? 1 : 2;
+        DeviceCall call(device);
+        hipStream_t st = call.st;
+        DevBuf<double> d_D;
+        DevBuf<ull> d_splits, clades, d_present;
+        DevBuf<u32> d_np;
+        const size_t per_call = PHY_BOOT_MAX_BATCH;
+        out->splits = host_array<uint64_t>(who.c_str(), (size_t)n_reps * S * W);
+        static_assert(sizeof(ull) == sizeof(uint64_t), "the bit sets are copied out as uint64");
+        for (size_t b0 = 0; b0 < (size_t)n_reps; b0 += per_call) {
+            const u32 nb = (u32)std::min(per_call, (size_t)n_reps - b0);
+            upload(d_D, D + b0 * TT, (size_t)nb * TT, st);
+            if (present) upload(d_present, reinterpret_cast<const ull*>(present) + b0 * W, (size_t)nb * W, st), upload(d_np, npres.data() + b0, nb, st);
+            d_splits.ensure((size_t)nb * S * W + 2);
+            if (!in_lds) clades.ensure((size_t)nb * T * W + 2);
+            nj_launch(st, d_D.p, T, W, nb, nullptr, d_np.p, present ? d_present.p : nullptr, d_splits.p, in_lds ? nullptr : clades.p);
+            HIP_CHECK(hipGetLastError());
+            call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * S * W, d_splits.p, (size_t)nb * S * W);
+            call.wait();
+            ++out->batches;
+        }
+        out->waits = call.waits;
+        fill_empty_slots(slots(out));
+    });
 }
 
 }  // namespace
@@ -957,8 +992,8 @@ int so_phy_build(int device, int64_t n_taxa, int64_t n_fam, const int64_t* col_o
         hipLaunchKernelGGL(k_phy_keep, grid256(L), dim3(256), 0, st, flag.p, pos.p, L, d_keep.p);
         hipLaunchKernelGGL(k_phy_gather, dim3((Lp + 255u) / 256u, T), dim3(256), 0, st, matrix.p, L, Lp, d_keep.p, d_nk, kept.p);
         {
-            u32 nt, wps, ranges;
-            pair_grid(T, Lpw, 1u, nt, wps, ranges);
+            const u32 nt = pair_tiles(T);
+            const auto [wps, ranges] = pair_grid(nt, Lpw, 1u);
             hipLaunchKernelGGL(k_phy_pairs, dim3(nt * nt, ranges), dim3(256), 0, st, reinterpret_cast<const u32*>(kept.p), T, Lpw, d_nk, nt, wps, d_cmp.p, d_same.p, (size_t)0,
                                (size_t)0);
         }
@@ -1042,13 +1077,7 @@ int so_phy_subst(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matr
         check_device(who.c_str(), device);
         DeviceCall call(device);
         hipStream_t st = call.st;
-        {
-            size_t free_b = 0, total_b = 0;
-            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            if (bytes + bytes / 8 > free_b / 2)   // (a DevBuf takes an eighth more than it is asked for)
-                throw SoError(who + ": the tensor of " + std::to_string(nb) + " x " + std::to_string(P) + " pairs would take " + std::to_string(bytes) +
-                              " bytes, more than half of the free device memory (" + std::to_string(free_b) + " bytes free): ask for fewer replicates per call");
-        }
+        refuse_over_half_free(who, "tensor of " + std::to_string(nb) + " x " + std::to_string(P) + " pairs", bytes);
         DevBuf<u8> d_matrix, codes;
         DevBuf<int> d_keep, d_out;
         upload(d_matrix, matrix, (size_t)T * L, st), upload(d_keep, k32.data(), k32.size(), st);
@@ -1059,8 +1088,8 @@ int so_phy_subst(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matr
         hipLaunchKernelGGL(k_phy_code, dim3((Kp + 255u) / 256u, (T + PHY_BOOT_TAXA - 1u) / PHY_BOOT_TAXA, nb), dim3(256), 0, st, d_matrix.p, T, L, K, Kp, d_keep.p, (ull)seed,
                            (u32)(draw ? b0 : 0), draw ? 1u : 0u, codes.p);
         ev.mark(1, st);
-        u32 nt, cps, ranges;
-        subst_grid(T, Kp, nb, nt, cps, ranges);
+        const u32 nt = (20u * T + PHS_TILE - 1u) / PHS_TILE;   // tiles per side; columns per range (whole chunks), ranges
+        const auto [cps, ranges] = range_grid(Kp, PHS_CHUNK_COLS, (u64)nt * (nt + 1u) / 2u * nb, PHS_TARGET_WGS);
         hipLaunchKernelGGL(k_phy_subst, dim3(nt * nt, ranges, nb), dim3(256), 0, st, codes.p, T, Kp, nt, cps, d_out.p, (size_t)T * Kp, per);
         ev.mark(2, st);
         HIP_CHECK(hipGetLastError());
@@ -1074,54 +1103,7 @@ int so_phy_subst(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matr
 }
 
 int so_phy_nj_splits(int device, int64_t n_reps, int64_t n_taxa, const double* D, int32_t flags, so_phy_boot_result* out) {
-    const std::string who = "so_phy_nj_splits";
-    return guarded_call(g_phy_err, out, so_phy_boot_free, [&] {
-        if (!out) throw SoError(who + ": result pointer is NULL");
-        memset(out, 0, sizeof *out);
-        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: the clade bit sets in global scratch)");
-        if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
-        if (n_reps < 1 || n_reps >= (1ll << 31)) throw SoError(who + ": the matrices number 1 .. 2^31 - 1 (n_reps is " + std::to_string(n_reps) + ")");
-        if (!D) throw SoError(who + ": D is NULL");
-        const u32 T = (u32)n_taxa, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
-        const size_t TT = (size_t)T * T;
-        for (i64 b = 0; b < n_reps; ++b) {
-            const double* M = D + (size_t)b * TT;
-            for (u32 i = 0; i < T; ++i)
-                for (u32 j = 0; j < T; ++j) {
-                    if (!std::isfinite(M[(size_t)i * T + j])) throw SoError(who + ": matrix " + std::to_string(b) + " holds a value that is not finite");
-                    if (j < i && memcmp(&M[(size_t)i * T + j], &M[(size_t)j * T + i], sizeof(double)) != 0)
-                        throw SoError(who + ": matrix " + std::to_string(b) + " is not symmetric bit for bit");
-                }
-        }
-        out->n_taxa = n_taxa, out->n_reps = n_reps, out->n_splits = S, out->n_words = W;
-        check_device(who.c_str(), device);
-        if (S == 0) {   // two or three taxa: one topology, no split
-            fill_empty_slots(slots(out));
-            return;
-        }
-        const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
-        out->nj_tier = in_lds ? 1 : 2;
-        DeviceCall call(device);
-        hipStream_t st = call.st;
-        DevBuf<double> d_D;
-        DevBuf<ull> d_splits, clades;
-        const size_t per_call = PHY_BOOT_MAX_BATCH;
-        out->splits = host_array<uint64_t>(who.c_str(), (size_t)n_reps * S * W);
-        static_assert(sizeof(ull) == sizeof(uint64_t), "the bit sets are copied out as uint64");
-        for (size_t b0 = 0; b0 < (size_t)n_reps; b0 += per_call) {
-            const u32 nb = (u32)std::min(per_call, (size_t)n_reps - b0);
-            upload(d_D, D + b0 * TT, (size_t)nb * TT, st);
-            d_splits.ensure((size_t)nb * S * W + 2);
-            if (!in_lds) clades.ensure((size_t)nb * T * W + 2);
-            nj_launch(st, d_D.p, T, W, nb, nullptr, d_splits.p, in_lds ? nullptr : clades.p);
-            HIP_CHECK(hipGetLastError());
-            call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * S * W, d_splits.p, (size_t)nb * S * W);
-            call.wait();
-            ++out->batches;
-        }
-        out->waits = call.waits;
-        fill_empty_slots(slots(out));
-    });
+    return nj_call("so_phy_nj_splits", device, n_reps, n_taxa, D, nullptr, flags, out, so_phy_boot_free);
 }
 
 int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, uint64_t seed, int64_t n_reps,
@@ -1154,13 +1136,7 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
         const bool in_lds = S && nj_clades_fit(T, W);
         out->nj_tier = S ? (in_lds ? 1 : 2) : 0;
         const size_t per_rep = (size_t)T * Kp + 3u * TT * 8u + SW * 8u + (S && !in_lds ? (size_t)T * W * 8u : 0u) + 1u;
-        size_t batch = (size_t)call.tn.phy_boot_batch;
-        if (call.tn.phy_boot_batch <= 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            batch = std::max<size_t>(1, free_b / 2 / (per_rep + per_rep / 8));   // (a DevBuf takes an eighth more than it is asked for)
-        }
-        batch = std::min(std::min(batch, B), (size_t)PHY_BOOT_MAX_BATCH);
+        const size_t batch = device_batch(call, call.tn.phy_boot_batch, per_rep, std::min(B, (size_t)PHY_BOOT_MAX_BATCH));
         cols.ensure(batch * T * Kp + 16), d_cmp.ensure(batch * TT + 2), d_same.ensure(batch * TT + 2), d_D.ensure(batch * TT + 2), d_ok.ensure(batch + 2);
         d_splits.ensure(batch * SW + 2);
         if (S && !in_lds) clades.ensure(batch * T * W + 2);
@@ -1176,7 +1152,7 @@ int so_phy_boot(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
             HIP_CHECK(hipMemsetAsync(d_ok.p, 1, nb, st));
             hipLaunchKernelGGL(k_phy_boot_dist, dim3((unsigned)((TT + 255) / 256), nb), dim3(256), 0, st, d_cmp.p, d_same.p, (u32)TT, d_D.p, d_ok.p);
             ev.mark(1, st);
-            if (S) nj_launch(st, d_D.p, T, W, nb, d_ok.p, d_splits.p, in_lds ? nullptr : clades.p);
+            if (S) nj_launch(st, d_D.p, T, W, nb, d_ok.p, nullptr, nullptr, d_splits.p, in_lds ? nullptr : clades.p);
             ev.mark(2, st);
             if (S) hipLaunchKernelGGL(k_phy_boot_support, dim3((S + 255u) / 256u, nb), dim3(256), 0, st, d_ref.p, d_splits.p, S, W, d_ok.p, d_count.p);
             ev.mark(3, st);
@@ -1211,7 +1187,7 @@ int so_phy_gene_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t
         std::vector<int> src;
         std::vector<u32> woff;
         gene_layout(who, keep, fam_off, f0, n, src, woff);
-        const u32 T = (u32)n_taxa, L = (u32)n_cols, nf = (u32)n, nt = (T + PHY_TILE - 1u) / PHY_TILE;
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, nf = (u32)n, nt = pair_tiles(T);
         const size_t TT = (size_t)T * T;
         out->n_taxa = n_taxa, out->n_fam = n;
         check_device(who.c_str(), device);
@@ -1236,64 +1212,7 @@ int so_phy_gene_counts(int device, int64_t n_taxa, int64_t n_cols, const uint8_t
 }
 
 int so_phy_nj_subsets(int device, int64_t n_reps, int64_t n_taxa, const double* D, const uint64_t* present, int32_t flags, so_phy_gene_result* out) {
-    const std::string who = "so_phy_nj_subsets";
-    return guarded_call(g_phy_err, out, so_phy_gene_free, [&] {
-        if (!out) throw SoError(who + ": result pointer is NULL");
-        memset(out, 0, sizeof *out);
-        if (flags & ~1) throw SoError(who + ": unknown flag bits (bit 0: the clade bit sets in global scratch)");
-        if (n_taxa < 2 || n_taxa > PHY_MAX_TAXA) throw SoError(who + ": the taxa number 2 .. " + std::to_string(PHY_MAX_TAXA) + " (n_taxa is " + std::to_string(n_taxa) + ")");
-        if (n_reps < 1 || n_reps >= (1ll << 31)) throw SoError(who + ": the matrices number 1 .. 2^31 - 1 (n_reps is " + std::to_string(n_reps) + ")");
-        if (!D || !present) throw SoError(who + ": D or present is NULL");
-        const u32 T = (u32)n_taxa, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u;
-        const size_t TT = (size_t)T * T;
-        const u64 last_mask = (T & 63u) ? (1ull << (T & 63u)) - 1ull : ~0ull;
-        std::vector<u32> npres((size_t)n_reps);
-        std::vector<u32> rows;
-        for (i64 b = 0; b < n_reps; ++b) {
-            const double* M = D + (size_t)b * TT;
-            const uint64_t* P = present + (size_t)b * W;
-            if (P[W - 1u] & ~last_mask) throw SoError(who + ": the present words of matrix " + std::to_string(b) + " name a taxon beyond n_taxa - 1");
-            rows.clear();
-            for (u32 t = 0; t < T; ++t)
-                if ((P[t >> 6] >> (t & 63u)) & 1ull) rows.push_back(t);
-            npres[(size_t)b] = (u32)rows.size();
-            for (u32 i : rows)
-                for (u32 j : rows) {
-                    if (!std::isfinite(M[(size_t)i * T + j])) throw SoError(who + ": matrix " + std::to_string(b) + " holds a value that is not finite between two present taxa");
-                    if (j < i && memcmp(&M[(size_t)i * T + j], &M[(size_t)j * T + i], sizeof(double)) != 0)
-                        throw SoError(who + ": matrix " + std::to_string(b) + " is not symmetric bit for bit between two present taxa");
-                }
-        }
-        out->n_taxa = n_taxa, out->n_fam = n_reps, out->n_splits = S, out->n_words = W;
-        check_device(who.c_str(), device);
-        if (S == 0) {   // two or three taxa: one topology, no split
-            fill_empty_slots(slots(out));
-            return;
-        }
-        const bool in_lds = !(flags & 1) && nj_clades_fit(T, W);
-        out->nj_tier = in_lds ? 1 : 2;
-        DeviceCall call(device);
-        hipStream_t st = call.st;
-        DevBuf<double> d_D;
-        DevBuf<ull> d_splits, clades, d_present;
-        DevBuf<u32> d_np;
-        const size_t per_call = PHY_BOOT_MAX_BATCH;
-        out->splits = host_array<uint64_t>(who.c_str(), (size_t)n_reps * S * W);
-        for (size_t b0 = 0; b0 < (size_t)n_reps; b0 += per_call) {
-            const u32 nb = (u32)std::min(per_call, (size_t)n_reps - b0);
-            upload(d_D, D + b0 * TT, (size_t)nb * TT, st), upload(d_present, reinterpret_cast<const ull*>(present) + b0 * W, (size_t)nb * W, st);
-            upload(d_np, npres.data() + b0, nb, st);
-            d_splits.ensure((size_t)nb * S * W + 2);
-            if (!in_lds) clades.ensure((size_t)nb * T * W + 2);
-            nj_subset_launch(st, d_D.p, T, W, nb, nullptr, d_np.p, d_present.p, d_splits.p, in_lds ? nullptr : clades.p);
-            HIP_CHECK(hipGetLastError());
-            call.fetch(reinterpret_cast<ull*>(out->splits) + b0 * S * W, d_splits.p, (size_t)nb * S * W);
-            call.wait();
-            ++out->batches;
-        }
-        out->waits = call.waits;
-        fill_empty_slots(slots(out));
-    });
+    return nj_call("so_phy_nj_subsets", device, n_reps, n_taxa, D, present, flags, out, so_phy_gene_free);
 }
 
 int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matrix, int64_t n_keep, const int64_t* keep, int64_t n_fam, const int64_t* fam_off,
@@ -1304,7 +1223,7 @@ int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
         memset(out, 0, sizeof *out);
         if (flags & ~3) throw SoError(who + ": unknown flag bits (bit 0: every family's present words and splits in the result, bit 1: the stages timed by events)");
         gene_check(who, n_taxa, n_cols, matrix, n_keep, keep, n_fam, fam_off);
-        const u32 T = (u32)n_taxa, L = (u32)n_cols, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u, nt = (T + PHY_TILE - 1u) / PHY_TILE;
+        const u32 T = (u32)n_taxa, L = (u32)n_cols, W = (T + 63u) / 64u, S = T > 3u ? T - 3u : 0u, nt = pair_tiles(T);
         if (S && !ref_splits) throw SoError(who + ": ref_splits is NULL");
         std::vector<int> src;
         std::vector<u32> woff;
@@ -1333,13 +1252,7 @@ int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
         const bool in_lds = S && nj_clades_fit(T, W);
         out->nj_tier = S ? (in_lds ? 1 : 2) : 0;
         const size_t per_fam = 2u * TT * 4u + TT * 8u + SW * 8u + (S && !in_lds ? (size_t)T * W * 8u : 0u) + (size_t)W * 8u + 5u;
-        size_t batch = (size_t)call.tn.phy_gene_batch;
-        if (call.tn.phy_gene_batch <= 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            batch = std::max<size_t>(1, free_b / 2 / (per_fam + per_fam / 8));   // (a DevBuf takes an eighth more than it is asked for)
-        }
-        batch = std::min(std::min(batch, F), (size_t)PHY_BOOT_MAX_BATCH);
+        const size_t batch = device_batch(call, call.tn.phy_gene_batch, per_fam, std::min(F, (size_t)PHY_BOOT_MAX_BATCH));
         d_cmp.ensure(batch * TT + 2), d_same.ensure(batch * TT + 2), d_D.ensure(batch * TT + 2), d_ok.ensure(batch + 2), d_np.ensure(batch + 2);
         d_present.ensure(batch * W + 2), d_splits.ensure(batch * SW + 2);
         if (S && !in_lds) clades.ensure(batch * T * W + 2);
@@ -1355,7 +1268,7 @@ int so_phy_gene(int device, int64_t n_taxa, int64_t n_cols, const uint8_t* matri
             HIP_CHECK(hipMemsetAsync(d_ok.p, 1, nb, st));
             hipLaunchKernelGGL(k_phy_gene_dist, dim3((unsigned)((TT + 255) / 256), nb), dim3(256), 0, st, d_cmp.p, d_same.p, T, W, d_D.p, d_ok.p, d_present.p, d_np.p);
             ev.mark(1, st);
-            if (S) nj_subset_launch(st, d_D.p, T, W, nb, d_ok.p, d_np.p, d_present.p, d_splits.p, in_lds ? nullptr : clades.p);
+            if (S) nj_launch(st, d_D.p, T, W, nb, d_ok.p, d_np.p, d_present.p, d_splits.p, in_lds ? nullptr : clades.p);
             ev.mark(2, st);
             if (S)
                 hipLaunchKernelGGL(k_phy_gene_concord, dim3((S + 255u) / 256u, nb), dim3(256), 0, st, d_ref.p, d_splits.p, S, W, d_ok.p, d_np.p, d_present.p, d_dec.p, d_con.p);

@@ -235,9 +235,7 @@ class PanResult:
 
 def device_pan_genome(row, taxon, n_rows, n_file_rows, n_taxa, spec_max, core_min, perm, S, C, want_counts=True, device=0, flags=0):
     """count_matrix(), row_types() and rarefaction() in one device call -> PanResult; a refusal raises RuntimeError with the library's message"""
-    import ctypes as C_
     from . import _lib
-    L = _lib.load()
     row32, tax32 = np.ascontiguousarray(row, dtype=np.int32), np.ascontiguousarray(taxon, dtype=np.int32)
     if len(row32) != len(tax32):
         raise ValueError('device_pan_genome: row and taxon differ in length')
@@ -246,21 +244,14 @@ def device_pan_genome(row, taxon, n_rows, n_file_rows, n_taxa, spec_max, core_mi
     if len(S32) != n_taxa or len(C32) != n_taxa:
         raise ValueError('device_pan_genome: S and C hold one entry per taxon')
     size = len(perm32)
-    ptr = lambda a: C_.c_void_p(a.ctypes.data)
-    out = _lib.SoPanResult()
-    rc = L.so_pan_genome(int(device), len(row32), ptr(row32), ptr(tax32), int(n_rows), int(n_file_rows), int(n_taxa), int(spec_max), int(core_min), size,
-                         ptr(perm32), ptr(S32), ptr(C32), 1 if want_counts else 0, int(flags), C_.byref(out))
-    if rc != 0:
-        raise RuntimeError(L.so_pan_last_error().decode())
-    try:
+    with _lib.call('so_pan_genome', _lib.SoPanResult, 'so_pan_free', 'so_pan_last_error', int(device), len(row32), row32, tax32, int(n_rows), int(n_file_rows), int(n_taxa),
+                   int(spec_max), int(core_min), size, perm32, S32, C32, 1 if want_counts else 0, int(flags)) as out:
         arr = _lib.result_array
         steps = max(n_taxa - 1, 0)
         curve = lambda p: arr(p, size * steps, np.int64).reshape(size, steps)
         return PanResult(arr(out.counts, n_rows * n_taxa, np.int32).reshape(n_rows, n_taxa) if want_counts else None, arr(out.type, n_rows, np.uint8),
                          (int(out.n_core), int(out.n_share), int(out.n_spec)), curve(out.core), curve(out.spec), curve(out.panz),
                          {'tier': int(out.tier), 'waits': int(out.waits)})
-    finally:
-        L.so_pan_free(C_.byref(out))
 
 
 def pan_genome(table, n_taxa, ts=.05, tc=.95, size=SIZE, device_stage=False, want_counts=True, device=0):
@@ -349,27 +340,19 @@ def boot_content_distances(S, metric='jaccard'):
 
 def _device_shared(who, row, taxon, n_rows, n_taxa, seed, b0, nb, device, stats=None, want=True, timed=False):
     """so_pan_shared -> int32[max(nb, 1), T, T] (None without `want`); nb = 0: all rows"""
-    import ctypes as C_
     from . import _lib
-    L = _lib.load()
     row32, tax32 = np.ascontiguousarray(row, dtype=np.int32), np.ascontiguousarray(taxon, dtype=np.int32)
     if len(row32) != len(tax32):
         raise ValueError('%s: row and taxon differ in length' % who)
-    ptr = lambda a: C_.c_void_p(a.ctypes.data)
-    res = _lib.SoPanSharedResult()
     flags = (0 if want else 1) | (2 if timed else 0)
-    if L.so_pan_shared(int(device), len(row32), ptr(row32), ptr(tax32), int(n_rows), int(n_taxa), C_.c_uint64(int(seed) & (2 ** 64 - 1)), int(b0), int(nb), flags,
-                       C_.byref(res)) != 0:
-        raise RuntimeError(L.so_pan_last_error().decode())
-    try:
+    with _lib.call('so_pan_shared', _lib.SoPanSharedResult, 'so_pan_shared_free', 'so_pan_last_error', int(device), len(row32), row32, tax32, int(n_rows), int(n_taxa),
+                   int(seed) & (2 ** 64 - 1), int(b0), int(nb), flags) as res:
         if stats is not None:
             stats['waits'], stats['batches'], stats['ranges'], stats['bytes'] = int(res.waits), int(res.batches), int(res.ranges), int(res.bytes)
             if timed:
                 stats['draw_ms'], stats['product_ms'] = float(res.draw_ms), float(res.product_ms)
         n, T = int(res.n_reps), int(n_taxa)
         return _lib.result_array(res.shared, n * T * T, np.int32).reshape(n, T, T) if want else None
-    finally:
-        L.so_pan_shared_free(C_.byref(res))
 
 
 def device_shared_counts(row, taxon, n_rows, n_taxa, device=0, stats=None):
@@ -387,11 +370,6 @@ def device_boot_shared(row, taxon, n_rows, n_taxa, seed, b0, nb, device=0, stats
 
 class TooFewTaxa(ValueError):
     """fewer than two taxa: no pair, no tree (pan_genome.py exits with code 2)"""
-
-
-def _content_batch(B, T):
-    """replicates per device call of content_tree: what about 2^30 bytes of counts (int32 and int64) and distances hold"""
-    return max(1, min(B, 32768, (1 << 30) // max(1, 20 * T * T)))   # (32768: the most a device call takes)
 
 
 def content_tree(table, taxa, metric='jaccard', boot=0, seed=1, device_stage=False, device=0, stats=None):
@@ -429,26 +407,17 @@ def content_tree(table, taxa, metric='jaccard', boot=0, seed=1, device_stage=Fal
             raise ValueError('content_tree: no row to draw from')
         ref = phy.tree_splits(D)
         ns, W = max(T - 3, 0), (T + 63) // 64
-        ok, splits = np.zeros(boot, dtype=bool), np.zeros((boot, ns, W), dtype=np.uint64)
-        if device_stage:
-            step, calls = _content_batch(boot, T), 0
-            for b0 in range(0, boot, step):
-                nb = min(step, boot - b0)
-                Sb = device_boot_shared(table.row, tax, R, T, seed, b0, nb, device)
-                calls += 1
-                dist = [boot_content_distances(Sb[k], metric) for k in range(nb)]
-                good = [k for k in range(nb) if dist[k][1]]
-                if good and ns:
-                    splits[[b0 + k for k in good]] = phy.device_nj_splits(np.stack([dist[k][0] for k in good]), device)
-                    calls += 1
-                ok[[b0 + k for k in good]] = True
-            if stats is not None:
-                stats['calls'] = calls
+        if device_stage:   # a batch: what about 2^30 bytes of counts (int32 and int64) and distances hold
+            step = phy.batch_size(boot, 20 * T * T)
+            counts_of = lambda b0, nb: (device_boot_shared(table.row, tax, R, T, seed, b0, nb, device), 1)
+            trees_of = lambda Ds, idx: phy.device_nj_splits(Ds, device)
         else:
-            for b in range(boot):
-                Db, ok[b] = boot_content_distances(boot_shared(counts, seed, b), metric)
-                if ok[b]:
-                    splits[b] = phy.nj_splits(Db)
+            step = 1
+            counts_of = lambda b, _: ([boot_shared(counts, seed, b)], 0)
+            trees_of = lambda Ds, idx: phy.nj_splits(Ds[0])[None]
+        ok, splits, calls = phy.replicate_trees(boot, step, counts_of, lambda Sb, k: boot_content_distances(Sb[k], metric), trees_of, ns, W)
+        if stats is not None and device_stage:
+            stats['calls'] = calls
     except RuntimeError as e:
         raise ValueError('content_tree: %s' % e)
     valid = int(ok.sum())

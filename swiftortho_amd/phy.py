@@ -53,15 +53,24 @@ csrc/phy.hip) equal them array for array.
     and integer atomics, batches with one host wait each; so_phy_gene_counts and so_phy_nj_subsets for poisson and kimura, whose logarithm
     stays on the host with the printed tree's walk) only integers and bit sets come back: every array equals numpy's.  Refused: T outside
     2 .. 4096, offsets that do not rise from 0 to the kept columns, a kept column out of range, unknown flags, no device.
+
+The module imports `_lib` (ctypes declarations only: the library itself is loaded by the first device call), so the numpy definitions need
+no built library and no device.
 """
 import math
 import sys
 
 import numpy as np
 
-from . import rbh
+from . import _lib, rbh
 
 GAP = 45   # '-'
+_arr = _lib.result_array
+
+
+def _call(fn, result, free, *args):
+    """a device call of this module (_lib.call): a `with` block around the result; a refusal raises RuntimeError with the library's message"""
+    return _lib.call(fn, getattr(_lib, result), free, 'so_phy_last_error', *args)
 
 
 class Supermatrix:
@@ -115,22 +124,13 @@ def pick_rows(cols_q, cols_s, score, pair_q, pair_s):
 
 def device_pick_rows(cols_q, cols_s, score, pair_q, pair_s, device=0):
     """pick_rows() on the GPU (so_phy_rows); a refusal raises RuntimeError with the library's message"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
     q32, s32 = _codes32(cols_q, 'device_pick_rows'), _codes32(cols_s, 'device_pick_rows')
     sco = np.ascontiguousarray(score, dtype=np.float64)
     pq, ps = _codes32(pair_q, 'device_pick_rows'), _codes32(pair_s, 'device_pick_rows')
     if not (len(q32) == len(s32) == len(sco)) or len(pq) != len(ps):
         raise ValueError('device_pick_rows: the columns differ in length')
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    out = _lib.SoPhyResult()
-    if L.so_phy_rows(int(device), len(q32), ptr(q32), ptr(s32), ptr(sco), len(pq), ptr(pq), ptr(ps), 0, C.byref(out)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
-        return _lib.result_array(out.row, len(pq), np.int64)
-    finally:
-        L.so_phy_free(C.byref(out))
+    with _call('so_phy_rows', 'SoPhyResult', 'so_phy_free', int(device), len(q32), q32, s32, sco, len(pq), pq, ps, 0) as out:
+        return _arr(out.row, len(pq), np.int64)
 
 
 def _codes32(a, who):
@@ -312,28 +312,17 @@ def build(tk, g=1.0):
 def device_build(tk, g=1.0, want_matrix=True, device=0, out=None, stats=None):
     """build() in one device call (so_phy_build) -> (matrix or None, gaps, keep, cmp, same); a refusal raises RuntimeError with the
     library's message.  `out`: a uint8[T, L] array of the caller's that receives the matrix too -- a refused call leaves it untouched."""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    res = _lib.SoPhyResult()
     F, n = len(tk.col_off) - 1, len(tk.fam)
-    rc = L.so_phy_build(int(device), tk.n_taxa, F, ptr(tk.col_off), n, ptr(tk.fam), ptr(tk.slot), ptr(tk.kind), ptr(tk.res_off), ptr(tk.res_len), ptr(tk.qst),
-                        ptr(tk.sst), ptr(tk.run_off), ptr(tk.runs), len(tk.runs), ptr(tk.residues), len(tk.residues), float(g), 0 if want_matrix else 1, C.byref(res))
-    if rc != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
-        arr = _lib.result_array
+    with _call('so_phy_build', 'SoPhyResult', 'so_phy_free', int(device), tk.n_taxa, F, tk.col_off, n, tk.fam, tk.slot, tk.kind, tk.res_off, tk.res_len, tk.qst, tk.sst,
+               tk.run_off, tk.runs, len(tk.runs), tk.residues, len(tk.residues), float(g), 0 if want_matrix else 1) as res:
         T, nc, nk = tk.n_taxa, int(res.n_cols), int(res.n_keep)
-        matrix = arr(res.matrix, T * nc, np.uint8).reshape(T, nc) if want_matrix else None
+        matrix = _arr(res.matrix, T * nc, np.uint8).reshape(T, nc) if want_matrix else None
         if out is not None and matrix is not None:
             out[...] = matrix
         if stats is not None:
             stats['waits'] = int(res.waits)
-        return (matrix, arr(res.gaps, nc, np.int32), arr(res.keep, nc, np.int64)[:nk], arr(res.cmp, T * T, np.int64).reshape(T, T),
-                arr(res.same, T * T, np.int64).reshape(T, T))
-    finally:
-        L.so_phy_free(C.byref(res))
+        return (matrix, _arr(res.gaps, nc, np.int32), _arr(res.keep, nc, np.int64)[:nk], _arr(res.cmp, T * T, np.int64).reshape(T, T),
+                _arr(res.same, T * T, np.int64).reshape(T, T))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -760,57 +749,55 @@ def split_support(ref_splits, rep_splits, ok):
     return out
 
 
-def _boot_batch(B, per_rep_bytes):
-    """replicates per device call of the poisson path: SOHIT_PHY_BOOT_BATCH, else what about 2^30 bytes of counts and columns hold"""
+def batch_size(n, bytes_each, env=None):
+    """items (replicates, families) per device call of a path whose distances are made on the host: the switch `env` names
+    (SOHIT_PHY_BOOT_BATCH, SOHIT_PHY_GENE_BATCH) where it is set, else what about 2^30 bytes hold at bytes_each a piece; n and 32768 (the
+    most a device call takes) at the most, one at least"""
     import os
-    forced = int(os.environ.get('SOHIT_PHY_BOOT_BATCH', '0') or 0)
-    return max(1, min(B, 32768, forced if forced > 0 else (1 << 30) // max(1, per_rep_bytes)))   # (32768: the most a device call takes)
+    forced = int(os.environ.get(env, '0') or 0) if env else 0
+    return max(1, min(n, 32768, forced if forced > 0 else (1 << 30) // max(1, bytes_each)))
+
+
+def replicate_trees(n, step, counts_of, distance_of, trees_of, S, W):
+    """-> (ok bool[n], splits uint64[n, S, W], calls): the loop every tree per replicate or per family is made in, `step` items at a time.
+    counts_of(i0, k) -> (the inputs of items i0 .. i0 + k - 1, the device calls that took); distance_of(batch, j) -> (D float64[T, T], ok)
+    of item j of the batch; trees_of(D float64[m, T, T], idx) -> uint64[m, S, W], the splits of the items idx that have a distance, asked
+    for once per batch (a call) where there is such an item and S > 0.  An item without a distance is not ok, its splits are zeros."""
+    ok, splits, calls = np.zeros(n, dtype=bool), np.zeros((n, S, W), dtype=np.uint64), 0
+    for i0 in range(0, n, step):
+        k = min(step, n - i0)
+        batch, made = counts_of(i0, k)
+        dist = [distance_of(batch, j) for j in range(k)]
+        good = [j for j in range(k) if dist[j][1]]
+        idx = [i0 + j for j in good]
+        calls += made
+        if good and S:
+            splits[idx] = trees_of(np.stack([dist[j][0] for j in good]), idx)
+            calls += 1
+        ok[idx] = True
+    return ok, splits, calls
 
 
 def device_boot_counts(matrix, keep, seed, b0, nb, device=0):
     """boot_counts() of replicates b0 .. b0 + nb - 1 in one device call (so_phy_boot_counts) -> (cmp, same) int64[nb, T, T]"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
-    if matrix.ndim != 2:
-        raise ValueError('device_boot_counts: the matrix has two dimensions')
-    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    matrix, keep = _lib.matrix2d('device_boot_counts', matrix), np.ascontiguousarray(keep, dtype=np.int64)
     T, nc = matrix.shape
-    res = _lib.SoPhyBootResult()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    if L.so_phy_boot_counts(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(b0), int(nb), 0, C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
-        return (_lib.result_array(res.cmp, nb * T * T, np.int64).reshape(nb, T, T), _lib.result_array(res.same, nb * T * T, np.int64).reshape(nb, T, T))
-    finally:
-        L.so_phy_boot_free(C.byref(res))
+    with _call('so_phy_boot_counts', 'SoPhyBootResult', 'so_phy_boot_free', int(device), T, nc, matrix, len(keep), keep, int(seed) & _M64, int(b0), int(nb), 0) as res:
+        return _arr(res.cmp, nb * T * T, np.int64).reshape(nb, T, T), _arr(res.same, nb * T * T, np.int64).reshape(nb, T, T)
 
 
 def _device_subst(who, matrix, keep, seed, b0, nb, device, stats=None, want=True, timed=False):
     """so_phy_subst -> int32[max(nb, 1), P, 20, 20] (None without `want`); nb = 0: the kept columns"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
-    if matrix.ndim != 2:
-        raise ValueError('%s: the matrix has two dimensions' % who)
-    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    matrix, keep = _lib.matrix2d(who, matrix), np.ascontiguousarray(keep, dtype=np.int64)
     T, nc = matrix.shape
-    res = _lib.SoPhySubstResult()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
     flags = (0 if want else 1) | (2 if timed else 0)
-    if L.so_phy_subst(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(b0), int(nb), flags, C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
+    with _call('so_phy_subst', 'SoPhySubstResult', 'so_phy_subst_free', int(device), T, nc, matrix, len(keep), keep, int(seed) & _M64, int(b0), int(nb), flags) as res:
         if stats is not None:
             stats['waits'], stats['bytes'] = int(res.waits), int(res.bytes)
             if timed:
                 stats['code_ms'], stats['product_ms'] = float(res.code_ms), float(res.product_ms)
         n, P = int(res.n_reps), int(res.n_pairs)
-        return _lib.result_array(res.subst, n * P * 400, np.int32).reshape(n, P, 20, 20) if want else None
-    finally:
-        L.so_phy_subst_free(C.byref(res))
+        return _arr(res.subst, n * P * 400, np.int32).reshape(n, P, 20, 20) if want else None
 
 
 def device_subst_counts(matrix, keep, device=0, stats=None):
@@ -840,28 +827,25 @@ def model_subst(sm, model, device_stage=False, device=0):
     return sm.subst
 
 
+def _walk_args(who, D):
+    """-> (D as contiguous float64[nb, T, T], nb, T, S = T - 3 splits, W words per split): what the two walk calls take"""
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.ndim != 3 or D.shape[1] != D.shape[2]:
+        raise ValueError('%s: D is float64[nb, T, T]' % who)
+    nb, T = D.shape[0], D.shape[1]
+    return D, nb, T, max(T - 3, 0), (T + 63) // 64
+
+
 def device_nj_splits(D, device=0, clades_in_global=False, stats=None):
     """nj_splits() of nb matrices D float64[nb, T, T] in one device call (so_phy_nj_splits), a workgroup per matrix -> uint64[nb, T - 3, W].
     The device reads D[k][i] for D[i][k]: a D that is not symmetric bit for bit is refused, as a non-finite one is.  clades_in_global
     (tests): the clade bit sets in global scratch, where the call keeps them once they outgrow the LDS.  stats: 'nj_tier', where they were
     kept (0: T < 4, no walk; 1: LDS; 2: global scratch)"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    D = np.ascontiguousarray(D, dtype=np.float64)
-    if D.ndim != 3 or D.shape[1] != D.shape[2]:
-        raise ValueError('device_nj_splits: D is float64[nb, T, T]')
-    nb, T = D.shape[0], D.shape[1]
-    res = _lib.SoPhyBootResult()
-    if L.so_phy_nj_splits(int(device), nb, T, C.c_void_p(D.ctypes.data), 1 if clades_in_global else 0, C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
+    D, nb, T, S, W = _walk_args('device_nj_splits', D)
+    with _call('so_phy_nj_splits', 'SoPhyBootResult', 'so_phy_boot_free', int(device), nb, T, D, 1 if clades_in_global else 0) as res:
         if stats is not None:
             stats['nj_tier'] = int(res.nj_tier)
-        S, W = max(T - 3, 0), (T + 63) // 64
-        return _lib.result_array(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
-    finally:
-        L.so_phy_boot_free(C.byref(res))
+        return _arr(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
 
 
 def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, stats=None, timed=False):
@@ -870,41 +854,30 @@ def device_boot(matrix, keep, seed, B, ref_splits, want_splits=False, device=0, 
     None); a dropped replicate's splits are zeros.  stats: 'waits', 'batches'; a stats that comes with the key 'nj_tier' gets it filled
     (device_nj_splits: where the walk kept its bit sets; the callers that compare or print the whole dict see no new key); timed: also
     'counts_ms', 'trees_ms', 'support_ms', the device time of the stages by events"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
-    if matrix.ndim != 2:
-        raise ValueError('device_boot: the matrix has two dimensions')
-    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    matrix, keep = _lib.matrix2d('device_boot', matrix), np.ascontiguousarray(keep, dtype=np.int64)
     T, nc = matrix.shape
     S, W = max(T - 3, 0), (T + 63) // 64
     ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
     if ref.size != S * W:
         raise ValueError('device_boot: the printed tree has %d splits of %d words' % (S, W))
-    res = _lib.SoPhyBootResult()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    if L.so_phy_boot(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), C.c_uint64(int(seed) & _M64), int(B), ptr(ref), (1 if want_splits else 0) | (2 if timed else 0),
-                     C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
+    with _call('so_phy_boot', 'SoPhyBootResult', 'so_phy_boot_free', int(device), T, nc, matrix, len(keep), keep, int(seed) & _M64, int(B), ref,
+               (1 if want_splits else 0) | (2 if timed else 0)) as res:
         if stats is not None:
             stats['waits'], stats['batches'] = int(res.waits), int(res.batches)
             if 'nj_tier' in stats:
                 stats['nj_tier'] = int(res.nj_tier)
             if timed:
                 stats['counts_ms'], stats['trees_ms'], stats['support_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.support_ms)
-        splits = _lib.result_array(res.splits, B * S * W, np.uint64).reshape(B, S, W) if want_splits else None
-        return _lib.result_array(res.count, S, np.int32), int(res.valid), _lib.result_array(res.ok, B, np.uint8).astype(bool), splits
-    finally:
-        L.so_phy_boot_free(C.byref(res))
+        splits = _arr(res.splits, B * S * W, np.uint64).reshape(B, S, W) if want_splits else None
+        return _arr(res.count, S, np.int32), int(res.valid), _arr(res.ok, B, np.uint8).astype(bool), splits
 
 
 def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0, stats=None, want_splits=True):
     """-> (count int32[T - 3], valid, ok bool[B], splits uint64[B, T - 3, W] or None): everything bootstrap() is made from.  Host: the
     numpy definitions replicate by replicate.  device_stage, model p: so_phy_boot; poisson: the counts of a batch by so_phy_boot_counts,
     the distances on the host (the device's log is not numpy's), the trees by so_phy_nj_splits, the support by split_support; kimura
-    goes poisson's way, logdet too, with the tensors of the batch by so_phy_subst and the determinants on the host."""
+    goes poisson's way, logdet too, with the tensors of the batch by so_phy_subst and the determinants on the host.  Either way the
+    replicates go through replicate_trees, the host's one at a time."""
     B, seed = int(B), int(seed)
     if not 1 <= B < 2 ** 31:
         raise ValueError('bootstrap: B lies in 1 .. 2^31 - 1')
@@ -916,37 +889,29 @@ def bootstrap_replicates(sm, B, seed=1, model='p', device_stage=False, device=0,
     ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa, model_subst(sm, model, device_stage, device))) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
     if len(sm.keep) == 0:
         raise ValueError('bootstrap: no kept column to draw from')
-    if device_stage and model == 'p':
-        try:
+    try:
+        if device_stage and model == 'p':
             return device_boot(sm.matrix, sm.keep, seed, B, ref, want_splits, device, stats)
-        except RuntimeError as e:
-            raise ValueError('bootstrap: %s' % e)
-    ok, splits = np.zeros(B, dtype=bool), np.zeros((B, S, W), dtype=np.uint64)
-    if device_stage:
-        Kp = (len(sm.keep) + 15) & ~15
-        step = _boot_batch(B, T * Kp + 16 * T * T + (2 * T * Kp + 800 * T * (T - 1) if logdet else 0))   # (logdet: codes and the tensor, 1600 bytes a pair)
-        calls = 0
-        for b0 in range(0, B, step):
-            nb = min(step, B - b0)
-            try:
+        if device_stage:
+            Kp = (len(sm.keep) + 15) & ~15
+            step = batch_size(B, T * Kp + 16 * T * T + (2 * T * Kp + 800 * T * (T - 1) if logdet else 0), 'SOHIT_PHY_BOOT_BATCH')   # (logdet: codes and the tensor, 1600 bytes a pair)
+
+            def counts_of(b0, nb):
                 cmp_, same = device_boot_counts(sm.matrix, sm.keep, seed, b0, nb, device)
-                sub = device_boot_subst(sm.matrix, sm.keep, seed, b0, nb, device) if logdet else [None] * nb
-                dist = [boot_distances(cmp_[k], same[k], model, sub[k]) for k in range(nb)]
-                good = [k for k in range(nb) if dist[k][1]]
-                calls += 2 if logdet else 1
-                if good and S:
-                    splits[[b0 + k for k in good]] = device_nj_splits(np.stack([dist[k][0] for k in good]), device)
-                    calls += 1
-            except RuntimeError as e:
-                raise ValueError('bootstrap: %s' % e)
-            ok[[b0 + k for k in good]] = True
-        if stats is not None:
-            stats['calls'] = calls
-    else:
-        for b in range(B):
-            D, ok[b] = boot_distances(*boot_counts(sm.matrix, sm.keep, seed, b), model=model, subst=boot_subst(sm.matrix, sm.keep, seed, b) if logdet else None)
-            if ok[b]:
-                splits[b] = nj_splits(D)
+                return (cmp_, same, device_boot_subst(sm.matrix, sm.keep, seed, b0, nb, device) if logdet else [None] * nb), 2 if logdet else 1
+            trees_of = lambda D, idx: device_nj_splits(D, device)
+        else:
+            step = 1
+
+            def counts_of(b, _):
+                cmp_, same = boot_counts(sm.matrix, sm.keep, seed, b)
+                return ([cmp_], [same], [boot_subst(sm.matrix, sm.keep, seed, b) if logdet else None]), 0
+            trees_of = lambda D, idx: nj_splits(D[0])[None]
+        ok, splits, calls = replicate_trees(B, step, counts_of, lambda c, k: boot_distances(c[0][k], c[1][k], model, c[2][k]), trees_of, S, W)
+    except RuntimeError as e:
+        raise ValueError('bootstrap: %s' % e)
+    if stats is not None and device_stage:
+        stats['calls'] = calls
     return split_support(ref, splits, ok), int(ok.sum()), ok, splits if want_splits else None
 
 
@@ -1079,25 +1044,8 @@ def concordance(ref_splits, present, gene_splits, ok):
     return dec, con
 
 
-def _gene_result(res, L, free, F, S, W, want_splits, stats, timed):
-    from . import _lib
-    try:
-        if stats is not None:
-            stats['waits'], stats['batches'], stats['nj_tier'] = int(res.waits), int(res.batches), int(res.nj_tier)
-            if timed:
-                stats['counts_ms'], stats['trees_ms'], stats['concord_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.concord_ms)
-        arr = _lib.result_array
-        return (arr(res.decisive, S, np.int32), arr(res.concordant, S, np.int32), arr(res.ok, F, np.uint8).astype(bool), arr(res.n_present, F, np.int32),
-                arr(res.present, F * W, np.uint64).reshape(F, W) if want_splits else None, arr(res.splits, F * S * W, np.uint64).reshape(F, S, W) if want_splits else None)
-    finally:
-        free(res)
-
-
 def _gene_args(who, matrix, keep, fam_off):
-    matrix = np.ascontiguousarray(matrix, dtype=np.uint8)
-    if matrix.ndim != 2:
-        raise ValueError('%s: the matrix has two dimensions' % who)
-    return matrix, np.ascontiguousarray(keep, dtype=np.int64), np.ascontiguousarray(fam_off, dtype=np.int64)
+    return _lib.matrix2d(who, matrix), np.ascontiguousarray(keep, dtype=np.int64), np.ascontiguousarray(fam_off, dtype=np.int64)
 
 
 def device_gene(matrix, keep, fam_off, ref_splits, want_splits=False, device=0, stats=None, timed=False):
@@ -1105,71 +1053,43 @@ def device_gene(matrix, keep, fam_off, ref_splits, want_splits=False, device=0, 
     trees over the present taxa and their comparison with ref_splits stay on the device, in batches of families with one host wait each
     -> (decisive int32[T - 3], concordant int32[T - 3], ok bool[F], n_present int32[F], present uint64[F, W] or None, splits
     uint64[F, T - 3, W] or None).  stats: 'waits', 'batches', 'nj_tier'; timed: also 'counts_ms', 'trees_ms', 'concord_ms' by events"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
     matrix, keep, fam_off = _gene_args('device_gene', matrix, keep, fam_off)
     T, nc = matrix.shape
     F, S, W = len(fam_off) - 1, max(T - 3, 0), (T + 63) // 64
     ref = np.ascontiguousarray(ref_splits, dtype=np.uint64)
     if ref.size != S * W:
         raise ValueError('device_gene: the printed tree has %d splits of %d words' % (S, W))
-    res = _lib.SoPhyGeneResult()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    if L.so_phy_gene(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), F, ptr(fam_off), ptr(ref), (1 if want_splits else 0) | (2 if timed else 0), C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    return _gene_result(res, L, lambda r: L.so_phy_gene_free(C.byref(r)), F, S, W, want_splits, stats, timed)
+    with _call('so_phy_gene', 'SoPhyGeneResult', 'so_phy_gene_free', int(device), T, nc, matrix, len(keep), keep, F, fam_off, ref,
+               (1 if want_splits else 0) | (2 if timed else 0)) as res:
+        if stats is not None:
+            stats['waits'], stats['batches'], stats['nj_tier'] = int(res.waits), int(res.batches), int(res.nj_tier)
+            if timed:
+                stats['counts_ms'], stats['trees_ms'], stats['concord_ms'] = float(res.counts_ms), float(res.trees_ms), float(res.concord_ms)
+        return (_arr(res.decisive, S, np.int32), _arr(res.concordant, S, np.int32), _arr(res.ok, F, np.uint8).astype(bool), _arr(res.n_present, F, np.int32),
+                _arr(res.present, F * W, np.uint64).reshape(F, W) if want_splits else None, _arr(res.splits, F * S * W, np.uint64).reshape(F, S, W) if want_splits else None)
 
 
 def device_gene_counts(matrix, keep, fam_off, f0=0, nf=None, device=0):
     """family_counts() of the families f0 .. f0 + nf - 1 in one device call (so_phy_gene_counts) -> (cmp, same) int64[nf, T, T]"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
     matrix, keep, fam_off = _gene_args('device_gene_counts', matrix, keep, fam_off)
     T, nc = matrix.shape
     nf = len(fam_off) - 1 - int(f0) if nf is None else int(nf)
-    res = _lib.SoPhyGeneResult()
-    ptr = lambda a: C.c_void_p(a.ctypes.data)
-    if L.so_phy_gene_counts(int(device), T, nc, ptr(matrix), len(keep), ptr(keep), len(fam_off) - 1, ptr(fam_off), int(f0), nf, 0, C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
-        return (_lib.result_array(res.cmp, nf * T * T, np.int64).reshape(nf, T, T), _lib.result_array(res.same, nf * T * T, np.int64).reshape(nf, T, T))
-    finally:
-        L.so_phy_gene_free(C.byref(res))
+    with _call('so_phy_gene_counts', 'SoPhyGeneResult', 'so_phy_gene_free', int(device), T, nc, matrix, len(keep), keep, len(fam_off) - 1, fam_off, int(f0), nf, 0) as res:
+        return _arr(res.cmp, nf * T * T, np.int64).reshape(nf, T, T), _arr(res.same, nf * T * T, np.int64).reshape(nf, T, T)
 
 
 def device_nj_subsets(D, present, device=0, clades_in_global=False, stats=None):
     """nj_splits_subset() of nb matrices D float64[nb, T, T], each with its own present words uint64[nb, W], in one device call
     (so_phy_nj_subsets) -> uint64[nb, T - 3, W].  Only present x present is read; there D is finite and symmetric bit for bit, or the
     call is refused.  clades_in_global, stats['nj_tier']: as device_nj_splits"""
-    import ctypes as C
-    from . import _lib
-    L = _lib.load()
-    D = np.ascontiguousarray(D, dtype=np.float64)
-    if D.ndim != 3 or D.shape[1] != D.shape[2]:
-        raise ValueError('device_nj_subsets: D is float64[nb, T, T]')
-    nb, T = D.shape[0], D.shape[1]
-    S, W = max(T - 3, 0), (T + 63) // 64
+    D, nb, T, S, W = _walk_args('device_nj_subsets', D)
     present = np.ascontiguousarray(present, dtype=np.uint64)
     if present.shape != (nb, W):
         raise ValueError('device_nj_subsets: present is uint64[nb, %d]' % W)
-    res = _lib.SoPhyGeneResult()
-    if L.so_phy_nj_subsets(int(device), nb, T, C.c_void_p(D.ctypes.data), C.c_void_p(present.ctypes.data), 1 if clades_in_global else 0, C.byref(res)) != 0:
-        raise RuntimeError(L.so_phy_last_error().decode())
-    try:
+    with _call('so_phy_nj_subsets', 'SoPhyGeneResult', 'so_phy_gene_free', int(device), nb, T, D, present, 1 if clades_in_global else 0) as res:
         if stats is not None:
             stats['nj_tier'] = int(res.nj_tier)
-        return _lib.result_array(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
-    finally:
-        L.so_phy_gene_free(C.byref(res))
-
-
-def _gene_batch(F, per_family_bytes):
-    """families per device call of the poisson and kimura paths: SOHIT_PHY_GENE_BATCH, else what about 2^30 bytes of counts hold"""
-    import os
-    forced = int(os.environ.get('SOHIT_PHY_GENE_BATCH', '0') or 0)
-    return max(1, min(F, 32768, forced if forced > 0 else (1 << 30) // max(1, per_family_bytes)))
+        return _arr(res.splits, nb * S * W, np.uint64).reshape(nb, S, W)
 
 
 def gene_concordance(sm, model='p', device_stage=False, device=0, stats=None, want_splits=False):
@@ -1179,7 +1099,7 @@ def gene_concordance(sm, model='p', device_stage=False, device=0, stats=None, wa
     trees with the splits of the printed tree (tree_splits).  A family in which two present taxa share no compared column, or a present
     pair has no distance under the model, is dropped.  Host: the numpy definitions family by family.  device_stage, model p: so_phy_gene;
     poisson and kimura: the counts of a batch of families by so_phy_gene_counts, the distances on the host (the device's log is not
-    numpy's), the trees by so_phy_nj_subsets, the comparison by concordance()."""
+    numpy's), the trees by so_phy_nj_subsets, the comparison by concordance().  Either way the families go through replicate_trees."""
     if model not in GENE_MODELS:
         raise ConcordanceRefused(_NO_GENE_MODEL)
     if sm.matrix is None:
@@ -1189,43 +1109,28 @@ def gene_concordance(sm, model='p', device_stage=False, device=0, stats=None, wa
     keep = np.asarray(sm.keep, dtype=np.int64)
     ref = tree_splits(distances(sm.cmp, sm.same, model, sm.taxa)) if T >= 2 else np.zeros((0, W), dtype=np.uint64)
     r = family_ranges(keep, sm.col_off)
-    if device_stage and model == 'p':
-        try:
+    present = np.zeros((F, W), dtype=np.uint64)
+
+    def counts_of(f0, nf):
+        if device_stage:
+            cmp_, same = device_gene_counts(sm.matrix, keep, r, f0, nf, device)
+        else:
+            cmp_, same = family_counts(sm.matrix, keep[r[f0]:r[f0 + nf]], sm.col_off[f0:f0 + nf + 1])
+        present[f0:f0 + nf] = family_present(cmp_)
+        return (cmp_, same, present[f0:f0 + nf]), 1 if device_stage else 0
+    try:
+        if device_stage and model == 'p':
             dec, con, ok, npres, _, splits = device_gene(sm.matrix, keep, r, ref, want_splits, device, stats)
-        except RuntimeError as e:
-            raise ValueError('gene concordance: %s' % e)
-        return dec, con, ok, npres, splits
-    ok, npres = np.zeros(F, dtype=bool), np.zeros(F, dtype=np.int32)
-    present, splits = np.zeros((F, W), dtype=np.uint64), np.zeros((F, S, W), dtype=np.uint64)
-    step = _gene_batch(F, 16 * T * T) if device_stage else 1
-    calls = 0
-    for f0 in range(0, F, step):
-        nf = min(step, F - f0)
-        try:
-            if device_stage:
-                cmp_, same = device_gene_counts(sm.matrix, keep, r, f0, nf, device)
-                calls += 1
-            else:
-                cmp_, same = family_counts(sm.matrix, keep[r[f0]:r[f0 + nf]], sm.col_off[f0:f0 + nf + 1])
-            present[f0:f0 + nf] = family_present(cmp_)
-            dist = [gene_distances(cmp_[k], same[k], present[f0 + k], model) for k in range(nf)]
-            good = [k for k in range(nf) if dist[k][1]]
-            if good and S:
-                at = [f0 + k for k in good]
-                if device_stage:
-                    splits[at] = device_nj_subsets(np.stack([dist[k][0] for k in good]), present[at], device)
-                    calls += 1
-                else:
-                    for k in good:
-                        splits[f0 + k] = nj_splits_subset(dist[k][0], present[f0 + k])
-        except RuntimeError as e:
-            raise ValueError('gene concordance: %s' % e)
-        ok[[f0 + k for k in good]] = True
-    npres[:] = _popcount(present)
+            return dec, con, ok, npres, splits
+        trees_of = (lambda D, idx: device_nj_subsets(D, present[idx], device)) if device_stage else (lambda D, idx: nj_splits_subset(D[0], present[idx[0]])[None])
+        ok, splits, calls = replicate_trees(F, batch_size(F, 16 * T * T, 'SOHIT_PHY_GENE_BATCH') if device_stage else 1, counts_of,
+                                            lambda c, k: gene_distances(c[0][k], c[1][k], c[2][k], model), trees_of, S, W)
+    except RuntimeError as e:
+        raise ValueError('gene concordance: %s' % e)
     if stats is not None and device_stage:
         stats['calls'] = calls
     dec, con = concordance(ref, present, splits, ok)
-    return dec, con, ok, npres, splits if want_splits else None
+    return dec, con, ok, _popcount(present).astype(np.int32), splits if want_splits else None
 
 
 def gcf_labels(decisive, concordant):

@@ -320,3 +320,72 @@ def test_script_refusals(tmp_path):
         r = run_script(tmp_path, flags)
         assert r.returncode == 2 and r.stdout == b"" and r.stderr.startswith(b"rbh2phy: -B"), (flags, r.stderr)
         assert not os.path.exists(tree)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# batch_size and replicate_trees: how many items a device call takes, and the one loop every replicate and family goes through
+# ---------------------------------------------------------------------------------------------------------
+def test_batch_size(phy, monkeypatch):
+    env = "SOHIT_PHY_BOOT_BATCH"
+    monkeypatch.delenv(env, raising=False)
+    assert phy.batch_size(5000, 1 << 20) == 1024 and phy.batch_size(5000, 1 << 20, env) == 1024      # what 2^30 bytes hold
+    assert phy.batch_size(5, 1 << 20) == 5 and phy.batch_size(0, 1 << 20) == 1                          # n below it; one at least
+    assert phy.batch_size(10 ** 6, 1) == 32768 and phy.batch_size(10 ** 6, 0) == 32768 and phy.batch_size(10, 0) == 10   # the cap; bytes_each = 0
+    monkeypatch.setenv(env, "7")
+    assert phy.batch_size(5000, 1 << 20, env) == 7 and phy.batch_size(5, 1 << 20, env) == 5 and phy.batch_size(5000, 0, env) == 7
+    assert phy.batch_size(5000, 1 << 20) == 1024 and phy.batch_size(5000, 1 << 20, "SOHIT_PHY_GENE_BATCH") == 1024      # (another switch, or none)
+    monkeypatch.setenv(env, "1000000")
+    assert phy.batch_size(10 ** 6, 1 << 20, env) == 32768
+    for off in ("0", "-3", ""):
+        monkeypatch.setenv(env, off)
+        assert phy.batch_size(5000, 1 << 20, env) == 1024
+
+
+def _trees(phy, T, n, step, drop=()):
+    """replicate_trees over n replicates of a T-taxon matrix with numpy callbacks; a replicate in `drop` has no distance ->
+    (ok, splits, calls, the calls counts_of reported, the idx of every walk call)"""
+    m = pin.gap_matrix(np.random.RandomState(11), T, 60, .1)
+    keep = np.arange(60)
+    made, walks = [], []
+
+    def counts_of(i0, k):
+        made.append(1 + i0 % 2)
+        return [(b,) + phy.boot_counts(m, keep, 4, b) for b in range(i0, i0 + k)], made[-1]
+
+    def distance_of(batch, j):
+        b, cmp_, same = batch[j]
+        D, ok = phy.boot_distances(cmp_, same, "p")
+        return D, ok and b not in drop
+
+    def trees_of(D, idx):
+        walks.append(list(idx))
+        return np.stack([phy.nj_splits(d) for d in D])
+    S, W = max(T - 3, 0), (T + 63) // 64
+    ok, splits, calls = phy.replicate_trees(n, step, counts_of, distance_of, trees_of, S, W)
+    assert ok.dtype == bool and ok.shape == (n,) and splits.dtype == np.uint64 and splits.shape == (n, S, W)
+    # the literal loop, item by item
+    for b in range(n):
+        D, good = phy.boot_distances(*phy.boot_counts(m, keep, 4, b), model="p")
+        good = good and b not in drop
+        assert bool(ok[b]) is good and (splits[b] == (phy.nj_splits(D) if good else 0)).all(), (T, n, step, b)
+    return ok, splits, calls, made, walks
+
+
+def test_replicate_trees_any_step_gives_the_literal_loop(phy):
+    first = None
+    for step in (1, 3, 7):
+        ok, splits, calls, made, walks = _trees(phy, 5, 7, step, drop=(2,))
+        assert ok.tolist() == [True, True, False, True, True, True, True] and splits[:2].any() and not splits[2].any()
+        assert len(made) == -(-7 // step) and len(walks) == len(made) - (step == 1) and calls == sum(made) + len(walks)   # (step 1: the dropped one is a batch)
+        assert sorted(sum(walks, [])) == [0, 1, 3, 4, 5, 6]
+        first = first or (ok, splits)
+        assert (ok == first[0]).all() and (splits == first[1]).all()
+
+
+def test_replicate_trees_walk_only_where_a_tree_is_due(phy):
+    ok, splits, calls, made, walks = _trees(phy, 5, 7, 3, drop=(3, 4, 5))          # the middle batch has no item left: no walk call, zeros
+    assert walks == [[0, 1, 2], [6]] and calls == sum(made) + 2 and not ok[3:6].any() and not splits[3:6].any() and ok[[0, 1, 2, 6]].all()
+    ok, splits, calls, made, walks = _trees(phy, 3, 7, 3)                           # three taxa: no split, no walk call at all
+    assert walks == [] and calls == sum(made) and ok.all() and splits.shape == (7, 0, 1)
+    ok, splits, calls, made, walks = _trees(phy, 5, 0, 3)                           # nothing to do
+    assert made == [] and walks == [] and calls == 0 and ok.shape == (0,)
