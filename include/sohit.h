@@ -837,6 +837,50 @@ int64_t so_format_pairs(const char *kind, int32_t kind_len, const char *names, c
                         const double *v, int64_t n, char *out, int64_t cap);
 int64_t so_py_repr(const double *v, int64_t n, char *out, int64_t cap);
 
+/* The shared device primitives, one at a time (csrc/prim.hip) -- for the tests: every stage stands on the scans and run helpers of
+ * csrc/k_util.hip and on the library sorts of csrc/k_sort.hip / k_sortseg.hip, and these calls run the wrappers the stages call
+ * (csrc/kernels.h) on host arrays.  All arrays are the caller's (borrowed inputs, outputs of the stated length); 0 = done, 1 = refused with
+ * a message (so_prim_last_error).  No so_ctx: each call reads the SOHIT_* switches itself (SOHIT_POISON).
+ *   so_prim_scan_path  no device: the way scan_u32 takes n values (0 nothing launched, 1 one launch, 2 three kernels), *tiles its tiles.
+ *   so_prim_sort_tier  no device: the library's algorithm for a device-wide sort (kind 0 .. 2 below) of n keys: 0 one block, 1 merge sort,
+ *                      2 onesweep; *single_block / *merge_limit: the largest n of tiers 0 and 1, from the library's configuration types.
+ *   so_prim_seg_variant  no device: the instance a segmented sort (kind 3 .. 6) runs for n keys in nseg segments of a field `width` bits
+ *                      wide: kinds 3, 4: 0 library default, 2, 6 the tuned ones; kind 5: 0, 1, 2; kind 6: 0.
+ *   so_prim_scan       out[n] = exclusive (inclusive != 0: inclusive) prefix sums mod 2^32 of in[n]; the device input / output start
+ *                      in_skew / out_skew words (0 .. 3) behind a 16-byte boundary; in_place: one device range for both (the skews are
+ *                      equal).  guards[8]: the four words in front of and the four behind the device output range, set to 0xA5C3F00D
+ *                      before the scan.  *total: the sum; *path, *tiles: as so_prim_scan_path.
+ *   so_prim_effscan    hoff[n], cidx[n] = exclusive prefixes of c(t) = mark[t] ? scnt[t] : 0 and of [c(t) != 0]; the device mark starts
+ *                      mark_skew BYTES behind a 16-byte boundary, scnt, hoff and cidx scnt_skew words; guards[16]: hoff's eight, cidx's
+ *                      eight; totals[2] = {sum of c mod 2^32, non-zero c}.
+ *   so_prim_runs       n >= 1 keys of key_bytes 4 (int) or 8 (u64): head[n], rid[n] (key_runs), *n_runs, start[n + 2] (run_starts; set to
+ *                      0xA5C3F00D before: start[r] for every run, start[*n_runs] = n, the sentinel behind).
+ *   so_prim_number     number_by_first_appearance of nr >= 1 rows (cx, cy) of codes 0 .. n_codes - 1: X[nr], Y[nr],
+ *                      gene_code[min(n_codes, 2 nr)] (-1 behind the *n_genes genes), first[n_codes], flag[2 nr].
+ *   so_prim_sort       kind 0 sort_keys_u64, 1 sort_pairs_u64_u32, 2 sort_pairs_u64_u64 (begin_bit = 0), 3 sort_keys_u64_seg,
+ *                      4 sort_keys_u64_seg2, 5 sort_cand_keys_seg, 6 sort_keys_u64_seg_desc on key bits [begin_bit, end_bit).  Segments:
+ *                      kind 4 seg_begin[nseg] and seg_end[nseg], the others seg_begin[nseg + 1] (seg_end unused); they rise and end within
+ *                      n.  kout[n] (every byte 0xD6 before the sort), vout[n] for the pairs.  The scratch is what the matching
+ *                      *_temp_bytes asks for, asked before any array is read.  info[4] = {variant (so_prim_seg_variant; -1 for kinds
+ *                      0 .. 2), tier (so_prim_sort_tier -- kind 0 with begin_bit > 0 and end_bit = 64 has no tier 1: 2; -1 for kinds 3 .. 6), scratch bytes, bytes changed among the 256 behind the scratch}.
+ *                      kind | 0x100, n >= 2^31: the sort itself is asked, without scratch or arrays, and must refuse as its
+ *                      *_temp_bytes does.
+ * Refused: counts out of range (n >= 2^31 by the sorts themselves), null arrays, skews outside 0 .. 3, codes outside 0 .. n_codes - 1,
+ * segments that fall, overlap or end behind n, end_bit = 64 for the segmented sorts (by the sorts themselves), no HIP device. */
+int32_t so_prim_scan_path(int64_t n, int64_t *tiles);
+int32_t so_prim_sort_tier(int32_t kind, int64_t n, int64_t *single_block, int64_t *merge_limit);
+int32_t so_prim_seg_variant(int32_t kind, int64_t n, int64_t nseg, int32_t width);
+int so_prim_scan(int device, int64_t n, const uint32_t *in, int32_t in_skew, int32_t out_skew, int32_t inclusive, int32_t in_place, uint32_t *out,
+                 uint32_t *guards, uint32_t *total, int32_t *path, int64_t *tiles);
+int so_prim_effscan(int device, int64_t n, const uint8_t *mark, int32_t mark_skew, const uint32_t *scnt, int32_t scnt_skew, uint32_t *hoff,
+                    uint32_t *cidx, uint32_t *guards, uint32_t *totals, int64_t *tiles);
+int so_prim_runs(int device, int64_t n, int32_t key_bytes, const void *key, uint32_t *head, uint32_t *rid, uint32_t *start, int64_t *n_runs);
+int so_prim_number(int device, int64_t nr, int64_t n_codes, const int32_t *cx, const int32_t *cy, int32_t *X, int32_t *Y, int32_t *gene_code,
+                   uint32_t *first, uint32_t *flag, int64_t *n_genes);
+int so_prim_sort(int device, int32_t kind, int64_t n, const uint64_t *kin, const void *vin, int64_t nseg, const uint32_t *seg_begin,
+                 const uint32_t *seg_end, int32_t begin_bit, int32_t end_bit, uint64_t *kout, void *vout, int64_t *info);
+const char *so_prim_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

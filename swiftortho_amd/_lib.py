@@ -60,7 +60,9 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error", "so_pan_shared", "so_pan_shared_free",
            "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
            "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free",
-           "so_phy_gene", "so_phy_gene_counts", "so_phy_nj_subsets", "so_phy_gene_free"]
+           "so_phy_gene", "so_phy_gene_counts", "so_phy_nj_subsets", "so_phy_gene_free",
+           "so_prim_scan_path", "so_prim_sort_tier", "so_prim_seg_variant", "so_prim_scan", "so_prim_effscan", "so_prim_runs", "so_prim_number", "so_prim_sort",
+           "so_prim_last_error"]
 
 
 class SoMclResult(C.Structure):
@@ -351,6 +353,19 @@ def load():
     L.so_phy_gene_counts.argtypes = [C.c_int, i64, i64, vp, i64, vp, i64, vp, i64, i64, C.c_int32, C.POINTER(SoPhyGeneResult)]
     L.so_phy_nj_subsets.argtypes = [C.c_int, i64, i64, vp, vp, C.c_int32, C.POINTER(SoPhyGeneResult)]
     L.so_phy_gene_free.argtypes = [C.POINTER(SoPhyGeneResult)]
+    i32 = C.c_int32
+    L.so_prim_scan_path.restype = i32
+    L.so_prim_scan_path.argtypes = [i64, vp]
+    L.so_prim_sort_tier.restype = i32
+    L.so_prim_sort_tier.argtypes = [i32, i64, vp, vp]
+    L.so_prim_seg_variant.restype = i32
+    L.so_prim_seg_variant.argtypes = [i32, i64, i64, i32]
+    L.so_prim_scan.argtypes = [C.c_int, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.so_prim_effscan.argtypes = [C.c_int, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.so_prim_runs.argtypes = [C.c_int, i64, i32, vp, vp, vp, vp, vp]
+    L.so_prim_number.argtypes = [C.c_int, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.so_prim_sort.argtypes = [C.c_int, i32, i64, vp, vp, i64, vp, vp, i32, i32, vp, vp, vp]
+    L.so_prim_last_error.restype = cp
     L.so_set_option.argtypes = [vp, cp, cp]
     if L.so_abi_version() != 3:
         raise ImportError("libsohit.so ABI version mismatch")

@@ -289,15 +289,23 @@ __global__ __launch_bounds__(SS_THREADS) void k_scan_small(const u32* __restrict
 
 size_t scan_u32_temp_elems(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE + 2; }
 
+// which way scan_u32 takes n values: 0 nothing to launch, 1 the single launch (k_scan_small), 2 the three kernels; *tiles = tiles of SCAN_TILE values
+int scan_u32_path(size_t n, size_t* tiles) {
+    const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (tiles) *tiles = nb;
+    return nb == 0 ? 0 : nb <= SCAN_SMALL_TILES ? 1 : 2;
+}
+
 // out[i] = sum(in[0..i)) (exclusive) or sum(in[0..i]) (inclusive); in may alias out; 4-byte alignment suffices.
 // temp needs scan_u32_temp_elems(n) u32; temp[nblocks] receives the grand total (device side).
 const u32* scan_u32(const u32* in, u32* out, size_t n, bool inclusive, u32* temp, hipStream_t st) {
-    size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (nb == 0) {
+    size_t nb;
+    const int path = scan_u32_path(n, &nb);
+    if (path == 0) {
         HIP_CHECK(hipMemsetAsync(temp, 0, sizeof(u32), st));
         return temp;
     }
-    if (nb <= SCAN_SMALL_TILES) {
+    if (path == 1) {
         hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(SS_THREADS), 0, st, in, out, n, temp + nb, inclusive ? 1 : 0);
         return temp + nb;
     }

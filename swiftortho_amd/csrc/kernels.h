@@ -9,6 +9,7 @@ size_t scan_u32_temp_elems(size_t n);
 size_t effscan_temp_elems(size_t n);
 const u32* effscan(const u8* mark, const u32* scnt, size_t n, u32* hoff, u32* cidx, u32* temp, hipStream_t st);
 const u32* scan_u32(const u32* in, u32* out, size_t n, bool inclusive, u32* temp, hipStream_t st);  // returns device ptr to total
+int scan_u32_path(size_t n, size_t* tiles);   // the way scan_u32 takes n values: 0 no launch, 1 one launch, 2 three kernels; *tiles (nullable) = its tiles (effscan's too)
 void fill_u32(u32* p, size_t n, u32 v, hipStream_t st);
 // genes numbered by first appearance in cx0, cy0, cx1, ...; everything queued on st, no host wait.
 // first: n_codes words, flag/rank: 2*nr words, scan_tmp: scan_u32_temp_elems(2*nr), gene_code: min(n_codes, 2*nr) words.
@@ -26,11 +27,20 @@ template <class K>
 const u32* key_runs(const K* key, u32 n, u32* head, u32* rid, u32* scan_tmp, hipStream_t st);
 void run_starts(const u32* head, const u32* rid, u32 n, const u32* d_nruns, u32* start, hipStream_t st);
 
-// k_sort.hip
+// k_sort.hip (every sort and every *_temp_bytes refuses n above 2^31 - 1)
+// the library's algorithm for n keys with values of value_bytes (0: keys only): 0 one block, 1 merge sort, 2 onesweep; the two sizes at
+// which it changes (nullable), read from the library's configuration types
+int sort_u64_tier(size_t n, int value_bytes, size_t* single_block, size_t* merge_limit);
+bool sort_keys_skips_merge(int begin_bit, int end_bit);   // sort_keys_u64 on such a field goes from tier 0 straight to tier 2 (k_sort.hip)
 size_t sort_keys_u64_temp_bytes(size_t n, int bits);
 void sort_keys_u64(void* temp, size_t temp_bytes, const u64* in, u64* out, size_t n, int begin_bit, int end_bit, hipStream_t st);
 // seg[q] = first hit ordinal of batch query q in the pass, q in [qa, qb] (seg[qb] = H)
 void launch_query_segments(const u32* hoff, const u32* qoff, u32 qa, u32 qb, int AS, u32 H, u32* seg, hipStream_t st);
+// the instance a segmented sort of n keys in nseg segments runs: seg_variant (sort_keys_u64_seg, _seg2; width = end_bit - begin_bit):
+// 0 library default, 2 8-bit digits 256 x 16, 6 9-bit digits 512 x 8; cand_keys_cfg (sort_cand_keys_seg): 0 default, 1 256 x 16, 2 512 x 16
+int seg_variant(size_t n, u32 nseg, int width);
+int cand_keys_cfg(size_t n, u32 nseg);
+// (all four segmented sorts: end_bit must stay below 64, see k_sortseg.hip)
 size_t sort_keys_u64_seg_temp_bytes(size_t n, u32 nseg, int begin_bit, int end_bit);
 void sort_keys_u64_seg(void* temp, size_t temp_bytes, const u64* in, u64* out, size_t n, u32 nseg, const u32* seg, int begin_bit,
                        int end_bit, hipStream_t st);
