@@ -596,6 +596,37 @@ int so_pan_shared(int device, int64_t m, const int32_t *row, const int32_t *taxo
                   int64_t n_reps, int32_t flags, so_pan_shared_result *out);
 void so_pan_shared_free(so_pan_shared_result *result);
 
+/* Phyletic profiles on the device (csrc/phyletic.hip): the pairs of gene FAMILIES that co-occur across the genomes -- the product the other
+ * way round, P P^T over the rows of the presence matrix (phylogenetic profiling, Pellegrini et al. 1999) -- as swiftortho_amd/phyletic.py
+ * `linked_pairs()` defines them, integer for integer.  The reference has no such product; the numpy function is the definition.
+ * Input as for so_pan_genome: m members as pairs (row[k], taxon[k]) (a pair listed twice counts once), n_rows rows of which the first
+ * n_file_rows are lines of the groups file, n_taxa taxa.  present[r] = the distinct taxa of row r.  A row is ELIGIBLE iff r < n_file_rows and
+ * n_min <= present[r] <= n_max.  Two eligible rows a < b that share k taxa, u = present[a] + present[b] - k, are LINKED iff k >= k_min and
+ * k * den >= num * u: num / den is the Jaccard threshold, equality passes, no float takes part.
+ * flags bit 0: no pair arrays in the result (measurements); bit 1: events around the passes -- count_ms, emit_ms, sort_ms.
+ * Output (allocated by the library, released with so_phyletic_free()): present[n_rows]; the n_pairs linked pairs as a[], b[] (the rows' own
+ * numbers) and shared[] (k), ordered by (a, b), the same arrays from call to call; n_eligible; tiles: the pairs I <= J of tiles of 64
+ * eligible rows that were multiplied; waits: host waits of the call -- two, the count that sizes the output and the result (one when no
+ * pair is linked, none for n_rows = 0).  The product is never stored: every tile is thresholded where it is computed, once to count and
+ * once to emit.  n_rows = 0, fewer than two eligible rows (n_max < n_min included) and no linked pair are served.
+ * Refused with a message (so_phyletic_last_error) and nothing left allocated: a row or taxon out of range, n_taxa below 1 or above 4096,
+ * n_rows or m >= 2^31, n_file_rows outside 0 .. n_rows, n_min < 1, k_min < 1, num < 1, num > den, den >= 2^20, more than 64 * 65535 eligible
+ * rows, 2^31 linked pairs and more, pairs that with their sort scratch do not fit half of the free device memory (the message says how
+ * many bytes they would take), unknown flag bits, no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON). */
+typedef struct so_phyletic_result {
+    int64_t n_rows, n_eligible, n_pairs, tiles;
+    int32_t waits;
+    int32_t reserved;
+    double count_ms, emit_ms, sort_ms;   /* flags bit 1: device time of the count pass, the emit pass and the sort */
+    int32_t *present;                    /* n_rows */
+    int32_t *a, *b, *shared;             /* n_pairs, or empty (flags bit 0) */
+} so_phyletic_result;
+int so_phyletic_pairs(int device, int64_t m, const int32_t *row, const int32_t *taxon, int64_t n_rows, int64_t n_file_rows, int64_t n_taxa,
+                      int32_t n_min, int32_t n_max, int32_t k_min, int32_t num, int32_t den, int32_t flags, so_phyletic_result *out);
+void so_phyletic_free(so_phyletic_result *result);
+const char *so_phyletic_last_error(void);
+
 /* The operon pairs of the operon-clustering step on the device (csrc/operon.hip).  Replaces: the pair loop of scripts/operon_cluster.py
  * `operon_clust()` (136-168) -- for every operon the operons listed under the families of its genes, and per such pair the size of the
  * intersection of the two family sets -- as swiftortho_amd/operon.py `candidate_pairs()` restates it, count for count.  All of it is

@@ -19,6 +19,13 @@ bare tree) labels the tree's nodes with their bootstrap support over n replicate
 -- what the reference gets from `fasttree -boot`; with `-G T` the replicates run on the GPU.  `-K T` labels the nodes with their gene
 concordance factors (the share of the core families able to decide a branch whose own tree holds it; `boot/gcf` with `-B`) and writes
 the table of them to <name>.gcf.tsv.
+The phyletic-profile step has no counterpart in the reference and runs on request: `-L T` (default `F`; it needs nothing but the .clsr file)
+runs scripts/phyletic_links.py on it with the wrapper's -l and -u and with `-j` (Jaccard threshold, default 0.8) and `-k` (shared genomes at
+least, default 2) and leaves <name>.links.tsv, the pairs of gene families that co-occur across the genomes, and <name>.links.xyz; the
+modules of such families, <name>.links.clsr, come from `bin/find_cluster.py -i` that .xyz file with the wrapper's -A, -I and -G, as in the
+operon step.  With `-G T` the family pairs are found on the GPU.
+`-l` and `-u` are read by this step alone: the `-P` step runs scripts/pan_genome.py at that script's own defaults (.05, .95), as it always has, so
+with other values the families that take part here are not the rows <name>.pan types Share; at the defaults they are.
 
 Clustering step, as the reference has it (139-193): the gene ids of the .opc file are recoded to decimal numbers by first appearance
 (<name>.xyz, three columns), THAT file is clustered, and the numbers are mapped back into <name>.clsr (the .grp file in between is
@@ -43,7 +50,8 @@ from swiftortho_amd import nr  # noqa: E402
 from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
-        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1', '-K': 'F'}
+        '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1', '-K': 'F',
+        '-L': 'F', '-j': '0.8', '-k': '2'}
 
 
 def main(argv):
@@ -52,7 +60,7 @@ def main(argv):
         sys.stderr.write('run_all_fast: -B takes a whole number of replicates from 0 to 2^31 - 1, -S a seed from 0 to 2^64 - 1\n')
         return 2
     if a['-i'] == '':
-        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon]' % argv[0])
+        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon] [-L T [-l .05] [-u .95] [-j 0.8] [-k 2]]' % argv[0])
         raise SystemExit()
     fas, name = a['-i'], a['-i'].split(os.sep)[-1]
     t = time()
@@ -126,6 +134,16 @@ def main(argv):
             with open('%s_results/%s.gcf.tsv' % (fas, name), 'wb') as o:
                 o.write(phy.gcf_table(sm.taxa, st['gcf']['splits'], st['gcf']['decisive'], st['gcf']['concordant']))
         print('species tree time:', time() - t)
+    if a['-L'].upper()[:1] == 'T':
+        # phyletic profiles: the pairs of families that co-occur across the genomes, then their modules by the same clustering as above
+        t = time()
+        links = '%s_results/%s.links' % (fas, name)
+        with open(links + '.tsv', 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'phyletic_links.py'), '-i', fas, '-g', clsr, '-l', a['-l'], '-u', a['-u'], '-j', a['-j'],
+                            '-k', a['-k'], '-x', links + '.xyz', '-G', a['-G']], stdout=o, check=True)
+        with open(links + '.clsr', 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_cluster.py'), '-i', links + '.xyz', '-a', a['-A'], '-I', a['-I'], '-G', a['-G']], stdout=o, check=True)
+        print('phyletic profile time:', time() - t)
     if os.path.isfile(a['-p']):
         # operon clustering (run_all_fast.py:241-255): scored operon pairs from the gene families, then the same clustering as above
         t = time()

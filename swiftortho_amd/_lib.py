@@ -58,6 +58,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_orth_relations_cols", "so_orth_relations_records", "so_orth_rel_free", "so_mcl_rows", "so_mcl_readout", "so_mcl_rows_free",
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error", "so_pan_shared", "so_pan_shared_free",
+           "so_phyletic_pairs", "so_phyletic_free", "so_phyletic_last_error",
            "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
            "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free",
            "so_phy_gene", "so_phy_gene_counts", "so_phy_nj_subsets", "so_phy_gene_free",
@@ -127,6 +128,12 @@ class SoPanSharedResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_reps", "bytes")] + \
                [("waits", C.c_int32), ("batches", C.c_int32), ("ranges", C.c_int32), ("reserved", C.c_int32), ("draw_ms", C.c_double), ("product_ms", C.c_double),
                 ("shared", C.POINTER(C.c_int32))]
+
+
+class SoPhyleticResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_rows", "n_eligible", "n_pairs", "tiles")] + \
+               [("waits", C.c_int32), ("reserved", C.c_int32), ("count_ms", C.c_double), ("emit_ms", C.c_double), ("sort_ms", C.c_double),
+                ("present", C.POINTER(C.c_int32)), ("a", C.POINTER(C.c_int32)), ("b", C.POINTER(C.c_int32)), ("shared", C.POINTER(C.c_int32))]
 
 
 class SoOperonResult(C.Structure):
@@ -336,6 +343,9 @@ def load():
     L.so_pan_last_error.restype = cp
     L.so_pan_shared.argtypes = [C.c_int, i64, vp, vp, i64, i64, C.c_uint64, i64, i64, C.c_int32, C.POINTER(SoPanSharedResult)]
     L.so_pan_shared_free.argtypes = [C.POINTER(SoPanSharedResult)]
+    L.so_phyletic_pairs.argtypes = [C.c_int, i64, vp, vp, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SoPhyleticResult)]
+    L.so_phyletic_free.argtypes = [C.POINTER(SoPhyleticResult)]
+    L.so_phyletic_last_error.restype = cp
     L.so_operon_pairs.argtypes = [C.c_int, i64, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(SoOperonResult)]
     L.so_operon_free.argtypes = [C.POINTER(SoOperonResult)]
     L.so_operon_last_error.restype = cp

@@ -30,7 +30,7 @@
 // and transposes the 64 x 64 bits with 64 ballots into the replicate's tile-major words.  Replicates run along the grid, in batches whose
 // words fit half of the free device memory (SOHIT_PAN_BOOT_BATCH forces the size); SOHIT_PAN_SHARED_RANGES forces the number of ranges.
 // Integers only, one host wait per call whatever the number of batches.
-#include "tree_stage.h"
+#include "pan_bits.h"
 #include "../../include/sohit.h"
 
 #include <cstring>
@@ -46,20 +46,7 @@ enum { PAN_TIER_NONE = 0, PAN_TIER_LDS = 1, PAN_TIER_GLOBAL = 2 };
 // LDS bytes of k_pan_curve<true> for T taxa: words, 4 orders, (S, C) per step, 4 x 3 counters per step
 size_t pan_lds_bytes(u64 T) { return (size_t)(T * 8u + 4u * T * 4u + T * 8u + 12u * (T > 0 ? T - 1 : 0) * 4u); }
 
-// err |= 1: a row outside 0 .. n_rows - 1; err |= 2: a taxon outside 0 .. T - 1 (nothing is written for such a pair)
-__device__ __forceinline__ bool pan_pair(u32 i, const int* __restrict__ row, const int* __restrict__ tax, u32 n_rows, u32 T, u32& r, u32& t, u32* __restrict__ err) {
-    r = (u32)row[i], t = (u32)tax[i];
-    if (r >= n_rows) {
-        atomicOr(err, 1u);
-        return false;
-    }
-    if (t >= T) {
-        atomicOr(err, 2u);
-        return false;
-    }
-    return true;
-}
-
+// (pan_pair, the check of a member pair, and k_pan_rowbits, the row-major presence words of the draws: pan_bits.h)
 __global__ __launch_bounds__(256) void k_pan_count(u32 m, const int* __restrict__ row, const int* __restrict__ tax, u32 n_rows, u32 T, int* __restrict__ counts,
                                                    u32* __restrict__ err) {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
@@ -162,14 +149,6 @@ __global__ __launch_bounds__(256) void k_pan_curve(const ull* __restrict__ bits,
 }
 
 // ---- so_pan_shared: the families every pair of genomes shares, S = P^T P of the presence matrix, for the table or for bootstrap replicates ----
-// the row-major twin of k_pan_bits: bit t & 63 of rowbits[r * TW + (t >> 6)] is the presence of taxon t in row r (TW = ceil(T / 64))
-__global__ __launch_bounds__(256) void k_pan_rowbits(u32 m, const int* __restrict__ row, const int* __restrict__ tax, u32 n_rows, u32 T, u32 TW, ull* __restrict__ rowbits,
-                                                     u32* __restrict__ err) {
-    const u32 i = blockIdx.x * 256u + threadIdx.x;
-    u32 r, t;
-    if (i < m && pan_pair(i, row, tax, n_rows, T, r, t, err)) atomicOr(rowbits + (size_t)r * TW + (t >> 6), 1ull << (t & 63u));
-}
-
 // grid (groups of 4 draw tiles, groups of PAN_DRAW_BLOCKS blocks of 64 taxa, replicates); a wave per tile of 64 draws, a draw per lane.
 // Lane k reads the row-major word of its drawn row for a block of 64 taxa; ballot j is then bit j of all 64 lanes -- the tile-major word
 // of taxon 64 tb + j over the 64 drawn rows, which lane j keeps and stores: words[z][w * T + t] as k_pan_bits writes them.  A lane behind

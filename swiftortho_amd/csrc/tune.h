@@ -104,6 +104,9 @@ static inline int orth_tier_of(const char* v) {
 // k_pan_draw walks PAN_DRAW_BLOCKS blocks of 64 taxa per wave: the 64 bytes of a drawn row's words that share a cache line
 #define PAN_SH_TILE 64u
 #define PAN_SH_CHUNK 32u
+// ... and the family pairs the other way round (phyletic.hip, k_pp_tile): the same tile over 64 x 64 eligible families, whose K dimension is
+// the taxon words (at most 64): a chunk of 16 words of both sides is 16 KiB of LDS, so it is the registers, not the LDS, that say how many workgroups a CU holds
+#define PP_CHUNK 16u
 #define PAN_SH_TARGET_WGS 1024u
 #define PAN_DRAW_BLOCKS 8u
 #define PAN_MAX_TAXA 4096

@@ -257,6 +257,27 @@ def pan_genome_from_search(fasta_path, ts=.05, tc=.95, taxa=None, pan_device=Tru
     return list(taxa), res.types, res.totals, (res.core, res.spec, res.panz), t
 
 
+def family_links_from_search(fasta_path, jaccard='0.8', k_min=2, ts=.05, tc=.95, pan_device=True, **groups_from_search_kw):
+    """one process from a FASTA file to the phyletic profiles of its ortholog groups: groups_from_search(fasta_path,
+    **groups_from_search_kw), then phyletic.family_links on those groups -- what `scripts/phyletic_links.py -i x.fsa -g x.clsr -l ts -u tc
+    -j jaccard -k k_min` computes on the groups file of the same search, with no groups text in between.  pan_device: the family pairs
+    in one device call (phyletic.device_linked_pairs, so_phyletic_pairs), else by the numpy definition.
+    -> (taxa in sorted order, phyletic.Links -- the linked pairs of group rows by (a, b), the genomes they share, the genomes of every row --,
+    the dict of groups_from_search with pan_host (ids and taxa coded on the host) and links (the stage) added, in seconds)"""
+    from . import pan, phyletic
+    groups, t = groups_from_search(fasta_path, **groups_from_search_kw)
+    t0 = time.time()
+    with open(fasta_path, 'r') as f:
+        text = f.read()
+    taxa = sorted(pan.taxa_of_fasta(text))
+    table = pan.member_table_of(groups, pan.fasta_ids(text), taxa)
+    t['pan_host'] = time.time() - t0
+    t0 = time.time()
+    links = phyletic.family_links(table, taxa, ts, tc, jaccard, k_min, device_stage=pan_device, device=groups_from_search_kw.get('device', 0))
+    t['links'] = time.time() - t0
+    return taxa, links, t
+
+
 def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', boot=0, boot_seed=1, concordance=False, **search_kw):
     """one process from a FASTA file to the species tree of its taxa: self-search on the GPU with a CIGAR on every row, the core-gene
     table of `reference` (default: the taxon with most genes), the core-gene supermatrix from the rows' own alignments (swiftortho_amd.phy:
