@@ -627,6 +627,49 @@ int so_phyletic_pairs(int device, int64_t m, const int32_t *row, const int32_t *
 void so_phyletic_free(so_phyletic_result *result);
 const char *so_phyletic_last_error(void);
 
+/* Gene-fusion links on the device (csrc/fusion.hip): the pairs of proteins that align side by side on one composite protein and are not
+ * homologous to each other (the "Rosetta stone" method, Marcotte et al. 1999, Enright et al. 1999) -- as swiftortho_amd/fusion.py
+ * `fusion_links()` defines them, integer for integer.  The reference has no such script; the numpy function is the definition.
+ * Input: n hit rows in file order -- name codes q / s in 0 .. n_names - 1 and the int32 columns qst, qed, sst, sed (1-based, inclusive, as
+ * printed), slen and qlen (host arrays, borrowed; qlen is only copied into `link`), or so_hit records in DEVICE memory with the host maps
+ * query ordinal -> code (qmap, n_q) and subject ordinal -> code (smap, n_s).  tax[n_names]: taxon code of every name, in 0 .. n_taxa - 1.
+ * max_overlap >= 0; num / den: the subject coverage, 0 <= num <= den < 2^20, den >= 1.  flags bit 0: same_taxon; bit 1: events around the
+ * stages -- prep_ms (runs, eligibility, representatives, scan), keys_ms (the sort of all rows' keys), count_ms, count_again_ms (such a call runs
+ * the count pass a second time, for its time alone), emit_ms, sort_ms.
+ * A run = consecutive rows of one query code.  A row is ELIGIBLE iff s != q, (sed - sst + 1) * den >= num * slen (64-bit products, equality
+ * passes) and, with same_taxon, tax[s] != tax[q].  The REPRESENTATIVE of a run and a subject is the first eligible row of that subject in
+ * the run.  Two names are HOMOLOGOUS iff any of the n rows holds them as (q, s) or (s, q).  A LINK is a pair of representatives ra < rb of
+ * one run with min(qed) - max(qst) + 1 <= max_overlap, with same_taxon tax[s[ra]] == tax[s[rb]], and s[ra], s[rb] not homologous.
+ * Output (allocated by the library, released with so_fusion_free()): the n_links links as row_a[], row_b[], ascending by (row_a, row_b),
+ * the same arrays from call to call; link[8 * n_links]: per link q, s[ra], s[rb], qst[ra], qed[ra], qst[rb], qed[rb], qlen[ra] -- what a
+ * line of the text needs, so the records call downloads no record.  n_runs; n_eligible rows; n_reps representatives; n_pairs = the sum over
+ * the runs of m (m - 1) / 2 for m representatives; n_disjoint = the pairs that passed the interval and the taxon test, before the homology
+ * look-up; waits: host waits of the call -- two, the counters that size the output and the result (one without a link, none for n = 0).
+ * The pairs are never stored: a fixed grid walks them twice, once to count and once to emit.  n = 0 is served and launches nothing.
+ * Ordering of the records call: that of so_rbh_records -- it first waits for ALL work queued on the device, works on a stream of its own
+ * and has synchronised it when it returns.  The records are only read.
+ * Refused with a message (so_fusion_last_error) and nothing left allocated: a row with qst < 1, qed < qst, sst < 1, sed < sst or slen < 0,
+ * max_overlap, num or den outside their ranges, unknown flag bits, n >= 2^31, a name code, map index or taxon out of range, 2^31 links and
+ * more, links that with their sort scratch do not fit half of the free device memory (the message says how many bytes they would take),
+ * no HIP device.
+ * No so_ctx: the call reads the SOHIT_* switches itself (SOHIT_POISON). */
+typedef struct so_fusion_result {
+    int64_t n_runs, n_eligible, n_reps, n_pairs, n_disjoint, n_links;
+    int32_t waits;
+    int32_t reserved;
+    double prep_ms, keys_ms, count_ms, count_again_ms, emit_ms, sort_ms;   /* flags bit 1: device time of the stages */
+    int32_t *row_a, *row_b;                                /* n_links */
+    int32_t *link;                                         /* 8 * n_links */
+} so_fusion_result;
+int so_fusion_cols(int device, int64_t n, const int32_t *q, const int32_t *s, const int32_t *qst, const int32_t *qed, const int32_t *sst,
+                   const int32_t *sed, const int32_t *slen, const int32_t *qlen, int64_t n_names, const int32_t *tax, int64_t n_taxa,
+                   int64_t max_overlap, int32_t num, int32_t den, int32_t flags, so_fusion_result *out);
+int so_fusion_records(int device, const so_hit *d_hits, int64_t n, const int32_t *qmap, int64_t n_q, const int32_t *smap, int64_t n_s,
+                      int64_t n_names, const int32_t *tax, int64_t n_taxa, int64_t max_overlap, int32_t num, int32_t den, int32_t flags,
+                      so_fusion_result *out);
+void so_fusion_free(so_fusion_result *result);
+const char *so_fusion_last_error(void);
+
 /* The operon pairs of the operon-clustering step on the device (csrc/operon.hip).  Replaces: the pair loop of scripts/operon_cluster.py
  * `operon_clust()` (136-168) -- for every operon the operons listed under the families of its genes, and per such pair the size of the
  * intersection of the two family sets -- as swiftortho_amd/operon.py `candidate_pairs()` restates it, count for count.  All of it is

@@ -24,6 +24,11 @@ runs scripts/phyletic_links.py on it with the wrapper's -l and -u and with `-j` 
 least, default 2) and leaves <name>.links.tsv, the pairs of gene families that co-occur across the genomes, and <name>.links.xyz; the
 modules of such families, <name>.links.clsr, come from `bin/find_cluster.py -i` that .xyz file with the wrapper's -A, -I and -G, as in the
 operon step.  With `-G T` the family pairs are found on the GPU.
+The gene-fusion step has no counterpart in the reference either and runs on request: `-F T` (default `F`; it needs nothing but the .sc file)
+runs scripts/fusion_links.py on it at that script's defaults (this wrapper's -c and -s mean other things) and leaves <name>.fusion.tsv, the
+pairs of proteins that align side by side on one composite protein without being homologous, and <name>.fusion.xyz; the modules of such
+proteins, <name>.fusion.clsr, come from `bin/find_cluster.py -i` that .xyz file with the wrapper's -A, -I and -G (no link: an empty file).
+With `-G T` the links are found on the GPU.
 `-l` and `-u` are read by this step alone: the `-P` step runs scripts/pan_genome.py at that script's own defaults (.05, .95), as it always has, so
 with other values the families that take part here are not the rows <name>.pan types Share; at the defaults they are.
 
@@ -51,7 +56,7 @@ from swiftortho_amd.fsearch import parse_flags  # noqa: E402
 
 ARGS = {'-i': '', '-r': '', '-p': '', '-s': '1111111', '-c': '.5', '-y': '50', '-n': 'no', '-l': '.05', '-u': '.95', '-a': '1', '-A': 'mcl',
         '-I': '1.5', '-v': '1000', '-G': 'F', '-P': 'F', '-C': 'F', '-t': 'F', '-g': '1', '-m': 'p', '-B': '0', '-S': '1', '-K': 'F',
-        '-L': 'F', '-j': '0.8', '-k': '2'}
+        '-L': 'F', '-j': '0.8', '-k': '2', '-F': 'F'}
 
 
 def main(argv):
@@ -60,17 +65,18 @@ def main(argv):
         sys.stderr.write('run_all_fast: -B takes a whole number of replicates from 0 to 2^31 - 1, -S a seed from 0 to 2^64 - 1\n')
         return 2
     if a['-i'] == '':
-        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon] [-L T [-l .05] [-u .95] [-j 0.8] [-k 2]]' % argv[0])
+        print('  python %s -i foo.pep.fsa [-s seed] [-a gpus] [-v hits] [-c cov] [-y identity] [-n no|bsr|bal] [-A mcl|apc] [-I 1.5] [-p foo.operon] [-L T [-l .05] [-u .95] [-j 0.8] [-k 2]] [-F T]' % argv[0])
         raise SystemExit()
     fas, name = a['-i'], a['-i'].split(os.sep)[-1]
     t = time()
     opc = '%s_results/%s.opc' % (fas, name)
+    sc = '%s_results/%s.sc' % (fas, name)
     if a['-G'].upper()[:1] == 'T':
         # the same two files from one process: duplicates collapsed, searched once, multiplied back and turned into relations on the GPU
         # (pipeline.orthology_from_search(collapse=True)); the .sc is written for the record, nothing reads it
         from swiftortho_amd import pipeline
         os.makedirs(fas + '_results', exist_ok=True)
-        lines, _ = pipeline.orthology_from_search(fas, sc_path='%s_results/%s.sc' % (fas, name), coverage=float(a['-c']), identity=float(a['-y']), norm=a['-n'],
+        lines, _ = pipeline.orthology_from_search(fas, sc_path=sc, coverage=float(a['-c']), identity=float(a['-y']), norm=a['-n'],
                                                   device_stage='relations', collapse=True, **nr.collapsed_search_kw(a['-s'], a['-v']))
         with open(opc, 'wb') as o:
             if lines:
@@ -144,6 +150,16 @@ def main(argv):
         with open(links + '.clsr', 'wb') as o:
             subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_cluster.py'), '-i', links + '.xyz', '-a', a['-A'], '-I', a['-I'], '-G', a['-G']], stdout=o, check=True)
         print('phyletic profile time:', time() - t)
+    if a['-F'].upper()[:1] == 'T':
+        # gene-fusion links: the pairs of proteins that align side by side on one composite, then their modules by the same clustering as above
+        t = time()
+        fusion = '%s_results/%s.fusion' % (fas, name)
+        with open(fusion + '.tsv', 'wb') as o:
+            subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'fusion_links.py'), '-i', sc, '-x', fusion + '.xyz', '-G', a['-G']], stdout=o, check=True)
+        with open(fusion + '.clsr', 'wb') as o:
+            if os.path.getsize(fusion + '.xyz'):
+                subprocess.run([sys.executable, os.path.join(ROOT, 'bin', 'find_cluster.py'), '-i', fusion + '.xyz', '-a', a['-A'], '-I', a['-I'], '-G', a['-G']], stdout=o, check=True)
+        print('gene fusion time:', time() - t)
     if os.path.isfile(a['-p']):
         # operon clustering (run_all_fast.py:241-255): scored operon pairs from the gene families, then the same clustering as above
         t = time()

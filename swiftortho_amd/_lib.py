@@ -59,6 +59,7 @@ EXPORTS = ["so_abi_version", "so_set_option", "so_create", "so_destroy", "so_las
            "so_cnc_plan", "so_cnc_plan_free", "so_apc_rows", "so_apc_rows_free", "so_nr_expand", "so_nr_expand_free", "so_nr_last_error",
            "so_rbh_cols", "so_rbh_records", "so_rbh_free", "so_rbh_last_error", "so_pan_genome", "so_pan_free", "so_pan_last_error", "so_pan_shared", "so_pan_shared_free",
            "so_phyletic_pairs", "so_phyletic_free", "so_phyletic_last_error",
+           "so_fusion_cols", "so_fusion_records", "so_fusion_free", "so_fusion_last_error",
            "so_operon_pairs", "so_operon_free", "so_operon_last_error", "so_phy_rows", "so_phy_build", "so_phy_free", "so_phy_last_error",
            "so_phy_boot_counts", "so_phy_nj_splits", "so_phy_boot", "so_phy_boot_free", "so_phy_subst", "so_phy_subst_free",
            "so_phy_gene", "so_phy_gene_counts", "so_phy_nj_subsets", "so_phy_gene_free",
@@ -128,6 +129,12 @@ class SoPanSharedResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_taxa", "n_reps", "bytes")] + \
                [("waits", C.c_int32), ("batches", C.c_int32), ("ranges", C.c_int32), ("reserved", C.c_int32), ("draw_ms", C.c_double), ("product_ms", C.c_double),
                 ("shared", C.POINTER(C.c_int32))]
+
+
+class SoFusionResult(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "n_eligible", "n_reps", "n_pairs", "n_disjoint", "n_links")] + \
+               [("waits", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double) for n in ("prep_ms", "keys_ms", "count_ms", "count_again_ms", "emit_ms", "sort_ms")] + \
+               [("row_a", C.POINTER(C.c_int32)), ("row_b", C.POINTER(C.c_int32)), ("link", C.POINTER(C.c_int32))]
 
 
 class SoPhyleticResult(C.Structure):
@@ -346,6 +353,10 @@ def load():
     L.so_phyletic_pairs.argtypes = [C.c_int, i64, vp, vp, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SoPhyleticResult)]
     L.so_phyletic_free.argtypes = [C.POINTER(SoPhyleticResult)]
     L.so_phyletic_last_error.restype = cp
+    L.so_fusion_cols.argtypes = [C.c_int, i64] + [vp] * 8 + [i64, vp, i64, i64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SoFusionResult)]
+    L.so_fusion_records.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, i64, i64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SoFusionResult)]
+    L.so_fusion_free.argtypes = [C.POINTER(SoFusionResult)]
+    L.so_fusion_last_error.restype = cp
     L.so_operon_pairs.argtypes = [C.c_int, i64, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(SoOperonResult)]
     L.so_operon_free.argtypes = [C.POINTER(SoOperonResult)]
     L.so_operon_last_error.restype = cp

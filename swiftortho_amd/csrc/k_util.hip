@@ -2,6 +2,7 @@
 // Wave = 64 lanes on gfx950; 256-thread blocks = 4 waves; 16 B per lane loads.
 #include "common.h"
 #include "kernels.h"
+#include "scan64.h"
 
 #define SCAN_THREADS 256
 #define SCAN_ITERS 8
@@ -117,30 +118,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(const u32* __restri
 // [c(t) != 0] (compacted seed index).  Until round 6: k_effcnt wrote c and the flag to two arrays and two scans read them back -- 37
 // bytes per slot through six launches.  Here the pair travels as ONE 64-bit value, flag count << 32 | hits (a pass holds fewer than 2^32
 // hits: seed_stage), computed from mark / scnt where it is needed: 5 bytes read by the reduce, 5 read + 8 written by the apply.
-__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up((unsigned long long)v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 block_excl_scan_u64(u64 v, u64* lds4, u64* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const u64 inc = wave_incl_scan_u64(v, lane);
-    if (lane == 63) lds4[w] = inc;
-    __syncthreads();
-    u64 base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / 64; ++k) {
-        const u64 s = lds4[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
+// (wave_incl_scan_u64 and block_excl_scan_u64: scan64.h, shared with fusion.hip)
+static_assert(SCAN_THREADS == 256, "block_excl_scan_u64 is called with its default of 256 lanes");
 // four slots from i on: their effective counts (0 beyond n)
 __device__ __forceinline__ uint4 eff4(const u8* __restrict__ mark, const u32* __restrict__ scnt, size_t i, size_t n) {
     uint4 c = make_uint4(0, 0, 0, 0);

@@ -278,6 +278,67 @@ def family_links_from_search(fasta_path, jaccard='0.8', k_min=2, ts=.05, tc=.95,
     return taxa, links, t
 
 
+def fusion_links_from_search(fasta_path, coverage='0.7', max_overlap=0, same_taxon=True, device=0, collapse=False, sep='|', sc_path=None, device_stage=True,
+                             **search_kw):
+    """one process from a FASTA file to its gene-fusion links: self-search on the GPU, then ONE device call on the records where they lie
+    (fusion.device_fusion_links_from_records, so_fusion_records) -- what `bin/find_hit.py ... && scripts/fusion_links.py -i x.sc -c coverage
+    -o max_overlap -s T|F` prints, with no .sc text in between (`sc_path` still receives the file when named; nothing reads it).
+    collapse=True: exact duplicates are searched once and the records multiplied back on the device, as in core_genes_from_search.
+    device_stage=False: the records are downloaded and the numpy definition runs on them (no collapse then).
+    -> (names (bytes, ascending), fusion.Links -- fusion.links_text(names, links) is the script's output --, dict of stage wall times in
+    seconds: load, search, [write_sc,] fusion, and the counts rows, links)"""
+    from . import find_orth, fsearch, fusion, rbh
+    if collapse and not device_stage:
+        raise ValueError('fusion_links_from_search: collapse=True expands the records on the device: device_stage must be True')
+    num, den = fusion.coverage_fraction(coverage)
+    max_overlap = fusion.overlap_value(max_overlap)
+    t = {}
+    t0 = time.time()
+    full = open(fasta_path, 'rb').read()
+    data, tables = full, None
+    if collapse:
+        tables, data, ids = _collapse(full, t)
+    else:
+        ids = find_orth.fasta_ids(full)
+    s = fsearch.Searcher(device=device, **search_kw)
+    try:
+        s.load_ref_bytes(data)
+        s.load_queries_bytes(data)
+        t['load'] = time.time() - t0 - t.get('collapse', 0.)
+        t0 = time.time()
+        if device_stage:
+            if tables is not None:
+                _check_collapsed(s, tables)
+            dev, owned, t0 = _search_records(s, tables, sc_path, t, t0)
+            try:
+                names, links = fusion.device_fusion_links_from_records(dev, ids, ids, max_overlap, num, den, same_taxon, sep)
+                t['rows'] = len(dev)
+            finally:
+                if owned is not None:
+                    owned.close()
+        else:
+            hits = s.search()
+            t['search'] = time.time() - t0
+            t0 = time.time()
+            rec = hits.array()
+            if sc_path:
+                hits.write(sc_path, 'w')
+                t['write_sc'] = time.time() - t0
+                t0 = time.time()
+            hits.close()
+            names, qmap, smap = find_orth._record_maps(ids, ids)
+            col = lambda k: rec[k].astype('int64')
+            table = fusion.Table(names, qmap[col('qidx')].astype('int64'), smap[col('sidx')].astype('int64'), col('qst'), col('qed'), col('sst'), col('sed'), col('slen'),
+                                 col('qlen'))
+            links = fusion.fusion_links(table, rbh.name_taxa(names, sep)[0], max_overlap, num, den, same_taxon)
+            t['rows'] = len(rec)
+        t['fusion'] = time.time() - t0
+    finally:
+        s.close()
+    t['links'] = len(links)
+    return names, links, t
+
+
 def species_tree_from_search(fasta_path, reference='', gap_share=1.0, model='p', device_stage=True, device=0, sep='|', boot=0, boot_seed=1, concordance=False, **search_kw):
     """one process from a FASTA file to the species tree of its taxa: self-search on the GPU with a CIGAR on every row, the core-gene
     table of `reference` (default: the taxon with most genes), the core-gene supermatrix from the rows' own alignments (swiftortho_amd.phy:
